@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- iLQR iterations/sec of the batched hot path on N x MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--dtype f64|f32] [--batch B]
+    python bench.py --gpus N --steps K --warmup W [--dtype f64|f32] [--batch B] [--dump-outputs DIR]
 
 A "step" is one iLQR iteration over the whole batch: linearise every (b, t), backward
 Riccati sweep, rollouts of every trial alpha of the backtracking line search, accept.
@@ -171,6 +171,36 @@ def pmc_valu(dtype, batch, horizon):
     return best
 
 
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(path, arrays, axis=0, seed=0, budget=DUMP_BUDGET_BYTES):
+    """Write {name: array} (float32 / float64) as path/<name>.npy.  When the arrays hold more than `budget` bytes in
+    all, the same fixed, seeded sample of batch entries (axis `axis` of every array) is written instead of the whole
+    batch.  Returns {"dir": path, "arrays": {name: shape written}, "batch_entries": k, "of": batch}."""
+    batch = next(iter(arrays.values())).shape[axis]
+    total = sum(a.nbytes for a in arrays.values())
+    room = budget - 4096 * len(arrays)                   # (.npy headers)
+    idx = np.arange(batch)
+    if total > room:
+        k = max(1, room * batch // total)
+        idx = np.sort(np.random.default_rng(seed).choice(batch, k, replace=False))
+    os.makedirs(path, exist_ok=True)
+    shapes = {}
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError(f"{name}: dumped outputs are float32 or float64, got {a.dtype}")
+        a = np.ascontiguousarray(np.take(a, idx, axis=axis))
+        np.save(os.path.join(path, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return {"dir": path, "arrays": shapes, "batch_entries": len(idx), "of": batch}
+
+
+def handle_outputs(h, _lib):
+    """What a caller of the iteration path receives: trajectory, controls, gains and cost of every trajectory."""
+    return {"X": h.get(_lib.X), "U": h.get(_lib.U), "K": h.get(_lib.K), "U_ff": h.get(_lib.UFF), "cost": h.get(_lib.COST)}
+
+
 def timed_iterations(h, steps, warm=3):
     """(wall seconds per iteration, {phase: (ms, launches)}) of `steps` iterations on a handle whose problem is set."""
     h.initial_rollout()
@@ -319,6 +349,8 @@ def run_c4(args, world, rank, local_rank, ilqr_amd, _lib, problems, torch, dist)
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     wall = max_over_ranks(torch, dist, wall, world)
+    dumped = dump_outputs(args.dump_outputs, {"U_sim": u, "X_sim": x, "cost": c}, axis=1) \
+        if args.dump_outputs and rank == 0 else None
     if rank == 0:
         print(json.dumps({
             "metric": "MPC instance-steps/sec (8192 warm-started UA double pendulum instances, T=200, n=4 m=1)",
@@ -330,7 +362,7 @@ def run_c4(args, world, rank, local_rank, ilqr_amd, _lib, problems, torch, dist)
                        "instances_per_gpu": sb.hi - sb.lo, "horizon": 200,
                        "sharding": f"{world} contiguous shards (dist.shard_range), one scalar status all-reduce behind the steps"},
             "global_status": {"min_cost": st.min_cost, "n_active": st.n_active, "n_converged": st.n_converged},
-            "all_costs_finite": bool(np.isfinite(c).all())}))
+            "all_costs_finite": bool(np.isfinite(c).all()), **({"dumped_outputs": dumped} if dumped else {})}))
 
 
 def run_c5(args, world, rank, local_rank, ilqr_amd, _lib, problems, torch, dist):
@@ -365,6 +397,7 @@ def run_c5(args, world, rank, local_rank, ilqr_amd, _lib, problems, torch, dist)
     wall = time.perf_counter() - t0
     wall = max_over_ranks(torch, dist, wall, world)
     st = to_status(stats.cpu())
+    dumped = dump_outputs(args.dump_outputs, handle_outputs(h, _lib)) if args.dump_outputs and rank == 0 else None
     if rank == 0:
         print(json.dumps({
             "metric": "iLQR iterations/sec (synthetic LQ n=16 m=8, T=500, batch=1024)",
@@ -374,7 +407,8 @@ def run_c5(args, world, rank, local_rank, ilqr_amd, _lib, problems, torch, dist)
             "config": {"workload": "c5: synthetic linear-quadratic system n=16 m=8 N=500, fixed iterations", "batch": total,
                        "batch_per_gpu": hi - lo, "horizon": 500, "n_alpha": 10,
                        "sharding": f"{world} contiguous shards (dist.shard_range), one scalar status all-reduce behind the steps"},
-            "global_status": {"min_cost": st.min_cost, "n_active": st.n_active}}))
+            "global_status": {"min_cost": st.min_cost, "n_active": st.n_active},
+            **({"dumped_outputs": dumped} if dumped else {})}))
     h.close()
 
 
@@ -394,7 +428,7 @@ def main():
                     help="time the four-launch iteration over the materialised expansion (ILQR_FLAG_NO_FUSE) instead of the fused one")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (one rank per GPU); gloo = rehearsal of the N-rank control flow with several ranks "
-                         "on ONE card (tests): ranks map to device LOCAL_RANK % device_count, collectives run on host copies")
+                         "on ONE card (tests): ranks map to device LOCAL_RANK %% device_count, collectives run on host copies")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-phase-timing", action="store_true")
     ap.add_argument("--no-solve-extra", action="store_true", help="skip the solve_to_convergence / MPC / configs extras (profiling runs)")
@@ -405,6 +439,9 @@ def main():
                          "K steps -- a solve needs the global status once, at its end, and no shard needs another shard's "
                          "numbers to iterate.  One exchange costs the compute stream 25-50 us (status reduce, event, and a "
                          "collective kernel sharing the CUs): measured with --exchange --exchange-every 1 / 4")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (rank 0's shard; at most "
+                         f"{DUMP_BUDGET_BYTES // 1000000} MB in all: a fixed, seeded sample of the batch beyond that)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -512,6 +549,8 @@ def main():
     run_steps(args.steps)
     fence()
     wall = time.perf_counter() - t0
+    # (read before the phase timing below iterates the same handle further)
+    dumped = dump_outputs(args.dump_outputs, handle_outputs(h, _lib)) if args.dump_outputs and rank == 0 else None
 
     # ---- per-phase breakdown: the same K steps again with HIP start/stop events attached to every kernel
     # dispatch (hipExtLaunchKernelGGL: the dispatch's own begin/end timestamps, no extra stream packets)
@@ -574,6 +613,8 @@ def main():
                        else "single shard"},
             "all_costs_finite": finite,
         }
+        if dumped:
+            out["dumped_outputs"] = dumped
         if phases is not None:
             ab = h.algorithmic_bytes()
             tr = pmc_traffic(args.dtype, B, N)

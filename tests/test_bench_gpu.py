@@ -105,6 +105,29 @@ def test_headline_materialised_switch():
     assert "materialised" in d["config"]["iteration_path"] and d["roofline"]["bound"] == "hbm"
 
 
+@pytest.mark.parametrize("batch", [256, 2048])       # the persistent and the two-launch fused iteration
+def test_dump_outputs_are_the_last_timed_step(tmp_path, batch):
+    """--dump-outputs writes the state after warmup + steps iterations (not after the phase-timing pass that follows),
+    equal to the same iterations run directly through the library on the same seeded inputs."""
+    from ilqr_amd import _lib
+    d = _bench("--steps", "3", "--warmup", "2", "--batch", str(batch), "--no-cpu-baseline", "--no-solve-extra",
+               "--dump-outputs", str(tmp_path))
+    assert d["steps"] == 3 and d["dumped_outputs"]["batch_entries"] == batch
+    p = problems.ua_double_pendulum(integrator="rk4", N=200)
+    x0, U0 = problems.ua_batch(batch, seed=1000, restarts=False, N=200)
+    h = ilqr_amd.make_system(p["dynamics"], p["cost"], np.float32).make_handle(
+        horizon=200, batch=batch, n_alpha=10, n_trials=10, tol=p["tol"], maxiter=1 << 30, flags=_lib.FLAG_KEEP_ITERATING)
+    h.set_problem(x0, U0)
+    h.initial_rollout()
+    h.iterate(5)
+    ref = {"X": h.get(_lib.X), "U": h.get(_lib.U), "K": h.get(_lib.K), "U_ff": h.get(_lib.UFF), "cost": h.get(_lib.COST)}
+    h.close()
+    for name, want in ref.items():
+        got = np.load(tmp_path / f"{name}.npy")
+        assert got.dtype == np.float32 and got.shape == want.shape, name
+        np.testing.assert_allclose(got, want, rtol=1e-5, atol=1e-6, err_msg=name)
+
+
 @pytest.mark.parametrize("cfg,batch,unit", [("c4", "96", "MPC instance-steps/sec"), ("c5", "48", "iLQR iterations/sec")])
 def test_sharded_configs_one_rank(cfg, batch, unit):
     d = _bench("--config", cfg, "--batch", batch, "--steps", "2", "--warmup", "1")
