@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define ILQR_ABI_VERSION 3
+#define ILQR_ABI_VERSION 4
 
 typedef struct ilqr_solver_s* ilqr_handle;
 
@@ -249,6 +249,23 @@ int ilqr_mpc_rearm(ilqr_handle h, const void* x0, const void* U_init);
  * plant_integrator; warm start <- shift(U) repeating the last column }.
  * u_out [n_steps][B][n_u], x_out [n_steps][B][n_x] (state after each step), cost_out [n_steps][B]; may be NULL */
 int ilqr_mpc_run(ilqr_handle h, int n_steps, void* u_out, void* x_out, void* cost_out);
+
+/* ---- control limits (build extension: the reference is unconstrained) -------
+ * u_min <= u <= u_max, one pair per control component [n_u] each, shared by the whole batch; +-inf allowed.
+ * NULL, NULL clears them.  May be called between any two calls (also between ilqr_mpc_run calls); it takes effect
+ * from the next rollout / sweep on.  With limits set (control-limited DDP, Tassa, Mansard & Todorov, ICRA 2014):
+ *  - every rollout (iLQR_class.py:181-182) clamps u = u_old + alpha k + K (x - x_old) to the box (a NaN stays
+ *    NaN), the alpha = 0 head of a solve included: a U_init outside the box is projected;
+ *  - every backward step (iLQR_class.py:100-114) takes k as the exact minimiser of the Q function's quadratic
+ *    model over u_min - u_t <= du <= u_max - u_t, K = 0 on the clamped coordinates and -(Q_uu)_FF^-1 Q_ux,F on the
+ *    free ones; a step whose k moved uses the full value update (as mu != 0 does), any other step is the
+ *    unconstrained step exactly;
+ *  - ilqr_backward_pass / ilqr_forward_pass honour them; ilqr_backward_tensors returns ILQR_ERR_UNSUPPORTED;
+ *  - n_u = 1 solves and MPC keep the fused / persistent kernels (their control-limited instantiations); the (4, 2)
+ *    double pendulum, ILQR_FLAG_NO_FUSE and mu > 0 run linearise -> box sweep -> rollouts -> select.
+ * Returns ILQR_ERR_UNSUPPORTED for ILQR_SYS_LINEAR, ILQR_SYS_CUSTOM and n_x > 4 (clearing with NULL, NULL is valid on
+ * every handle), ILQR_ERR_INVALID_ARG for a NaN bound, u_min > u_max, or exactly one NULL pointer. */
+int ilqr_set_control_limits(ilqr_handle h, const double* u_min, const double* u_max);
 
 /* ---- multi-GPU hook -------------------------------------------
  * Writes 4 doubles to DEVICE memory `dev_out4` on the handle's stream:

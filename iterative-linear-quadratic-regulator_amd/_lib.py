@@ -31,7 +31,7 @@ FLAG_KEEP_ITERATING = 1
 FLAG_NO_FUSE = 2
 FLAG_NO_PERSIST = 4
 PHASES = ("linearize", "backward", "forward", "select", "other", "fused", "persist")
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 # every symbol include/ilqr_hip.h declares (tests check the library exports all of them)
 SYMBOLS = (
@@ -40,7 +40,10 @@ SYMBOLS = (
     "ilqr_initial_rollout", "ilqr_linearize", "ilqr_backward", "ilqr_forward", "ilqr_select", "ilqr_iterate",
     "ilqr_flush", "ilqr_solve", "ilqr_backward_pass", "ilqr_backward_tensors", "ilqr_forward_pass", "ilqr_eval_points", "ilqr_mpc_reset",
     "ilqr_mpc_rearm", "ilqr_mpc_run", "ilqr_status_reduce", "ilqr_timing_enable", "ilqr_timing_reset", "ilqr_timing_get", "ilqr_algorithmic_bytes",
+    "ilqr_set_control_limits",
 )
+# the built-in systems that take control limits (ilqr_set_control_limits)
+BOX_SYSTEMS = (SYS_PENDULUM, SYS_UA_DOUBLE_PENDULUM, SYS_DOUBLE_PENDULUM)
 
 
 class Config(C.Structure):
@@ -119,6 +122,7 @@ def load():
     lib.ilqr_timing_enable.argtypes = [vp, ci]
     lib.ilqr_timing_get.argtypes = [vp, C.POINTER(cd), C.POINTER(C.c_int64)]
     lib.ilqr_algorithmic_bytes.argtypes = [vp, C.POINTER(cd)]
+    lib.ilqr_set_control_limits.argtypes = [vp, vp, vp]
     if lib.ilqr_abi_version() != ABI_VERSION:
         raise RuntimeError("libilqr_hip.so ABI version mismatch: rebuild the library")
     _lib = lib
@@ -336,6 +340,16 @@ class Handle:
     def status_reduce(self, dev_ptr):
         """Write {min cost, max |dcost|, #active, #converged} (4 doubles) to DEVICE memory at dev_ptr."""
         self._chk(self.lib.ilqr_status_reduce(self.h, C.c_void_p(int(dev_ptr))))
+
+    # ---- control limits ---------------------------------------------------------------------------
+    def set_control_limits(self, u_min, u_max):
+        """u_min <= u <= u_max ([n_u] doubles each) for every control of the batch; (None, None) clears them."""
+        if u_min is None and u_max is None:
+            self._chk(self.lib.ilqr_set_control_limits(self.h, None, None))
+            return
+        lo = np.ascontiguousarray(u_min, dtype=np.float64).reshape(self.n_u)
+        hi = np.ascontiguousarray(u_max, dtype=np.float64).reshape(self.n_u)
+        self._chk(self.lib.ilqr_set_control_limits(self.h, _ptr(lo), _ptr(hi)))
 
     # ---- measurement ------------------------------------------------------------------------------
     def timing_enable(self, on=True):

@@ -85,6 +85,16 @@ template <> struct FusedStep<float, 1> {
         tile16_step_f32<false>(c, lc, V, vx, Kj, kff, pd, none, srd, off, 0);
         out = (i == 0) ? Kj : kff;
     }
+    // with control limits: u = u_t, [lo, hi] = [u_min, u_max]
+    static ILQR_DEV void step_box(const Tile& c, const LaneConst<float>& lc, int i, int j, float u, float lo, float hi,
+                                  float& V, float& vx, float& out, bool& pd) {
+        RawTileQ none;
+        const i32x4 srd = {0, 0, 0, 0};
+        const TileOffsets off = {0, 0, 0};
+        float Kj, kff;
+        tile16_step_f32<false, true>(c, lc, V, vx, Kj, kff, pd, none, srd, off, 0, u, lo, hi);
+        out = (i == 0) ? Kj : kff;
+    }
 };
 template <> struct FusedStep<double, 1> {
     using Tile = Tile16<double>;
@@ -92,6 +102,12 @@ template <> struct FusedStep<double, 1> {
     static ILQR_DEV void step(const Tile& c, const LaneConst<double>& lc, int i, int j, double& V, double& vx, double& out, bool& pd) {
         double Kj, kff;
         tile16_step<double, false>(c, lc, 0.0, V, vx, Kj, kff, pd);
+        out = (i == 0) ? Kj : kff;
+    }
+    static ILQR_DEV void step_box(const Tile& c, const LaneConst<double>& lc, int i, int j, double u, double lo, double hi,
+                                  double& V, double& vx, double& out, bool& pd) {
+        double Kj, kff;
+        tile16_step<double, false, true>(c, lc, 0.0, V, vx, Kj, kff, pd, u, lo, hi);
         out = (i == 0) ? Kj : kff;
     }
 };
@@ -135,8 +151,11 @@ ILQR_DEV void lds_poke(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXE
 
 // The roles of a workgroup as functions of one struct, so that the fused kernel below and the persistent kernel
 // (persistent.hpp: the whole iteration loop of a workgroup's trajectories in one launch) run the same code.
-template <typename T, typename Dyn, int INTEG, int TPW, bool PK> struct FusedWG {
+// BOX (control limits, n_u = 1): the producers put u_t into the tile's padding (scalar kTile16 of the TL = 52), the sweep
+// hands it to the step's tail with the limits (tile16_step_f32 / tile16_step, BOX).
+template <typename T, typename Dyn, int INTEG, int TPW, bool PK, bool BOX = false> struct FusedWG {
     static constexpr int NX = Dyn::NX, NU = Dyn::NU;
+    static_assert(!BOX || (NU == 1 && fused_tl<1>() > kTile16), "control limits: n_u = 1, u_t in the tile's padding");
     static_assert((NU == 1 && NX >= 2 && NX <= 4) || (NX == 4 && NU == 2), "the fused sweep serves the DPP tiles: n_u = 1, or (4, 2)");
     static_assert(TPW == 16 || TPW == 4, "16 or 4 trajectories per workgroup");
     static_assert(!PK || (sizeof(T) == 4 && TPW == 16 && INTEG != ILQR_INT_BACKWARD_EULER), "pair producers: fp32, 16-trajectory workgroups, explicit integrators");
@@ -260,22 +279,29 @@ template <typename T, typename Dyn, int INTEG, int TPW, bool PK> struct FusedWG 
         lc.tr_byte = 4 * ((lane & 48) | (j << 2) | i);
         bool all_pd = true;
         using FS = FusedStep<T, NU>;
-        int goff = (N - 1) * rstride;
-        // this trajectory's tile of time step r of unit k sits at unit_base(k) + r * TPW * TL: a compile-time offset per step
-        auto unit_base = [&](int k) -> const T* { return L.ring + (size_t)(k % RU) * UNIT + tile_off(0, tl); };
-        constexpr auto step_off = [](int r) { return PK ? (r / 2) * TPW * PS + (r % 2) * TL : r * TPW * TL; };
-        auto one_step = [&](const typename FS::Tile& c) {
-            T out;
-            bool pd;
-            FS::step(c, lc, i, j, V, vx, out, pd);
-            all_pd = all_pd && pd;
-            if (DROP || storer) buf_store1(rgain, rec_off, uniform(goff), out);
-            goff -= rstride;
-        };
+        const T blo = BOX ? a.u_lo[0] : T(0), bhi = BOX ? a.u_hi[0] : T(0);   // (read once: the loop must not reload them)
         // Two tile buffers used alternately (US is even, so the buffer of a step is a compile-time choice: no copies);
         // the tile of step s + 1 is read from LDS while step s computes.  The flag of the next unit is fetched one step
         // before it is needed, so its LDS round trip is not exposed either.
         typename FS::Tile tq[2];
+        T uq[2] = {T(0), T(0)};   // BOX: u_t of the tile in tq[q]
+        auto load = [&](int q, const T* tp) {
+            FS::load(tq[q], tp, i, j, l16);
+            if constexpr (BOX) uq[q] = tp[kTile16];
+        };
+        int goff = (N - 1) * rstride;
+        // this trajectory's tile of time step r of unit k sits at unit_base(k) + r * TPW * TL: a compile-time offset per step
+        auto unit_base = [&](int k) -> const T* { return L.ring + (size_t)(k % RU) * UNIT + tile_off(0, tl); };
+        constexpr auto step_off = [](int r) { return PK ? (r / 2) * TPW * PS + (r % 2) * TL : r * TPW * TL; };
+        auto one_step = [&](int q) {
+            T out;
+            bool pd;
+            if constexpr (BOX) FS::step_box(tq[q], lc, i, j, uq[q], blo, bhi, V, vx, out, pd);
+            else FS::step(tq[q], lc, i, j, V, vx, out, pd);
+            all_pd = all_pd && pd;
+            if (DROP || storer) buf_store1(rgain, rec_off, uniform(goff), out);
+            goff -= rstride;
+        };
 #ifdef ILQR_FUSED_STAMPS   // diagnostic build (tools/fused_stamps.py): where a sweep wave's time goes
         const long long st_t0 = __builtin_readcyclecounter();
         long long st_spin = 0;
@@ -285,7 +311,7 @@ template <typename T, typename Dyn, int INTEG, int TPW, bool PK> struct FusedWG 
 #ifdef ILQR_FUSED_STAMPS
         const long long st_first = __builtin_readcyclecounter();
 #endif
-        FS::load(tq[0], unit_base(0), i, j, l16);
+        load(0, unit_base(0));
         const int n_full = N / US, rem = N % US;
         for (int k = 0; k < n_full; ++k) {
             const T* ub = unit_base(k);
@@ -295,7 +321,7 @@ template <typename T, typename Dyn, int INTEG, int TPW, bool PK> struct FusedWG 
             for (int r = 0; r < US; ++r) {
                 if (r == US - 2 && more) flag = lds_peek(&L.ready[(k + 1) % RU]);
                 if (r < US - 1) {
-                    FS::load(tq[(r + 1) & 1], ub + step_off(r + 1), i, j, l16);
+                    load((r + 1) & 1, ub + step_off(r + 1));
                 } else if (more) {
 #ifdef ILQR_FUSED_STAMPS
                     const long long w0 = __builtin_readcyclecounter();
@@ -308,9 +334,9 @@ template <typename T, typename Dyn, int INTEG, int TPW, bool PK> struct FusedWG 
 #ifdef ILQR_FUSED_STAMPS
                     st_spin += __builtin_readcyclecounter() - w0;
 #endif
-                    FS::load(tq[0], unit_base(k + 1), i, j, l16);
+                    load(0, unit_base(k + 1));
                 }
-                one_step(tq[r & 1]);
+                one_step(r & 1);
             }
             // every read of this unit has been issued (LDS serves a wave in order): its L.ring slot may be overwritten
             compiler_fence();
@@ -321,8 +347,8 @@ template <typename T, typename Dyn, int INTEG, int TPW, bool PK> struct FusedWG 
 #pragma unroll
             for (int r = 0; r < US - 1; ++r) {
                 if (r < rem) {
-                    if (r + 1 < rem) FS::load(tq[(r + 1) & 1], ub + step_off(r + 1), i, j, l16);
-                    one_step(tq[r & 1]);
+                    if (r + 1 < rem) load((r + 1) & 1, ub + step_off(r + 1));
+                    one_step(r & 1);
                 }
             }
         }
@@ -409,6 +435,11 @@ template <typename T, typename Dyn, int INTEG, int TPW, bool PK> struct FusedWG 
 #pragma unroll
                 for (int q = 0; q < NV; ++q) dst[TL / 4 + q] = tile_b[q];
             }
+            if constexpr (BOX) {      // u_t into each tile's padding
+                T* dt_ = reinterpret_cast<T*>(dst);
+                if (ina) dt_[kTile16] = ua[0];
+                if (inb) dt_[TL + kTile16] = ub[0];
+            }
             compiler_fence();
             if (lane == 0) lds_poke(&L.ready[k % RU], k + 1);
         }
@@ -458,6 +489,7 @@ template <typename T, typename Dyn, int INTEG, int TPW, bool PK> struct FusedWG 
                 vec_u4* dst = reinterpret_cast<vec_u4*>(L.ring + (size_t)(k % RU) * UNIT + tile_off(r, tl));
 #pragma unroll
                 for (int q = 0; q < NQ; ++q) dst[q] = w[q];
+                if constexpr (BOX) reinterpret_cast<T*>(dst)[kTile16] = u[0];   // u_t into the tile's padding
             }
             compiler_fence();
             if (lane == 0) lds_poke(&L.ready[k % RU], k + 1);
@@ -466,9 +498,10 @@ template <typename T, typename Dyn, int INTEG, int TPW, bool PK> struct FusedWG 
     }
 };
 
-template <typename T, typename Dyn, int INTEG, int TPW, bool PK>
+// BOX: with control limits (FusedWG, BOX); the rollouts that follow are forward_ring_kernel_box
+template <typename T, typename Dyn, int INTEG, int TPW, bool PK, bool BOX = false>
 __global__ void __launch_bounds__((fused_threads<T, TPW, PK>())) backward_fused16_kernel(KArgs<T> a) {
-    using W = FusedWG<T, Dyn, INTEG, TPW, PK>;
+    using W = FusedWG<T, Dyn, INTEG, TPW, PK, BOX>;
     extern __shared__ __attribute__((aligned(16))) unsigned char fused_lds[];
     const typename W::Lds L = W::carve(fused_lds);
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;

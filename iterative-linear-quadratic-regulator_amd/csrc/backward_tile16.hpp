@@ -449,8 +449,11 @@ template <typename T> struct LaneConst {
 // One Riccati step (iLQR_class.py:100-114) on the lane-distributed state:
 //   V  = V_xx[i][j] at lane (i, j);  vx = V_x[j] ("column form": replicated down the rows).
 // Returns K[j] (column form) and k (replicated); pd = Q_uu (+mu) > 0.
-template <typename T, bool REG>
-ILQR_DEV void tile16_step(const Tile16<T>& c, const LaneConst<T>& lc, T mu, T& V, T& vx, T& Kj, T& kff, bool& pd) {
+// BOX (control limits, !REG only): u_t and the limits u_min, u_max of this trajectory's step; see the tail.
+template <typename T, bool REG, bool BOX = false>
+ILQR_DEV void tile16_step(const Tile16<T>& c, const LaneConst<T>& lc, T mu, T& V, T& vx, T& Kj, T& kff, bool& pd,
+                          T ut = T(0), T blo = T(0), T bhi = T(0)) {
+    static_assert(!(BOX && REG), "control limits take the fused kernels, which run without regularisation");
     // P = f_x' V_xx :  P[i][j] = sum_d A[(i+d)%4][i] * V[(i+d)%4][j]
     const T P = contract_col(c.ski, V);
     // pu = f_u' V_xx :  pu[j] = sum_i b[i] V[i][j]   (sum down the rows, result in every row)
@@ -482,6 +485,18 @@ ILQR_DEV void tile16_step(const Tile16<T>& c, const LaneConst<T>& lc, T mu, T& V
         // short form (:113-114): V_x = Q_x + K'Q_u ; V_xx = Q_xx + Q_ux' K
         V = Qxx + Quxi * Kj;
         vx = Qx + Kj * Qu;
+        if constexpr (BOX) {
+            // control limits (kernels.hpp, box_gains, n_u = 1): k clamped to [u_min - u_t, u_max - u_t]; a clamped step has
+            // K = 0, so V_xx = Q_xx and V_x = Q_x + Q_ux' k.  An unclamped step keeps the values above bit for bit.
+            const T lo = blo - ut, hi = bhi - ut;
+            const bool out = kff < lo || kff > hi;
+            const T kc = clamp_keep_nan(kff, lo, hi);
+            const T vxc = Qx + Qux * kc;
+            V = out ? Qxx : V;
+            vx = out ? vxc : vx;
+            Kj = out ? T(0) : Kj;
+            kff = kc;
+        }
     } else {
         // full update for a regularised gain
         const T Ki = -(Quxi * inv);
@@ -525,9 +540,12 @@ ILQR_DEV void tile16_step(const Tile16<T>& c, const LaneConst<T>& lc, T mu, T& V
 #define ILQR_QB1 "quad_perm:[1,1,1,1]"
 #define ILQR_QB2 "quad_perm:[2,2,2,2]"
 #define ILQR_QB3 "quad_perm:[3,3,3,3]"
-template <bool REFILL>
+// BOX (control limits): u_t and the limits u_min, u_max of this trajectory's step, applied in the tail only.
+template <bool REFILL, bool BOX = false>
 ILQR_DEV void tile16_step_f32(const TileQ& c, const LaneConst<float>& lc, float& V, float& vx, float& Kj, float& kff,
-                              bool& pd, RawTileQ& prev, const i32x4& srd, const TileOffsets& off, int soff) {
+                              bool& pd, RawTileQ& prev, const i32x4& srd, const TileOffsets& off, int soff,
+                              float ut = 0.0f, float blo = 0.0f, float bhi = 0.0f) {
+    using T = float;
     float P, pu, qx, qu, quu, Qxx, Qux, Quxi, t, t2, inv, si1, si2, si3;
 #define DPPT " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
 #define DPPE " row_mask:0xf bank_mask:0xf bound_ctrl:1"
@@ -602,6 +620,18 @@ ILQR_DEV void tile16_step_f32(const TileQ& c, const LaneConst<float>& lc, float&
     kff = -(qu * inv);
     V = fmaf(Quxi, Kj, Qxx);
     vx = fmaf(Kj, qu, qx);
+    if constexpr (BOX) {
+        // control limits (kernels.hpp, box_gains, n_u = 1): k clamped to [u_min - u_t, u_max - u_t]; a clamped step has
+        // K = 0, so V_xx = Q_xx and V_x = Q_x + Q_ux' k.  An unclamped step keeps the values above bit for bit.
+        const T lo = blo - ut, hi = bhi - ut;
+        const bool out = kff < lo || kff > hi;
+        const T kc = clamp_keep_nan(kff, lo, hi);
+        const T vxc = fmaf(Qux, kc, qx);
+        V = out ? Qxx : V;
+        vx = out ? vxc : vx;
+        Kj = out ? T(0) : Kj;
+        kff = kc;
+    }
 }
 
 // Workgroup = 4 waves = 16 trajectories, launched with > 80 KiB of (unused) dynamic LDS so that a CU

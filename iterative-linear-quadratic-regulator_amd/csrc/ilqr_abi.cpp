@@ -238,6 +238,17 @@ int ilqr_debug_set_stream(ilqr_handle h, void* stream) {
     if (!h || !h->impl) return ILQR_ERR_INVALID_ARG;
     return h->impl->debug_set_stream(stream);
 }
+int ilqr_set_control_limits(ilqr_handle h, const double* u_min, const double* u_max) {
+    if (!h || !h->impl) return ILQR_ERR_INVALID_ARG;
+    const ilqr_config& c = h->impl->cfg;
+    if (!u_min && !u_max) return h->impl->set_control_limits(nullptr, nullptr);   // clearing: valid on every handle
+    if (c.system == ILQR_SYS_LINEAR || c.system == ILQR_SYS_CUSTOM || c.n_x > 4) {
+        h->impl->err = "set_control_limits: control limits are not supported for linear systems, user-defined systems "
+                       "or n_x > 4";
+        return ILQR_ERR_UNSUPPORTED;
+    }
+    return h->impl->set_control_limits(u_min, u_max);
+}
 int ilqr_timing_enable(ilqr_handle h, int on) { ILQR_FWD(h, timing_enable(on)); }
 int ilqr_timing_reset(ilqr_handle h) { ILQR_FWD(h, timing_reset()); }
 int ilqr_timing_get(ilqr_handle h, double ms[ILQR_N_PHASES], int64_t launches[ILQR_N_PHASES]) {

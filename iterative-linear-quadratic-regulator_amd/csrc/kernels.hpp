@@ -40,6 +40,7 @@ namespace ilqr {
 #endif
 constexpr int kMaxAlpha = 16;
 constexpr int kCounterRing = 64;
+constexpr int kBoxMaxU = 2;   // control limits: the built-in systems with n_x <= 4 (n_u <= 2)
 
 template <typename T> struct KArgs {
     int B, N, n_slots, integ, maxiter, flags;
@@ -63,11 +64,19 @@ template <typename T> struct KArgs {
     int t_first;       // linearize_wave_kernel: first time step of the launch (0, or N-1 for the sparse form)
     const T* params;
     long long* probe;  // diagnostic: {shader cycles, 100 MHz ticks} of block 0 per kernel, or nullptr
+    // control limits (ilqr_set_control_limits), read by the BOX kernels only (forward_kernel_box,
+    // forward_ring_kernel_box, backward_box_kernel, the BOX fused / persistent kernels); appended so the fields above keep
+    // their offsets
+    T u_lo[kBoxMaxU], u_hi[kBoxMaxU];
+    int box;           // limits are set: the fused / persistent launchers pick their BOX instantiations
 };
 
 constexpr int gain_record(int nx, int nu) { return ((nu * nx + nu) + 3) / 4 * 4; }
 
 ILQR_DEV bool traj_active(int status) { return (status & 0xff) == ILQR_TRAJ_ACTIVE; }
+
+// u clamped to [lo, hi]; a NaN stays NaN (as np.clip): a diverged candidate must not get a finite cost at a bound
+template <typename T> ILQR_DEV T clamp_keep_nan(T v, T lo, T hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // element offset of vector (slot, t, b) in X (Tn = N + 1, C = n_x) or U (Tn = N, C = n_u)
 ILQR_DEV size_t vec_at(size_t B, int Tn, int C, int slot, int t, size_t b) {
@@ -442,13 +451,14 @@ ILQR_DEV bool gain_solve(const T (*Quu)[NU], const T (*Qux)[NX], const T* Qu, T 
     }
 }
 
-// One Riccati step on register tiles (iLQR_class.py:100-114).  tile = the E scalars
+// The expansion of the Q function at one step (iLQR_class.py:100-104).  tile = the E scalars
 // of one (b, t) in ILQR_LIN order.
 template <typename T, int NX, int NU>
-ILQR_DEV bool riccati_step(const T* tile, T mu, T* Vx, T (*Vxx)[NX], T (*K)[NX], T* k) {
+ILQR_DEV void riccati_q(const T* tile, const T* Vx, const T (*Vxx)[NX], T* Qx, T* Qu, T (*Qxx)[NX], T (*Qux)[NX],
+                        T (*Quu)[NU]) {
     constexpr int oFX = 0, oFU = NX * NX, oLX = oFU + NX * NU, oLU = oLX + NX, oLXX = oLU + NU,
                   oLUX = oLXX + NX * NX, oLUU = oLUX + NU * NX;
-    T Qx[NX], Qu[NU], P[NX][NX], Pu[NU][NX], Qxx[NX][NX], Qux[NU][NX], Quu[NU][NU];
+    T P[NX][NX], Pu[NU][NX];
     // Q_x = l_x + f_x' V_x ; Q_u = l_u + f_u' V_x
 #pragma unroll
     for (int j = 0; j < NX; ++j) {
@@ -509,13 +519,14 @@ ILQR_DEV bool riccati_step(const T* tile, T mu, T* Vx, T (*Vxx)[NX], T (*K)[NX],
             Quu[i][j] = tile[oLUU + i * NU + j] + acc;
         }
     }
-    T Qr[NU][NU];
-#pragma unroll
-    for (int i = 0; i < NU; ++i)
-#pragma unroll
-        for (int j = 0; j < NU; ++j) Qr[i][j] = Quu[i][j] + ((i == j) ? mu : T(0));
-    const bool pd = gain_solve<T, NX, NU>(Qr, Qux, Qu, K, k);
-    if (mu == T(0)) {
+}
+
+// V_x, V_xx at t from the Q function and the gains: short form (iLQR_class.py:113-114) or the full form, exact for
+// any gain (a regularised one, or the box-constrained gains of backward_box_kernel)
+template <typename T, int NX, int NU>
+ILQR_DEV void riccati_value(bool full, const T* Qx, const T* Qu, const T (*Qxx)[NX], const T (*Qux)[NX],
+                            const T (*Quu)[NU], const T (*K)[NX], const T* k, T* Vx, T (*Vxx)[NX]) {
+    if (!full) {
         // short form (iLQR_class.py:113-114): V_x = Q_x + K'Q_u ; V_xx = Q_xx + Q_ux' K
 #pragma unroll
         for (int i = 0; i < NX; ++i) {
@@ -565,6 +576,21 @@ ILQR_DEV bool riccati_step(const T* tile, T mu, T* Vx, T (*Vxx)[NX], T (*K)[NX],
             }
         }
     }
+}
+
+// One Riccati step on register tiles (iLQR_class.py:100-114).  tile = the E scalars
+// of one (b, t) in ILQR_LIN order.
+template <typename T, int NX, int NU>
+ILQR_DEV bool riccati_step(const T* tile, T mu, T* Vx, T (*Vxx)[NX], T (*K)[NX], T* k) {
+    T Qx[NX], Qu[NU], Qxx[NX][NX], Qux[NU][NX], Quu[NU][NU];
+    riccati_q<T, NX, NU>(tile, Vx, Vxx, Qx, Qu, Qxx, Qux, Quu);
+    T Qr[NU][NU];
+#pragma unroll
+    for (int i = 0; i < NU; ++i)
+#pragma unroll
+        for (int j = 0; j < NU; ++j) Qr[i][j] = Quu[i][j] + ((i == j) ? mu : T(0));
+    const bool pd = gain_solve<T, NX, NU>(Qr, Qux, Qu, K, k);
+    riccati_value<T, NX, NU>(mu != T(0), Qx, Qu, Qxx, Qux, Quu, K, k, Vx, Vxx);
     return pd;
 }
 
@@ -619,12 +645,128 @@ __global__ void __launch_bounds__(64) backward_lane_kernel(KArgs<T> a) {
 }
 
 // ---------------------------------------------------------------------------
+// Control limits: the box-constrained gains of control-limited DDP (Tassa, Mansard & Todorov, ICRA 2014).
+// k = argmin 1/2 du' Qr du + Q_u' du  subject to  lo <= du <= hi  (lo = u_min - u_t, hi = u_max - u_t);
+// a coordinate is clamped when k_i sits at a bound and the QP gradient there points out of the box; clamped
+// rows of K are 0, the free rows -(Qr)_FF^-1 Q_ux,F.  K, k arrive as the unconstrained gains of gain_solve.
+// n_u = 1, and a Qr that is not positive definite: k clamped coordinate-wise, the clamped rows of K zeroed.
+// n_u = 2, Qr positive definite: an unconstrained minimiser outside the box puts the minimiser on the box's
+// boundary, and on each of the four edges it is the clamp of the one-dimensional minimiser: the least of those.
+// Returns whether k moved (then the full value update applies); a NaN k stays NaN and moves nothing.
+// ---------------------------------------------------------------------------
+template <typename T, int NX, int NU>
+ILQR_DEV bool box_gains(const T (*Qr)[NU], const T (*Qux)[NX], const T* Qu, const T* lo, const T* hi, bool pd,
+                        T (*K)[NX], T* k) {
+    bool out = false;
+#pragma unroll
+    for (int i = 0; i < NU; ++i) out = out || k[i] < lo[i] || k[i] > hi[i];
+    if (!out) return false;
+    if (NU == 1 || !pd) {
+#pragma unroll
+        for (int i = 0; i < NU; ++i) {
+            if (k[i] < lo[i] || k[i] > hi[i]) {
+                k[i] = clamp_keep_nan(k[i], lo[i], hi[i]);
+#pragma unroll
+                for (int j = 0; j < NX; ++j) K[i][j] = T(0);
+            }
+        }
+        return true;
+    }
+    if constexpr (NU == 2) {
+        const T q01 = T(0.5) * (Qr[0][1] + Qr[1][0]);
+        T best = T(0), d[2] = {T(0), T(0)};
+        bool have = false;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int i = e >> 1, j = 1 - i;
+            const T v = (e & 1) ? hi[i] : lo[i];
+            if (__builtin_isinf(v)) continue;   // an infinite bound has no edge
+            const T w = clamp_keep_nan(-(Qu[j] + q01 * v) / Qr[j][j], lo[j], hi[j]);
+            T c[2];
+            c[i] = v;
+            c[j] = w;
+            const T J = T(0.5) * (Qr[0][0] * c[0] * c[0] + T(2) * q01 * c[0] * c[1] + Qr[1][1] * c[1] * c[1]) +
+                        Qu[0] * c[0] + Qu[1] * c[1];
+            if (!have || J < best) { best = J; d[0] = c[0]; d[1] = c[1]; have = true; }
+        }
+        const T g0 = Qr[0][0] * d[0] + q01 * d[1] + Qu[0], g1 = q01 * d[0] + Qr[1][1] * d[1] + Qu[1];
+        const bool c0 = (d[0] == lo[0] && g0 > T(0)) || (d[0] == hi[0] && g0 < T(0));
+        const bool c1 = (d[1] == lo[1] && g1 > T(0)) || (d[1] == hi[1] && g1 < T(0));
+        k[0] = d[0];
+        k[1] = d[1];
+        if (c0 || c1) {
+#pragma unroll
+            for (int j = 0; j < NX; ++j) {
+                K[0][j] = c0 ? T(0) : -(Qux[0][j] / Qr[0][0]);
+                K[1][j] = c1 ? T(0) : -(Qux[1][j] / Qr[1][1]);
+            }
+        }
+    }
+    return true;
+}
+
+// backward sweep with control limits ("box sweep"): backward_lane_kernel's lane per trajectory over the generic
+// expansion, with the box QP above at every step; u_t is read from the trajectory (slot 0 after a canonicalising
+// linearize).  Every solve with limits set uses it (SolverT::box_on).
+template <typename T, int NX, int NU>
+__global__ void __launch_bounds__(64) backward_box_kernel(KArgs<T> a) {
+    constexpr int E = 2 * NX * NX + 2 * NX * NU + NX + NU + NU * NU;
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= a.B) return;
+    const int st = a.status[b];
+    if (!traj_active(st)) return;
+    const int slot = a.reset_slots ? 0 : a.cur_slot[b];
+    if (a.reset_slots) a.cur_slot[b] = 0;   // linearize moved this trajectory into slot 0 (see linearize_kernel)
+    const size_t B = a.B;
+    T Vx[NX], Vxx[NX][NX];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) Vx[i] = a.term[(size_t)i * B + b];
+#pragma unroll
+    for (int i = 0; i < NX; ++i)
+#pragma unroll
+        for (int j = 0; j < NX; ++j) Vxx[i][j] = a.term[(size_t)(NX + i * NX + j) * B + b];
+    bool all_pd = true;
+    for (int t = a.N - 1; t >= 0; --t) {
+        T tile[E], u[NU];
+        const T* src = a.lin + ((size_t)t * E) * B + b;
+#pragma unroll
+        for (int e = 0; e < E; ++e) tile[e] = src[(size_t)e * B];
+        vec_load<T, NU>(a.U + vec_at(B, a.N, NU, slot, t, b), u);
+        T Qx[NX], Qu[NU], Qxx[NX][NX], Qux[NU][NX], Quu[NU][NU], Qr[NU][NU];
+        riccati_q<T, NX, NU>(tile, Vx, Vxx, Qx, Qu, Qxx, Qux, Quu);
+#pragma unroll
+        for (int i = 0; i < NU; ++i)
+#pragma unroll
+            for (int j = 0; j < NU; ++j) Qr[i][j] = Quu[i][j] + ((i == j) ? a.mu : T(0));
+        T K[NU][NX], k[NU], lo[NU], hi[NU];
+        const bool pd = gain_solve<T, NX, NU>(Qr, Qux, Qu, K, k);
+        all_pd = all_pd && pd;
+#pragma unroll
+        for (int i = 0; i < NU; ++i) {
+            lo[i] = a.u_lo[i] - u[i];
+            hi[i] = a.u_hi[i] - u[i];
+        }
+        const bool moved = box_gains<T, NX, NU>(Qr, Qux, Qu, lo, hi, pd, K, k);
+        riccati_value<T, NX, NU>(moved || a.mu != T(0), Qx, Qu, Qxx, Qux, Quu, K, k, Vx, Vxx);
+        constexpr int R = gain_record(NX, NU);
+        T* rec = a.gains + ((size_t)t * B + b) * R;
+#pragma unroll
+        for (int i = 0; i < NU; ++i)
+#pragma unroll
+            for (int j = 0; j < NX; ++j) rec[i * NX + j] = K[i][j];
+#pragma unroll
+        for (int i = 0; i < NU; ++i) rec[NU * NX + i] = k[i];
+    }
+    if (!all_pd) a.status[b] = st | ILQR_TRAJ_FLAG_NON_PD;
+}
+
+// ---------------------------------------------------------------------------
 // forward rollout: one lane per (trajectory, alpha) candidate; blockIdx.y = alpha
 // index.  Replaces iLQR._forward_pass_scan (iLQR_class.py:193-247), all trial
 // alphas of the backtracking loop (:279-302) at once.
 // ---------------------------------------------------------------------------
-template <typename T, typename Dyn, int INTEG>
-__global__ void __launch_bounds__(64) forward_kernel(KArgs<T> a) {
+template <typename T, typename Dyn, int INTEG, bool BOX>
+ILQR_DEV void forward_body(const KArgs<T>& a) {
     constexpr int NX = Dyn::NX, NU = Dyn::NU;
     constexpr int R = gain_record(NX, NU);
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -682,6 +824,7 @@ __global__ void __launch_bounds__(64) forward_kernel(KArgs<T> a) {
             for (int i = 0; i < NX; ++i) fb += g[j * NX + i] * dx[i];
             // u = u_old + alpha * k + K (x - x_old)   (iLQR_class.py:181-182)
             u[j] = uo[j] + alpha * g[NU * NX + j] + fb;
+            if constexpr (BOX) u[j] = clamp_keep_nan(u[j], a.u_lo[j], a.u_hi[j]);
         }
         vec_store<T, NX>(Xc + t * sX, x);
         vec_store<T, NU>(Uc + t * sU, u);
@@ -709,6 +852,11 @@ __global__ void __launch_bounds__(64) forward_kernel(KArgs<T> a) {
     a.costs[(size_t)ai * B + b] = cost;
     cp.stop(a.probe, 1);
 }
+template <typename T, typename Dyn, int INTEG>
+__global__ void __launch_bounds__(64) forward_kernel(KArgs<T> a) { forward_body<T, Dyn, INTEG, false>(a); }
+// with control limits: every control clamped to [u_lo, u_hi] before it is stored, costed and integrated
+template <typename T, typename Dyn, int INTEG>
+__global__ void __launch_bounds__(64) forward_kernel_box(KArgs<T> a) { forward_body<T, Dyn, INTEG, true>(a); }
 
 // ---------------------------------------------------------------------------
 // forward rollout, ring form (small systems, tensors < 2 GiB): identical arithmetic to forward_kernel, but
@@ -723,7 +871,7 @@ __global__ void __launch_bounds__(64) forward_kernel(KArgs<T> a) {
 // The rollout of candidate ai of trajectory b by this lane; in_range = the lane has a candidate at all.  The lanes of a
 // wave may hold any mix of (b, ai) -- forward_ring_kernel gives a wave 64 neighbouring trajectories of one alpha, the
 // persistent kernel (persistent.hpp) all candidates of a workgroup's trajectories -- as long as the whole wave calls it.
-template <typename T, typename Dyn, int INTEG>
+template <typename T, typename Dyn, int INTEG, bool BOX = false>
 ILQR_DEV void rollout_ring(const KArgs<T>& a, int b, int ai, bool in_range, bool force_init = false) {
     constexpr int NX = Dyn::NX, NU = Dyn::NU;
     using In = FwdIn<T, NX, NU>;
@@ -757,6 +905,12 @@ ILQR_DEV void rollout_ring(const KArgs<T>& a, int b, int ai, bool in_range, bool
     // (a local copy: when the argument block is memory -- the persistent kernel's roles -- a read of a.dt inside the step
     // loop is a load hipcc waits for with vmcnt(0), which drains the register ring every step)
     const T dt = a.dt;
+    T lo[NU], hi[NU];   // (BOX: the limits in registers, for the same reason)
+#pragma unroll
+    for (int j = 0; j < NU; ++j) {
+        lo[j] = BOX ? a.u_lo[j] : T(0);
+        hi[j] = BOX ? a.u_hi[j] : T(0);
+    }
     // The parameter block is copied into registers once: the asm statements below carry "memory" clobbers
     // (they pin the order of loads and stores the vmcnt arithmetic relies on), and a clobber would otherwise
     // make hipcc reload every parameter from memory after each of them.
@@ -822,6 +976,10 @@ ILQR_DEV void rollout_ring(const KArgs<T>& a, int b, int ai, bool in_range, bool
             u[j] = uo[j] + alpha * in.gain(NU * NX + j) + fb;   // iLQR_class.py:181-182
         }
         }
+        if constexpr (BOX) {
+#pragma unroll
+            for (int j = 0; j < NU; ++j) u[j] = clamp_keep_nan(u[j], lo[j], hi[j]);
+        }
         // exactly NST stores per step for every wave that is still running (they are counted)
         if (DROP || live) {
             buf_store_vec<T, NX>(rXc, vXc, uniform(t * stepX), x);
@@ -875,6 +1033,14 @@ __global__ void __launch_bounds__(64) forward_ring_kernel(KArgs<T> a) {
     const int ai = blockIdx.y;
     if (a.init_mode && blockIdx.x == 0 && ai == 0 && threadIdx.x == 0) a.counters[a.counter_idx] = 0;   // the select that follows counts into it
     rollout_ring<T, Dyn, INTEG>(a, b, ai, b < a.B);
+}
+// with control limits (the clamp of forward_kernel_box); the ring guards see it by its name
+template <typename T, typename Dyn, int INTEG>
+__global__ void __launch_bounds__(64) forward_ring_kernel_box(KArgs<T> a) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    const int ai = blockIdx.y;
+    if (a.init_mode && blockIdx.x == 0 && ai == 0 && threadIdx.x == 0) a.counters[a.counter_idx] = 0;
+    rollout_ring<T, Dyn, INTEG, true>(a, b, ai, b < a.B);
 }
 
 // ---------------------------------------------------------------------------

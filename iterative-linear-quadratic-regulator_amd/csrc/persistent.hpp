@@ -34,9 +34,9 @@ ILQR_DEV void drain_stores() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); 
 // every role's loop-invariant scalars live across all the others and spilled 150-220 VGPRs in the middle of the rollout's
 // self-counted register ring -- which csrc/check_ring_kernels.py rejects, rightly: a spill there copies registers whose
 // loads have not landed.  The kernel's argument block reaches a role through a pointer to the caller's copy.
-template <typename T, typename Dyn, int INTEG>
+template <typename T, typename Dyn, int INTEG, bool BOX = false>
 __device__ __attribute__((noinline)) void role_rollout(const KArgs<T>* a, int b, int ai, bool in_range, int init) {
-    rollout_ring<T, Dyn, INTEG>(*a, b, ai, in_range, init != 0);
+    rollout_ring<T, Dyn, INTEG, BOX>(*a, b, ai, in_range, init != 0);
 }
 // (The LDS pointers are carved from the workgroup's dynamic allocation INSIDE each role: handed over as function
 // arguments they would be generic pointers, and every tile read of the sweep a flat_load instead of a ds_read.)
@@ -59,9 +59,10 @@ __device__ __attribute__((noinline)) void role_produce(const KArgs<T>* a, int b0
 // PK: the 16-trajectory form runs the pair producers (4 sweep + 4 producer waves = 512 threads: 256 VGPRs per lane, which
 // the rollout's register ring (165) and the pair producers (234) both fit; eight scalar producers would cap the kernel
 // at 168 and make the ring rollout spill -- the build rejects that, csrc/check_ring_kernels.py)
-template <typename T, typename Dyn, int INTEG, int TPW, bool PK>
+// BOX: with control limits (the BOX sweep of FusedWG and the clamped rollout_ring)
+template <typename T, typename Dyn, int INTEG, int TPW, bool PK, bool BOX = false>
 __global__ void __launch_bounds__((fused_threads<T, TPW, PK>())) ilqr_persistent_kernel(KArgs<T> a, PArgs<T> pa) {
-    using W = FusedWG<T, Dyn, INTEG, TPW, PK>;
+    using W = FusedWG<T, Dyn, INTEG, TPW, PK, BOX>;
     constexpr int NX = Dyn::NX, NU = Dyn::NU;
     constexpr int NT = fused_threads<T, TPW, PK>();
     extern __shared__ __attribute__((aligned(16))) unsigned char fused_lds[];
@@ -83,7 +84,7 @@ __global__ void __launch_bounds__((fused_threads<T, TPW, PK>())) ilqr_persistent
         if (pa.do_init) {
             // ---- head of a solve (iLQR_class.py:257-259): every trajectory, alpha = 0, through the carried K and X --------
             if (wave == 0) {
-                role_rollout<T, Dyn, INTEG>(ka, b0 + lane, 0, lane < TPW && b0 + lane < a.B, 1);
+                role_rollout<T, Dyn, INTEG, BOX>(ka, b0 + lane, 0, lane < TPW && b0 + lane < a.B, 1);
                 drain_stores();
                 const int b = b0 + lane;
                 if (lane < TPW && b < a.B) {        // (the lane that rolled the candidate out accepts it: no barrier needed)
@@ -118,7 +119,7 @@ __global__ void __launch_bounds__((fused_threads<T, TPW, PK>())) ilqr_persistent
                 const int lg = wave * 64 + lane;
                 const int tl = lg % TPW, ai = lg / TPW;
                 if (wave * 64 < TPW * a.n_pass)    // (wave-uniform: waves beyond the last candidate skip the role)
-                    role_rollout<T, Dyn, INTEG>(ka, b0 + tl, ai, ai < a.n_pass && b0 + tl < a.B, 0);
+                    role_rollout<T, Dyn, INTEG, BOX>(ka, b0 + tl, ai, ai < a.n_pass && b0 + tl < a.B, 0);
             }
             drain_stores();
             __syncthreads();

@@ -56,6 +56,7 @@ struct SolverBase {
     virtual int timing_reset() = 0;
     virtual int timing_get(double* ms, int64_t* launches) = 0;
     virtual int algorithmic_bytes(double* bytes) = 0;
+    virtual int set_control_limits(const double* u_min, const double* u_max) = 0;
 };
 
 int system_dims(int system, int n_x, int n_u);  // 1 if (system, n_x, n_u) is a known combination
@@ -113,6 +114,12 @@ template <typename T> struct Ops {
     bool canonical = false;  // linearize moves every current trajectory into slot 0 (then cur_slot is reset)
     bool const_lin = false;  // the system's expansion has constant matrices (Linear dynamics + parameter-block cost): KArgs::const_lin
     bool (*sweep_reads_sparse)(T mu) = nullptr;   // does the backward dispatch take the constant-matrix form for this mu?
+    // control limits (ilqr_set_control_limits): the generic-layout linearisation, the box sweep and the clamped rollouts
+    // (kernels.hpp); null where limits are not supported
+    void (*linearize_box[5])(const KArgs<T>&, hipStream_t) = {};
+    void (*backward_box)(const KArgs<T>&, hipStream_t) = nullptr;
+    void (*forward_box[5])(const KArgs<T>&, hipStream_t) = {};
+    bool fused_box = false;   // fused[] / persist[] also launch their BOX instantiations (KArgs::box)
 };
 
 // linearize / forward are compiled once per integrator so the integrator switch folds away and each
@@ -147,8 +154,88 @@ inline int persist_small_max() {
 template <typename Dyn, typename = void> struct has_rebind { static constexpr bool value = false; };
 template <typename Dyn> struct has_rebind<Dyn, std::void_t<typename Dyn::template rebind<float>>> { static constexpr bool value = true; };
 
+// the fused kernel's launch (BX: its control-limited instantiation, FusedWG BOX)
+template <typename T, typename Dyn, int I, bool BX>
+void launch_fused_kernel(const KArgs<T>& a, hipStream_t s) {
+    // one workgroup = 16 trajectories (4 sweep waves + the producer waves, tiles through ~104 KB of LDS: one per
+    // CU), or 4 trajectories (1 sweep wave, ~52 KB) while the batch then still fits the chip one workgroup per CU
+    // (measured, fp32 fused kernel: B = 1024 35 vs 41 us, B = 2048 41 vs 41, B = 4096 73 vs 47)
+    // fp32 with an explicit integrator and a system that can be instantiated on a float pair: pair producers
+    constexpr bool CAN_PK = sizeof(T) == 4 && I != ILQR_INT_BACKWARD_EULER && has_rebind<Dyn>::value && !ILQR_NO_PAIR_PRODUCERS;
+    static const bool ok = [] {
+        bool r = hipFuncSetAttribute((const void*)backward_fused16_kernel<T, Dyn, I, 16, false, BX>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, fused_lds_bytes<T, 16, false, Dyn::NU>()) == hipSuccess;
+        r = r && hipFuncSetAttribute((const void*)backward_fused16_kernel<T, Dyn, I, 4, false, BX>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, fused_lds_bytes<T, 4, false, Dyn::NU>()) == hipSuccess;
+        if constexpr (CAN_PK)
+            r = r && hipFuncSetAttribute((const void*)backward_fused16_kernel<T, Dyn, I, 16, true, BX>,
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, fused_lds_bytes<T, 16, true, Dyn::NU>()) == hipSuccess;
+        (void)hipGetLastError();
+        return r;
+    }();
+    (void)ok;
+    static const int force = getenv("ILQR_FUSED_TPW") ? atoi(getenv("ILQR_FUSED_TPW")) : 0;   // A/B switch
+    static const int small_max = getenv("ILQR_FUSED_SMALL_MAX") ? atoi(getenv("ILQR_FUSED_SMALL_MAX")) : 1024;
+    // Pair producers (two time steps per lane in packed FP32, bit-identical) are built and tested but OFF by default
+    // in this kernel: with a ring of 4 units they measured the same as the scalar ones (48.6 vs 48.1 us at B = 4096:
+    // the kernel is bound by the sweep waves' chain, and four lone pair waves deliver their first unit later and let
+    // the ring run dry); with 5 slots (133 KB of LDS, the build's value now) 44.7-45.8 against 46.4 us -- one
+    // microsecond, for a third fewer vector instructions in the same time (bench.py's issue-rate fraction would fall
+    // from 0.70 to ~0.6 with nothing else changing).  ILQR_FUSED_PAIRS=1 selects them; the 16-trajectory persistent
+    // kernel always uses them (register budget).
+    static const bool no_pk = getenv("ILQR_FUSED_PAIRS") == nullptr;                          // A/B switch
+    const bool small = force ? force == 4 : a.B <= small_max;
+    if (small) {
+        ILQR_LAUNCH((backward_fused16_kernel<T, Dyn, I, 4, false, BX>), dim3((a.B + 3) / 4), dim3(fused_threads<T, 4, false>()),
+                    (fused_lds_bytes<T, 4, false, Dyn::NU>()), s, a);
+        return;
+    }
+    if constexpr (CAN_PK) {
+        if (!no_pk) {
+            ILQR_LAUNCH((backward_fused16_kernel<T, Dyn, I, 16, true, BX>), dim3((a.B + 15) / 16), dim3(fused_threads<T, 16, true>()),
+                        (fused_lds_bytes<T, 16, true, Dyn::NU>()), s, a);
+            return;
+        }
+    }
+    ILQR_LAUNCH((backward_fused16_kernel<T, Dyn, I, 16, false, BX>), dim3((a.B + 15) / 16), dim3(fused_threads<T, 16, false>()),
+                (fused_lds_bytes<T, 16, false, Dyn::NU>()), s, a);
+}
+
+// the persistent kernel's launch (BX: its control-limited instantiation)
+template <typename T, typename Dyn, int I, bool BX>
+void launch_persist_kernel(const KArgs<T>& a, const PArgs<T>& pa, hipStream_t s) {
+    constexpr bool BIG = I != ILQR_INT_BACKWARD_EULER && has_rebind<Dyn>::value && !ILQR_NO_PAIR_PRODUCERS;
+    static const bool ok = [] {
+        bool r = hipFuncSetAttribute((const void*)ilqr_persistent_kernel<T, Dyn, I, 4, false, BX>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, fused_lds_bytes<T, 4, false, Dyn::NU>()) == hipSuccess;
+        if constexpr (BIG)
+            r = r && hipFuncSetAttribute((const void*)ilqr_persistent_kernel<T, Dyn, I, 16, true, BX>,
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, fused_lds_bytes<T, 16, true, Dyn::NU>()) == hipSuccess;
+        (void)hipGetLastError();
+        return r;
+    }();
+    (void)ok;
+    if constexpr (BIG) {
+        if (a.B > persist_small_max()) {
+            ILQR_LAUNCH((ilqr_persistent_kernel<T, Dyn, I, 16, true, BX>), dim3((a.B + 15) / 16), dim3(fused_threads<T, 16, true>()),
+                        (fused_lds_bytes<T, 16, true, Dyn::NU>()), s, a, pa);
+            return;
+        }
+    }
+    ILQR_LAUNCH((ilqr_persistent_kernel<T, Dyn, I, 4, false, BX>), dim3((a.B + 3) / 4), dim3(fused_threads<T, 4, false>()),
+                (fused_lds_bytes<T, 4, false, Dyn::NU>()), s, a, pa);
+}
+
+// the systems that take control limits (ilqr_set_control_limits)
+template <typename Dyn> constexpr bool box_system() {
+    return Dyn::ID == ILQR_SYS_PENDULUM || Dyn::ID == ILQR_SYS_UA_DOUBLE_PENDULUM || Dyn::ID == ILQR_SYS_DOUBLE_PENDULUM;
+}
+
 template <typename T, typename Dyn, bool TILE, int INTEG> void set_integrator_ops(Ops<T>& o) {
     constexpr bool SMALL = all_integrators<Dyn>::value;
+    // control limits on the fused and persistent kernels: n_u = 1 (u_t rides the tile's padding, FusedWG)
+    constexpr bool FUSED_BOX = box_system<Dyn>() && Dyn::NU == 1;
+    if constexpr (TILE && FUSED_BOX) o.fused_box = true;
     // n_x > 4 only has the closed-form integrators: fold the others onto euler so nothing big is compiled
     constexpr int I = (SMALL || INTEG == ILQR_INT_DISCRETE) ? INTEG : ILQR_INT_EULER;
     o.linearize[INTEG] = [](const KArgs<T>& a, hipStream_t s) {
@@ -158,48 +245,11 @@ template <typename T, typename Dyn, bool TILE, int INTEG> void set_integrator_op
     };
     if constexpr (TILE && ((ILQR_FUSE_INTEG_MASK >> I) & 1)) {
         o.fused[INTEG] = [](const KArgs<T>& a, hipStream_t s) {
-            // one workgroup = 16 trajectories (4 sweep waves + the producer waves, tiles through ~104 KB of LDS: one per
-            // CU), or 4 trajectories (1 sweep wave, ~52 KB) while the batch then still fits the chip one workgroup per CU
-            // (measured, fp32 fused kernel: B = 1024 35 vs 41 us, B = 2048 41 vs 41, B = 4096 73 vs 47)
-            // fp32 with an explicit integrator and a system that can be instantiated on a float pair: pair producers
-            constexpr bool CAN_PK = sizeof(T) == 4 && I != ILQR_INT_BACKWARD_EULER && has_rebind<Dyn>::value && !ILQR_NO_PAIR_PRODUCERS;
-            static const bool ok = [] {
-                bool r = hipFuncSetAttribute((const void*)backward_fused16_kernel<T, Dyn, I, 16, false>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, fused_lds_bytes<T, 16, false, Dyn::NU>()) == hipSuccess;
-                r = r && hipFuncSetAttribute((const void*)backward_fused16_kernel<T, Dyn, I, 4, false>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, fused_lds_bytes<T, 4, false, Dyn::NU>()) == hipSuccess;
-                if constexpr (CAN_PK)
-                    r = r && hipFuncSetAttribute((const void*)backward_fused16_kernel<T, Dyn, I, 16, true>,
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, fused_lds_bytes<T, 16, true, Dyn::NU>()) == hipSuccess;
-                (void)hipGetLastError();
-                return r;
-            }();
-            (void)ok;
-            static const int force = getenv("ILQR_FUSED_TPW") ? atoi(getenv("ILQR_FUSED_TPW")) : 0;   // A/B switch
-            static const int small_max = getenv("ILQR_FUSED_SMALL_MAX") ? atoi(getenv("ILQR_FUSED_SMALL_MAX")) : 1024;
-            // Pair producers (two time steps per lane in packed FP32, bit-identical) are built and tested but OFF by default
-            // in this kernel: with a ring of 4 units they measured the same as the scalar ones (48.6 vs 48.1 us at B = 4096:
-            // the kernel is bound by the sweep waves' chain, and four lone pair waves deliver their first unit later and let
-            // the ring run dry); with 5 slots (133 KB of LDS, the build's value now) 44.7-45.8 against 46.4 us -- one
-            // microsecond, for a third fewer vector instructions in the same time (bench.py's issue-rate fraction would fall
-            // from 0.70 to ~0.6 with nothing else changing).  ILQR_FUSED_PAIRS=1 selects them; the 16-trajectory persistent
-            // kernel always uses them (register budget).
-            static const bool no_pk = getenv("ILQR_FUSED_PAIRS") == nullptr;                          // A/B switch
-            const bool small = force ? force == 4 : a.B <= small_max;
-            if (small) {
-                ILQR_LAUNCH((backward_fused16_kernel<T, Dyn, I, 4, false>), dim3((a.B + 3) / 4), dim3(fused_threads<T, 4, false>()),
-                            (fused_lds_bytes<T, 4, false, Dyn::NU>()), s, a);
-                return;
+            // with limits set (KArgs::box): the control-limited instantiation, n_u = 1 built-in systems only (FusedWG, BOX)
+            if constexpr (FUSED_BOX) {
+                if (a.box) { launch_fused_kernel<T, Dyn, I, true>(a, s); return; }
             }
-            if constexpr (CAN_PK) {
-                if (!no_pk) {
-                    ILQR_LAUNCH((backward_fused16_kernel<T, Dyn, I, 16, true>), dim3((a.B + 15) / 16), dim3(fused_threads<T, 16, true>()),
-                                (fused_lds_bytes<T, 16, true, Dyn::NU>()), s, a);
-                    return;
-                }
-            }
-            ILQR_LAUNCH((backward_fused16_kernel<T, Dyn, I, 16, false>), dim3((a.B + 15) / 16), dim3(fused_threads<T, 16, false>()),
-                        (fused_lds_bytes<T, 16, false, Dyn::NU>()), s, a);
+            launch_fused_kernel<T, Dyn, I, false>(a, s);
         };
     }
     // The persistent kernel (persistent.hpp): fp32 only (tried for fp64 in the 4-trajectory form: as a noinline role the fp64
@@ -211,25 +261,10 @@ template <typename T, typename Dyn, bool TILE, int INTEG> void set_integrator_op
         constexpr bool BIG = I != ILQR_INT_BACKWARD_EULER && has_rebind<Dyn>::value && !ILQR_NO_PAIR_PRODUCERS;
         o.persist_big = o.persist_big || BIG;
         o.persist[INTEG] = [](const KArgs<T>& a, const PArgs<T>& pa, hipStream_t s) {
-            static const bool ok = [] {
-                bool r = hipFuncSetAttribute((const void*)ilqr_persistent_kernel<T, Dyn, I, 4, false>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, fused_lds_bytes<T, 4, false, Dyn::NU>()) == hipSuccess;
-                if constexpr (BIG)
-                    r = r && hipFuncSetAttribute((const void*)ilqr_persistent_kernel<T, Dyn, I, 16, true>,
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, fused_lds_bytes<T, 16, true, Dyn::NU>()) == hipSuccess;
-                (void)hipGetLastError();
-                return r;
-            }();
-            (void)ok;
-            if constexpr (BIG) {
-                if (a.B > persist_small_max()) {
-                    ILQR_LAUNCH((ilqr_persistent_kernel<T, Dyn, I, 16, true>), dim3((a.B + 15) / 16), dim3(fused_threads<T, 16, true>()),
-                                (fused_lds_bytes<T, 16, true, Dyn::NU>()), s, a, pa);
-                    return;
-                }
+            if constexpr (FUSED_BOX) {
+                if (a.box) { launch_persist_kernel<T, Dyn, I, true>(a, pa, s); return; }
             }
-            ILQR_LAUNCH((ilqr_persistent_kernel<T, Dyn, I, 4, false>), dim3((a.B + 3) / 4), dim3(fused_threads<T, 4, false>()),
-                        (fused_lds_bytes<T, 4, false, Dyn::NU>()), s, a, pa);
+            launch_persist_kernel<T, Dyn, I, false>(a, pa, s);
         };
         o.persist_any_batch[INTEG] = BIG;
     }
@@ -249,6 +284,26 @@ template <typename T, typename Dyn, bool TILE, int INTEG> void set_integrator_op
         }
         ILQR_LAUNCH((forward_kernel<T, Dyn, I>), grid, block, 0, s, a);
     };
+    if constexpr (box_system<Dyn>()) {
+        // control limits: linearise into the generic [N][E][B] expansion the box sweep reads, clamped rollouts
+        o.linearize_box[INTEG] = [](const KArgs<T>& a, hipStream_t s) {
+            const size_t total = (size_t)a.B * (a.N + 1);
+            ILQR_LAUNCH((linearize_kernel<T, Dyn, false, I>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a);
+        };
+        o.forward_box[INTEG] = [](const KArgs<T>& a, hipStream_t s) {
+            const dim3 grid((a.B + 63) / 64, a.n_pass), block(64);
+            if constexpr (has_fwd_in<T, Dyn::NX, Dyn::NU>::value && ((ILQR_RING_INTEG_MASK >> I) & 1)) {
+                static const bool plain = getenv("ILQR_FORWARD_PLAIN") != nullptr;
+                const size_t bytes_x = (size_t)a.n_slots * (a.N + 1) * Dyn::NX * a.B * sizeof(T);
+                const size_t bytes_g = (size_t)a.N * a.B * gain_record(Dyn::NX, Dyn::NU) * sizeof(T);
+                if (std::max(bytes_x, bytes_g) <= kDescriptorMax && !plain) {
+                    ILQR_LAUNCH((forward_ring_kernel_box<T, Dyn, I>), grid, block, 0, s, a);
+                    return;
+                }
+            }
+            ILQR_LAUNCH((forward_kernel_box<T, Dyn, I>), grid, block, 0, s, a);
+        };
+    }
 }
 
 template <typename T, typename Dyn> Ops<T> make_ops() {
@@ -313,6 +368,11 @@ template <typename T, typename Dyn> Ops<T> make_ops() {
     } else {
         o.backward = [](const KArgs<T>& a, hipStream_t s) {
             ILQR_LAUNCH((backward_lane_kernel<T, NX, NU>), dim3((a.B + 63) / 64), dim3(64), 0, s, a);
+        };
+    }
+    if constexpr (box_system<Dyn>()) {
+        o.backward_box = [](const KArgs<T>& a, hipStream_t s) {
+            ILQR_LAUNCH((backward_box_kernel<T, NX, NU>), dim3((a.B + 63) / 64), dim3(64), 0, s, a);
         };
     }
     o.eval = [](const EvalArgs<T>& a, hipStream_t s) {
@@ -510,6 +570,8 @@ template <typename T> struct DeviceState {
     bool slots_stale = false;   // linearize has moved the active trajectories to slot 0, cur_slot not yet reset
     bool lin_const = false;     // `lin` holds the library's own linearisation of a system whose matrices are constant (KArgs::const_lin)
     bool lin_full = true;       // every record of `lin` holds its matrices (false after a sparse linearise: see KArgs::lin_sparse)
+    T *box_lin = nullptr, *box_term = nullptr;   // generic expansion [N][E][B] and terminal [n + n^2][B] of the box sweep
+    bool box_lin_valid = false;                   // the last linearize wrote box_lin (not lin)
 };
 
 template <typename T> class SolverT : public SolverBase {
@@ -535,6 +597,9 @@ template <typename T> class SolverT : public SolverBase {
     PhaseTimer timer;
     bool have_problem = false, have_rollout = false, mpc_ready = false;
     int iter_seq = 0;
+    // control limits (ilqr_set_control_limits): u_min <= u <= u_max for every control of every trajectory
+    bool box_on = false;
+    double box_lo[kBoxMaxU] = {0}, box_hi[kBoxMaxU] = {0};
 
     ~SolverT() override {
         if (stream) hipStreamSynchronize(stream);
@@ -558,6 +623,8 @@ template <typename T> class SolverT : public SolverBase {
         hipFree(s.X); hipFree(s.U); hipFree(s.gains); hipFree(s.lin); hipFree(s.term); hipFree(s.x0);
         hipFree(s.costs); hipFree(s.cost); hipFree(s.cost_prev); hipFree(s.alpha_taken);
         hipFree(s.cur_slot); hipFree(s.status); hipFree(s.iters); hipFree(s.accepted); hipFree(s.counters);
+        if (s.box_lin != s.lin) hipFree(s.box_lin);
+        if (s.box_term != s.term) hipFree(s.box_term);
         s = DeviceState<T>();
     }
 
@@ -650,6 +717,11 @@ template <typename T> class SolverT : public SolverBase {
         a.status = s.status; a.iters = s.iters; a.accepted = s.accepted; a.counters = s.counters; a.params = params;
         a.reset_slots = 0;
         a.probe = probe_on ? probe : nullptr;
+        for (int i = 0; i < kBoxMaxU; ++i) {
+            a.u_lo[i] = (T)box_lo[i];
+            a.u_hi[i] = (T)box_hi[i];
+        }
+        a.box = box_on ? 1 : 0;
         return a;
     }
 
@@ -854,6 +926,12 @@ template <typename T> class SolverT : public SolverBase {
             case ILQR_X0: return down_tc(dst, st.x0, NX, 1);
             case ILQR_PLANT_X: return down_tc(dst, plant_x, NX, 1);
             case ILQR_LIN:
+                if (box_on) {   // control limits: the box sweep's expansion, in the generic layout
+                    if (lin_stale || !st.box_lin_valid) {
+                        if (int rl = do_linearize(st, true)) return rl;
+                    }
+                    return down_tc(dst, st.box_lin, E, N);
+                }
                 if (!st.lin_full || lin_stale) {   // the hot path wrote gradients only, or nothing (fused): bring the records up to date first
                     if (int rl = do_linearize(st, true)) return rl;
                 }
@@ -871,6 +949,21 @@ template <typename T> class SolverT : public SolverBase {
     // ---- stages ---------------------------------------------------------------------
     // full = false: the sweep that follows may be the constant-matrix form, which reads the matrices at t = N-1 only
     int do_linearize(DeviceState<T>& s, bool full = false) {
+        if (box_on) {
+            // control limits: the generic expansion for the box sweep (ops.linearize_box)
+            if (int rb = ensure_box(s)) return rb;
+            KArgs<T> a = kargs(s);
+            a.lin = s.box_lin; a.term = s.box_term;
+            timer.begin(ILQR_PHASE_LINEARIZE, stream);
+            ops.linearize_box[cfg.integrator](a, stream);
+            timer.end(stream);
+            s.slots_stale = true;
+            s.lin_const = false;
+            s.box_lin_valid = true;
+            if (&s == &st) lin_stale = false;
+            return check_launch();
+        }
+        s.box_lin_valid = false;
         KArgs<T> a = kargs(s);
         const bool sparse = !full && ops.const_lin && ops.sweep_reads_sparse && ops.sweep_reads_sparse((T)cfg.mu);
         a.lin_sparse = sparse ? 1 : 0;
@@ -894,6 +987,15 @@ template <typename T> class SolverT : public SolverBase {
     int do_backward(DeviceState<T>& s) {
         KArgs<T> a = kargs(s);
         a.reset_slots = s.slots_stale ? 1 : 0;
+        if (box_on) {
+            if (!s.box_lin_valid) { err = "backward: control limits were set after the last linearize"; return ILQR_ERR_STATE; }
+            a.lin = s.box_lin; a.term = s.box_term;
+            timer.begin(ILQR_PHASE_BACKWARD, stream);
+            ops.backward_box(a, stream);
+            timer.end(stream);
+            s.slots_stale = false;
+            return check_launch();
+        }
         a.const_lin = s.lin_const ? 1 : 0;
         a.lin_sparse = (s.lin_const && !s.lin_full) ? 1 : 0;    // where the CONST sweep finds l_x, l_u (KArgs::lin_sparse)
         timer.begin(ILQR_PHASE_BACKWARD, stream);
@@ -912,7 +1014,8 @@ template <typename T> class SolverT : public SolverBase {
         a.counter_idx = 0;
         for (int i = 0; i < n; ++i) a.alphas[i] = (T)alphas[i];
         timer.begin(ILQR_PHASE_FORWARD, stream);
-        ops.forward[cfg.integrator](a, stream);
+        if (box_on) ops.forward_box[cfg.integrator](a, stream);
+        else ops.forward[cfg.integrator](a, stream);
         timer.end(stream);
         return check_launch();
     }
@@ -941,7 +1044,7 @@ template <typename T> class SolverT : public SolverBase {
 
     bool fused_ok() const {
         static const bool off = getenv("ILQR_NO_FUSE") != nullptr;   // A/B switch, and bench.py's materialised leg
-        return !off && !force_unfused && !(cfg.flags & ILQR_FLAG_NO_FUSE) && ops.fused[cfg.integrator] && cfg.mu == 0.0 && (int)trial_alphas.size() <= A &&
+        return !off && !force_unfused && (!box_on || ops.fused_box) && !(cfg.flags & ILQR_FLAG_NO_FUSE) && ops.fused[cfg.integrator] && cfg.mu == 0.0 && (int)trial_alphas.size() <= A &&
                (size_t)N * B * R * sizeof(T) <= kDescriptorMax;
     }
     bool force_unfused = false;
@@ -1200,6 +1303,43 @@ template <typename T> class SolverT : public SolverBase {
         return sync();
     }
 
+    // ---- control limits -----------------------------------------------------------------
+    // the box sweep's generic expansion reuses `lin` / `term` when they are large enough (the DPP tiles: 48 >= E = 22 / 46,
+    // 64 >= 58 scalars per (t, b); 20 >= n + n^2 terminal scalars), so limits cost no memory there
+    int ensure_box(DeviceState<T>& s) {
+        if (s.box_lin) return ILQR_OK;
+        if (ops.lin_stride >= E) s.box_lin = s.lin;
+        else ILQR_HIPCHK(hipMalloc((void**)&s.box_lin, (size_t)N * E * B * sizeof(T)));
+        if ((ops.tile16 ? 20 : NX + NX * NX) >= NX + NX * NX) s.box_term = s.term;
+        else ILQR_HIPCHK(hipMalloc((void**)&s.box_term, (size_t)(NX + NX * NX) * B * sizeof(T)));
+        return ILQR_OK;
+    }
+    int set_control_limits(const double* u_min, const double* u_max) override {
+        if (!u_min && !u_max) {
+            if (int rf = flush_select()) return rf;
+            if (box_on) lin_stale = true;     // the expansion in HBM is the box sweep's
+            box_on = false;
+            return ILQR_OK;
+        }
+        if (!u_min || !u_max) { err = "set_control_limits: give both u_min and u_max, or neither"; return ILQR_ERR_INVALID_ARG; }
+        if (!ops.backward_box || !ops.linearize_box[cfg.integrator] || !ops.forward_box[cfg.integrator] || NU > kBoxMaxU) {
+            err = "set_control_limits: control limits are supported for the pendulum, UA double pendulum and double pendulum only";
+            return ILQR_ERR_UNSUPPORTED;
+        }
+        for (int i = 0; i < NU; ++i) {
+            if (std::isnan(u_min[i]) || std::isnan(u_max[i]) || u_min[i] > u_max[i]) {
+                err = "set_control_limits: u_min and u_max must not be NaN and u_min <= u_max";
+                return ILQR_ERR_INVALID_ARG;
+            }
+        }
+        if (int rf = flush_select()) return rf;
+        if (int rb = ensure_box(st)) return rb;
+        for (int i = 0; i < NU; ++i) { box_lo[i] = u_min[i]; box_hi[i] = u_max[i]; }
+        if (!box_on) lin_stale = true;        // the expansion in HBM is the unconstrained sweep's
+        box_on = true;
+        return ILQR_OK;
+    }
+
     // ---- pure functional calls --------------------------------------------------------
     int ensure_fn() {
         if (fn.X) return ILQR_OK;
@@ -1231,6 +1371,7 @@ template <typename T> class SolverT : public SolverBase {
     // the Riccati sweep alone, on an expansion the caller computed (its own autodiff, identified model, ...)
     int backward_tensors(const void* lin, const void* term, void* Uff, void* K) override {
         if (!lin || !term) { err = "backward_tensors: NULL input"; return ILQR_ERR_INVALID_ARG; }
+        if (box_on) { err = "backward_tensors: the box QP needs the controls u_t, which an expansion does not carry (clear the limits)"; return ILQR_ERR_UNSUPPORTED; }
         int rc;
         if ((rc = ensure_fn()) || (rc = reset_fn())) return rc;
         if ((rc = up_lin(lin, fn.lin))) return rc;

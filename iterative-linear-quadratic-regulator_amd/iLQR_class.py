@@ -30,10 +30,36 @@ def horizon_steps(T, dt):
     return len(np.arange(0, T + dt, dt)) - 1
 
 
+def control_limits(system, u_min, u_max):
+    """Validated (u_min, u_max) as float64 [n_u] arrays (a scalar is broadcast), or None for no limits.  Raises
+    ValueError for a wrong shape, NaN, u_min > u_max, one bound without the other, or a system without limits."""
+    if u_min is None and u_max is None:
+        return None
+    if u_min is None or u_max is None:
+        raise ValueError("give both u_min and u_max (use +-inf for a side without a limit)")
+    if getattr(system, "SYSTEM_ID", None) not in _lib.BOX_SYSTEMS:
+        raise ValueError(f"control limits are supported for the pendulum, UA double pendulum and double pendulum "
+                         f"only, not for {type(system).__name__}")
+    n_u = system.n_u
+    out = []
+    for name, v in (("u_min", u_min), ("u_max", u_max)):
+        a = np.asarray(v, dtype=np.float64)
+        if a.ndim == 0:
+            a = np.full(n_u, float(a))
+        if a.shape != (n_u,):
+            raise ValueError(f"{name} must be a scalar or have shape ({n_u},), but got {a.shape}")
+        if np.isnan(a).any():
+            raise ValueError(f"{name} must not contain NaN")
+        out.append(np.ascontiguousarray(a))
+    if (out[0] > out[1]).any():
+        raise ValueError(f"u_min must be <= u_max, got {out[0]} > {out[1]}")
+    return out[0], out[1]
+
+
 class iLQR:
     def __init__(self, system: System, T=None, x_0=None, U_init=None, tol=1e-5, maxiter=100,
                  alpha_factor=0.5, min_alpha=1e-8, verbose=True, *, N=None, n_alpha=None, n_trials=10,
-                 dtype=None, device=0, mu=0.0, plant=None, flags=0, stream=None):
+                 dtype=None, device=0, mu=0.0, plant=None, flags=0, stream=None, u_min=None, u_max=None):
         self.system = system
         self.T = T
         self.tol, self.maxiter = tol, maxiter
@@ -69,6 +95,7 @@ class iLQR:
             raise ValueError("the MPC plant must be the same system with the same parameters "
                              "(only its integrator may differ, run_iLQR_MPC.py:58-75)")
         self.plant = plant
+        limits = control_limits(system, u_min, u_max)   # checked before any device is touched
         trial_count = 0
         a = 1.0
         for _ in range(n_trials):         # how many alphas the Python loop can reach (:281, :300-302)
@@ -83,9 +110,24 @@ class iLQR:
             maxiter=maxiter, alpha_factor=alpha_factor, min_alpha=min_alpha, mu=mu,
             plant_integrator=None if plant is None else plant.integrator, device=device, flags=flags,
             stream=stream)   # stream: a hipStream_t (e.g. torch.cuda.current_stream().cuda_stream); None = a private one
+        if limits is not None:
+            self._h.set_control_limits(*limits)
+        self.u_min, self.u_max = (None, None) if limits is None else limits
         self._h.set_problem(x_0.reshape(self.B, self.n_x), U_init.reshape(self.B, self.n_u, self.N))
         self.status = None
         self.iterations = None
+
+    def set_control_limits(self, u_min, u_max):
+        """Box constraints u_min <= u <= u_max on every control (control-limited DDP; include/ilqr_hip.h,
+        ilqr_set_control_limits): scalars or [n_u] arrays, +-inf allowed; (None, None) removes them.  Takes effect from
+        the next rollout / backward pass on, also between MPC steps."""
+        limits = control_limits(self.system, u_min, u_max)
+        if limits is None:
+            self._h.set_control_limits(None, None)
+            self.u_min = self.u_max = None
+        else:
+            self._h.set_control_limits(*limits)
+            self.u_min, self.u_max = limits
 
     # ---- state attributes (iLQR_class.py:55-61): reads are synchronised host copies ----
     def _out(self, a):

@@ -48,8 +48,9 @@ def open_loop_figure(path, tspan, X_bar, U_bar):
     return path
 
 
-def closed_loop_figure(path, tspan_sim, X_sim, U_sim, x_target):
-    """run_iLQR_MPC.py:150-186.  X_sim (n_x, N_sim+1), U_sim (n_u, N_sim), tspan_sim (N_sim+1)."""
+def closed_loop_figure(path, tspan_sim, X_sim, U_sim, x_target, u_bounds=None):
+    """run_iLQR_MPC.py:150-186.  X_sim (n_x, N_sim+1), U_sim (n_u, N_sim), tspan_sim (N_sim+1).
+    u_bounds: (u_min, u_max) control limits, drawn as dashed lines on the control panel."""
     X_sim, U_sim = np.asarray(X_sim), np.asarray(U_sim)
     n_x, n_u = X_sim.shape[0], U_sim.shape[0]
     plt, fig = _figure(n_x + 1)
@@ -66,6 +67,11 @@ def closed_loop_figure(path, tspan_sim, X_sim, U_sim, x_target):
     ax = plt.subplot(n_x + 1, 1, n_x + 1)
     for j in range(n_u):
         ax.plot(tspan_sim[:-1], U_sim[j, :], "k-", linewidth=2, label="Control Input")
+    if u_bounds is not None:
+        for k, v in enumerate(np.unique(np.concatenate([np.ravel(u_bounds[0]), np.ravel(u_bounds[1])]))):
+            if np.isfinite(v):
+                ax.axhline(v, color="m", linestyle="--", linewidth=1.5, label="Control limit" if k == 0 else None)
+        ax.legend()
     ax.set_title("Optimal Control Input")
     ax.set_xlabel("Time (s)")
     ax.set_ylabel("Control (torque)")
