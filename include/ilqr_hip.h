@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define ILQR_ABI_VERSION 4
+#define ILQR_ABI_VERSION 5
 
 typedef struct ilqr_solver_s* ilqr_handle;
 
@@ -266,6 +266,25 @@ int ilqr_mpc_run(ilqr_handle h, int n_steps, void* u_out, void* x_out, void* cos
  * Returns ILQR_ERR_UNSUPPORTED for ILQR_SYS_LINEAR, ILQR_SYS_CUSTOM and n_x > 4 (clearing with NULL, NULL is valid on
  * every handle), ILQR_ERR_INVALID_ARG for a NaN bound, u_min > u_max, or exactly one NULL pointer. */
 int ilqr_set_control_limits(ilqr_handle h, const double* u_min, const double* u_max);
+
+/* ---- per-trajectory parameters (build extension: the reference has one parameter set per solver object) -----
+ * Every trajectory of the batch may have its own system parameters and x_target (a heterogeneous fleet, domain
+ * randomisation, one goal per instance), and every MPC plant its own system parameters (model mismatch: the plant is
+ * stepped at its row, the controller plans with the model's).  Q, R, Q_f and dt stay shared by the batch.
+ *   which = ILQR_BATCH_MODEL: rows [B][n_sys + n_x] = system parameters (parameter-block order) then x_target;
+ *           ILQR_BATCH_PLANT: rows [B][n_sys] = the MPC plant's system parameters.
+ * n_sys = 3 for the pendulum, 9 for the double pendulums.  NULL clears (the model falls back to the parameter block;
+ * the plant to the model's rows, else the block).  Plant rows without model rows: a nominal shared model and a
+ * perturbed plant per instance.  May be called between any two calls (also between ilqr_mpc_run calls); it takes
+ * effect from the next kernel on.  Each row is derived on the host in double by the formulas of the parameter block,
+ * so a trajectory whose row equals the block computes exactly what it computes without rows.
+ * Honoured by ilqr_initial_rollout, ilqr_linearize, ilqr_forward, ilqr_iterate, ilqr_solve, ilqr_mpc_run,
+ * ilqr_backward_pass and ilqr_forward_pass.  ilqr_backward_tensors (the caller's expansion) and ilqr_eval_points
+ * (points, not trajectories) keep using the parameter block.
+ * Returns ILQR_ERR_UNSUPPORTED for ILQR_SYS_LINEAR and ILQR_SYS_CUSTOM (clearing with NULL is valid on every handle),
+ * ILQR_ERR_INVALID_ARG for a bad `which`, a row_len other than the above, or a non-finite value. */
+enum { ILQR_BATCH_MODEL = 0, ILQR_BATCH_PLANT = 1 };
+int ilqr_set_batch_params(ilqr_handle h, int which, const double* rows, int row_len);
 
 /* ---- multi-GPU hook -------------------------------------------
  * Writes 4 doubles to DEVICE memory `dev_out4` on the handle's stream:

@@ -31,7 +31,7 @@ FLAG_KEEP_ITERATING = 1
 FLAG_NO_FUSE = 2
 FLAG_NO_PERSIST = 4
 PHASES = ("linearize", "backward", "forward", "select", "other", "fused", "persist")
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 # every symbol include/ilqr_hip.h declares (tests check the library exports all of them)
 SYMBOLS = (
@@ -40,8 +40,10 @@ SYMBOLS = (
     "ilqr_initial_rollout", "ilqr_linearize", "ilqr_backward", "ilqr_forward", "ilqr_select", "ilqr_iterate",
     "ilqr_flush", "ilqr_solve", "ilqr_backward_pass", "ilqr_backward_tensors", "ilqr_forward_pass", "ilqr_eval_points", "ilqr_mpc_reset",
     "ilqr_mpc_rearm", "ilqr_mpc_run", "ilqr_status_reduce", "ilqr_timing_enable", "ilqr_timing_reset", "ilqr_timing_get", "ilqr_algorithmic_bytes",
-    "ilqr_set_control_limits",
+    "ilqr_set_control_limits", "ilqr_set_batch_params",
 )
+# ilqr_set_batch_params: which rows
+BATCH_MODEL, BATCH_PLANT = 0, 1
 # the built-in systems that take control limits (ilqr_set_control_limits)
 BOX_SYSTEMS = (SYS_PENDULUM, SYS_UA_DOUBLE_PENDULUM, SYS_DOUBLE_PENDULUM)
 
@@ -123,6 +125,7 @@ def load():
     lib.ilqr_timing_get.argtypes = [vp, C.POINTER(cd), C.POINTER(C.c_int64)]
     lib.ilqr_algorithmic_bytes.argtypes = [vp, C.POINTER(cd)]
     lib.ilqr_set_control_limits.argtypes = [vp, vp, vp]
+    lib.ilqr_set_batch_params.argtypes = [vp, ci, vp, ci]
     if lib.ilqr_abi_version() != ABI_VERSION:
         raise RuntimeError("libilqr_hip.so ABI version mismatch: rebuild the library")
     _lib = lib
@@ -350,6 +353,18 @@ class Handle:
         lo = np.ascontiguousarray(u_min, dtype=np.float64).reshape(self.n_u)
         hi = np.ascontiguousarray(u_max, dtype=np.float64).reshape(self.n_u)
         self._chk(self.lib.ilqr_set_control_limits(self.h, _ptr(lo), _ptr(hi)))
+
+    # ---- per-trajectory parameters ----------------------------------------------------------------
+    def set_batch_params(self, which, rows):
+        """which = BATCH_MODEL: rows (B, n_sys + n_x) system parameters then x_target; BATCH_PLANT: (B, n_sys) of the
+        MPC plant.  None clears them."""
+        if rows is None:
+            self._chk(self.lib.ilqr_set_batch_params(self.h, int(which), None, 0))
+            return
+        r = np.ascontiguousarray(rows, dtype=np.float64)
+        if r.ndim != 2 or r.shape[0] != self.B:
+            raise ValueError(f"batch parameter rows must have shape ({self.B}, row_len), but got {r.shape}")
+        self._chk(self.lib.ilqr_set_batch_params(self.h, int(which), _ptr(r), int(r.shape[1])))
 
     # ---- measurement ------------------------------------------------------------------------------
     def timing_enable(self, on=True):

@@ -96,15 +96,18 @@ class SolveResult:
 
 
 def solve(dynamics, cost, x0, U_init, *, T=None, N=None, tol=1e-5, maxiter=100, alpha_factor=0.5,
-          min_alpha=1e-8, n_alpha=None, mu=0.0, dtype=np.float64, device=0, verbose=False, u_min=None, u_max=None):
+          min_alpha=1e-8, n_alpha=None, mu=0.0, dtype=np.float64, device=0, verbose=False, u_min=None, u_max=None,
+          batch_params=None):
     """Solve one trajectory (x0 (n,), U_init (m, N)) or a batch (x0 (B, n), U_init (B, m, N)).
-    u_min, u_max: control limits (scalars or [n_u], see iLQR.set_control_limits)."""
+    u_min, u_max: control limits (scalars or [n_u], see iLQR.set_control_limits); batch_params: per-trajectory system
+    parameters and x_target (a dict for batch_param_rows)."""
     system = make_system(dynamics, cost, dtype)
     U_init = np.asarray(U_init)
     if N is None and T is None:
         N = U_init.shape[-1]
     s = iLQR(system, T, x0, U_init, tol=tol, maxiter=maxiter, alpha_factor=alpha_factor, min_alpha=min_alpha,
-             verbose=verbose, N=N, n_alpha=n_alpha, mu=mu, dtype=dtype, device=device, u_min=u_min, u_max=u_max)
+             verbose=verbose, N=N, n_alpha=n_alpha, mu=mu, dtype=dtype, device=device, u_min=u_min, u_max=u_max,
+             batch_params=batch_params)
     X, U, c = s.optimize_trajectory()
     return SolveResult(X=X, U=U, cost=c, K=s.K, k=s.U_ff, iters=s.iterations, status=s.status, solver=s)
 
@@ -116,9 +119,11 @@ class MPCState:
 
 
 def mpc_init(dynamics, cost, x0, U_init, *, plant_integrator="midpoint", T=None, N=None, tol=1e-5, maxiter=10,
-             n_alpha=None, dtype=np.float64, device=0, u_min=None, u_max=None):
+             n_alpha=None, dtype=np.float64, device=0, u_min=None, u_max=None, batch_params=None, plant_params=None):
     """Receding-horizon controller state (run_iLQR_MPC.py:58-106): optimiser model = ``dynamics``,
-    plant = the same system with ``plant_integrator``; u_min, u_max: control limits of every solve."""
+    plant = the same system with ``plant_integrator``; u_min, u_max: control limits of every solve; batch_params: the
+    model's per-trajectory parameters and targets, plant_params: each plant's own system parameters (model mismatch),
+    both dicts for batch_param_rows."""
     system = make_system(dynamics, cost, dtype)
     if isinstance(dynamics, System):
         raise ValueError("mpc_init needs a dynamics description (dict) so it can build the plant twin")
@@ -127,7 +132,7 @@ def mpc_init(dynamics, cost, x0, U_init, *, plant_integrator="midpoint", T=None,
     if N is None and T is None:
         N = U_init.shape[-1]
     s = iLQR(system, T, x0, U_init, tol=tol, maxiter=maxiter, verbose=False, N=N, n_alpha=n_alpha, dtype=dtype,
-             device=device, plant=plant, u_min=u_min, u_max=u_max)
+             device=device, plant=plant, u_min=u_min, u_max=u_max, batch_params=batch_params, plant_params=plant_params)
     s.mpc_reset(x0, U_init)
     return MPCState(solver=s)
 

@@ -153,7 +153,10 @@ ILQR_DEV void lds_poke(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXE
 // (persistent.hpp: the whole iteration loop of a workgroup's trajectories in one launch) run the same code.
 // BOX (control limits, n_u = 1): the producers put u_t into the tile's padding (scalar kTile16 of the TL = 52), the sweep
 // hands it to the step's tail with the limits (tile16_step_f32 / tile16_step, BOX).
-template <typename T, typename Dyn, int INTEG, int TPW, bool PK, bool BOX = false> struct FusedWG {
+// HET (per-trajectory parameters, KArgs::rows): the producers expand at their trajectory's row (both halves of a pair
+// producer's lane belong to one trajectory, so SplatParams over the lane's copy serves it), the sweep takes l_f_x / l_f_xx
+// at the row's x_target.  The roles are used through FusedWG (HET = false) and FusedWGHet below.
+template <typename T, typename Dyn, int INTEG, int TPW, bool PK, bool BOX, bool HET> struct FusedRoles {
     static constexpr int NX = Dyn::NX, NU = Dyn::NU;
     static_assert(!BOX || (NU == 1 && fused_tl<1>() > kTile16), "control limits: n_u = 1, u_t in the tile's padding");
     static_assert((NU == 1 && NX >= 2 && NX <= 4) || (NX == 4 && NU == 2), "the fused sweep serves the DPP tiles: n_u = 1, or (4, 2)");
@@ -246,7 +249,13 @@ template <typename T, typename Dyn, int INTEG, int TPW, bool PK, bool BOX = fals
         const bool act = valid && traj_active(st);
         const int slot = act ? L.s_slot[tl] : 0;
         // terminal expansion at x_N of the accepted trajectory (iLQR_class.py:136-138), which also moves to slot 0
-        const T* __restrict__ pp = a.params;
+        T ph[HET ? PL::TOTAL : 1];   // HET: the block with this trajectory's row (the terminal cost reads x_target, Q_f)
+        if constexpr (HET) {
+#pragma unroll
+            for (int q = 0; q < PL::TOTAL; ++q) ph[q] = a.params[q];
+            load_row<PL::Q>(ph, a.rows, B, b);
+        }
+        const T* __restrict__ pp = HET ? ph : a.params;
         T xN[NX];
         vec_load<T, NX>(a.X + vec_at(B, N + 1, NX, slot, N, b), xN);
         if (act && slot != 0 && l16 == 0) vec_store<T, NX>(a.X + vec_at(B, N + 1, NX, 0, N, b), xN);
@@ -366,7 +375,7 @@ template <typename T, typename Dyn, int INTEG, int TPW, bool PK, bool BOX = fals
     // ---- producer role (waves NSW .. NSW+P-1; pw = the producer's index) ----------------------------------------------------
     static ILQR_DEV void produce(const KArgs<T>& a_, const Lds& L, int b0, int pw, int lane) {
         // (the fields the unit loop reads, as locals: the persistent kernel's roles get the argument block as memory)
-        struct { int B; T dt; T* X; T* U; const T* params; } a = {a_.B, a_.dt, a_.X, a_.U, a_.params};
+        struct { int B; T dt; T* X; T* U; const T* params; const T* rows; } a = {a_.B, a_.dt, a_.X, a_.U, a_.params, a_.rows};
         const size_t B = a.B;
         const int N = a_.N;
         const int n_units = (N + US - 1) / US;
@@ -384,6 +393,7 @@ template <typename T, typename Dyn, int INTEG, int TPW, bool PK, bool BOX = fals
         T pl[PL::TOTAL];
 #pragma unroll
         for (int q = 0; q < PL::TOTAL; ++q) pl[q] = a.params[q];
+        if constexpr (HET) load_row<PL::Q>(pl, a.rows, B, b);
         const SplatParams p{pl};
         const T2 dt2 = a.dt;
         for (int k = pw; k < n_units; k += P) {
@@ -455,6 +465,7 @@ template <typename T, typename Dyn, int INTEG, int TPW, bool PK, bool BOX = fals
         T p[PL::TOTAL];
 #pragma unroll
         for (int q = 0; q < PL::TOTAL; ++q) p[q] = a.params[q];
+        if constexpr (HET) load_row<PL::Q>(p, a.rows, B, b);
         for (int k = pw; k < n_units; k += P) {
             const int t = N - 1 - k * US - r;
             const bool inr = t >= 0;
@@ -498,10 +509,16 @@ template <typename T, typename Dyn, int INTEG, int TPW, bool PK, bool BOX = fals
     }
 };
 
-// BOX: with control limits (FusedWG, BOX); the rollouts that follow are forward_ring_kernel_box
 template <typename T, typename Dyn, int INTEG, int TPW, bool PK, bool BOX = false>
+struct FusedWG : FusedRoles<T, Dyn, INTEG, TPW, PK, BOX, false> {};
+template <typename T, typename Dyn, int INTEG, int TPW, bool PK, bool BOX = false>
+struct FusedWGHet : FusedRoles<T, Dyn, INTEG, TPW, PK, BOX, true> {};
+
+// BOX: with control limits (FusedWG, BOX); the rollouts that follow are forward_ring_kernel_box
+// HET: per-trajectory parameters (FusedWGHet); the rollouts that follow are forward_ring_kernel(_box)_het
+template <typename T, typename Dyn, int INTEG, int TPW, bool PK, bool BOX = false, bool HET = false>
 __global__ void __launch_bounds__((fused_threads<T, TPW, PK>())) backward_fused16_kernel(KArgs<T> a) {
-    using W = FusedWG<T, Dyn, INTEG, TPW, PK, BOX>;
+    using W = std::conditional_t<HET, FusedWGHet<T, Dyn, INTEG, TPW, PK, BOX>, FusedWG<T, Dyn, INTEG, TPW, PK, BOX>>;
     extern __shared__ __attribute__((aligned(16))) unsigned char fused_lds[];
     const typename W::Lds L = W::carve(fused_lds);
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;

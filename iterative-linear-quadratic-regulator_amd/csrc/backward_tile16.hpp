@@ -117,7 +117,9 @@ ILQR_DEV void buf_store1(__amdgpu_buffer_rsrc_t r, int voff, int soff, double v)
 }
 
 // a C-vector of T in 16-, 8- or 4-byte pieces (vec_pieces(C * sizeof(T)) stores)
-template <typename T, int C> ILQR_DEV void buf_store_vec(__amdgpu_buffer_rsrc_t r, int voff, int soff, const T* v) {
+// (NOP2: two wait states instead of one behind a 16-byte store, for kernels where hipcc may put the store's soffset in
+// VCC -- verify_ring_isa.store_pk_hazards then asks for the wait states of a non-SGPR offset)
+template <typename T, int C, bool NOP2 = false> ILQR_DEV void buf_store_vec(__amdgpu_buffer_rsrc_t r, int voff, int soff, const T* v) {
     constexpr int BYTES = C * (int)sizeof(T), PB = BYTES % 16 == 0 ? 16 : BYTES % 8 == 0 ? 8 : 4, NP = BYTES / PB;
     unsigned w[BYTES / 4];
     __builtin_memcpy(w, v, BYTES);
@@ -133,7 +135,8 @@ template <typename T, int C> ILQR_DEV void buf_store_vec(__amdgpu_buffer_rsrc_t 
             // before it has executed, wherever the scheduler puts it.
             const u32x4 q = {w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]};
             __builtin_amdgcn_raw_buffer_store_b128(q, r, voff + 16 * k, soff, 0);
-            asm volatile("s_nop 0" : : "v"(q));
+            if constexpr (NOP2) asm volatile("s_nop 1" : : "v"(q));
+            else asm volatile("s_nop 0" : : "v"(q));
         } else if constexpr (PB == 8) {
             const u32x2 q = {w[2 * k], w[2 * k + 1]};
             __builtin_amdgcn_raw_buffer_store_b64(q, r, voff + 8 * k, soff, 0);

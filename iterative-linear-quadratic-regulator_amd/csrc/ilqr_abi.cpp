@@ -249,6 +249,19 @@ int ilqr_set_control_limits(ilqr_handle h, const double* u_min, const double* u_
     }
     return h->impl->set_control_limits(u_min, u_max);
 }
+int ilqr_set_batch_params(ilqr_handle h, int which, const double* rows, int row_len) {
+    if (!h || !h->impl) return ILQR_ERR_INVALID_ARG;
+    const ilqr_config& c = h->impl->cfg;
+    if (which != ILQR_BATCH_MODEL && which != ILQR_BATCH_PLANT) {
+        h->impl->err = "set_batch_params: which must be ILQR_BATCH_MODEL or ILQR_BATCH_PLANT";
+        return ILQR_ERR_INVALID_ARG;
+    }
+    if (rows && (c.system == ILQR_SYS_LINEAR || c.system == ILQR_SYS_CUSTOM)) {
+        h->impl->err = "set_batch_params: per-trajectory parameters are not supported for linear or user-defined systems";
+        return ILQR_ERR_UNSUPPORTED;
+    }
+    return h->impl->set_batch_params(which, rows, row_len);   // (clearing with NULL: valid on every handle)
+}
 int ilqr_timing_enable(ilqr_handle h, int on) { ILQR_FWD(h, timing_enable(on)); }
 int ilqr_timing_reset(ilqr_handle h) { ILQR_FWD(h, timing_reset()); }
 int ilqr_timing_get(ilqr_handle h, double ms[ILQR_N_PHASES], int64_t launches[ILQR_N_PHASES]) {

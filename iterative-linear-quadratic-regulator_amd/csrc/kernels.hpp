@@ -69,7 +69,21 @@ template <typename T> struct KArgs {
     // their offsets
     T u_lo[kBoxMaxU], u_hi[kBoxMaxU];
     int box;           // limits are set: the fused / persistent launchers pick their BOX instantiations
+    // per-trajectory parameters (ilqr_set_batch_params), read by the HET kernels only (the *_het kernels, the HET fused /
+    // persistent roles); appended after the limits for the same reason.  rows: [n_sys + n_x][B] derived system constants
+    // then x_target of every trajectory (SoA: a wave's load of one entry is coalesced); plant_rows: [n_sys][B] of the MPC
+    // plant (the model's rows when the plant has none of its own)
+    const T* rows;
+    const T* plant_rows;
+    int het;           // rows are set: the launchers pick their HET instantiations
 };
+
+// A HET lane's parameters: its trajectory's row over the first NH = n_sys + n_x entries of its parameter copy, the shared
+// block behind them.  The templates index the copy with compile-time constants, so they run unchanged on per-lane values.
+template <int NH, typename T> ILQR_DEV void load_row(T* p, const T* __restrict__ rows, size_t B, int b) {
+#pragma unroll
+    for (int q = 0; q < NH; ++q) p[q] = rows[(size_t)q * B + b];
+}
 
 constexpr int gain_record(int nx, int nu) { return ((nu * nx + nu) + 3) / 4 * 4; }
 
@@ -214,7 +228,8 @@ ILQR_DEV void tile16_pack(P p, T dt, const T* x, const T* u, const T (*fx)[Dyn::
 // (iLQR_class.py:318-331) + l_f_x / l_f_xx (:136-138), hoisted out of the
 // sequential scan because it does not depend on the carry.
 // ---------------------------------------------------------------------------
-template <typename T, typename Dyn, bool TILE16, int INTEG>
+// HET: per-trajectory parameters (KArgs::rows)
+template <typename T, typename Dyn, bool TILE16, int INTEG, bool HET = false>
 __global__ void __launch_bounds__(TILE16 ? 64 : 256) linearize_kernel(KArgs<T> a) {
     constexpr int NX = Dyn::NX, NU = Dyn::NU;
     constexpr int E = 2 * NX * NX + 2 * NX * NU + NX + NU + NU * NU;
@@ -234,6 +249,7 @@ __global__ void __launch_bounds__(TILE16 ? 64 : 256) linearize_kernel(KArgs<T> a
     T p[PL::TOTAL];
 #pragma unroll
     for (int q = 0; q < PL::TOTAL; ++q) p[q] = a.params[q];
+    if constexpr (HET) load_row<PL::Q>(p, a.rows, B, b);   // (b < B on every lane: idx % B)
     T x[NX], u[NU];
     // Canonicalisation: accepting a candidate only moves cur_slot[b] (no copy), so after a few iterations
     // neighbouring trajectories live in different slots and every wave-wide access of the rollout -- 64
@@ -765,7 +781,7 @@ __global__ void __launch_bounds__(64) backward_box_kernel(KArgs<T> a) {
 // index.  Replaces iLQR._forward_pass_scan (iLQR_class.py:193-247), all trial
 // alphas of the backtracking loop (:279-302) at once.
 // ---------------------------------------------------------------------------
-template <typename T, typename Dyn, int INTEG, bool BOX>
+template <typename T, typename Dyn, int INTEG, bool BOX, bool HET = false>
 ILQR_DEV void forward_body(const KArgs<T>& a) {
     constexpr int NX = Dyn::NX, NU = Dyn::NU;
     constexpr int R = gain_record(NX, NU);
@@ -782,7 +798,14 @@ ILQR_DEV void forward_body(const KArgs<T>& a) {
     const int slot = a.cur_slot[b];
     const int cslot = (slot + 1 + ai) % a.n_slots;
     const T alpha = a.alphas[ai];
-    const T* __restrict__ p = a.params;
+    using PLf = ParamLayout<Dyn::NSYS, NX, NU>;
+    T ph[HET ? PLf::QS : 1];   // HET: the block's [system constants | x_target | Q | R | Q_f] with this trajectory's row
+    if constexpr (HET) {
+#pragma unroll
+        for (int i = 0; i < PLf::QS; ++i) ph[i] = a.params[i];
+        load_row<PLf::Q>(ph, a.rows, B, b);
+    }
+    const T* __restrict__ p = HET ? ph : a.params;
     T x[NX], u[NU];
 #pragma unroll
     for (int i = 0; i < NX; ++i) x[i] = a.x0[(size_t)i * B + b];
@@ -857,6 +880,11 @@ __global__ void __launch_bounds__(64) forward_kernel(KArgs<T> a) { forward_body<
 // with control limits: every control clamped to [u_lo, u_hi] before it is stored, costed and integrated
 template <typename T, typename Dyn, int INTEG>
 __global__ void __launch_bounds__(64) forward_kernel_box(KArgs<T> a) { forward_body<T, Dyn, INTEG, true>(a); }
+// per-trajectory parameters (KArgs::rows), without and with limits
+template <typename T, typename Dyn, int INTEG>
+__global__ void __launch_bounds__(64) forward_kernel_het(KArgs<T> a) { forward_body<T, Dyn, INTEG, false, true>(a); }
+template <typename T, typename Dyn, int INTEG>
+__global__ void __launch_bounds__(64) forward_kernel_box_het(KArgs<T> a) { forward_body<T, Dyn, INTEG, true, true>(a); }
 
 // ---------------------------------------------------------------------------
 // forward rollout, ring form (small systems, tensors < 2 GiB): identical arithmetic to forward_kernel, but
@@ -871,7 +899,7 @@ __global__ void __launch_bounds__(64) forward_kernel_box(KArgs<T> a) { forward_b
 // The rollout of candidate ai of trajectory b by this lane; in_range = the lane has a candidate at all.  The lanes of a
 // wave may hold any mix of (b, ai) -- forward_ring_kernel gives a wave 64 neighbouring trajectories of one alpha, the
 // persistent kernel (persistent.hpp) all candidates of a workgroup's trajectories -- as long as the whole wave calls it.
-template <typename T, typename Dyn, int INTEG, bool BOX = false>
+template <typename T, typename Dyn, int INTEG, bool BOX = false, bool HET = false>
 ILQR_DEV void rollout_ring(const KArgs<T>& a, int b, int ai, bool in_range, bool force_init = false) {
     constexpr int NX = Dyn::NX, NU = Dyn::NU;
     using In = FwdIn<T, NX, NU>;
@@ -885,7 +913,9 @@ ILQR_DEV void rollout_ring(const KArgs<T>& a, int b, int ai, bool in_range, bool
     constexpr int SLOT_REGS = (NX + NU + R) * (int)sizeof(T) / 4;
     constexpr int PF_CNT = (63 / (NLD + NST)) + 1 > ILQR_RING_PF_MAX ? ILQR_RING_PF_MAX : (63 / (NLD + NST)) + 1;
     // (the fp64 backward-Euler step -- Newton loop with an LU solve -- needs more registers of its own: one slot fewer)
-    constexpr int RING_CAP = (sizeof(T) == 8 && INTEG == ILQR_INT_BACKWARD_EULER) ? 104 : 130;
+    // (HET: the trajectory's row -- n_sys + n_x scalars -- lives in VGPRs beside the ring, which is that much shallower)
+    constexpr int RING_CAP = ((sizeof(T) == 8 && INTEG == ILQR_INT_BACKWARD_EULER) ? 104 : 130) -
+                             (HET ? (Dyn::NSYS + NX) * (int)sizeof(T) / 4 : 0);
     constexpr int PF = PF_CNT * SLOT_REGS > RING_CAP ? RING_CAP / SLOT_REGS : PF_CNT;
     static_assert(PF >= 2, "ring too shallow to be worth it");
     // status, accepted flag and slot in one memory round trip (bitwise &: no short-circuit between the loads)
@@ -918,6 +948,7 @@ ILQR_DEV void rollout_ring(const KArgs<T>& a, int b, int ai, bool in_range, bool
     T p[PLp::QS];   // [system constants | x_target | Q | R | Q_f]: all the rollout reads
 #pragma unroll
     for (int i = 0; i < PLp::QS; ++i) p[i] = a.params[i];
+    if constexpr (HET) load_row<PLp::Q>(p, a.rows, B, bb);   // (a dead lane reads trajectory 0's row)
     T x[NX], u[NU];
 #pragma unroll
     for (int i = 0; i < NX; ++i) x[i] = a.x0[(size_t)i * B + bb];
@@ -982,8 +1013,8 @@ ILQR_DEV void rollout_ring(const KArgs<T>& a, int b, int ai, bool in_range, bool
         }
         // exactly NST stores per step for every wave that is still running (they are counted)
         if (DROP || live) {
-            buf_store_vec<T, NX>(rXc, vXc, uniform(t * stepX), x);
-            buf_store_vec<T, NU>(rUc, vUc, uniform(t * stepU), u);
+            buf_store_vec<T, NX, HET>(rXc, vXc, uniform(t * stepX), x);
+            buf_store_vec<T, NU, HET>(rUc, vUc, uniform(t * stepU), u);
         }
         cost += Cost<T, Dyn>::stage(p, dt, x, u);
         T xn[NX];
@@ -1041,6 +1072,21 @@ __global__ void __launch_bounds__(64) forward_ring_kernel_box(KArgs<T> a) {
     const int ai = blockIdx.y;
     if (a.init_mode && blockIdx.x == 0 && ai == 0 && threadIdx.x == 0) a.counters[a.counter_idx] = 0;
     rollout_ring<T, Dyn, INTEG, true>(a, b, ai, b < a.B);
+}
+// per-trajectory parameters (KArgs::rows), without and with limits; the ring guards see them by their names
+template <typename T, typename Dyn, int INTEG>
+__global__ void __launch_bounds__(64) forward_ring_kernel_het(KArgs<T> a) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    const int ai = blockIdx.y;
+    if (a.init_mode && blockIdx.x == 0 && ai == 0 && threadIdx.x == 0) a.counters[a.counter_idx] = 0;
+    rollout_ring<T, Dyn, INTEG, false, true>(a, b, ai, b < a.B);
+}
+template <typename T, typename Dyn, int INTEG>
+__global__ void __launch_bounds__(64) forward_ring_kernel_box_het(KArgs<T> a) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    const int ai = blockIdx.y;
+    if (a.init_mode && blockIdx.x == 0 && ai == 0 && threadIdx.x == 0) a.counters[a.counter_idx] = 0;
+    rollout_ring<T, Dyn, INTEG, true, true>(a, b, ai, b < a.B);
 }
 
 // ---------------------------------------------------------------------------
@@ -1278,6 +1324,7 @@ template <typename T> struct MpcArgs {
     const T* params;
     T* U; const int* cur_slot; T* x0; T* plant_x;
     T* u_log; T* x_log; T* cost_log; const T* cost;  // logs in the ABI layout [n_steps][B][...], or NULL
+    const T* plant_rows;  // HET: [n_sys][B] system constants of every trajectory's plant (KArgs::plant_rows)
 };
 
 // Workgroup = 64 trajectories x kMpcChunks slices of the horizon (threadIdx.y): the shift U[t] <- U[t + 1] reads its
@@ -1285,7 +1332,8 @@ template <typename T> struct MpcArgs {
 // dependent load / store pairs: 66 us of the c4 step, now a few).  Slice 0 also runs the plant step.  Horizons beyond
 // kMpcChunks * (32 / n_u) + 1 steps fall back to the walk.
 constexpr int kMpcChunks = 16, kMpcSliceScalars = 32;   // a slice keeps at most 32 scalars per lane in registers
-template <typename T, typename Dyn>
+// HET: the plant of every trajectory at its own system constants (MpcArgs::plant_rows)
+template <typename T, typename Dyn, bool HET = false>
 __global__ void __launch_bounds__(64 * kMpcChunks) mpc_advance_kernel(MpcArgs<T> a) {
     constexpr int NX = Dyn::NX, NU = Dyn::NU;
     constexpr int kMpcSlice = kMpcSliceScalars / NU > 0 ? kMpcSliceScalars / NU : 1;
@@ -1320,7 +1368,13 @@ __global__ void __launch_bounds__(64 * kMpcChunks) mpc_advance_kernel(MpcArgs<T>
     T x[NX], xn[NX];
 #pragma unroll
     for (int i = 0; i < NX; ++i) x[i] = a.plant_x[(size_t)i * B + b];
-    Stepper<T, Dyn>::step(a.plant_integ, a.params, a.dt, x, u0, xn);
+    if constexpr (HET) {
+        T pp[Dyn::NSYS];   // the plant's system constants (all a step reads)
+        load_row<Dyn::NSYS>(pp, a.plant_rows, B, b);
+        Stepper<T, Dyn>::step(a.plant_integ, pp, a.dt, x, u0, xn);
+    } else {
+        Stepper<T, Dyn>::step(a.plant_integ, a.params, a.dt, x, u0, xn);
+    }
 #pragma unroll
     for (int i = 0; i < NX; ++i) {
         a.plant_x[(size_t)i * B + b] = xn[i];

@@ -38,6 +38,11 @@ template <typename T, typename Dyn, int INTEG, bool BOX = false>
 __device__ __attribute__((noinline)) void role_rollout(const KArgs<T>* a, int b, int ai, bool in_range, int init) {
     rollout_ring<T, Dyn, INTEG, BOX>(*a, b, ai, in_range, init != 0);
 }
+// per-trajectory parameters (KArgs::rows)
+template <typename T, typename Dyn, int INTEG, bool BOX = false>
+__device__ __attribute__((noinline)) void role_rollout_het(const KArgs<T>* a, int b, int ai, bool in_range, int init) {
+    rollout_ring<T, Dyn, INTEG, BOX, true>(*a, b, ai, in_range, init != 0);
+}
 // (The LDS pointers are carved from the workgroup's dynamic allocation INSIDE each role: handed over as function
 // arguments they would be generic pointers, and every tile read of the sweep a flat_load instead of a ds_read.)
 template <typename W, typename T>
@@ -60,9 +65,14 @@ __device__ __attribute__((noinline)) void role_produce(const KArgs<T>* a, int b0
 // the rollout's register ring (165) and the pair producers (234) both fit; eight scalar producers would cap the kernel
 // at 168 and make the ring rollout spill -- the build rejects that, csrc/check_ring_kernels.py)
 // BOX: with control limits (the BOX sweep of FusedWG and the clamped rollout_ring)
-template <typename T, typename Dyn, int INTEG, int TPW, bool PK, bool BOX = false>
+// HET: per-trajectory parameters (FusedWGHet, role_rollout_het); the plant step reads KArgs::plant_rows
+template <typename T, typename Dyn, int INTEG, int TPW, bool PK, bool BOX = false, bool HET = false>
 __global__ void __launch_bounds__((fused_threads<T, TPW, PK>())) ilqr_persistent_kernel(KArgs<T> a, PArgs<T> pa) {
-    using W = FusedWG<T, Dyn, INTEG, TPW, PK, BOX>;
+    using W = std::conditional_t<HET, FusedWGHet<T, Dyn, INTEG, TPW, PK, BOX>, FusedWG<T, Dyn, INTEG, TPW, PK, BOX>>;
+    auto rollout = [](const KArgs<T>* ka_, int b, int ai, bool in_range, int init) {
+        if constexpr (HET) role_rollout_het<T, Dyn, INTEG, BOX>(ka_, b, ai, in_range, init);
+        else role_rollout<T, Dyn, INTEG, BOX>(ka_, b, ai, in_range, init);
+    };
     constexpr int NX = Dyn::NX, NU = Dyn::NU;
     constexpr int NT = fused_threads<T, TPW, PK>();
     extern __shared__ __attribute__((aligned(16))) unsigned char fused_lds[];
@@ -84,7 +94,7 @@ __global__ void __launch_bounds__((fused_threads<T, TPW, PK>())) ilqr_persistent
         if (pa.do_init) {
             // ---- head of a solve (iLQR_class.py:257-259): every trajectory, alpha = 0, through the carried K and X --------
             if (wave == 0) {
-                role_rollout<T, Dyn, INTEG, BOX>(ka, b0 + lane, 0, lane < TPW && b0 + lane < a.B, 1);
+                rollout(ka, b0 + lane, 0, lane < TPW && b0 + lane < a.B, 1);
                 drain_stores();
                 const int b = b0 + lane;
                 if (lane < TPW && b < a.B) {        // (the lane that rolled the candidate out accepts it: no barrier needed)
@@ -119,7 +129,7 @@ __global__ void __launch_bounds__((fused_threads<T, TPW, PK>())) ilqr_persistent
                 const int lg = wave * 64 + lane;
                 const int tl = lg % TPW, ai = lg / TPW;
                 if (wave * 64 < TPW * a.n_pass)    // (wave-uniform: waves beyond the last candidate skip the role)
-                    role_rollout<T, Dyn, INTEG, BOX>(ka, b0 + tl, ai, ai < a.n_pass && b0 + tl < a.B, 0);
+                    rollout(ka, b0 + tl, ai, ai < a.n_pass && b0 + tl < a.B, 0);
             }
             drain_stores();
             __syncthreads();
@@ -171,7 +181,13 @@ __global__ void __launch_bounds__((fused_threads<T, TPW, PK>())) ilqr_persistent
                 T x[NX], xn[NX];
 #pragma unroll
                 for (int i = 0; i < NX; ++i) x[i] = m.plant_x[(size_t)i * B + b];
-                Stepper<T, Dyn>::step(m.plant_integ, a.params, a.dt, x, u0, xn);
+                if constexpr (HET) {
+                    T pp[Dyn::NSYS];   // the plant's system constants (all a step reads)
+                    load_row<Dyn::NSYS>(pp, a.plant_rows, B, b);
+                    Stepper<T, Dyn>::step(m.plant_integ, pp, a.dt, x, u0, xn);
+                } else {
+                    Stepper<T, Dyn>::step(m.plant_integ, a.params, a.dt, x, u0, xn);
+                }
                 const int step = m.step + ms;
 #pragma unroll
                 for (int i = 0; i < NX; ++i) {

@@ -57,6 +57,7 @@ struct SolverBase {
     virtual int timing_get(double* ms, int64_t* launches) = 0;
     virtual int algorithmic_bytes(double* bytes) = 0;
     virtual int set_control_limits(const double* u_min, const double* u_max) = 0;
+    virtual int set_batch_params(int which, const double* rows, int row_len) = 0;
 };
 
 int system_dims(int system, int n_x, int n_u);  // 1 if (system, n_x, n_u) is a known combination
@@ -120,6 +121,10 @@ template <typename T> struct Ops {
     void (*backward_box)(const KArgs<T>&, hipStream_t) = nullptr;
     void (*forward_box[5])(const KArgs<T>&, hipStream_t) = {};
     bool fused_box = false;   // fused[] / persist[] also launch their BOX instantiations (KArgs::box)
+    // per-trajectory parameters (ilqr_set_batch_params): linearize[] / forward[] / forward_box[] / fused[] / persist[] and
+    // mpc_advance launch their HET instantiations when KArgs::het (MpcArgs::plant_rows) is set; the built-in systems only
+    bool het = false;
+    bool persist_het[5] = {};   // persist[i] has a HET instantiation (else a HET solve takes the fused multi-launch loop)
 };
 
 // linearize / forward are compiled once per integrator so the integrator switch folds away and each
@@ -154,8 +159,13 @@ inline int persist_small_max() {
 template <typename Dyn, typename = void> struct has_rebind { static constexpr bool value = false; };
 template <typename Dyn> struct has_rebind<Dyn, std::void_t<typename Dyn::template rebind<float>>> { static constexpr bool value = true; };
 
-// the fused kernel's launch (BX: its control-limited instantiation, FusedWG BOX)
-template <typename T, typename Dyn, int I, bool BX>
+// the fused kernel's launch (BX: its control-limited instantiation, FusedWG BOX; HT: per-trajectory parameters,
+// backward_fused16_kernel, HET)
+template <typename T, typename Dyn, int I, int TPW, bool PK, bool BX, bool HT> constexpr auto fused_kernel() {
+    if constexpr (HT) return backward_fused16_kernel<T, Dyn, I, TPW, PK, BX, true>;
+    else return backward_fused16_kernel<T, Dyn, I, TPW, PK, BX>;
+}
+template <typename T, typename Dyn, int I, bool BX, bool HT = false>
 void launch_fused_kernel(const KArgs<T>& a, hipStream_t s) {
     // one workgroup = 16 trajectories (4 sweep waves + the producer waves, tiles through ~104 KB of LDS: one per
     // CU), or 4 trajectories (1 sweep wave, ~52 KB) while the batch then still fits the chip one workgroup per CU
@@ -163,12 +173,12 @@ void launch_fused_kernel(const KArgs<T>& a, hipStream_t s) {
     // fp32 with an explicit integrator and a system that can be instantiated on a float pair: pair producers
     constexpr bool CAN_PK = sizeof(T) == 4 && I != ILQR_INT_BACKWARD_EULER && has_rebind<Dyn>::value && !ILQR_NO_PAIR_PRODUCERS;
     static const bool ok = [] {
-        bool r = hipFuncSetAttribute((const void*)backward_fused16_kernel<T, Dyn, I, 16, false, BX>,
+        bool r = hipFuncSetAttribute((const void*)fused_kernel<T, Dyn, I, 16, false, BX, HT>(),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, fused_lds_bytes<T, 16, false, Dyn::NU>()) == hipSuccess;
-        r = r && hipFuncSetAttribute((const void*)backward_fused16_kernel<T, Dyn, I, 4, false, BX>,
+        r = r && hipFuncSetAttribute((const void*)fused_kernel<T, Dyn, I, 4, false, BX, HT>(),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, fused_lds_bytes<T, 4, false, Dyn::NU>()) == hipSuccess;
         if constexpr (CAN_PK)
-            r = r && hipFuncSetAttribute((const void*)backward_fused16_kernel<T, Dyn, I, 16, true, BX>,
+            r = r && hipFuncSetAttribute((const void*)fused_kernel<T, Dyn, I, 16, true, BX, HT>(),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, fused_lds_bytes<T, 16, true, Dyn::NU>()) == hipSuccess;
         (void)hipGetLastError();
         return r;
@@ -186,30 +196,34 @@ void launch_fused_kernel(const KArgs<T>& a, hipStream_t s) {
     static const bool no_pk = getenv("ILQR_FUSED_PAIRS") == nullptr;                          // A/B switch
     const bool small = force ? force == 4 : a.B <= small_max;
     if (small) {
-        ILQR_LAUNCH((backward_fused16_kernel<T, Dyn, I, 4, false, BX>), dim3((a.B + 3) / 4), dim3(fused_threads<T, 4, false>()),
+        ILQR_LAUNCH((fused_kernel<T, Dyn, I, 4, false, BX, HT>()), dim3((a.B + 3) / 4), dim3(fused_threads<T, 4, false>()),
                     (fused_lds_bytes<T, 4, false, Dyn::NU>()), s, a);
         return;
     }
     if constexpr (CAN_PK) {
         if (!no_pk) {
-            ILQR_LAUNCH((backward_fused16_kernel<T, Dyn, I, 16, true, BX>), dim3((a.B + 15) / 16), dim3(fused_threads<T, 16, true>()),
+            ILQR_LAUNCH((fused_kernel<T, Dyn, I, 16, true, BX, HT>()), dim3((a.B + 15) / 16), dim3(fused_threads<T, 16, true>()),
                         (fused_lds_bytes<T, 16, true, Dyn::NU>()), s, a);
             return;
         }
     }
-    ILQR_LAUNCH((backward_fused16_kernel<T, Dyn, I, 16, false, BX>), dim3((a.B + 15) / 16), dim3(fused_threads<T, 16, false>()),
+    ILQR_LAUNCH((fused_kernel<T, Dyn, I, 16, false, BX, HT>()), dim3((a.B + 15) / 16), dim3(fused_threads<T, 16, false>()),
                 (fused_lds_bytes<T, 16, false, Dyn::NU>()), s, a);
 }
 
-// the persistent kernel's launch (BX: its control-limited instantiation)
-template <typename T, typename Dyn, int I, bool BX>
+// the persistent kernel's launch (BX: its control-limited instantiation; HT: per-trajectory parameters)
+template <typename T, typename Dyn, int I, int TPW, bool PK, bool BX, bool HT> constexpr auto persist_kernel() {
+    if constexpr (HT) return ilqr_persistent_kernel<T, Dyn, I, TPW, PK, BX, true>;
+    else return ilqr_persistent_kernel<T, Dyn, I, TPW, PK, BX>;
+}
+template <typename T, typename Dyn, int I, bool BX, bool HT = false>
 void launch_persist_kernel(const KArgs<T>& a, const PArgs<T>& pa, hipStream_t s) {
     constexpr bool BIG = I != ILQR_INT_BACKWARD_EULER && has_rebind<Dyn>::value && !ILQR_NO_PAIR_PRODUCERS;
     static const bool ok = [] {
-        bool r = hipFuncSetAttribute((const void*)ilqr_persistent_kernel<T, Dyn, I, 4, false, BX>,
+        bool r = hipFuncSetAttribute((const void*)persist_kernel<T, Dyn, I, 4, false, BX, HT>(),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, fused_lds_bytes<T, 4, false, Dyn::NU>()) == hipSuccess;
         if constexpr (BIG)
-            r = r && hipFuncSetAttribute((const void*)ilqr_persistent_kernel<T, Dyn, I, 16, true, BX>,
+            r = r && hipFuncSetAttribute((const void*)persist_kernel<T, Dyn, I, 16, true, BX, HT>(),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, fused_lds_bytes<T, 16, true, Dyn::NU>()) == hipSuccess;
         (void)hipGetLastError();
         return r;
@@ -217,12 +231,12 @@ void launch_persist_kernel(const KArgs<T>& a, const PArgs<T>& pa, hipStream_t s)
     (void)ok;
     if constexpr (BIG) {
         if (a.B > persist_small_max()) {
-            ILQR_LAUNCH((ilqr_persistent_kernel<T, Dyn, I, 16, true, BX>), dim3((a.B + 15) / 16), dim3(fused_threads<T, 16, true>()),
+            ILQR_LAUNCH((persist_kernel<T, Dyn, I, 16, true, BX, HT>()), dim3((a.B + 15) / 16), dim3(fused_threads<T, 16, true>()),
                         (fused_lds_bytes<T, 16, true, Dyn::NU>()), s, a, pa);
             return;
         }
     }
-    ILQR_LAUNCH((ilqr_persistent_kernel<T, Dyn, I, 4, false, BX>), dim3((a.B + 3) / 4), dim3(fused_threads<T, 4, false>()),
+    ILQR_LAUNCH((persist_kernel<T, Dyn, I, 4, false, BX, HT>()), dim3((a.B + 3) / 4), dim3(fused_threads<T, 4, false>()),
                 (fused_lds_bytes<T, 4, false, Dyn::NU>()), s, a, pa);
 }
 
@@ -230,24 +244,42 @@ void launch_persist_kernel(const KArgs<T>& a, const PArgs<T>& pa, hipStream_t s)
 template <typename Dyn> constexpr bool box_system() {
     return Dyn::ID == ILQR_SYS_PENDULUM || Dyn::ID == ILQR_SYS_UA_DOUBLE_PENDULUM || Dyn::ID == ILQR_SYS_DOUBLE_PENDULUM;
 }
+// Bit i set: integrator i gets the persistent kernel's per-trajectory-parameter instantiation (else a solve with rows set
+// takes the fused multi-launch loop).  Independent of ILQR_PERSIST_INTEG_MASK, which keeps the shared-parameter routing.
+#ifndef ILQR_PERSIST_HET_INTEG_MASK
+#define ILQR_PERSIST_HET_INTEG_MASK 0x1f
+#endif
 
 template <typename T, typename Dyn, bool TILE, int INTEG> void set_integrator_ops(Ops<T>& o) {
     constexpr bool SMALL = all_integrators<Dyn>::value;
     // control limits on the fused and persistent kernels: n_u = 1 (u_t rides the tile's padding, FusedWG)
     constexpr bool FUSED_BOX = box_system<Dyn>() && Dyn::NU == 1;
     if constexpr (TILE && FUSED_BOX) o.fused_box = true;
+    // per-trajectory parameters (ilqr_set_batch_params): the systems that take control limits
+    constexpr bool HETS = box_system<Dyn>();
+    if constexpr (HETS) o.het = true;
     // n_x > 4 only has the closed-form integrators: fold the others onto euler so nothing big is compiled
     constexpr int I = (SMALL || INTEG == ILQR_INT_DISCRETE) ? INTEG : ILQR_INT_EULER;
     o.linearize[INTEG] = [](const KArgs<T>& a, hipStream_t s) {
         const size_t total = (size_t)a.B * (a.N + 1);
         constexpr int TPB = TILE ? 64 : 256;
+        if constexpr (HETS) {
+            if (a.het) {
+                ILQR_LAUNCH((linearize_kernel<T, Dyn, TILE, I, true>), dim3((unsigned)((total + TPB - 1) / TPB)), dim3(TPB), 0, s, a);
+                return;
+            }
+        }
         ILQR_LAUNCH((linearize_kernel<T, Dyn, TILE, I>), dim3((unsigned)((total + TPB - 1) / TPB)), dim3(TPB), 0, s, a);
     };
     if constexpr (TILE && ((ILQR_FUSE_INTEG_MASK >> I) & 1)) {
         o.fused[INTEG] = [](const KArgs<T>& a, hipStream_t s) {
             // with limits set (KArgs::box): the control-limited instantiation, n_u = 1 built-in systems only (FusedWG, BOX)
             if constexpr (FUSED_BOX) {
+                if (a.box && a.het) { launch_fused_kernel<T, Dyn, I, true, true>(a, s); return; }
                 if (a.box) { launch_fused_kernel<T, Dyn, I, true>(a, s); return; }
+            }
+            if constexpr (HETS) {
+                if (a.het) { launch_fused_kernel<T, Dyn, I, false, true>(a, s); return; }
             }
             launch_fused_kernel<T, Dyn, I, false>(a, s);
         };
@@ -260,9 +292,17 @@ template <typename T, typename Dyn, bool TILE, int INTEG> void set_integrator_op
                   ((ILQR_RING_INTEG_MASK >> I) & 1) && ((ILQR_PERSIST_INTEG_MASK >> I) & 1)) {
         constexpr bool BIG = I != ILQR_INT_BACKWARD_EULER && has_rebind<Dyn>::value && !ILQR_NO_PAIR_PRODUCERS;
         o.persist_big = o.persist_big || BIG;
+        constexpr bool PHET = HETS && ((ILQR_PERSIST_HET_INTEG_MASK >> I) & 1);
+        o.persist_het[INTEG] = PHET;
         o.persist[INTEG] = [](const KArgs<T>& a, const PArgs<T>& pa, hipStream_t s) {
+            if constexpr (FUSED_BOX && PHET) {
+                if (a.box && a.het) { launch_persist_kernel<T, Dyn, I, true, true>(a, pa, s); return; }
+            }
             if constexpr (FUSED_BOX) {
                 if (a.box) { launch_persist_kernel<T, Dyn, I, true>(a, pa, s); return; }
+            }
+            if constexpr (PHET) {
+                if (a.het) { launch_persist_kernel<T, Dyn, I, false, true>(a, pa, s); return; }
             }
             launch_persist_kernel<T, Dyn, I, false>(a, pa, s);
         };
@@ -278,9 +318,15 @@ template <typename T, typename Dyn, bool TILE, int INTEG> void set_integrator_op
             const size_t bytes_g = (size_t)a.N * a.B * gain_record(Dyn::NX, Dyn::NU) * sizeof(T);
             const bool fits = std::max(bytes_x, bytes_g) <= kDescriptorMax;
             if (fits && !plain) {
+                if constexpr (HETS) {
+                    if (a.het) { ILQR_LAUNCH((forward_ring_kernel_het<T, Dyn, I>), grid, block, 0, s, a); return; }
+                }
                 ILQR_LAUNCH((forward_ring_kernel<T, Dyn, I>), grid, block, 0, s, a);
                 return;
             }
+        }
+        if constexpr (HETS) {
+            if (a.het) { ILQR_LAUNCH((forward_kernel_het<T, Dyn, I>), grid, block, 0, s, a); return; }
         }
         ILQR_LAUNCH((forward_kernel<T, Dyn, I>), grid, block, 0, s, a);
     };
@@ -288,6 +334,10 @@ template <typename T, typename Dyn, bool TILE, int INTEG> void set_integrator_op
         // control limits: linearise into the generic [N][E][B] expansion the box sweep reads, clamped rollouts
         o.linearize_box[INTEG] = [](const KArgs<T>& a, hipStream_t s) {
             const size_t total = (size_t)a.B * (a.N + 1);
+            if (a.het) {
+                ILQR_LAUNCH((linearize_kernel<T, Dyn, false, I, true>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a);
+                return;
+            }
             ILQR_LAUNCH((linearize_kernel<T, Dyn, false, I>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a);
         };
         o.forward_box[INTEG] = [](const KArgs<T>& a, hipStream_t s) {
@@ -297,10 +347,12 @@ template <typename T, typename Dyn, bool TILE, int INTEG> void set_integrator_op
                 const size_t bytes_x = (size_t)a.n_slots * (a.N + 1) * Dyn::NX * a.B * sizeof(T);
                 const size_t bytes_g = (size_t)a.N * a.B * gain_record(Dyn::NX, Dyn::NU) * sizeof(T);
                 if (std::max(bytes_x, bytes_g) <= kDescriptorMax && !plain) {
+                    if (a.het) { ILQR_LAUNCH((forward_ring_kernel_box_het<T, Dyn, I>), grid, block, 0, s, a); return; }
                     ILQR_LAUNCH((forward_ring_kernel_box<T, Dyn, I>), grid, block, 0, s, a);
                     return;
                 }
             }
+            if (a.het) { ILQR_LAUNCH((forward_kernel_box_het<T, Dyn, I>), grid, block, 0, s, a); return; }
             ILQR_LAUNCH((forward_kernel_box<T, Dyn, I>), grid, block, 0, s, a);
         };
     }
@@ -379,6 +431,9 @@ template <typename T, typename Dyn> Ops<T> make_ops() {
         ILQR_LAUNCH((eval_points_kernel<T, Dyn>), dim3((a.npts + 63) / 64), dim3(64), 0, s, a);
     };
     o.mpc_advance = [](const MpcArgs<T>& a, hipStream_t s) {
+        if constexpr (box_system<Dyn>()) {
+            if (a.plant_rows) { ILQR_LAUNCH((mpc_advance_kernel<T, Dyn, true>), dim3((a.B + 63) / 64), dim3(64, kMpcChunks), 0, s, a); return; }
+        }
         ILQR_LAUNCH((mpc_advance_kernel<T, Dyn>), dim3((a.B + 63) / 64), dim3(64, kMpcChunks), 0, s, a);
     };
     o.n_dev_params = ParamLayout<Dyn::NSYS, NX, NU>::TOTAL;
@@ -465,7 +520,8 @@ template <typename T, int NX, int NU> Ops<T> make_ops_wave() {
 
 template <typename T> bool find_ops(int system, int nx, int nu, Ops<T>* out);
 
-// host: ABI parameter block (doubles) -> device parameter block (see dynamics.hpp)
+// host: ABI parameter block (doubles) -> device parameter block (see dynamics.hpp); also the source of every per-trajectory
+// row (SolverT::set_batch_params), so a row and a block with the same values derive the same constants
 inline std::vector<double> build_device_params(int system, int nx, int nu, const double* p) {
     std::vector<double> d;
     const double* q = p;
@@ -600,12 +656,20 @@ template <typename T> class SolverT : public SolverBase {
     // control limits (ilqr_set_control_limits): u_min <= u <= u_max for every control of every trajectory
     bool box_on = false;
     double box_lo[kBoxMaxU] = {0}, box_hi[kBoxMaxU] = {0};
+    // per-trajectory parameters (ilqr_set_batch_params): rows [n_sys + n_x][B] of the model (derived constants, x_target),
+    // plant_rows [n_sys][B] of the MPC plant; device tensors of the handle's dtype
+    std::vector<double> abi_params;   // the parameter block as given at ilqr_create
+    T *rows = nullptr, *plant_rows = nullptr;
+    bool model_rows_set = false, plant_rows_set = false;
+    bool het_on() const { return model_rows_set || plant_rows_set; }
 
     ~SolverT() override {
         if (stream) hipStreamSynchronize(stream);
         free_state(st);
         free_state(fn);
         hipFree(params);
+        hipFree(rows);
+        hipFree(plant_rows);
         hipFree(staging);
         hipFree(plant_x);
         hipFree(eval_buf);
@@ -687,6 +751,7 @@ template <typename T> class SolverT : public SolverBase {
         }
         std::vector<double> dp = build_device_params(c.system, NX, NU, c.params);
         if ((int)dp.size() != ops.n_dev_params) { err = "internal: device parameter block size mismatch"; return ILQR_ERR_INVALID_ARG; }
+        abi_params.assign(c.params, c.params + c.n_params);
         std::vector<T> dpt(dp.begin(), dp.end());
         ILQR_HIPCHK(hipMalloc((void**)&params, dpt.size() * sizeof(T)));
         ILQR_HIPCHK(hipMemcpy(params, dpt.data(), dpt.size() * sizeof(T), hipMemcpyHostToDevice));
@@ -722,6 +787,9 @@ template <typename T> class SolverT : public SolverBase {
             a.u_hi[i] = (T)box_hi[i];
         }
         a.box = box_on ? 1 : 0;
+        a.het = het_on() ? 1 : 0;
+        a.rows = het_on() ? rows : nullptr;
+        a.plant_rows = het_on() ? (plant_rows_set ? plant_rows : rows) : nullptr;
         return a;
     }
 
@@ -1053,6 +1121,7 @@ template <typename T> class SolverT : public SolverBase {
         static const bool off = getenv("ILQR_NO_PERSIST") != nullptr;   // A/B switch
         const size_t bytes_x = (size_t)st.n_slots * (N + 1) * NX * B * sizeof(T);
         return !off && !(cfg.flags & ILQR_FLAG_NO_PERSIST) && fused_ok() && ops.persist[cfg.integrator] && bytes_x <= kDescriptorMax &&
+               (!het_on() || ops.persist_het[cfg.integrator]) &&
                (B <= persist_small_max() || ops.persist_any_batch[cfg.integrator]);
     }
     int launch_persist(int n_iters, bool do_init, int n_mpc, const MpcArgs<T>* mpc) {
@@ -1340,6 +1409,57 @@ template <typename T> class SolverT : public SolverBase {
         return ILQR_OK;
     }
 
+    // ---- per-trajectory parameters ------------------------------------------------------
+    // which = ILQR_BATCH_MODEL: host rows [B][n_sys_abi + n_x] (system parameters in the block's order, x_target);
+    // ILQR_BATCH_PLANT: [B][n_sys_abi].  Every row is derived by build_device_params on a copy of the block with the row
+    // spliced in, and uploaded batch-innermost.  A plant without model rows leaves the model at the block: its rows are
+    // then the block's own, broadcast.
+    int set_batch_params(int which, const double* host_rows, int row_len) override {
+        if (which != ILQR_BATCH_MODEL && which != ILQR_BATCH_PLANT) { err = "set_batch_params: which must be ILQR_BATCH_MODEL or ILQR_BATCH_PLANT"; return ILQR_ERR_INVALID_ARG; }
+        const int ns = (int)abi_params.size() - (NX + 2 * NX * NX + NU * NU);   // system parameters of the ABI block
+        const int nh = ops.n_sys_dev + NX;     // device row: derived constants, x_target
+        if (host_rows) {
+            if (!ops.het) {
+                err = "set_batch_params: per-trajectory parameters are supported for the pendulum, UA double pendulum and double pendulum only";
+                return ILQR_ERR_UNSUPPORTED;
+            }
+            const int want = which == ILQR_BATCH_MODEL ? ns + NX : ns;
+            if (row_len != want) { err = "set_batch_params: row_len must be " + std::to_string(want); return ILQR_ERR_INVALID_ARG; }
+            for (size_t i = 0; i < (size_t)B * row_len; ++i)
+                if (!std::isfinite(host_rows[i])) { err = "set_batch_params: every value must be finite"; return ILQR_ERR_INVALID_ARG; }
+        }
+        if (int rf = flush_select()) return rf;
+        if (iter_graph) { hipGraphExecDestroy(iter_graph); iter_graph = nullptr; }   // (captured with the old arguments)
+        lin_stale = true;   // an expansion in HBM was taken at the old parameters
+        if (!rows) ILQR_HIPCHK(hipMalloc((void**)&rows, (size_t)nh * B * sizeof(T)));
+        if (which == ILQR_BATCH_PLANT && host_rows && !plant_rows) ILQR_HIPCHK(hipMalloc((void**)&plant_rows, (size_t)ops.n_sys_dev * B * sizeof(T)));
+        // one derived row per trajectory: [nh][B] (model) or [n_sys][B] (plant)
+        auto upload = [&](T* dev, int n_out, const double* src, int len) -> int {
+            std::vector<T> soa((size_t)n_out * B);
+            std::vector<double> blk = abi_params;
+            for (int b = 0; b < B; ++b) {
+                if (src) std::copy(src + (size_t)b * len, src + (size_t)(b + 1) * len, blk.begin());   // sys params, then x_target
+                const std::vector<double> d = build_device_params(cfg.system, NX, NU, blk.data());
+                for (int q = 0; q < n_out; ++q) soa[(size_t)q * B + b] = (T)d[q];
+            }
+            ILQR_HIPCHK(hipMemcpyAsync(dev, soa.data(), soa.size() * sizeof(T), hipMemcpyHostToDevice, stream));
+            ILQR_HIPCHK(hipStreamSynchronize(stream));
+            return ILQR_OK;
+        };
+        if (which == ILQR_BATCH_MODEL) {
+            model_rows_set = host_rows != nullptr;
+            if (host_rows) return upload(rows, nh, host_rows, row_len);
+        } else {
+            plant_rows_set = host_rows != nullptr;
+            if (host_rows) {
+                if (int ru = upload(plant_rows, ops.n_sys_dev, host_rows, row_len)) return ru;
+            }
+        }
+        // a plant without model rows: the model's rows are the block's
+        if (plant_rows_set && !model_rows_set) return upload(rows, nh, nullptr, 0);
+        return ILQR_OK;
+    }
+
     // ---- pure functional calls --------------------------------------------------------
     int ensure_fn() {
         if (fn.X) return ILQR_OK;
@@ -1502,6 +1622,7 @@ template <typename T> class SolverT : public SolverBase {
             m.B = B; m.N = N; m.plant_integ = cfg.plant_integrator; m.step = 0; m.dt = (T)cfg.dt; m.params = params;
             m.U = st.U; m.cur_slot = st.cur_slot; m.x0 = st.x0; m.plant_x = plant_x;
             m.u_log = mpc_u_log; m.x_log = mpc_x_log; m.cost_log = mpc_cost_log; m.cost = st.cost;
+            m.plant_rows = kargs(st).plant_rows;
             int rcp = launch_persist(cfg.maxiter, true, n_steps, &m);
             if (rcp) return rcp;
             have_rollout = true;
@@ -1513,6 +1634,7 @@ template <typename T> class SolverT : public SolverBase {
             m.B = B; m.N = N; m.plant_integ = cfg.plant_integrator; m.step = k; m.dt = (T)cfg.dt; m.params = params;
             m.U = st.U; m.cur_slot = st.cur_slot; m.x0 = st.x0; m.plant_x = plant_x;
             m.u_log = mpc_u_log; m.x_log = mpc_x_log; m.cost_log = mpc_cost_log; m.cost = st.cost;
+            m.plant_rows = kargs(st).plant_rows;
             timer.begin(ILQR_PHASE_OTHER, stream);
             ops.mpc_advance(m, stream);
             timer.end(stream);

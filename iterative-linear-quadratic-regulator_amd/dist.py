@@ -147,6 +147,17 @@ class StatusExchange:
                             n_active=int(round(float(g[:, 2].sum()))), n_converged=int(round(float(g[:, 3].sum()))))
 
 
+def shard_params(system, B, params, lo, hi, with_target=True):
+    """Rows lo:hi of the global batch's per-trajectory parameters (a dict for batch_param_rows), as such a dict."""
+    from .iLQR_class import batch_param_rows
+    rows = batch_param_rows(system, B, params, with_target)[lo:hi]
+    names = system.param_names()
+    out = {name: rows[:, j].copy() for j, name in enumerate(names)}
+    if with_target:
+        out["x_target"] = rows[:, len(names):].copy()
+    return out
+
+
 class ShardedBatch:
     """Splits a global batch (x0 (B, n), U_init (B, m, N)) over the ranks of the default process group
     and solves the local shard with ``iLQR``; ``global_status()`` is the RCCL all-reduce."""
@@ -163,7 +174,12 @@ class ShardedBatch:
         # the handle launches on torch's current stream, so torch events / collectives are ordered with its kernels
         ilqr_kw.setdefault("stream", torch.cuda.current_stream(device).cuda_stream or None)
         self._x0, self._U0 = x0[self.lo:self.hi], U_init[self.lo:self.hi]
-        self.solver = iLQR(system_factory(), None, self._x0, self._U0, device=device, verbose=False, **ilqr_kw)
+        system = system_factory()
+        # per-trajectory parameters are given for the global batch: this shard's rows, as for x0
+        for key, with_target in (("batch_params", True), ("plant_params", False)):
+            if ilqr_kw.get(key) is not None:
+                ilqr_kw[key] = shard_params(system, len(x0), ilqr_kw[key], self.lo, self.hi, with_target)
+        self.solver = iLQR(system, None, self._x0, self._U0, device=device, verbose=False, **ilqr_kw)
         self._stats = torch.zeros(4, dtype=torch.float64, device=f"cuda:{device}")
         self._xchg = None
 

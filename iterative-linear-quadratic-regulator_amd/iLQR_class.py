@@ -56,10 +56,53 @@ def control_limits(system, u_min, u_max):
     return out[0], out[1]
 
 
+def batch_param_rows(system, B, params, with_target=True):
+    """Per-trajectory parameter rows for ``ilqr_set_batch_params`` as a (B, row_len) float64 array.
+
+    params: {name: scalar or (B,)} for the system parameters (``system.param_names()``) and, with with_target,
+    ``"x_target"``: (n_x,) or (B, n_x).  Every name not given takes the system's own value.  Columns: the system
+    parameters in parameter-block order, then x_target (with_target).  Raises ValueError for an unknown name, a wrong
+    shape, a non-finite value, or a system without per-trajectory parameters.  Pure host code (no GPU)."""
+    if getattr(system, "SYSTEM_ID", None) not in _lib.BOX_SYSTEMS or getattr(system, "PARAM_NAMES", None) is None:
+        raise ValueError(f"per-trajectory parameters are supported for the pendulum, UA double pendulum and double "
+                         f"pendulum only, not for {type(system).__name__}")
+    B = int(B)
+    if B < 1:
+        raise ValueError(f"B must be >= 1, got {B}")
+    params = {} if params is None else dict(params)
+    names = system.param_names()
+    allowed = set(names) | ({"x_target"} if with_target else set())
+    unknown = sorted(set(params) - allowed)
+    if unknown:
+        raise ValueError(f"unknown parameter name(s) {unknown}; expected some of {sorted(allowed)}")
+    n_sys = len(names)
+    block = system.param_block()
+    n = system.n_x
+    rows = np.empty((B, n_sys + (n if with_target else 0)), dtype=np.float64)
+    for j, name in enumerate(names):
+        v = np.asarray(params.get(name, block[j]), dtype=np.float64)
+        if v.ndim == 0:
+            v = np.full(B, float(v))
+        if v.shape != (B,):
+            raise ValueError(f"{name} must be a scalar or have shape ({B},), but got {v.shape}")
+        rows[:, j] = v
+    if with_target:
+        xt = np.asarray(params.get("x_target", block[n_sys:n_sys + n]), dtype=np.float64)
+        if xt.shape == (n,):
+            xt = np.broadcast_to(xt, (B, n))
+        if xt.shape != (B, n):
+            raise ValueError(f"x_target must have shape ({n},) or ({B}, {n}), but got {xt.shape}")
+        rows[:, n_sys:] = xt
+    if not np.isfinite(rows).all():
+        raise ValueError("batch parameters must be finite (no NaN or inf)")
+    return rows
+
+
 class iLQR:
     def __init__(self, system: System, T=None, x_0=None, U_init=None, tol=1e-5, maxiter=100,
                  alpha_factor=0.5, min_alpha=1e-8, verbose=True, *, N=None, n_alpha=None, n_trials=10,
-                 dtype=None, device=0, mu=0.0, plant=None, flags=0, stream=None, u_min=None, u_max=None):
+                 dtype=None, device=0, mu=0.0, plant=None, flags=0, stream=None, u_min=None, u_max=None,
+                 batch_params=None, plant_params=None):
         self.system = system
         self.T = T
         self.tol, self.maxiter = tol, maxiter
@@ -96,6 +139,8 @@ class iLQR:
                              "(only its integrator may differ, run_iLQR_MPC.py:58-75)")
         self.plant = plant
         limits = control_limits(system, u_min, u_max)   # checked before any device is touched
+        model_rows = None if batch_params is None else batch_param_rows(system, self.B, batch_params)
+        plant_rows = None if plant_params is None else batch_param_rows(system, self.B, plant_params, with_target=False)
         trial_count = 0
         a = 1.0
         for _ in range(n_trials):         # how many alphas the Python loop can reach (:281, :300-302)
@@ -113,6 +158,11 @@ class iLQR:
         if limits is not None:
             self._h.set_control_limits(*limits)
         self.u_min, self.u_max = (None, None) if limits is None else limits
+        if model_rows is not None:
+            self._h.set_batch_params(_lib.BATCH_MODEL, model_rows)
+        if plant_rows is not None:
+            self._h.set_batch_params(_lib.BATCH_PLANT, plant_rows)
+        self.batch_params, self.plant_params = model_rows, plant_rows
         self._h.set_problem(x_0.reshape(self.B, self.n_x), U_init.reshape(self.B, self.n_u, self.N))
         self.status = None
         self.iterations = None
@@ -128,6 +178,20 @@ class iLQR:
         else:
             self._h.set_control_limits(*limits)
             self.u_min, self.u_max = limits
+
+    def set_batch_params(self, params):
+        """Per-trajectory system parameters and x_target of the model (include/ilqr_hip.h, ilqr_set_batch_params):
+        a dict for batch_param_rows, or None to fall back to the system's own.  Takes effect from the next kernel on."""
+        rows = None if params is None else batch_param_rows(self.system, self.B, params)
+        self._h.set_batch_params(_lib.BATCH_MODEL, rows)
+        self.batch_params = rows
+
+    def set_plant_params(self, params):
+        """Per-trajectory system parameters of the MPC plant (model mismatch): a dict of system parameters for
+        batch_param_rows (no x_target), or None to step the plant at the model's parameters again."""
+        rows = None if params is None else batch_param_rows(self.system, self.B, params, with_target=False)
+        self._h.set_batch_params(_lib.BATCH_PLANT, rows)
+        self.plant_params = rows
 
     # ---- state attributes (iLQR_class.py:55-61): reads are synchronised host copies ----
     def _out(self, a):

@@ -21,5 +21,7 @@ class MyUADoublePendulum(System):
         self.d1, self.d2, self.theta1, self.theta2 = float(d1), float(d2), float(theta1), float(theta2)
         self._set_cost(x_target, Q, R, Q_f)
 
+    PARAM_NAMES = ("g", "m1", "m2", "l1", "l2", "d1", "d2", "theta1", "theta2")
+
     def _system_params(self):
         return [self.g, self.m1, self.m2, self.l1, self.l2, self.d1, self.d2, self.theta1, self.theta2]

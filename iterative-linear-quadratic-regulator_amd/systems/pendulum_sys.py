@@ -18,5 +18,7 @@ class MyPendulum(System):
         self.g, self.l, self.d = float(g), float(l), float(d)
         self._set_cost(x_target, Q, R, Q_f)
 
+    PARAM_NAMES = ("g", "l", "d")
+
     def _system_params(self):
         return [self.g, self.l, self.d]

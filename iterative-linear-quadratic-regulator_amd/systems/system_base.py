@@ -69,6 +69,15 @@ class System:
                  np.asarray(self.Q_f, dtype=np.float64).reshape(n * n)]
         return np.concatenate(parts)
 
+    # names of the system parameters in parameter-block order (ilqr_set_batch_params), or None: no per-trajectory rows
+    PARAM_NAMES = None
+
+    def param_names(self):
+        """Names of the system parameters in parameter-block order (the leading part of ``param_block()``)."""
+        if self.PARAM_NAMES is None:
+            raise ValueError(f"{type(self).__name__} has no per-trajectory system parameters")
+        return tuple(self.PARAM_NAMES)
+
     def same_dynamics(self, other):
         """Same continuous dynamics and cost (the MPC plant may differ from the model in its integrator only)."""
         return np.array_equal(self.param_block(), other.param_block())
