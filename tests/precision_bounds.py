@@ -1,0 +1,48 @@
+"""fp64 parity bounds of the device kernels against the fp64 oracle, in one place (test helper, not a test module).
+
+Every bound is a matrix-level relative error, max|got - want| <= bound * max|want| (`rel_err`).  The GPU tests
+(tests/test_fp64_resolution_gpu.py and the fp64 sites of the older parity files) assert them; the CPU test
+tests/test_precision_bounds_cpu.py runs the same operations through the oracle in fp32 and asserts that an fp32 result
+misses each bound by at least SEPARATION, so a float-width intermediate in an fp64 kernel cannot pass.
+
+Caps: SINGLE_STAGE for one sweep / one rollout, SOLVE for whole solves and closed loops.  Each bound below is about
+100x the worst case measured on the MI355X (the number in the comment), and never above its cap.
+"""
+import numpy as np
+
+SINGLE_STAGE = 1e-9
+SOLVE = 1e-8
+SEPARATION = 10.0
+
+BOUNDS = {
+    # one backward sweep, K_t and k_t
+    "sweep": 2e-12,            # pendulum / UA / dp (DPP tile sweep, (4, 2) step), N <= 200: measured 1.8e-14
+    "sweep_wave": 2e-13,       # LQ (16, 8) and (8, 4), wave kernels: measured 1.6e-15
+    "sweep_c5": 5e-13,         # LQ (16, 8) at N = 500, f64 MFMA sweep: measured 5.1e-15
+    "sweep_mu": 3e-12,         # Levenberg mu > 0: measured 2.4e-14
+    "sweep_tensors": 8e-11,    # RiccatiSweep on random caller-supplied expansions: measured 7.2e-13 (16, 8, 40)
+    # one rollout: X, U and cost
+    "rollout": 3e-13,          # measured 2.4e-15 (LQ (16, 8)); UA, every integrator, 5.6e-16
+    # whole solves: K, X, U, cost (every route, c1 .. c5 shapes, control limits): measured 1.7e-13 (dp, box)
+    "solve": 2e-11,
+    # U_ff of a whole solve, against the control scale max(|U_ff|, |U|): at a converged trajectory k_t = -Q_uu^-1 Q_u
+    # is a residual (Q_u -> 0 by cancellation, |k| ~ 1e-4 of |U|), so against its own size it is conditioning-limited
+    # (measured up to 2.5e-9 relative to max|U_ff|, UA N = 7); against the control it corrects: measured 1.6e-13
+    "solve_uff": 2e-11,
+    # MPC closed loops (U_sim, X_sim, costs): measured 1.7e-14
+    "mpc": 2e-12,
+}
+
+
+def rel_err(got, want, scale=None):
+    """max|got - want| / max(max|want|, scale) in float64."""
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    ref = max(np.abs(want).max(), 0.0 if scale is None else float(np.abs(scale).max()), 1e-300)
+    return float(np.abs(got - want).max() / ref)
+
+
+def assert_close(got, want, key, what="", scale=None):
+    """rel_err(got, want, scale) <= BOUNDS[key]; the measured error is printed (pytest -s shows it)."""
+    err, bound = rel_err(got, want, scale), BOUNDS[key]
+    print(f"MEASURED {key} {what}: {err:.3e}")
+    assert err <= bound, f"{what}: relative error {err:.3e} > {bound:.1e} ({key})"

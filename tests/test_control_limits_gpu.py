@@ -16,6 +16,7 @@ from ilqr_amd import _lib, problems
 from oracle.build import oracle_from_spec
 
 from box_ddp_ref import BoxDDP, box_backward_pass, box_forward_pass, box_mpc_closed_loop
+from precision_bounds import assert_close
 
 pytestmark = pytest.mark.gpu
 
@@ -122,6 +123,9 @@ def test_full_solve_matches_reference(name):
         np.testing.assert_allclose(uff[b], o.U_ff, rtol=1e-4, atol=1e-7)
         np.testing.assert_allclose(X[b], Xo, rtol=1e-5, atol=1e-7)
         np.testing.assert_allclose(U[b], Uo, rtol=1e-5, atol=1e-7)
+        for what, got, want in (("K", K[b], o.K), ("X", X[b], Xo), ("U", U[b], Uo), ("cost", cost[b], co)):
+            assert_close(got, want, "solve", f"{name} box {what}")
+        assert_close(uff[b], o.U_ff, "solve_uff", f"{name} box U_ff", scale=Uo)
 
 
 def _solve(sysm, x0, U0, dtype, flags, **lim):

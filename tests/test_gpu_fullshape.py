@@ -30,6 +30,8 @@ from ilqr_amd import _lib, problems
 from oracle.c_oracle import COracle
 from oracle.parallel import solve_many
 
+from precision_bounds import assert_close
+
 pytestmark = pytest.mark.gpu
 
 RTOL = 1e-5
@@ -158,6 +160,10 @@ def test_c3_fp64_full_batch_is_exact():
         np.testing.assert_allclose(uff[b], r["U_ff"], rtol=RTOL, atol=1e-9)
         np.testing.assert_allclose(X[b], r["X"], rtol=1e-6, atol=1e-8)
         np.testing.assert_allclose(U[b], r["U"], rtol=1e-6, atol=1e-8)
+        for what in ("K", "X", "U"):
+            got = {"K": K, "X": X, "U": U}[what][b]
+            assert_close(got, r[what], "solve", f"c3 fp64 {what} (trajectory {b})")
+        assert_close(uff[b], r["U_ff"], "solve_uff", f"c3 fp64 U_ff (trajectory {b})", scale=r["U"])
 
 
 def test_c2_full_shape():
@@ -179,6 +185,9 @@ def test_c2_full_shape():
             np.testing.assert_allclose(K[b], r["K"], rtol=1e-4, atol=1e-7)
             np.testing.assert_allclose(uff[b], r["U_ff"], rtol=1e-4, atol=1e-7)
             np.testing.assert_allclose(U[b], r["U"], rtol=1e-5, atol=1e-7)
+            for what, got in (("K", K[b]), ("X", X[b]), ("U", U[b]), ("cost", cost[b])):
+                assert_close(got, r[what], "solve", f"c2 {what} (trajectory {b})")
+            assert_close(uff[b], r["U_ff"], "solve_uff", f"c2 U_ff (trajectory {b})", scale=r["U"])
     # fp32: rollout cost and the first sweep's gains for the whole batch
     s32 = ilqr_amd.iLQR(ilqr_amd.make_system(p["dynamics"], p["cost"], np.float32), None, x0, U0, N=200, verbose=False)
     z = lambda *sh: np.zeros(sh)
@@ -249,6 +258,42 @@ def test_c4_shard_full_shape():
     # (the closed-loop state likewise: 3 of 1024 instances beyond 1e-3 of the state scale, max 6.5e-3; 99.5th percentile 6.6e-4)
     dx = np.abs(X32 - X_sim).max(axis=(0, 2)) / max(1.0, np.abs(X_sim).max())
     assert np.quantile(dx, 0.995) <= 1e-3 and dx.max() <= 2e-2, (np.quantile(dx, 0.995), dx.max())
+    # the outliers, one by one from the worst down (measured: instances 257, 548, 523; cost 1.4e-3, 7.0e-5, 5.0e-5, state
+    # 6.5e-3, 1.1e-3, 1.06e-3), replayed through the fp32 C oracle's closed loop: each step matches it at 1e-4, or the
+    # step is a cold solve (step 0) that the device, solving that instance alone, reproduces and ends at another iteration
+    # count than the oracle.  Measured: instance 257 step 0 -- 8 device iterations against another count in the oracle,
+    # final costs 1.36e-3 apart, and the device's cost after 8 iterations is 1.35e-3 from the oracle's after 8: the two
+    # fp32 solves part before the end, so "stopping one iteration early" alone does not explain it.  That gap is held at
+    # 2e-3.  Every other instance is held to the round-2 bounds: cost 1e-4, state 1e-3 of the state scale.
+    rel_b = rel.max(axis=0)
+    out = []
+    mask = (rel_b > 1e-4) | (dx > 1e-3)
+    while mask.any():
+        b = int(np.argmax(np.where(mask, np.maximum(rel_b / 1e-4, dx / 1e-3), -1.0)))
+        out.append(b)
+        mask[b] = False
+    print(f"MEASURED c4 fp32 outliers {out}: cost {rel_b[out] if out else []}, state {dx[out] if out else []}")
+    for b in out:
+        x, U_guess, state = x032[b].copy(), U032[b].copy(), None
+        for k in range(n_sim):
+            r = co32.solve(x, U_guess, tol=p["tol"], maxiter=p["maxiter"], state=state)
+            if abs(float(c32[k, b]) - float(r["cost"])) > 1e-4 * abs(float(r["cost"])):
+                # only a cold solve (step 0) can be replayed alone on the device; later steps start from it
+                assert k == 0, f"fp32 outlier {b}: step {k} differs from the fp32 oracle's closed loop"
+                one = ilqr_amd.iLQR(ilqr_amd.make_system(p["dynamics"], p["cost"], np.float32), None, x032[b:b + 1],
+                                    U032[b:b + 1], N=200, tol=p["tol"], maxiter=p["maxiter"], verbose=False)
+                _, _, c_one = one.optimize_trajectory()
+                _close(c_one[0], c32[0, b], 1e-6, f"outlier {b}: the device's solve alone vs its MPC step 0")
+                it = int(one.iterations[0])
+                assert it != r["iterations"], (b, it, r["iterations"])
+                _close(c32[0, b], r["cost"], 2e-3, f"outlier {b}: fp32 device vs fp32 oracle, cold solve")
+                break
+            x = np.asarray(plant32.step(x, r["U"][:, 0], jac=False)[0], np.float32)
+            U_guess = np.concatenate([r["U"][:, 1:], r["U"][:, -1:]], axis=1).astype(np.float32)
+            state = (r["X"], r["U_ff"], r["K"])
+    keep = np.setdiff1d(np.arange(B), out)
+    assert len(out) <= 4, out
+    assert rel_b[keep].max() <= 1e-4 and dx[keep].max() <= 1e-3, (rel_b[keep].max(), dx[keep].max())
 
 
 def test_c5_shard_full_shape():
@@ -271,6 +316,8 @@ def test_c5_shard_full_shape():
             if dtype == np.float64:
                 np.testing.assert_allclose(K[b], K_o, rtol=RTOL, atol=1e-9)
                 np.testing.assert_allclose(uff[b], uff_o, rtol=RTOL, atol=1e-9)
+                assert_close(K[b], K_o, "sweep_c5", "c5 K")
+                assert_close(uff[b], uff_o, "sweep_c5", "c5 k")
             _close(K[b], K_o, RTOL, "K")
             _close(uff[b], uff_o, RTOL, "k")
         Xs, Us, cost = s.optimize_trajectory()
@@ -328,6 +375,8 @@ def test_c5_whole_batch_on_one_gpu():
             if dtype == np.float64:
                 np.testing.assert_allclose(K[b], K_o, rtol=RTOL, atol=1e-9)
                 np.testing.assert_allclose(uff[b], uff_o, rtol=RTOL, atol=1e-9)
+                assert_close(K[b], K_o, "sweep_c5", "c5 B=1024 K")
+                assert_close(uff[b], uff_o, "sweep_c5", "c5 B=1024 k")
             _close(K[b], K_o, RTOL, "K")
             _close(uff[b], uff_o, RTOL, "k")
         Xs, Us, cost = s.optimize_trajectory()
@@ -339,6 +388,8 @@ def test_c5_whole_batch_on_one_gpu():
                 assert int(s.iterations[b]) == r["iterations"]
                 np.testing.assert_allclose(Us[b], r["U"], rtol=1e-5, atol=1e-8)
                 np.testing.assert_allclose(s.K[b], r["K"], rtol=1e-5, atol=1e-9)
+                assert_close(s.K[b], r["K"], "solve", "c5 B=1024 solve K")
+                assert_close(Us[b], r["U"], "solve", "c5 B=1024 solve U")
 
 
 def test_c1_as_the_driver_runs_it():
@@ -358,5 +409,8 @@ def test_c1_as_the_driver_runs_it():
             np.testing.assert_allclose(U, g["U"], rtol=1e-5, atol=1e-7)
             np.testing.assert_allclose(s.K, g["K"], rtol=1e-4, atol=1e-7)
             np.testing.assert_allclose(s.U_ff, g["U_ff"], rtol=1e-4, atol=1e-7)
+            for what, got in (("K", s.K), ("X", X), ("U", U), ("cost", cost)):
+                assert_close(got, g[what], "solve", f"c1 {what}")
+            assert_close(s.U_ff, g["U_ff"], "solve_uff", "c1 U_ff", scale=g["U"])
         else:
             _close(X, g["X"], 1e-4, "X fp32")

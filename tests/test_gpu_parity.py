@@ -11,6 +11,8 @@ from ilqr_amd import _lib, problems
 from oracle import backward_pass, forward_pass, iLQROracle, mpc_closed_loop
 from oracle.build import oracle_from_spec, oracle_from_system
 
+from precision_bounds import assert_close
+
 pytestmark = pytest.mark.gpu
 
 RTOL = 1e-5
@@ -76,6 +78,8 @@ def test_backward_pass_matches_oracle(name, dtype):
         if dtype == np.float64:
             np.testing.assert_allclose(K[b], K_o, rtol=RTOL, atol=1e-9)
             np.testing.assert_allclose(uff[b], uff_o, rtol=RTOL, atol=1e-9)
+            assert_close(K[b], K_o, "sweep", f"{name} K")
+            assert_close(uff[b], uff_o, "sweep", f"{name} k")
         _close(K[b], K_o, RTOL, "K")
         _close(uff[b], uff_o, RTOL, "k")
 
@@ -104,6 +108,9 @@ def test_forward_pass_matches_oracle(name, alpha, dtype):
         if dtype == np.float64:
             np.testing.assert_allclose(Xn[b], Xo, rtol=1e-6, atol=1e-8)
             np.testing.assert_allclose(Un[b], Uo, rtol=1e-6, atol=1e-8)
+            assert_close(Xn[b], Xo, "rollout", f"{name} X")
+            assert_close(Un[b], Uo, "rollout", f"{name} U")
+            assert_close(c[b], co, "rollout", f"{name} cost")
         else:
             _close(Xn[b], Xo, 1e-4, "X")
 
@@ -154,6 +161,9 @@ def test_full_solve_matches_oracle(name, maxiter):
         np.testing.assert_allclose(uff[b], o.U_ff, rtol=1e-4, atol=1e-7)
         np.testing.assert_allclose(X[b], Xo, rtol=1e-5, atol=1e-7)
         np.testing.assert_allclose(U[b], Uo, rtol=1e-5, atol=1e-7)
+        for what, got, want in (("K", K[b], o.K), ("X", X[b], Xo), ("U", U[b], Uo), ("cost", cost[b], co)):
+            assert_close(got, want, "solve", f"{name} {what}")
+        assert_close(uff[b], o.U_ff, "solve_uff", f"{name} U_ff", scale=Uo)
 
 
 def test_unbatched_api_matches_reference_layouts():
@@ -235,12 +245,16 @@ def test_linear_quadratic_wave_kernels_match_oracle(n, m, N):
         uff_o, K_o = backward_pass(orc, X[b], U[b])
         np.testing.assert_allclose(K[b], K_o, rtol=RTOL, atol=1e-9)
         np.testing.assert_allclose(uff[b], uff_o, rtol=RTOL, atol=1e-9)
+        assert_close(K[b], K_o, "sweep_wave", f"({n}, {m}) K")
+        assert_close(uff[b], uff_o, "sweep_wave", f"({n}, {m}) k")
     Xs, Us, cost = s.optimize_trajectory()
     for b in range(B):
         o = iLQROracle(orc, N=N, x_0=x0[b], U_init=U0[b], tol=1e-9, maxiter=4)
         Xo, Uo, co = o.optimize_trajectory()
         np.testing.assert_allclose(cost[b], co, rtol=RTOL)
         np.testing.assert_allclose(Us[b], Uo, rtol=1e-5, atol=1e-8)
+        assert_close(Us[b], Uo, "solve", f"({n}, {m}) U")
+        assert_close(cost[b], co, "solve", f"({n}, {m}) cost")
         assert o.history[0][1] == 1.0   # LQ: the full step is accepted and is optimal
     # known answer: iLQR gains of an LQ problem = finite-horizon discrete Riccati recursion
     A, Bm, dt = p["dynamics"]["A"], p["dynamics"]["B"], p["dynamics"]["dt"]
@@ -269,6 +283,8 @@ def test_levenberg_regularisation_matches_oracle(name):
         uff_o, K_o = backward_pass(orc, X[b], U[b], mu=mu)
         np.testing.assert_allclose(K[b], K_o, rtol=RTOL, atol=1e-9)
         np.testing.assert_allclose(uff[b], uff_o, rtol=RTOL, atol=1e-9)
+        assert_close(K[b], K_o, "sweep_mu", f"{name} K")
+        assert_close(uff[b], uff_o, "sweep_mu", f"{name} k")
 
 
 @pytest.mark.parametrize("B,N", [(1, 7), (5, 13), (17, 41), (67, 9)])
@@ -285,6 +301,8 @@ def test_ragged_batch_and_horizon_sizes(B, N):
         _, Uo, co = o.optimize_trajectory()
         np.testing.assert_allclose(cost[b], co, rtol=RTOL)
         np.testing.assert_allclose(s.K[b], o.K, rtol=1e-4, atol=1e-7)
+        assert_close(s.K[b], o.K, "solve", f"B={B} N={N} K")
+        assert_close(cost[b], co, "solve", f"B={B} N={N} cost")
 
 
 def test_finished_trajectories_are_frozen():
@@ -433,6 +451,9 @@ def test_riccati_sweep_on_caller_supplied_tensors(n, m, N, dtype):
         k_o, K_o = backward_tensors(*[a[b] for a in ex])
         _close(K[b], K_o, RTOL, f"K n={n} m={m}")
         _close(k[b], k_o, RTOL, f"k n={n} m={m}")
+        if dtype == np.float64:
+            assert_close(K[b], K_o, "sweep_tensors", f"K n={n} m={m}")
+            assert_close(k[b], k_o, "sweep_tensors", f"k n={n} m={m}")
 
 
 def test_tensor_sweep_reproduces_the_system_sweep():

@@ -1,0 +1,136 @@
+"""The fp64 bounds of tests/precision_bounds.py separate the precisions (no GPU needed).
+
+Each operation the fp64 resolution tests check (tests/test_fp64_resolution_gpu.py) is run here through the oracle in fp32
+-- the C oracle's fp32 build where it has the operation, the NumPy oracle in fp32 for the Levenberg and caller-tensor
+sweeps -- on the same fp32-rounded inputs, and compared with the fp64 oracle.  Every component must miss its fp64 bound
+by at least SEPARATION: a device kernel that did part of its work at float width would fail the GPU test."""
+import numpy as np
+import pytest
+
+from ilqr_amd import problems
+from oracle import backward_pass
+from oracle.build import oracle_from_spec
+from oracle.c_oracle import COracle
+from oracle.ilqr import backward_tensors
+
+from precision_bounds import BOUNDS, SEPARATION, SINGLE_STAGE, SOLVE, rel_err
+
+F32 = np.float32
+
+
+def _rd(a):
+    return np.asarray(a, np.float64).astype(F32).astype(np.float64)
+
+
+def _rand_traj(n, m, N, seed, scale):
+    rng = np.random.default_rng(seed)
+    return _rd(rng.standard_normal((n, N + 1)) * scale), _rd(rng.standard_normal((m, N)) * scale)
+
+
+def _separates(key, errors):
+    bound = BOUNDS[key]
+    for what, err in errors.items():
+        assert err >= SEPARATION * bound, f"{key} {what}: the fp32 error {err:.3e} is within {SEPARATION:g}x of {bound:.1e}"
+
+
+def test_bounds_are_within_their_caps():
+    for key, bound in BOUNDS.items():
+        cap = SOLVE if key in ("solve", "solve_uff", "mpc") else SINGLE_STAGE
+        assert 0 < bound <= cap, (key, bound)
+
+
+@pytest.mark.parametrize("name,N", [("pendulum", 200), ("ua", 200), ("dp", 200)])
+def test_sweep_bound_separates(name, N):
+    p = {"pendulum": problems.pendulum_open_loop(N=N, integrator="rk4"), "ua": problems.ua_double_pendulum(N=N),
+         "dp": problems.double_pendulum(N=N)}[name]
+    c64, c32 = COracle(p["dynamics"], p["cost"]), COracle(p["dynamics"], p["cost"], dtype=F32)
+    n, m = c64.n, c64.m
+    X, U = _rand_traj(n, m, N, seed=11, scale=0.7)
+    k64, K64 = c64.backward_pass(X, U)
+    k32, K32 = c32.backward_pass(X, U)
+    _separates("sweep", {"K": rel_err(K32, K64), "k": rel_err(k32, k64)})
+
+
+@pytest.mark.parametrize("n,m,N,key", [(16, 8, 60, "sweep_wave"), (8, 4, 33, "sweep_wave"), (16, 8, 500, "sweep_c5")])
+def test_lq_sweep_bounds_separate(n, m, N, key):
+    p = problems.linear_quadratic(n=n, m=m, N=N)
+    c64, c32 = COracle(p["dynamics"], p["cost"]), COracle(p["dynamics"], p["cost"], dtype=F32)
+    X, U = _rand_traj(n, m, N, seed=4, scale=1.0)
+    k64, K64 = c64.backward_pass(X, U)
+    k32, K32 = c32.backward_pass(X, U)
+    _separates(key, {"K": rel_err(K32, K64), "k": rel_err(k32, k64)})
+
+
+@pytest.mark.parametrize("name", ["ua", "lq16"])
+def test_levenberg_bound_separates(name):
+    p = problems.linear_quadratic(n=16, m=8, N=25) if name == "lq16" else problems.ua_double_pendulum(N=60)
+    o64 = oracle_from_spec(p["dynamics"], p["cost"])
+    o32 = oracle_from_spec(p["dynamics"], p["cost"], dtype=F32)
+    X, U = _rand_traj(o64.n_x, o64.n_u, p["N"], seed=8, scale=0.5)
+    k64, K64 = backward_pass(o64, X, U, mu=0.37)
+    k32, K32 = backward_pass(o32, X, U, mu=0.37)
+    _separates("sweep_mu", {"K": rel_err(K32, K64), "k": rel_err(k32, k64)})
+
+
+@pytest.mark.parametrize("n,m,N", [(4, 1, 120), (16, 8, 40)])
+def test_tensor_sweep_bound_separates(n, m, N):
+    rng = np.random.default_rng(100 + n * 10 + m)
+    f_x = np.eye(n) * 0.95 + rng.standard_normal((N, n, n)) * (0.3 / np.sqrt(n))
+    f_u = rng.standard_normal((N, n, m)) * 0.5
+    W = rng.standard_normal((N, n + m, n + m)) * 0.3
+    H = W @ np.swapaxes(W, -1, -2) + np.eye(n + m) * 0.5
+    Wf = rng.standard_normal((n, n))
+    ex = [_rd(a) for a in (f_x, f_u, rng.standard_normal((N, n)), rng.standard_normal((N, m)), H[:, :n, :n],
+                           H[:, n:, :n], H[:, n:, n:], rng.standard_normal(n), Wf @ Wf.T + np.eye(n))]
+    k64, K64 = backward_tensors(*ex)
+    k32, K32 = backward_tensors(*ex, dtype=F32)
+    _separates("sweep_tensors", {"K": rel_err(K32, K64), "k": rel_err(k32, k64)})
+
+
+@pytest.mark.parametrize("integrator", ["rk4", "backward_euler", "euler", "midpoint"])
+def test_rollout_bound_separates(integrator):
+    p = problems.ua_double_pendulum(N=100, integrator=integrator)
+    c64, c32 = COracle(p["dynamics"], p["cost"]), COracle(p["dynamics"], p["cost"], dtype=F32)
+    n, m, N = 4, 1, 100
+    rng = np.random.default_rng(5)
+    X, U = _rand_traj(n, m, N, seed=3, scale=0.3)
+    uff, K, x0 = _rd(rng.standard_normal((m, N)) * 0.1), _rd(rng.standard_normal((N, m, n)) * 0.1), \
+        _rd(rng.standard_normal(n) * 0.3)
+    for alpha in (1.0, 0.25):
+        X64, U64, c64_ = c64.forward_pass(x0, alpha, X, U, uff, K)
+        X32, U32, c32_ = c32.forward_pass(x0, alpha, X, U, uff, K)
+        _separates("rollout", {"X": rel_err(X32, X64), "U": rel_err(U32, U64), "cost": rel_err(c32_, c64_)})
+
+
+@pytest.mark.parametrize("N", [41, 200])
+def test_solve_bound_separates(N):
+    p = problems.ua_double_pendulum(N=N)
+    c64, c32 = COracle(p["dynamics"], p["cost"]), COracle(p["dynamics"], p["cost"], dtype=F32)
+    x0, U0 = problems.ua_batch(4, seed=N, restarts=True, N=N)
+    for b in range(4):
+        x, U = _rd(x0[b]), _rd(U0[b])
+        r64, r32 = c64.solve(x, U, tol=p["tol"], maxiter=10), c32.solve(x, U, tol=p["tol"], maxiter=10)
+        _separates("solve", {w: rel_err(r32[w], r64[w]) for w in ("K", "X", "U", "cost")})
+        _separates("solve_uff", {"U_ff": rel_err(r32["U_ff"], r64["U_ff"], scale=r64["U"])})
+
+
+def test_mpc_bound_separates():
+    p = problems.ua_double_pendulum(N=100)
+    x0, U0 = problems.ua_batch(2, seed=2, restarts=False, N=100)
+    loops = {}
+    for dt in (np.float64, F32):
+        co = COracle(p["dynamics"], p["cost"], dtype=dt)
+        plant = COracle(p["dynamics"], p["cost"], integrator="backward_euler", dtype=dt)
+        x, U_guess, state = _rd(x0[0]), _rd(U0[0]), None
+        us, xs, cs = [], [], []
+        for _ in range(3):
+            r = co.solve(x, U_guess, tol=p["tol"], maxiter=10, state=state)
+            x = plant.step(x, r["U"][:, 0], jac=False)[0]
+            us.append(r["U"][:, 0].astype(np.float64))
+            xs.append(x.astype(np.float64))
+            cs.append(float(r["cost"]))
+            U_guess = np.concatenate([r["U"][:, 1:], r["U"][:, -1:]], axis=1)
+            state = (r["X"], r["U_ff"], r["K"])
+        loops[dt] = (np.array(us), np.array(xs), np.array(cs))
+    a, b = loops[np.float64], loops[F32]
+    _separates("mpc", {"U_sim": rel_err(b[0], a[0]), "X_sim": rel_err(b[1], a[1]), "costs": rel_err(b[2], a[2])})

@@ -13,6 +13,8 @@ from ilqr_amd import problems
 from oracle import iLQROracle, mpc_closed_loop
 from oracle.build import oracle_from_spec
 
+from precision_bounds import assert_close
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -37,6 +39,8 @@ def test_open_loop_driver_default_arguments(tmp_path, capsys):
     np.testing.assert_allclose(out["X"], g["X"], rtol=1e-5, atol=1e-7)
     np.testing.assert_allclose(out["U"], g["U"], rtol=1e-5, atol=1e-7)
     np.testing.assert_allclose(out["K"], g["K"], rtol=1e-4, atol=1e-7)
+    for what in ("K", "X", "U", "cost"):
+        assert_close(out[what], g[what], "solve", f"open-loop driver {what}")
     assert fig.exists() and fig.stat().st_size > 10000
     text = capsys.readouterr().out
     assert f"Initial cost: {float(g['initial_cost']):.4f}" in text       # iLQR_class.py:262
