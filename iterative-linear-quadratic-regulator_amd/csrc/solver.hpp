@@ -1033,7 +1033,10 @@ template <typename T> class SolverT : public SolverBase {
         }
         s.box_lin_valid = false;
         KArgs<T> a = kargs(s);
-        const bool sparse = !full && ops.const_lin && ops.sweep_reads_sparse && ops.sweep_reads_sparse((T)cfg.mu);
+        // (the sparse form's dense gradients [N][B][n_x + n_u] at the front of the buffer must end before the records of
+        // t = N-1 begin: at N = 1 they would share record 0, whose matrices the linearisation writes over them)
+        const bool fits = (size_t)(N - 1) * ops.lin_stride >= (size_t)N * (NX + NU);
+        const bool sparse = !full && fits && ops.const_lin && ops.sweep_reads_sparse && ops.sweep_reads_sparse((T)cfg.mu);
         a.lin_sparse = sparse ? 1 : 0;
         s.lin_full = !sparse;
         timer.begin(ILQR_PHASE_LINEARIZE, stream);

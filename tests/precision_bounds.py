@@ -31,7 +31,41 @@ BOUNDS = {
     "solve_uff": 2e-11,
     # MPC closed loops (U_sim, X_sim, costs): measured 1.7e-14
     "mpc": 2e-12,
+    # one MPC plant step on the device's own (x, u_0), every plant integrator, shared and per-trajectory rows: measured
+    # 3.7e-15 (dp, euler plant)
+    "plant_step": 4e-13,
+    # LQ closed loop against its exact answer (lq_closed_loop), every linear shape, N = 1 .. 514: measured 1.9e-14
+    # ((2, 1), N = 514)
+    "mpc_lq": 2e-12,
 }
+
+
+def lq_closed_loop(A, Bm, Q, R, Q_f, x_target, dt, N, x0, n_steps):
+    """The exact receding-horizon loop of a time-invariant LQ problem (x+ = A x + B u; stage cost dt ((x - x_t)' Q (x - x_t)
+    + u' R u), terminal (x - x_t)' Q_f (x - x_t)), in float64.  Every solve of the loop ends at the optimum, whose first
+    control is the affine feedback u = K_0 x + k_0 of the finite-horizon Riccati recursion (the gains as in
+    tests/test_gpu_parity.py::test_linear_quadratic_wave_kernels_match_oracle, plus the affine term of the target):
+        K_t = -(R dt + B' P B)^-1 B' P A,  k_t = -(R dt + B' P B)^-1 B' s,
+        P <- Q dt + A' P (A + B K_t),      s <- -Q dt x_t + K_t' R dt k_t + (A + B K_t)' (P B k_t + s),
+    from P = Q_f, s = -Q_f x_t.  Returns (u (n_steps, m), x after each step (n_steps, n))."""
+    A, Bm = np.asarray(A, np.float64), np.asarray(Bm, np.float64)
+    Qd, Rd, P = np.asarray(Q, np.float64) * dt, np.asarray(R, np.float64) * dt, np.asarray(Q_f, np.float64).copy()
+    xt = np.asarray(x_target, np.float64)
+    s = -P @ xt
+    for _ in range(N):
+        H = Rd + Bm.T @ P @ Bm
+        K = -np.linalg.solve(H, Bm.T @ P @ A)
+        k = -np.linalg.solve(H, Bm.T @ s)
+        Acl = A + Bm @ K
+        s = -Qd @ xt + K.T @ Rd @ k + Acl.T @ (P @ Bm @ k + s)
+        P = Qd + A.T @ P @ Acl
+    x, us, xs = np.asarray(x0, np.float64), [], []
+    for _ in range(n_steps):
+        u = K @ x + k
+        x = A @ x + Bm @ u
+        us.append(u)
+        xs.append(x)
+    return np.array(us), np.array(xs)
 
 
 def rel_err(got, want, scale=None):

@@ -13,7 +13,7 @@ from oracle.build import oracle_from_spec
 from oracle.c_oracle import COracle
 from oracle.ilqr import backward_tensors
 
-from precision_bounds import BOUNDS, SEPARATION, SINGLE_STAGE, SOLVE, rel_err
+from precision_bounds import BOUNDS, SEPARATION, SINGLE_STAGE, SOLVE, lq_closed_loop, rel_err
 
 F32 = np.float32
 
@@ -35,7 +35,7 @@ def _separates(key, errors):
 
 def test_bounds_are_within_their_caps():
     for key, bound in BOUNDS.items():
-        cap = SOLVE if key in ("solve", "solve_uff", "mpc") else SINGLE_STAGE
+        cap = SOLVE if key in ("solve", "solve_uff", "mpc", "mpc_lq") else SINGLE_STAGE
         assert 0 < bound <= cap, (key, bound)
 
 
@@ -134,3 +134,52 @@ def test_mpc_bound_separates():
         loops[dt] = (np.array(us), np.array(xs), np.array(cs))
     a, b = loops[np.float64], loops[F32]
     _separates("mpc", {"U_sim": rel_err(b[0], a[0]), "X_sim": rel_err(b[1], a[1]), "costs": rel_err(b[2], a[2])})
+
+
+@pytest.mark.parametrize("name", ["pendulum", "ua", "dp"])
+@pytest.mark.parametrize("integrator", ["euler", "midpoint", "rk4", "backward_euler"])
+def test_plant_step_bound_separates(name, integrator):
+    """One MPC plant step (tests/test_mpc_steps_gpu.py): the fp32 oracle's step misses the fp64 bound."""
+    p = {"pendulum": problems.pendulum_mpc(N=10), "ua": problems.ua_double_pendulum(N=10),
+         "dp": problems.double_pendulum(N=10)}[name]
+    c64 = COracle(p["dynamics"], p["cost"], integrator=integrator)
+    c32 = COracle(p["dynamics"], p["cost"], integrator=integrator, dtype=F32)
+    rng = np.random.default_rng(6)
+    worst = np.inf
+    for _ in range(8):
+        x, u = _rd(rng.standard_normal(c64.n) * 0.7), _rd(rng.standard_normal(c64.m) * 2.0)
+        worst = min(worst, rel_err(c32.step(x, u, jac=False)[0], c64.step(x, u, jac=False)[0]))
+    _separates("plant_step", {"x_next": worst})
+
+
+def _lq_loop(c, plant, x, U, n_steps, maxiter=5):
+    us, xs, state = [], [], None
+    for _ in range(n_steps):
+        r = c.solve(x, U, tol=1e-5, maxiter=maxiter, state=state)
+        x = plant.step(x, r["U"][:, 0], jac=False)[0]
+        us.append(r["U"][:, 0].astype(np.float64))
+        xs.append(x.astype(np.float64))
+        U = np.concatenate([r["U"][:, 1:], r["U"][:, -1:]], axis=1)
+        state = (r["X"], r["U_ff"], r["K"])
+    return np.array(us), np.array(xs)
+
+
+@pytest.mark.parametrize("n,m,N,target", [(4, 2, 258, False), (4, 2, 66, True), (16, 8, 500, False), (2, 1, 2, False)])
+def test_mpc_lq_bound_separates(n, m, N, target):
+    """The LQ closed loop of tests/test_mpc_steps_gpu.py against its exact answer (lq_closed_loop): the fp64 oracle meets
+    the bound (the known answer is the loop's), the fp32 oracle misses it by SEPARATION."""
+    p = problems.linear_quadratic(n=n, m=m, N=N)
+    cost = dict(p["cost"])
+    if target:
+        cost["x_target"] = np.linspace(-0.5, 0.5, n)
+    d = p["dynamics"]
+    x0 = _rd(problems.lq_batch(1, n, m, N)[0][0])
+    want_u, want_x = lq_closed_loop(d["A"], d["B"], cost["Q"], cost["R"], cost["Q_f"], cost["x_target"], d["dt"], N,
+                                    x0, 3)
+    got = {}
+    for dt in (np.float64, F32):
+        co = COracle(d, cost, dtype=dt)
+        got[dt] = _lq_loop(co, co, x0, np.zeros((m, N)), 3)
+    for what, j, want in (("u", 0, want_u), ("x", 1, want_x)):
+        assert rel_err(got[np.float64][j], want) <= BOUNDS["mpc_lq"], (what, rel_err(got[np.float64][j], want))
+    _separates("mpc_lq", {"u": rel_err(got[F32][0], want_u), "x": rel_err(got[F32][1], want_x)})
