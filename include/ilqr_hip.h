@@ -79,7 +79,8 @@ enum {
     ILQR_TRAJ_CONVERGED = 1,         /* |cost - cost_prev| <= tol (iLQR_class.py:267) */
     ILQR_TRAJ_LINESEARCH_FAILED = 2, /* no alpha accepted (iLQR_class.py:304-307) */
     ILQR_TRAJ_MAXITER = 3,           /* ran maxiter iterations (iLQR_class.py:309-311) */
-    ILQR_TRAJ_FLAG_NON_PD = 0x100    /* some Q_uu was not positive definite: LU fallback used */
+    ILQR_TRAJ_FLAG_NON_PD = 0x100,   /* some Q_uu was not positive definite: LU fallback used */
+    ILQR_TRAJ_FLAG_INFEASIBLE = 0x200 /* state limits: still violated by more than ctol after max_outer inner solves */
 };
 
 enum {
@@ -140,9 +141,13 @@ typedef enum ilqr_field {
     ILQR_LIN = 10,     /* [B][N][E] raw expansion of the last ilqr_linearize, E = 2n^2+2nm+n+m+m^2, per step:
                           f_x (n*n) f_u (n*m) l_x (n) l_u (m) l_xx (n*n) l_ux (m*n) l_uu (m*m), row-major (get only) */
     ILQR_PLANT_X = 11, /* [B][n_x] MPC plant state */
-    ILQR_PROBE = 12    /* 8 x int64 diagnostic clock stamps {shader cycles, 100 MHz ticks} of workgroup 0:
+    ILQR_PROBE = 12,   /* 8 x int64 diagnostic clock stamps {shader cycles, 100 MHz ticks} of workgroup 0:
                           [0,1] backward sweep, [2,3] forward rollout; filled only when the environment variable
                           ILQR_CLOCK_PROBE is set at ilqr_create (get only) */
+    ILQR_MULTIPLIERS = 13, /* [B][N+1][2 n_x] state-limit multipliers lam_t, upper bounds (x_max) first, row t = 0 and
+                              the constraints of infinite bounds 0; handle dtype (get only, see ilqr_set_state_limits) */
+    ILQR_VIOLATION = 14,   /* [B]  max over t = 1..N, j of max(0, c) on the accepted X of the last inner solve; handle dtype (get only) */
+    ILQR_OUTER_ITERS = 15  /* [B]  int32 inner solves run by the last state-limited ilqr_solve (get only) */
 } ilqr_field;
 
 /* Phases timed by ilqr_timing_* (HIP events recorded on the handle's stream). */
@@ -285,6 +290,38 @@ int ilqr_set_control_limits(ilqr_handle h, const double* u_min, const double* u_
  * ILQR_ERR_INVALID_ARG for a bad `which`, a row_len other than the above, or a non-finite value. */
 enum { ILQR_BATCH_MODEL = 0, ILQR_BATCH_PLANT = 1 };
 int ilqr_set_batch_params(ilqr_handle h, int which, const double* rows, int row_len);
+
+/* ---- state limits (build extension: the reference has no constraints on the state) ------------------------
+ * x_min <= x_t <= x_max for t = 1..N (x_0 is given), one pair per state component [n_x] each, shared by the whole
+ * batch.  Every finite bound is one constraint per time step, c = x_t[j] - x_max[j] <= 0 or c = x_min[j] - x_t[j] <= 0;
+ * an infinite bound is no constraint at all.  NULL, NULL clears them.  Solved by the PHR augmented Lagrangian:
+ *  - J_A = J + sum_{t=1..N} sum_j phi(c_j(x_t), lam_{t,j}, rho), phi(c, lam, rho) = (max(0, lam + rho c)^2 - lam^2) / (2 rho),
+ *    J the reference's cost (stage cost times dt plus terminal cost), phi not scaled by dt.  The linearisation adds
+ *    +-max(0, lam + rho c) to l_x[j] and rho to l_xx[j][j] where lam + rho c > 0 (t = N: to V_x, V_xx); every rollout
+ *    adds phi to its trial cost;
+ *  - an inner solve is exactly the solve without state limits (with control limits: the box-DDP solve) on J_A with lam
+ *    and rho held: same acceptance, line search, convergence |dJ_A| <= tol, and maxiter per inner solve;
+ *  - outer loop, per trajectory: lam = 0, rho = rho0 at the head of ilqr_solve.  After each of its inner solves, in
+ *    any status, v = max over t, j of max(0, c) on its accepted X (ILQR_VIOLATION).  v <= ctol: done.  Otherwise, after
+ *    its max_outer-th inner solve: done, with ILQR_TRAJ_FLAG_INFEASIBLE.  Otherwise lam <- max(0, lam + rho c) at every
+ *    (t, j), rho <- min(rho * rho_factor, rho_max), cost <- J_A of the current (X, U) under the new multipliers (no new
+ *    rollout: X is the rollout of U), and the next inner solve starts from the current X, U and gains;
+ *  - ILQR_ITERS counts backward passes over all inner solves, ILQR_OUTER_ITERS the inner solves; the status word is
+ *    the last inner solve's, plus the flag; after ilqr_solve, cost_out and ILQR_COST hold the plain J of the final
+ *    trajectory (until the next ilqr_initial_rollout / ilqr_iterate / ilqr_set_problem), while ILQR_TRIAL_COSTS,
+ *    ILQR_LIN and the inner loop work on J_A.  ilqr_iterate runs inner iterations on J_A with the current multipliers
+ *    and no outer update;
+ *  - composes with control limits, per-trajectory parameters, every integrator and mu > 0.  Every state-limited call
+ *    runs linearise -> box sweep -> rollouts -> select as separate launches, whatever cfg->flags say (the fused and
+ *    persistent kernels have no state limits);
+ *  - ilqr_backward_pass, ilqr_forward_pass, ilqr_backward_tensors (no multipliers) and ilqr_mpc_reset, ilqr_mpc_rearm,
+ *    ilqr_mpc_run return ILQR_ERR_UNSUPPORTED while limits are set.
+ * Defaults (the Python layer's): ctol = 1e-4, rho0 = 1, rho_factor = 10, rho_max = 1e8, max_outer = 10.
+ * Returns ILQR_ERR_UNSUPPORTED for ILQR_SYS_LINEAR and ILQR_SYS_CUSTOM (clearing with NULL, NULL is valid on every
+ * handle), ILQR_ERR_INVALID_ARG for a NaN bound, x_min > x_max, exactly one NULL pointer, ctol <= 0, rho0 <= 0,
+ * rho_factor < 1, rho_max < rho0 or max_outer < 1. */
+int ilqr_set_state_limits(ilqr_handle h, const double* x_min, const double* x_max, double ctol, double rho0,
+                          double rho_factor, double rho_max, int max_outer);
 
 /* ---- multi-GPU hook -------------------------------------------
  * Writes 4 doubles to DEVICE memory `dev_out4` on the handle's stream:

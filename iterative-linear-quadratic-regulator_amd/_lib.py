@@ -24,9 +24,11 @@ OK, ERR_INVALID_ARG, ERR_HIP, ERR_UNSUPPORTED, ERR_NO_DEVICE, ERR_STATE = range(
 F32, F64 = 0, 1
 SYS_PENDULUM, SYS_UA_DOUBLE_PENDULUM, SYS_DOUBLE_PENDULUM, SYS_LINEAR, SYS_CUSTOM = range(5)
 INTEGRATORS = {"euler": 0, "midpoint": 1, "rk4": 2, "backward_euler": 3, "discrete": 4}
-(X, U, K, UFF, X0, COST, STATUS, ITERS, ALPHA, TRIAL_COSTS, LIN, PLANT_X, PROBE) = range(13)
+(X, U, K, UFF, X0, COST, STATUS, ITERS, ALPHA, TRIAL_COSTS, LIN, PLANT_X, PROBE, MULTIPLIERS, VIOLATION,
+ OUTER_ITERS) = range(16)
 TRAJ_ACTIVE, TRAJ_CONVERGED, TRAJ_LINESEARCH_FAILED, TRAJ_MAXITER = range(4)
 TRAJ_FLAG_NON_PD = 0x100
+TRAJ_FLAG_INFEASIBLE = 0x200
 FLAG_KEEP_ITERATING = 1
 FLAG_NO_FUSE = 2
 FLAG_NO_PERSIST = 4
@@ -40,12 +42,14 @@ SYMBOLS = (
     "ilqr_initial_rollout", "ilqr_linearize", "ilqr_backward", "ilqr_forward", "ilqr_select", "ilqr_iterate",
     "ilqr_flush", "ilqr_solve", "ilqr_backward_pass", "ilqr_backward_tensors", "ilqr_forward_pass", "ilqr_eval_points", "ilqr_mpc_reset",
     "ilqr_mpc_rearm", "ilqr_mpc_run", "ilqr_status_reduce", "ilqr_timing_enable", "ilqr_timing_reset", "ilqr_timing_get", "ilqr_algorithmic_bytes",
-    "ilqr_set_control_limits", "ilqr_set_batch_params",
+    "ilqr_set_control_limits", "ilqr_set_batch_params", "ilqr_set_state_limits",
 )
 # ilqr_set_batch_params: which rows
 BATCH_MODEL, BATCH_PLANT = 0, 1
-# the built-in systems that take control limits (ilqr_set_control_limits)
+# the built-in systems that take control limits (ilqr_set_control_limits), and state limits (ilqr_set_state_limits)
 BOX_SYSTEMS = (SYS_PENDULUM, SYS_UA_DOUBLE_PENDULUM, SYS_DOUBLE_PENDULUM)
+# ilqr_set_state_limits: the outer loop's settings when the caller gives none (include/ilqr_hip.h)
+STATE_LIMIT_DEFAULTS = dict(ctol=1e-4, rho0=1.0, rho_factor=10.0, rho_max=1e8, max_outer=10)
 
 
 class Config(C.Structure):
@@ -126,6 +130,7 @@ def load():
     lib.ilqr_algorithmic_bytes.argtypes = [vp, C.POINTER(cd)]
     lib.ilqr_set_control_limits.argtypes = [vp, vp, vp]
     lib.ilqr_set_batch_params.argtypes = [vp, ci, vp, ci]
+    lib.ilqr_set_state_limits.argtypes = [vp, vp, vp, cd, cd, cd, cd, ci]
     if lib.ilqr_abi_version() != ABI_VERSION:
         raise RuntimeError("libilqr_hip.so ABI version mismatch: rebuild the library")
     _lib = lib
@@ -222,10 +227,10 @@ class Handle:
         B, n, m, N = self.B, self.n_x, self.n_u, self.N
         return {X: (B, n, N + 1), U: (B, m, N), K: (B, N, m, n), UFF: (B, m, N), X0: (B, n), COST: (B,),
                 STATUS: (B,), ITERS: (B,), ALPHA: (B,), TRIAL_COSTS: (B, self.A), LIN: (B, N, self.E),
-                PLANT_X: (B, n), PROBE: (8,)}[field]
+                PLANT_X: (B, n), PROBE: (8,), MULTIPLIERS: (B, N + 1, 2 * n), VIOLATION: (B,), OUTER_ITERS: (B,)}[field]
 
     def get(self, field):
-        dt = np.int32 if field in (STATUS, ITERS) else (np.int64 if field == PROBE else self.np_dtype)
+        dt = np.int32 if field in (STATUS, ITERS, OUTER_ITERS) else (np.int64 if field == PROBE else self.np_dtype)
         out = np.empty(self.shape(field), dtype=dt)
         self._chk(self.lib.ilqr_get(self.h, field, _ptr(out), out.nbytes))
         return out
@@ -353,6 +358,18 @@ class Handle:
         lo = np.ascontiguousarray(u_min, dtype=np.float64).reshape(self.n_u)
         hi = np.ascontiguousarray(u_max, dtype=np.float64).reshape(self.n_u)
         self._chk(self.lib.ilqr_set_control_limits(self.h, _ptr(lo), _ptr(hi)))
+
+    # ---- state limits -----------------------------------------------------------------------------
+    def set_state_limits(self, x_min, x_max, ctol=1e-4, rho0=1.0, rho_factor=10.0, rho_max=1e8, max_outer=10):
+        """x_min <= x_t <= x_max ([n_x] doubles each, +-inf = no constraint) for t = 1..N, solved by the augmented
+        Lagrangian with these outer-loop settings; (None, None) clears them."""
+        if x_min is None and x_max is None:
+            self._chk(self.lib.ilqr_set_state_limits(self.h, None, None, 0.0, 0.0, 0.0, 0.0, 0))
+            return
+        lo = np.ascontiguousarray(x_min, dtype=np.float64).reshape(self.n_x)
+        hi = np.ascontiguousarray(x_max, dtype=np.float64).reshape(self.n_x)
+        self._chk(self.lib.ilqr_set_state_limits(self.h, _ptr(lo), _ptr(hi), float(ctol), float(rho0),
+                                                 float(rho_factor), float(rho_max), int(max_outer)))
 
     # ---- per-trajectory parameters ----------------------------------------------------------------
     def set_batch_params(self, which, rows):

@@ -93,23 +93,30 @@ class SolveResult:
     iters: np.ndarray    # ([B]) backward passes executed
     status: object       # 'converged' | 'linesearch_failed' | 'maxiter' (list for a batch)
     solver: iLQR
+    multipliers: object = None       # ([B,] N+1, 2 n_x) state-limit multipliers, or None without state limits
+    violation: object = None         # ([B]) max state-limit violation of the final trajectory, or None
+    outer_iterations: object = None  # ([B]) inner solves of the augmented Lagrangian, or None
 
 
 def solve(dynamics, cost, x0, U_init, *, T=None, N=None, tol=1e-5, maxiter=100, alpha_factor=0.5,
           min_alpha=1e-8, n_alpha=None, mu=0.0, dtype=np.float64, device=0, verbose=False, u_min=None, u_max=None,
-          batch_params=None):
+          batch_params=None, x_min=None, x_max=None, state_limit_options=None):
     """Solve one trajectory (x0 (n,), U_init (m, N)) or a batch (x0 (B, n), U_init (B, m, N)).
     u_min, u_max: control limits (scalars or [n_u], see iLQR.set_control_limits); batch_params: per-trajectory system
-    parameters and x_target (a dict for batch_param_rows)."""
+    parameters and x_target (a dict for batch_param_rows); x_min, x_max, state_limit_options: state limits (see
+    iLQR.set_state_limits)."""
     system = make_system(dynamics, cost, dtype)
     U_init = np.asarray(U_init)
     if N is None and T is None:
         N = U_init.shape[-1]
     s = iLQR(system, T, x0, U_init, tol=tol, maxiter=maxiter, alpha_factor=alpha_factor, min_alpha=min_alpha,
              verbose=verbose, N=N, n_alpha=n_alpha, mu=mu, dtype=dtype, device=device, u_min=u_min, u_max=u_max,
-             batch_params=batch_params)
+             batch_params=batch_params, x_min=x_min, x_max=x_max, state_limit_options=state_limit_options)
     X, U, c = s.optimize_trajectory()
-    return SolveResult(X=X, U=U, cost=c, K=s.K, k=s.U_ff, iters=s.iterations, status=s.status, solver=s)
+    al = s.x_min is not None
+    return SolveResult(X=X, U=U, cost=c, K=s.K, k=s.U_ff, iters=s.iterations, status=s.status, solver=s,
+                       multipliers=s.multipliers if al else None, violation=s.violation if al else None,
+                       outer_iterations=s.outer_iterations if al else None)
 
 
 @dataclass

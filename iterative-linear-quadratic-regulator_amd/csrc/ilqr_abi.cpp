@@ -262,6 +262,17 @@ int ilqr_set_batch_params(ilqr_handle h, int which, const double* rows, int row_
     }
     return h->impl->set_batch_params(which, rows, row_len);   // (clearing with NULL: valid on every handle)
 }
+int ilqr_set_state_limits(ilqr_handle h, const double* x_min, const double* x_max, double ctol, double rho0,
+                          double rho_factor, double rho_max, int max_outer) {
+    if (!h || !h->impl) return ILQR_ERR_INVALID_ARG;
+    const ilqr_config& c = h->impl->cfg;
+    if (!x_min && !x_max) return h->impl->set_state_limits(nullptr, nullptr, 0, 0, 0, 0, 0);   // clearing: valid on every handle
+    if (c.system == ILQR_SYS_LINEAR || c.system == ILQR_SYS_CUSTOM) {
+        h->impl->err = "set_state_limits: state limits are not supported for linear or user-defined systems";
+        return ILQR_ERR_UNSUPPORTED;
+    }
+    return h->impl->set_state_limits(x_min, x_max, ctol, rho0, rho_factor, rho_max, max_outer);
+}
 int ilqr_timing_enable(ilqr_handle h, int on) { ILQR_FWD(h, timing_enable(on)); }
 int ilqr_timing_reset(ilqr_handle h) { ILQR_FWD(h, timing_reset()); }
 int ilqr_timing_get(ilqr_handle h, double ms[ILQR_N_PHASES], int64_t launches[ILQR_N_PHASES]) {

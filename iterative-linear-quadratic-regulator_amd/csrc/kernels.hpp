@@ -41,6 +41,7 @@ namespace ilqr {
 constexpr int kMaxAlpha = 16;
 constexpr int kCounterRing = 64;
 constexpr int kBoxMaxU = 2;   // control limits: the built-in systems with n_x <= 4 (n_u <= 2)
+constexpr int kALMaxX = 4;    // state limits: the same systems (n_x <= 4)
 
 template <typename T> struct KArgs {
     int B, N, n_slots, integ, maxiter, flags;
@@ -76,6 +77,14 @@ template <typename T> struct KArgs {
     const T* rows;
     const T* plant_rows;
     int het;           // rows are set: the launchers pick their HET instantiations
+    // state limits (ilqr_set_state_limits), read by the AL kernels only (linearize_al_kernel, forward_kernel_al*,
+    // al_update_kernel, al_cost_kernel); appended after the rows for the same reason.  A finite x_hi[j] is the constraint
+    // x_t[j] - x_hi[j] <= 0 (bit j of al_mask), a finite x_lo[j] is x_lo[j] - x_t[j] <= 0 (bit n_x + j), t = 1..N.
+    // lam: [N+1][2 n_x][B] multipliers (upper bounds first, row t = 0 unused), rho: [B] penalties
+    T x_lo[kALMaxX], x_hi[kALMaxX];
+    int al_mask;
+    const T* lam;
+    const T* rho;
 };
 
 // A HET lane's parameters: its trajectory's row over the first NH = n_sys + n_x entries of its parameter copy, the shared
@@ -223,6 +232,49 @@ ILQR_DEV void tile16_pack(P p, T dt, const T* x, const T* u, const T (*fx)[Dyn::
 }
 
 // ---------------------------------------------------------------------------
+// State limits (ilqr_set_state_limits): the PHR augmented Lagrangian.  Constraint q of x_t, t = 1..N:
+// q < n_x: c = x_t[q] - x_hi[q];  q >= n_x: c = x_lo[q - n_x] - x_t[q - n_x];  only the finite bounds (KArgs::al_mask).
+// phi(c, lam, rho) = (max(0, lam + rho c)^2 - lam^2) / (2 rho), not scaled by dt.  A bound that never binds (lam = 0,
+// c < 0) adds exactly 0 to every cost, gradient and Hessian.
+// ---------------------------------------------------------------------------
+template <typename T, int NX> ILQR_DEV T al_constraint(const KArgs<T>& a, const T* x, int q) {
+    return q < NX ? x[q < NX ? q : 0] - a.x_hi[q < NX ? q : 0] : a.x_lo[q < NX ? 0 : q - NX] - x[q < NX ? 0 : q - NX];
+}
+template <typename T> ILQR_DEV T al_pos(T v) { return v > T(0) ? v : T(0); }
+// lam_t of trajectory b; the constraints that do not exist read as 0
+template <typename T, int NX> ILQR_DEV void al_load_lam(const KArgs<T>& a, size_t B, int b, int t, T* lam) {
+#pragma unroll
+    for (int q = 0; q < 2 * NX; ++q) lam[q] = ((a.al_mask >> q) & 1) ? a.lam[((size_t)t * 2 * NX + q) * B + b] : T(0);
+}
+// sum of phi over the constraints of one point, in constraint order
+template <typename T, int NX> ILQR_DEV T al_phi(const KArgs<T>& a, const T* x, const T* lam, T rho) {
+    T s = T(0);
+#pragma unroll
+    for (int q = 0; q < 2 * NX; ++q) {
+        if ((a.al_mask >> q) & 1) {
+            const T m = al_pos(lam[q] + rho * al_constraint<T, NX>(a, x, q));
+            s += (m * m - lam[q] * lam[q]) / (T(2) * rho);
+        }
+    }
+    return s;
+}
+// d phi / dx into g (+-max(0, lam + rho c)), d2 phi / dx2 into H (rho on the diagonal where lam + rho c > 0)
+template <typename T, int NX>
+ILQR_DEV void al_expand(const KArgs<T>& a, const T* x, const T* lam, T rho, T* g, T (*H)[NX]) {
+#pragma unroll
+    for (int q = 0; q < 2 * NX; ++q) {
+        if ((a.al_mask >> q) & 1) {
+            const int j = q % NX;
+            const T v = lam[q] + rho * al_constraint<T, NX>(a, x, q);
+            const T m = al_pos(v);
+            if (q < NX) g[j] += m;
+            else g[j] -= m;
+            if (v > T(0)) H[j][j] += rho;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // linearize: one lane per (b, t) point, t in [0, N]; t == N is the terminal
 // expansion.  Replaces iLQR._get_all_derivatives_for_backward_pass
 // (iLQR_class.py:318-331) + l_f_x / l_f_xx (:136-138), hoisted out of the
@@ -364,6 +416,81 @@ __global__ void __launch_bounds__(TILE16 ? 64 : 256) linearize_kernel(KArgs<T> a
     T g[NX], gu[NU], lxx[NX][NX], lux[NU][NX], luu[NU][NU];
     Cost<T, Dyn>::grad(p, a.dt, x, u, g, gu);
     Cost<T, Dyn>::hess(p, a.dt, x, u, lxx, lux, luu);
+#pragma unroll
+    for (int i = 0; i < NX; ++i) out[(size_t)(e++) * B] = g[i];
+#pragma unroll
+    for (int i = 0; i < NU; ++i) out[(size_t)(e++) * B] = gu[i];
+#pragma unroll
+    for (int i = 0; i < NX * NX; ++i) out[(size_t)(e++) * B] = lxx[i / NX][i % NX];
+#pragma unroll
+    for (int i = 0; i < NU * NX; ++i) out[(size_t)(e++) * B] = lux[i / NX][i % NX];
+#pragma unroll
+    for (int i = 0; i < NU * NU; ++i) out[(size_t)(e++) * B] = luu[i / NU][i % NU];
+}
+
+// With state limits: linearize_kernel's generic form ([N][E][B] records, the box sweep's input) of J_A, the terminal at
+// t = N.  A kernel of its own so that linearize_kernel's instantiations stay as they are.
+template <typename T, typename Dyn, int INTEG, bool HET = false>
+__global__ void __launch_bounds__(256) linearize_al_kernel(KArgs<T> a) {
+    constexpr int NX = Dyn::NX, NU = Dyn::NU;
+    constexpr int E = 2 * NX * NX + 2 * NX * NU + NX + NU + NU * NU;
+    using PL = ParamLayout<Dyn::NSYS, NX, NU>;
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t B = a.B;
+    const int t = (int)(idx / B);
+    const int b = (int)(idx % B);
+    const bool inr = t <= a.N;
+    const int st_raw = inr ? a.status[b] : 0;
+    const int slot_raw = inr ? a.cur_slot[b] : 0;
+    if (!inr || !traj_active(st_raw)) return;
+    T p[PL::TOTAL];
+#pragma unroll
+    for (int q = 0; q < PL::TOTAL; ++q) p[q] = a.params[q];
+    if constexpr (HET) load_row<PL::Q>(p, a.rows, B, b);
+    // canonicalisation into slot 0, as linearize_kernel
+    const int slot = slot_raw;
+    T x[NX], u[NU];
+    vec_load<T, NX>(a.X + vec_at(B, a.N + 1, NX, slot, t, b), x);
+    if (slot != 0) vec_store<T, NX>(a.X + vec_at(B, a.N + 1, NX, 0, t, b), x);
+    if (t < a.N) {
+        vec_load<T, NU>(a.U + vec_at(B, a.N, NU, slot, t, b), u);
+        if (slot != 0) vec_store<T, NU>(a.U + vec_at(B, a.N, NU, 0, t, b), u);
+    } else {
+#pragma unroll
+        for (int i = 0; i < NU; ++i) u[i] = T(0);
+    }
+    T lam[2 * NX], rho = T(0);   // this point's multipliers and the trajectory's penalty (x_0 is given: none at t = 0)
+    if (t >= 1) {
+        al_load_lam<T, NX>(a, B, b, t, lam);
+        rho = a.rho[b];
+    }
+    if (t == a.N) {
+        T g[NX], H[NX][NX];
+        Cost<T, Dyn>::l_f_x(p, x, g);
+        Cost<T, Dyn>::l_f_xx(p, x, H);
+        al_expand<T, NX>(a, x, lam, rho, g, H);   // the t = N terms go into V_x, V_xx
+#pragma unroll
+        for (int i = 0; i < NX; ++i) a.term[(size_t)i * B + b] = g[i];
+#pragma unroll
+        for (int i = 0; i < NX * NX; ++i) a.term[(size_t)(NX + i) * B + b] = H[i / NX][i % NX];
+        return;
+    }
+    T xn[NX], fx[NX][NX], fu[NX][NU];
+    Stepper<T, Dyn>::step_jac(INTEG, p, a.dt, x, u, xn, fx, fu);
+    T* out = a.lin + ((size_t)t * E) * B + b;
+    int e = 0;
+#pragma unroll
+    for (int i = 0; i < NX; ++i)
+#pragma unroll
+        for (int j = 0; j < NX; ++j) out[(size_t)(e++) * B] = fx[i][j];
+#pragma unroll
+    for (int i = 0; i < NX; ++i)
+#pragma unroll
+        for (int j = 0; j < NU; ++j) out[(size_t)(e++) * B] = fu[i][j];
+    T g[NX], gu[NU], lxx[NX][NX], lux[NU][NX], luu[NU][NU];
+    Cost<T, Dyn>::grad(p, a.dt, x, u, g, gu);
+    Cost<T, Dyn>::hess(p, a.dt, x, u, lxx, lux, luu);
+    if (t >= 1) al_expand<T, NX>(a, x, lam, rho, g, lxx);
 #pragma unroll
     for (int i = 0; i < NX; ++i) out[(size_t)(e++) * B] = g[i];
 #pragma unroll
@@ -781,7 +908,8 @@ __global__ void __launch_bounds__(64) backward_box_kernel(KArgs<T> a) {
 // index.  Replaces iLQR._forward_pass_scan (iLQR_class.py:193-247), all trial
 // alphas of the backtracking loop (:279-302) at once.
 // ---------------------------------------------------------------------------
-template <typename T, typename Dyn, int INTEG, bool BOX, bool HET = false>
+// AL: state limits, phi(x_t) added to the candidate's cost for t = 1..N (lam_t requested one step ahead)
+template <typename T, typename Dyn, int INTEG, bool BOX, bool HET = false, bool AL = false>
 ILQR_DEV void forward_body(const KArgs<T>& a) {
     constexpr int NX = Dyn::NX, NU = Dyn::NU;
     constexpr int R = gain_record(NX, NU);
@@ -829,6 +957,9 @@ ILQR_DEV void forward_body(const KArgs<T>& a) {
     vec_load<T, NU>(Uo, uo);
 #pragma unroll
     for (int r = 0; r < R; ++r) g[r] = G[r];
+    constexpr int NL = AL ? 2 * NX : 1;
+    T lam[NL], lam_n[NL];
+    const T rho = AL ? a.rho[b] : T(0);
     for (int t = 0; t < N; ++t) {
         const int tn = (t + 1 < N) ? t + 1 : t;
         if constexpr (PREFETCH) {
@@ -852,10 +983,21 @@ ILQR_DEV void forward_body(const KArgs<T>& a) {
         vec_store<T, NX>(Xc + t * sX, x);
         vec_store<T, NU>(Uc + t * sU, u);
         cost += Cost<T, Dyn>::stage(p, a.dt, x, u);
+        if constexpr (AL) {
+            if (t > 0) cost += al_phi<T, NX>(a, x, lam, rho);
+            // lam_{t+1} (row N exists: the terminal's), requested after this step's inputs were used and before its
+            // arithmetic: issued at the loop head, the (masked, branchy) loads made the in-order vmcnt wait for them there
+            al_load_lam<T, NX>(a, B, b, t + 1, lam_n);
+        }
         T xn[NX];
         Stepper<T, Dyn>::step(INTEG, p, a.dt, x, u, xn);  // integrator folded at compile time
 #pragma unroll
         for (int i = 0; i < NX; ++i) x[i] = xn[i];
+        if constexpr (AL) {
+            // (after the step: taking lam_n earlier would wait for its loads before the step's arithmetic)
+#pragma unroll
+            for (int q = 0; q < NL; ++q) lam[q] = lam_n[q];
+        }
         if constexpr (PREFETCH) {
 #pragma unroll
             for (int i = 0; i < NX; ++i) xo[i] = xo_n[i];
@@ -872,6 +1014,7 @@ ILQR_DEV void forward_body(const KArgs<T>& a) {
     }
     vec_store<T, NX>(Xc + N * sX, x);
     cost += Cost<T, Dyn>::terminal(p, x);
+    if constexpr (AL) cost += al_phi<T, NX>(a, x, lam, rho);
     a.costs[(size_t)ai * B + b] = cost;
     cp.stop(a.probe, 1);
 }
@@ -885,6 +1028,12 @@ template <typename T, typename Dyn, int INTEG>
 __global__ void __launch_bounds__(64) forward_kernel_het(KArgs<T> a) { forward_body<T, Dyn, INTEG, false, true>(a); }
 template <typename T, typename Dyn, int INTEG>
 __global__ void __launch_bounds__(64) forward_kernel_box_het(KArgs<T> a) { forward_body<T, Dyn, INTEG, true, true>(a); }
+// with state limits: the clamped rollout (+-inf bounds when no control limits are set) plus the phi terms; never the
+// ring form, whose self-counted load ring must not see the multiplier loads
+template <typename T, typename Dyn, int INTEG>
+__global__ void __launch_bounds__(64) forward_kernel_al(KArgs<T> a) { forward_body<T, Dyn, INTEG, true, false, true>(a); }
+template <typename T, typename Dyn, int INTEG>
+__global__ void __launch_bounds__(64) forward_kernel_al_het(KArgs<T> a) { forward_body<T, Dyn, INTEG, true, true, true>(a); }
 
 // ---------------------------------------------------------------------------
 // forward rollout, ring form (small systems, tensors < 2 GiB): identical arithmetic to forward_kernel, but
@@ -1193,6 +1342,156 @@ __global__ void __launch_bounds__(256) select_kernel(KArgs<T> a) {
         // needs no memset launch per iteration
         if (blockIdx.x == 0 && threadIdx.x == 0) a.counters[(a.counter_idx + 1) % kCounterRing] = 0;
     }
+}
+
+// ---------------------------------------------------------------------------
+// State limits: the outer loop of the augmented Lagrangian, one lane per trajectory (include/ilqr_hip.h,
+// ilqr_set_state_limits).  The inner solves are the ordinary multi-launch loop on J_A; these kernels run between them.
+// ---------------------------------------------------------------------------
+template <typename T> struct ALArgs {
+    T* lam;          // [N+1][2 n_x][B] (KArgs::lam, writable)
+    T* rho;          // [B]
+    T* viol;         // [B] max over t, q of max(0, c) on the accepted trajectory of the last inner solve
+    T* cost_plain;   // [B] plain J of the final trajectory (al_cost_kernel)
+    int* outer;      // [B] inner solves run in this solve
+    int* live;       // [B] the trajectory is still in the outer loop
+    int* base;       // [B] backward passes of its earlier inner solves (iters counts the current one, against maxiter)
+    int* count;      // trajectories re-armed by the last al_update_kernel
+    T ctol, rho0, rho_factor, rho_max;
+    int max_outer;
+};
+
+// head of a solve: lam = 0 (a memset), rho = rho0, every trajectory in the outer loop
+template <typename T>
+__global__ void __launch_bounds__(256) al_reset_kernel(ALArgs<T> s, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    s.rho[b] = s.rho0;
+    s.viol[b] = T(0);
+    s.outer[b] = 0;
+    s.live[b] = 1;
+    s.base[b] = 0;
+}
+
+// The parameter copy of a cost-only lane (stage / terminal read the first QS entries), with its row (HET).
+template <typename T, typename Dyn, bool HET> struct CostParams {
+    using PL = ParamLayout<Dyn::NSYS, Dyn::NX, Dyn::NU>;
+    T ph[HET ? PL::QS : 1];
+    const T* p;
+    ILQR_DEV CostParams(const KArgs<T>& a, int b) {
+        if constexpr (HET) {
+#pragma unroll
+            for (int i = 0; i < PL::QS; ++i) ph[i] = a.params[i];
+            load_row<PL::Q>(ph, a.rows, (size_t)a.B, b);
+        }
+        p = HET ? ph : a.params;
+    }
+};
+
+// After an inner solve, for every trajectory still in the outer loop: the violation of its accepted X; done when it is
+// <= ctol, done and ILQR_TRAJ_FLAG_INFEASIBLE after its max_outer-th inner solve, otherwise lam <- max(0, lam + rho c),
+// rho <- min(rho rho_factor, rho_max), cost = cost_prev = J_A of (X, U) under the new multipliers (summed in the
+// rollout's order; X is already the rollout of U), and re-armed: ACTIVE, accepted = 0, iters moved into base.
+template <typename T, typename Dyn, bool HET = false>
+__global__ void __launch_bounds__(64) al_update_kernel(KArgs<T> a, ALArgs<T> s) {
+    constexpr int NX = Dyn::NX, NU = Dyn::NU;
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    bool rearm = false;
+    if (b < a.B && s.live[b]) {
+        const size_t B = a.B;
+        const int N = a.N;
+        const int slot = a.cur_slot[b];
+        const T* Xb = a.X + vec_at(B, N + 1, NX, slot, 0, b);
+        const T* Ub = a.U + vec_at(B, N, NU, slot, 0, b);
+        const size_t sX = B * NX, sU = B * NU;
+        T v = T(0);
+        for (int t = 1; t <= N; ++t) {
+            T x[NX];
+            vec_load<T, NX>(Xb + t * sX, x);
+#pragma unroll
+            for (int q = 0; q < 2 * NX; ++q) {
+                if ((a.al_mask >> q) & 1) {
+                    const T c = al_constraint<T, NX>(a, x, q);
+                    v = c > v ? c : v;
+                }
+            }
+        }
+        const int outer = s.outer[b] + 1;
+        s.outer[b] = outer;
+        s.viol[b] = v;
+        if (v <= s.ctol) {
+            s.live[b] = 0;
+        } else if (outer >= s.max_outer) {
+            a.status[b] = a.status[b] | ILQR_TRAJ_FLAG_INFEASIBLE;
+            s.live[b] = 0;
+        } else {
+            const CostParams<T, Dyn, HET> cp(a, b);
+            const T rho = s.rho[b];
+            T rn = rho * s.rho_factor;
+            rn = rn < s.rho_max ? rn : s.rho_max;
+            s.rho[b] = rn;
+            T cost = T(0);
+            for (int t = 0; t <= N; ++t) {
+                T x[NX], u[NU];
+                vec_load<T, NX>(Xb + t * sX, x);
+                if (t < N) {
+                    vec_load<T, NU>(Ub + t * sU, u);
+                    cost += Cost<T, Dyn>::stage(cp.p, a.dt, x, u);
+                } else {
+                    cost += Cost<T, Dyn>::terminal(cp.p, x);
+                }
+                if (t == 0) continue;
+                T lam[2 * NX];
+#pragma unroll
+                for (int q = 0; q < 2 * NX; ++q) {
+                    lam[q] = T(0);
+                    if ((a.al_mask >> q) & 1) {
+                        T* l = s.lam + ((size_t)t * 2 * NX + q) * B + b;
+                        lam[q] = al_pos(*l + rho * al_constraint<T, NX>(a, x, q));
+                        *l = lam[q];
+                    }
+                }
+                cost += al_phi<T, NX>(a, x, lam, rn);
+            }
+            a.cost[b] = cost;
+            a.cost_prev[b] = cost;
+            a.status[b] = ILQR_TRAJ_ACTIVE;
+            a.accepted[b] = 0;
+            s.base[b] += a.iters[b];
+            a.iters[b] = 0;
+            rearm = true;
+        }
+    }
+    const unsigned long long m = __ballot(rearm);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(s.count, (int)__popcll(m));
+}
+
+// End of a state-limited solve: the plain J (no phi terms) of every final trajectory, summed in the rollout's order,
+// and iters = backward passes of all its inner solves.
+template <typename T, typename Dyn, bool HET = false>
+__global__ void __launch_bounds__(64) al_cost_kernel(KArgs<T> a, ALArgs<T> s) {
+    constexpr int NX = Dyn::NX, NU = Dyn::NU;
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= a.B) return;
+    const size_t B = a.B;
+    const int N = a.N;
+    const int slot = a.cur_slot[b];
+    const T* Xb = a.X + vec_at(B, N + 1, NX, slot, 0, b);
+    const T* Ub = a.U + vec_at(B, N, NU, slot, 0, b);
+    const CostParams<T, Dyn, HET> cp(a, b);
+    T cost = T(0);
+    for (int t = 0; t < N; ++t) {
+        T x[NX], u[NU];
+        vec_load<T, NX>(Xb + t * (B * NX), x);
+        vec_load<T, NU>(Ub + t * (B * NU), u);
+        cost += Cost<T, Dyn>::stage(cp.p, a.dt, x, u);
+    }
+    T x[NX];
+    vec_load<T, NX>(Xb + N * (B * NX), x);
+    cost += Cost<T, Dyn>::terminal(cp.p, x);
+    s.cost_plain[b] = cost;
+    a.iters[b] += s.base[b];
+    s.base[b] = 0;
 }
 
 // ---------------------------------------------------------------------------

@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include <cstdint>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -58,6 +59,8 @@ struct SolverBase {
     virtual int algorithmic_bytes(double* bytes) = 0;
     virtual int set_control_limits(const double* u_min, const double* u_max) = 0;
     virtual int set_batch_params(int which, const double* rows, int row_len) = 0;
+    virtual int set_state_limits(const double* x_min, const double* x_max, double ctol, double rho0, double rho_factor,
+                                 double rho_max, int max_outer) = 0;
 };
 
 int system_dims(int system, int n_x, int n_u);  // 1 if (system, n_x, n_u) is a known combination
@@ -125,6 +128,13 @@ template <typename T> struct Ops {
     // mpc_advance launch their HET instantiations when KArgs::het (MpcArgs::plant_rows) is set; the built-in systems only
     bool het = false;
     bool persist_het[5] = {};   // persist[i] has a HET instantiation (else a HET solve takes the fused multi-launch loop)
+    // state limits (ilqr_set_state_limits): the augmented-Lagrangian linearisation and rollouts (generic layout, flat
+    // rollout; the box sweep is backward_box), the outer update and the final plain cost; HET picked by KArgs::het.
+    // Null where state limits are not supported.
+    void (*linearize_al[5])(const KArgs<T>&, hipStream_t) = {};
+    void (*forward_al[5])(const KArgs<T>&, hipStream_t) = {};
+    void (*al_update)(const KArgs<T>&, const ALArgs<T>&, hipStream_t) = nullptr;
+    void (*al_cost)(const KArgs<T>&, const ALArgs<T>&, hipStream_t) = nullptr;
 };
 
 // linearize / forward are compiled once per integrator so the integrator switch folds away and each
@@ -355,6 +365,18 @@ template <typename T, typename Dyn, bool TILE, int INTEG> void set_integrator_op
             if (a.het) { ILQR_LAUNCH((forward_kernel_box_het<T, Dyn, I>), grid, block, 0, s, a); return; }
             ILQR_LAUNCH((forward_kernel_box<T, Dyn, I>), grid, block, 0, s, a);
         };
+        // state limits: the box sweep's generic expansion of J_A and the flat clamped rollout with the phi terms (never
+        // the ring form: its step loop's self-counted loads must not meet the multiplier loads)
+        o.linearize_al[INTEG] = [](const KArgs<T>& a, hipStream_t s) {
+            const dim3 grid((unsigned)(((size_t)a.B * (a.N + 1) + 255) / 256)), block(256);
+            if (a.het) { ILQR_LAUNCH((linearize_al_kernel<T, Dyn, I, true>), grid, block, 0, s, a); return; }
+            ILQR_LAUNCH((linearize_al_kernel<T, Dyn, I>), grid, block, 0, s, a);
+        };
+        o.forward_al[INTEG] = [](const KArgs<T>& a, hipStream_t s) {
+            const dim3 grid((a.B + 63) / 64, a.n_pass), block(64);
+            if (a.het) { ILQR_LAUNCH((forward_kernel_al_het<T, Dyn, I>), grid, block, 0, s, a); return; }
+            ILQR_LAUNCH((forward_kernel_al<T, Dyn, I>), grid, block, 0, s, a);
+        };
     }
 }
 
@@ -425,6 +447,14 @@ template <typename T, typename Dyn> Ops<T> make_ops() {
     if constexpr (box_system<Dyn>()) {
         o.backward_box = [](const KArgs<T>& a, hipStream_t s) {
             ILQR_LAUNCH((backward_box_kernel<T, NX, NU>), dim3((a.B + 63) / 64), dim3(64), 0, s, a);
+        };
+        o.al_update = [](const KArgs<T>& a, const ALArgs<T>& al, hipStream_t s) {
+            if (a.het) { ILQR_LAUNCH((al_update_kernel<T, Dyn, true>), dim3((a.B + 63) / 64), dim3(64), 0, s, a, al); return; }
+            ILQR_LAUNCH((al_update_kernel<T, Dyn>), dim3((a.B + 63) / 64), dim3(64), 0, s, a, al);
+        };
+        o.al_cost = [](const KArgs<T>& a, const ALArgs<T>& al, hipStream_t s) {
+            if (a.het) { ILQR_LAUNCH((al_cost_kernel<T, Dyn, true>), dim3((a.B + 63) / 64), dim3(64), 0, s, a, al); return; }
+            ILQR_LAUNCH((al_cost_kernel<T, Dyn>), dim3((a.B + 63) / 64), dim3(64), 0, s, a, al);
         };
     }
     o.eval = [](const EvalArgs<T>& a, hipStream_t s) {
@@ -662,6 +692,15 @@ template <typename T> class SolverT : public SolverBase {
     T *rows = nullptr, *plant_rows = nullptr;
     bool model_rows_set = false, plant_rows_set = false;
     bool het_on() const { return model_rows_set || plant_rows_set; }
+    // state limits (ilqr_set_state_limits): bounds shared by the batch, the outer loop's settings and per-trajectory state
+    bool al_on = false;
+    double al_lo[kALMaxX] = {0}, al_hi[kALMaxX] = {0};
+    int al_mask = 0;            // KArgs::al_mask
+    double al_ctol = 0, al_rho0 = 0, al_rho_factor = 0, al_rho_max = 0;
+    int al_max_outer = 0;
+    T *al_lam = nullptr, *al_rho = nullptr, *al_viol = nullptr, *al_cost_plain = nullptr;
+    int *al_outer = nullptr, *al_live = nullptr, *al_base = nullptr, *al_count = nullptr;
+    bool al_cost_valid = false; // al_cost_plain holds the plain J of the last solve's trajectories (ILQR_COST)
 
     ~SolverT() override {
         if (stream) hipStreamSynchronize(stream);
@@ -670,6 +709,8 @@ template <typename T> class SolverT : public SolverBase {
         hipFree(params);
         hipFree(rows);
         hipFree(plant_rows);
+        hipFree(al_lam); hipFree(al_rho); hipFree(al_viol); hipFree(al_cost_plain);
+        hipFree(al_outer); hipFree(al_live); hipFree(al_base); hipFree(al_count);
         hipFree(staging);
         hipFree(plant_x);
         hipFree(eval_buf);
@@ -790,6 +831,22 @@ template <typename T> class SolverT : public SolverBase {
         a.het = het_on() ? 1 : 0;
         a.rows = het_on() ? rows : nullptr;
         a.plant_rows = het_on() ? (plant_rows_set ? plant_rows : rows) : nullptr;
+        if (al_on) {
+            if (!box_on) {
+                // the state-limited path always runs the box sweep and the clamped rollout: with +-inf bounds they move nothing
+                for (int i = 0; i < kBoxMaxU; ++i) {
+                    a.u_lo[i] = -std::numeric_limits<T>::infinity();
+                    a.u_hi[i] = std::numeric_limits<T>::infinity();
+                }
+            }
+            for (int i = 0; i < kALMaxX; ++i) {
+                a.x_lo[i] = (T)al_lo[i];
+                a.x_hi[i] = (T)al_hi[i];
+            }
+            a.al_mask = al_mask;
+            a.lam = al_lam;
+            a.rho = al_rho;
+        }
         return a;
     }
 
@@ -944,6 +1001,8 @@ template <typename T> class SolverT : public SolverBase {
         if ((rc = up_ct(U, st.U, st.cur_slot, NU, N))) return rc;
         have_problem = true;
         have_rollout = false;
+        al_cost_valid = false;
+        if (al_on) return al_reset();     // multipliers of a fresh solver: lam = 0, rho = rho0
         return ILQR_OK;
     }
 
@@ -957,6 +1016,9 @@ template <typename T> class SolverT : public SolverBase {
             case ILQR_COST: case ILQR_ALPHA: return b * sizeof(T);
             case ILQR_STATUS: case ILQR_ITERS: return b * sizeof(int32_t);
             case ILQR_PROBE: return 8 * sizeof(long long);
+            case ILQR_MULTIPLIERS: return b * (N + 1) * 2 * NX * sizeof(T);
+            case ILQR_VIOLATION: return b * sizeof(T);
+            case ILQR_OUTER_ITERS: return b * sizeof(int32_t);
             case ILQR_TRIAL_COSTS: return b * A * sizeof(T);
             case ILQR_LIN: return b * N * E * sizeof(T);
             default: return 0;
@@ -994,7 +1056,7 @@ template <typename T> class SolverT : public SolverBase {
             case ILQR_X0: return down_tc(dst, st.x0, NX, 1);
             case ILQR_PLANT_X: return down_tc(dst, plant_x, NX, 1);
             case ILQR_LIN:
-                if (box_on) {   // control limits: the box sweep's expansion, in the generic layout
+                if (box_on || al_on) {   // control / state limits: the box sweep's expansion, in the generic layout
                     if (lin_stale || !st.box_lin_valid) {
                         if (int rl = do_linearize(st, true)) return rl;
                     }
@@ -1005,7 +1067,16 @@ template <typename T> class SolverT : public SolverBase {
                 }
                 return down_lin(dst, st.lin);
             case ILQR_TRIAL_COSTS: return down_tc(dst, st.costs, A, 1);
-            case ILQR_COST: ILQR_HIPCHK(hipMemcpyAsync(dst, st.cost, bytes, hipMemcpyDeviceToHost, stream)); return sync();
+            case ILQR_COST:
+                // after a state-limited solve: its plain J (st.cost holds J_A, which the inner loop goes on comparing against)
+                ILQR_HIPCHK(hipMemcpyAsync(dst, al_cost_valid ? al_cost_plain : st.cost, bytes, hipMemcpyDeviceToHost, stream));
+                return sync();
+            case ILQR_MULTIPLIERS: case ILQR_VIOLATION: case ILQR_OUTER_ITERS:
+                if (!al_lam) { err = "get: no state limits have been set on this handle"; return ILQR_ERR_STATE; }
+                if (field == ILQR_MULTIPLIERS) return down_tc(dst, al_lam, 2 * NX, N + 1);
+                ILQR_HIPCHK(hipMemcpyAsync(dst, field == ILQR_VIOLATION ? (const void*)al_viol : (const void*)al_outer, bytes,
+                                           hipMemcpyDeviceToHost, stream));
+                return sync();
             case ILQR_ALPHA: ILQR_HIPCHK(hipMemcpyAsync(dst, st.alpha_taken, bytes, hipMemcpyDeviceToHost, stream)); return sync();
             case ILQR_STATUS: ILQR_HIPCHK(hipMemcpyAsync(dst, st.status, bytes, hipMemcpyDeviceToHost, stream)); return sync();
             case ILQR_ITERS: ILQR_HIPCHK(hipMemcpyAsync(dst, st.iters, bytes, hipMemcpyDeviceToHost, stream)); return sync();
@@ -1017,13 +1088,14 @@ template <typename T> class SolverT : public SolverBase {
     // ---- stages ---------------------------------------------------------------------
     // full = false: the sweep that follows may be the constant-matrix form, which reads the matrices at t = N-1 only
     int do_linearize(DeviceState<T>& s, bool full = false) {
-        if (box_on) {
-            // control limits: the generic expansion for the box sweep (ops.linearize_box)
+        if (box_on || al_on) {
+            // control limits: the generic expansion for the box sweep (ops.linearize_box); state limits: that of J_A
             if (int rb = ensure_box(s)) return rb;
             KArgs<T> a = kargs(s);
             a.lin = s.box_lin; a.term = s.box_term;
             timer.begin(ILQR_PHASE_LINEARIZE, stream);
-            ops.linearize_box[cfg.integrator](a, stream);
+            if (al_on) ops.linearize_al[cfg.integrator](a, stream);
+            else ops.linearize_box[cfg.integrator](a, stream);
             timer.end(stream);
             s.slots_stale = true;
             s.lin_const = false;
@@ -1058,8 +1130,8 @@ template <typename T> class SolverT : public SolverBase {
     int do_backward(DeviceState<T>& s) {
         KArgs<T> a = kargs(s);
         a.reset_slots = s.slots_stale ? 1 : 0;
-        if (box_on) {
-            if (!s.box_lin_valid) { err = "backward: control limits were set after the last linearize"; return ILQR_ERR_STATE; }
+        if (box_on || al_on) {
+            if (!s.box_lin_valid) { err = "backward: limits were set after the last linearize"; return ILQR_ERR_STATE; }
             a.lin = s.box_lin; a.term = s.box_term;
             timer.begin(ILQR_PHASE_BACKWARD, stream);
             ops.backward_box(a, stream);
@@ -1085,7 +1157,8 @@ template <typename T> class SolverT : public SolverBase {
         a.counter_idx = 0;
         for (int i = 0; i < n; ++i) a.alphas[i] = (T)alphas[i];
         timer.begin(ILQR_PHASE_FORWARD, stream);
-        if (box_on) ops.forward_box[cfg.integrator](a, stream);
+        if (al_on) ops.forward_al[cfg.integrator](a, stream);
+        else if (box_on) ops.forward_box[cfg.integrator](a, stream);
         else ops.forward[cfg.integrator](a, stream);
         timer.end(stream);
         return check_launch();
@@ -1115,7 +1188,7 @@ template <typename T> class SolverT : public SolverBase {
 
     bool fused_ok() const {
         static const bool off = getenv("ILQR_NO_FUSE") != nullptr;   // A/B switch, and bench.py's materialised leg
-        return !off && !force_unfused && (!box_on || ops.fused_box) && !(cfg.flags & ILQR_FLAG_NO_FUSE) && ops.fused[cfg.integrator] && cfg.mu == 0.0 && (int)trial_alphas.size() <= A &&
+        return !off && !force_unfused && !al_on && (!box_on || ops.fused_box) && !(cfg.flags & ILQR_FLAG_NO_FUSE) && ops.fused[cfg.integrator] && cfg.mu == 0.0 && (int)trial_alphas.size() <= A &&
                (size_t)N * B * R * sizeof(T) <= kDescriptorMax;
     }
     bool force_unfused = false;
@@ -1159,6 +1232,7 @@ template <typename T> class SolverT : public SolverBase {
         // ignores status / accepted and clears counter slot 0, the select's init mode rewrites status, iteration count
         // and accepted flag of every trajectory -- two launches, no memsets (an MPC step used to pay three).
         const double zero = 0.0;
+        al_cost_valid = false;
         if ((rc = do_forward(st, &zero, 1, true))) return rc;
         if ((rc = do_select(st, &zero, 1, false, true, 0))) return rc;
         have_rollout = true;
@@ -1265,6 +1339,7 @@ template <typename T> class SolverT : public SolverBase {
 
     int iterate(int n) override {
         if (!have_rollout) { err = "iterate before initial_rollout"; return ILQR_ERR_STATE; }
+        al_cost_valid = false;
         static const bool want_graph = getenv("ILQR_USE_GRAPH") != nullptr;
         int i = 0;
         if (want_graph && graph_ok && !timer.on && n >= 1) {
@@ -1309,6 +1384,12 @@ template <typename T> class SolverT : public SolverBase {
             return ILQR_OK;
         }
         if ((rc = initial_rollout())) return rc;
+        return run_iterations();
+    }
+    // the multi-launch iteration loop of run_solve_loop, after the head of the solve: iterations until no trajectory is
+    // active or maxiter (also each inner solve of a state-limited solve, solve_al)
+    int run_iterations() {
+        int rc;
         if (!loop_ev[0]) {
             ILQR_HIPCHK(hipEventCreateWithFlags(&loop_ev[0], hipEventDisableTiming));
             ILQR_HIPCHK(hipEventCreateWithFlags(&loop_ev[1], hipEventDisableTiming));
@@ -1368,11 +1449,114 @@ template <typename T> class SolverT : public SolverBase {
 
     int solve(int32_t* iters, void* cost) override {
         if (!have_problem) { err = "solve before set_problem"; return ILQR_ERR_STATE; }
+        if (al_on) return solve_al(iters, cost);
         int rc = run_solve_loop();
         if (rc) return rc;
         if (iters) ILQR_HIPCHK(hipMemcpyAsync(iters, st.iters, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, stream));
         if (cost) ILQR_HIPCHK(hipMemcpyAsync(cost, st.cost, (size_t)B * sizeof(T), hipMemcpyDeviceToHost, stream));
         return sync();
+    }
+
+    // ---- state limits (augmented Lagrangian) ----------------------------------------------
+    ALArgs<T> al_args() const {
+        ALArgs<T> s{};
+        s.lam = al_lam; s.rho = al_rho; s.viol = al_viol; s.cost_plain = al_cost_plain;
+        s.outer = al_outer; s.live = al_live; s.base = al_base; s.count = al_count;
+        s.ctol = (T)al_ctol; s.rho0 = (T)al_rho0; s.rho_factor = (T)al_rho_factor; s.rho_max = (T)al_rho_max;
+        s.max_outer = al_max_outer;
+        return s;
+    }
+    int al_alloc() {
+        if (al_lam) return ILQR_OK;
+        const size_t b = B;
+        ILQR_HIPCHK(hipMalloc((void**)&al_lam, (size_t)(N + 1) * 2 * NX * b * sizeof(T)));
+        ILQR_HIPCHK(hipMalloc((void**)&al_rho, b * sizeof(T)));
+        ILQR_HIPCHK(hipMalloc((void**)&al_viol, b * sizeof(T)));
+        ILQR_HIPCHK(hipMalloc((void**)&al_cost_plain, b * sizeof(T)));
+        ILQR_HIPCHK(hipMalloc((void**)&al_outer, b * sizeof(int)));
+        ILQR_HIPCHK(hipMalloc((void**)&al_live, b * sizeof(int)));
+        ILQR_HIPCHK(hipMalloc((void**)&al_base, b * sizeof(int)));
+        ILQR_HIPCHK(hipMalloc((void**)&al_count, sizeof(int)));
+        return ILQR_OK;
+    }
+    // lam = 0, rho = rho0, outer counts 0, every trajectory in the outer loop
+    int al_reset() {
+        ILQR_HIPCHK(hipMemsetAsync(al_lam, 0, (size_t)(N + 1) * 2 * NX * B * sizeof(T), stream));
+        ILQR_LAUNCH(al_reset_kernel<T>, dim3((B + 255) / 256), dim3(256), 0, stream, al_args(), B);
+        return check_launch();
+    }
+    // ilqr_solve with state limits: the head of the solve, then inner solves (the multi-launch loop: fused_ok() is false)
+    // and outer updates until no trajectory is re-armed.  The host reads one count per outer iteration.
+    int solve_al(int32_t* iters, void* cost) {
+        int rc;
+        if ((rc = flush_select())) return rc;
+        if ((rc = al_reset())) return rc;
+        if ((rc = initial_rollout())) return rc;
+        for (int outer = 0;; ++outer) {
+            if ((rc = run_iterations())) return rc;
+            if ((rc = flush_select())) return rc;
+            if ((rc = fix_slots(st))) return rc;
+            ILQR_HIPCHK(hipMemsetAsync(al_count, 0, sizeof(int), stream));
+            timer.begin(ILQR_PHASE_OTHER, stream);
+            ops.al_update(kargs(st), al_args(), stream);
+            timer.end(stream);
+            if ((rc = check_launch())) return rc;
+            ILQR_HIPCHK(hipMemcpyAsync(h_counter, al_count, sizeof(int), hipMemcpyDeviceToHost, stream));
+            ILQR_HIPCHK(hipStreamSynchronize(stream));
+            // (every trajectory leaves after at most max_outer inner solves: the bound only guards against a broken count)
+            if (h_counter[0] == 0 || outer >= al_max_outer) break;
+        }
+        timer.begin(ILQR_PHASE_OTHER, stream);
+        ops.al_cost(kargs(st), al_args(), stream);
+        timer.end(stream);
+        if ((rc = check_launch())) return rc;
+        al_cost_valid = true;
+        if (iters) ILQR_HIPCHK(hipMemcpyAsync(iters, st.iters, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, stream));
+        if (cost) ILQR_HIPCHK(hipMemcpyAsync(cost, al_cost_plain, (size_t)B * sizeof(T), hipMemcpyDeviceToHost, stream));
+        return sync();
+    }
+    int set_state_limits(const double* x_min, const double* x_max, double ctol, double rho0, double rho_factor,
+                         double rho_max, int max_outer) override {
+        if (!x_min && !x_max) {
+            if (int rf = flush_select()) return rf;
+            if (al_on) lin_stale = true;      // the expansion in HBM is J_A's
+            al_on = false;
+            al_cost_valid = false;
+            return ILQR_OK;
+        }
+        if (!x_min || !x_max) { err = "set_state_limits: give both x_min and x_max, or neither"; return ILQR_ERR_INVALID_ARG; }
+        if (!ops.backward_box || !ops.linearize_al[cfg.integrator] || !ops.forward_al[cfg.integrator] || !ops.al_update ||
+            NX > kALMaxX || NU > kBoxMaxU) {
+            err = "set_state_limits: state limits are supported for the pendulum, UA double pendulum and double pendulum only";
+            return ILQR_ERR_UNSUPPORTED;
+        }
+        int mask = 0;
+        for (int i = 0; i < NX; ++i) {
+            if (std::isnan(x_min[i]) || std::isnan(x_max[i]) || x_min[i] > x_max[i]) {
+                err = "set_state_limits: x_min and x_max must not be NaN and x_min <= x_max";
+                return ILQR_ERR_INVALID_ARG;
+            }
+            if (!std::isinf(x_max[i])) mask |= 1 << i;          // an infinite bound is no constraint
+            if (!std::isinf(x_min[i])) mask |= 1 << (NX + i);
+        }
+        if (!(ctol > 0) || !(rho0 > 0) || !(rho_factor >= 1) || !(rho_max >= rho0) || max_outer < 1) {
+            err = "set_state_limits: need ctol > 0, rho0 > 0, rho_factor >= 1, rho_max >= rho0 and max_outer >= 1";
+            return ILQR_ERR_INVALID_ARG;
+        }
+        if (int rf = flush_select()) return rf;
+        if (int rb = ensure_box(st)) return rb;
+        if (int ra = al_alloc()) return ra;
+        if (iter_graph) { hipGraphExecDestroy(iter_graph); iter_graph = nullptr; }   // (captured with the old arguments)
+        for (int i = 0; i < kALMaxX; ++i) {
+            al_lo[i] = i < NX && !std::isinf(x_min[i]) ? x_min[i] : 0.0;
+            al_hi[i] = i < NX && !std::isinf(x_max[i]) ? x_max[i] : 0.0;
+        }
+        al_mask = mask;
+        al_ctol = ctol; al_rho0 = rho0; al_rho_factor = rho_factor; al_rho_max = rho_max; al_max_outer = max_outer;
+        lin_stale = true;          // an expansion in HBM has no (or other) multiplier terms
+        al_on = true;
+        al_cost_valid = false;
+        return al_reset();
     }
 
     // ---- control limits -----------------------------------------------------------------
@@ -1478,7 +1662,13 @@ template <typename T> class SolverT : public SolverBase {
         return ILQR_OK;
     }
 
+    // the functional calls and the MPC loop carry no multipliers
+    int al_refuse(const char* what) {
+        err = std::string(what) + ": not supported while state limits are set (clear them with NULL, NULL)";
+        return ILQR_ERR_UNSUPPORTED;
+    }
     int backward_pass(const void* X, const void* U, void* Uff, void* K) override {
+        if (al_on) return al_refuse("backward_pass");
         if (!X || !U) { err = "backward_pass: NULL input"; return ILQR_ERR_INVALID_ARG; }
         int rc;
         if ((rc = ensure_fn()) || (rc = reset_fn())) return rc;
@@ -1493,6 +1683,7 @@ template <typename T> class SolverT : public SolverBase {
 
     // the Riccati sweep alone, on an expansion the caller computed (its own autodiff, identified model, ...)
     int backward_tensors(const void* lin, const void* term, void* Uff, void* K) override {
+        if (al_on) return al_refuse("backward_tensors");
         if (!lin || !term) { err = "backward_tensors: NULL input"; return ILQR_ERR_INVALID_ARG; }
         if (box_on) { err = "backward_tensors: the box QP needs the controls u_t, which an expansion does not carry (clear the limits)"; return ILQR_ERR_UNSUPPORTED; }
         int rc;
@@ -1521,6 +1712,7 @@ template <typename T> class SolverT : public SolverBase {
 
     int forward_pass(const void* x0, double alpha, const void* X, const void* U, const void* Uff, const void* K,
                      void* Xn, void* Un, void* cost) override {
+        if (al_on) return al_refuse("forward_pass");
         if (!x0 || !X || !U || !Uff || !K) { err = "forward_pass: NULL input"; return ILQR_ERR_INVALID_ARG; }
         int rc;
         if ((rc = ensure_fn()) || (rc = reset_fn())) return rc;
@@ -1583,6 +1775,7 @@ template <typename T> class SolverT : public SolverBase {
 
     // ---- MPC ----------------------------------------------------------------------------
     int mpc_reset(const void* x0, const void* U) override {
+        if (al_on) return al_refuse("mpc_reset");
         int rc = set_problem(x0, U);
         if (rc) return rc;
         if ((rc = up_tc(x0, plant_x, NX, 1))) return rc;
@@ -1595,6 +1788,7 @@ template <typename T> class SolverT : public SolverBase {
     // its loop on the same solver object, so step 0's alpha = 0 rollout is u = U_guess + K_warm (x - X_warm)
     // (SURVEY Q1 / Q2); mpc_reset() is the cold start of run_iLQR_UA_MPC.py, whose warm-up is side-effect free.
     int mpc_rearm(const void* x0, const void* U) override {
+        if (al_on) return al_refuse("mpc_rearm");
         if (!x0 || !U) { err = "mpc_rearm: NULL pointer"; return ILQR_ERR_INVALID_ARG; }
         if (!have_problem) { err = "mpc_rearm before set_problem / mpc_reset"; return ILQR_ERR_STATE; }
         int rc;
@@ -1608,6 +1802,7 @@ template <typename T> class SolverT : public SolverBase {
     }
 
     int mpc_run(int n_steps, void* u_out, void* x_out, void* cost_out) override {
+        if (al_on) return al_refuse("mpc_run");
         if (!mpc_ready) { err = "mpc_run before mpc_reset"; return ILQR_ERR_STATE; }
         if (cfg.plant_integrator < 0) { err = "mpc_run: the handle was created without a plant integrator"; return ILQR_ERR_STATE; }
         if (n_steps < 1) { err = "mpc_run: n_steps < 1"; return ILQR_ERR_INVALID_ARG; }

@@ -56,6 +56,54 @@ def control_limits(system, u_min, u_max):
     return out[0], out[1]
 
 
+def state_limits(system, x_min, x_max, options=None):
+    """Validated state limits as (x_min, x_max, options): float64 [n_x] arrays (a scalar is broadcast, +-inf = no
+    constraint) and the outer loop's settings (``_lib.STATE_LIMIT_DEFAULTS`` updated by ``options``), or None for no
+    limits.  Raises ValueError, with "state limits" in the message, for a wrong shape, NaN, x_min > x_max, one bound
+    without the other, an unknown or bad option, or a system without state limits.  Pure host code (no GPU)."""
+    if x_min is None and x_max is None:
+        if options:
+            raise ValueError("state limits: options were given without x_min / x_max")
+        return None
+    if x_min is None or x_max is None:
+        raise ValueError("state limits: give both x_min and x_max (use +-inf for a side without a limit)")
+    if getattr(system, "SYSTEM_ID", None) not in _lib.BOX_SYSTEMS:
+        raise ValueError(f"state limits are supported for the pendulum, UA double pendulum and double pendulum "
+                         f"only, not for {type(system).__name__}")
+    n = system.n_x
+    out = []
+    for name, v in (("x_min", x_min), ("x_max", x_max)):
+        a = np.asarray(v, dtype=np.float64)
+        if a.ndim == 0:
+            a = np.full(n, float(a))
+        if a.shape != (n,):
+            raise ValueError(f"state limits: {name} must be a scalar or have shape ({n},), but got {a.shape}")
+        if np.isnan(a).any():
+            raise ValueError(f"state limits: {name} must not contain NaN")
+        out.append(np.ascontiguousarray(a))
+    if (out[0] > out[1]).any():
+        raise ValueError(f"state limits: x_min must be <= x_max, got {out[0]} > {out[1]}")
+    opts = dict(_lib.STATE_LIMIT_DEFAULTS)
+    unknown = sorted(set(options or {}) - set(opts))
+    if unknown:
+        raise ValueError(f"state limits: unknown option(s) {unknown}; expected some of {sorted(opts)}")
+    opts.update(options or {})
+    try:
+        for k in ("ctol", "rho0", "rho_factor", "rho_max"):
+            opts[k] = float(opts[k])
+        mo = opts["max_outer"]
+        if isinstance(mo, bool) or int(mo) != mo:
+            raise ValueError
+        opts["max_outer"] = int(mo)
+    except (TypeError, ValueError):
+        raise ValueError(f"state limits: options must be numbers (max_outer an integer), got {options}") from None
+    if not (opts["ctol"] > 0 and opts["rho0"] > 0 and opts["rho_factor"] >= 1 and opts["rho_max"] >= opts["rho0"]
+            and opts["max_outer"] >= 1) or not all(np.isfinite(opts[k]) for k in ("ctol", "rho0", "rho_factor")):
+        raise ValueError(f"state limits: need ctol > 0, rho0 > 0, rho_factor >= 1, rho_max >= rho0 and max_outer >= 1, "
+                         f"got {opts}")
+    return out[0], out[1], opts
+
+
 def batch_param_rows(system, B, params, with_target=True):
     """Per-trajectory parameter rows for ``ilqr_set_batch_params`` as a (B, row_len) float64 array.
 
@@ -102,7 +150,7 @@ class iLQR:
     def __init__(self, system: System, T=None, x_0=None, U_init=None, tol=1e-5, maxiter=100,
                  alpha_factor=0.5, min_alpha=1e-8, verbose=True, *, N=None, n_alpha=None, n_trials=10,
                  dtype=None, device=0, mu=0.0, plant=None, flags=0, stream=None, u_min=None, u_max=None,
-                 batch_params=None, plant_params=None):
+                 batch_params=None, plant_params=None, x_min=None, x_max=None, state_limit_options=None):
         self.system = system
         self.T = T
         self.tol, self.maxiter = tol, maxiter
@@ -139,6 +187,7 @@ class iLQR:
                              "(only its integrator may differ, run_iLQR_MPC.py:58-75)")
         self.plant = plant
         limits = control_limits(system, u_min, u_max)   # checked before any device is touched
+        xlimits = state_limits(system, x_min, x_max, state_limit_options)
         model_rows = None if batch_params is None else batch_param_rows(system, self.B, batch_params)
         plant_rows = None if plant_params is None else batch_param_rows(system, self.B, plant_params, with_target=False)
         trial_count = 0
@@ -158,6 +207,9 @@ class iLQR:
         if limits is not None:
             self._h.set_control_limits(*limits)
         self.u_min, self.u_max = (None, None) if limits is None else limits
+        self.x_min = self.x_max = self.state_limit_options = None
+        if xlimits is not None:
+            self._apply_state_limits(xlimits)
         if model_rows is not None:
             self._h.set_batch_params(_lib.BATCH_MODEL, model_rows)
         if plant_rows is not None:
@@ -178,6 +230,40 @@ class iLQR:
         else:
             self._h.set_control_limits(*limits)
             self.u_min, self.u_max = limits
+
+    def set_state_limits(self, x_min, x_max, **options):
+        """Bounds x_min <= x_t <= x_max on the state, t = 1..N (include/ilqr_hip.h, ilqr_set_state_limits): scalars or
+        [n_x] arrays, +-inf for a side without a limit; (None, None) removes them.  Solved by the PHR augmented
+        Lagrangian around the inner iLQR solve; options: ctol (1e-4), rho0 (1), rho_factor (10), rho_max (1e8),
+        max_outer (10).  optimize_trajectory() then reports the plain cost J, and .multipliers, .violation,
+        .outer_iterations; a trajectory still violating by more than ctol after max_outer inner solves has
+        .infeasible set.  The functional passes and the MPC calls refuse while limits are set."""
+        self._apply_state_limits(state_limits(self.system, x_min, x_max, options))
+
+    def _apply_state_limits(self, xlimits):
+        if xlimits is None:
+            self._h.set_state_limits(None, None)
+            self.x_min = self.x_max = self.state_limit_options = None
+        else:
+            self._h.set_state_limits(xlimits[0], xlimits[1], **xlimits[2])
+            self.x_min, self.x_max, self.state_limit_options = xlimits
+
+    @property
+    def multipliers(self):
+        """State-limit multipliers ([B,] N+1, 2 n_x): upper bounds (x_max) first, row t = 0 unused."""
+        return self._out(self._h.get(_lib.MULTIPLIERS))
+
+    @property
+    def violation(self):
+        """max over t, j of max(0, c) on the accepted trajectory of the last inner solve ([B])."""
+        v = self._h.get(_lib.VIOLATION)
+        return ready(v) if self.batched else v[0]
+
+    @property
+    def outer_iterations(self):
+        """Inner solves run by the last state-limited optimize_trajectory() ([B])."""
+        n = self._h.get(_lib.OUTER_ITERS)
+        return n if self.batched else int(n[0])
 
     def set_batch_params(self, params):
         """Per-trajectory system parameters and x_target of the model (include/ilqr_hip.h, ilqr_set_batch_params):
@@ -267,14 +353,18 @@ class iLQR:
     # ---- optimize_trajectory (iLQR_class.py:250-313) --------------------------------------------
     def optimize_trajectory(self):
         h = self._h
-        if self.verbose and not self.batched:
+        if self.verbose and not self.batched and self.x_min is None:
             self._solve_verbose()
         else:
-            h.solve()
+            h.solve()       # (state limits: the outer loop runs inside ilqr_solve, so no per-iteration printout)
         st = h.get(_lib.STATUS)
         self.iterations = h.get(_lib.ITERS)
         self.status = [STATUS_NAMES[int(s) & 0xff] for s in st]
         self.non_pd = (st & _lib.TRAJ_FLAG_NON_PD) != 0
+        self.infeasible = (st & _lib.TRAJ_FLAG_INFEASIBLE) != 0
+        if self.verbose and self.x_min is not None:
+            print(f"state limits: outer iterations max {int(np.max(self.outer_iterations))}, max violation "
+                  f"{float(np.max(self.violation)):.3e}, infeasible {int(np.sum(self.infeasible))}")
         if self.verbose and self.batched:
             counts = {v: self.status.count(v) for v in STATUS_NAMES.values()}
             print(f"iLQR batch of {self.B}: {counts}, iterations min/max "

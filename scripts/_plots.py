@@ -21,14 +21,18 @@ def _figure(n_rows):
     return plt, fig
 
 
-def open_loop_figure(path, tspan, X_bar, U_bar):
-    """run_iLQR_open_loop.py:115-145.  X_bar (n_x, N+1), U_bar (n_u, N), tspan (N+1)."""
+def open_loop_figure(path, tspan, X_bar, U_bar, x_bounds=None):
+    """run_iLQR_open_loop.py:115-145.  X_bar (n_x, N+1), U_bar (n_u, N), tspan (N+1).
+    x_bounds: {state index: (lower, upper)} state limits, drawn as dashed lines on that state's panel."""
     X_bar, U_bar = np.asarray(X_bar), np.asarray(U_bar)
     n_x, n_u = X_bar.shape[0], U_bar.shape[0]
     plt, fig = _figure(n_x + 1)
     for i, lab in enumerate(state_labels(n_x)):
         ax = plt.subplot(n_x + 1, 1, i + 1)
         ax.plot(tspan, X_bar[i, :], "b-", linewidth=2, label="iLQR")
+        for k, v in enumerate((x_bounds or {}).get(i, ())):
+            if np.isfinite(v):
+                ax.axhline(v, color="m", linestyle="--", linewidth=1.5, label="State limit" if k == 0 else None)
         if i == 0:
             ax.set_title("Optimal State Trajectories")
             ax.legend()
