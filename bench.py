@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- iLQR iterations/sec of the batched hot path on N x MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--dtype f64|f32] [--batch B] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dtype f64|f32] [--batch B] [--dump-outputs DIR] [--full]
 
 A "step" is one iLQR iteration over the whole batch: linearise every (b, t), backward
 Riccati sweep, rollouts of every trial alpha of the backtracking line search, accept.
@@ -17,9 +17,13 @@ timed region.  For N > 1 launch with torch.distributed.run (one rank per GPU, RC
 rank owns an independent shard (weak scaling, no data-path collective); the only exchange
 is the per-step all-reduce of {min cost, max |dcost|, #active, #converged}.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` for the
-backward-sweep kernel (HIP events on the kernel's own stream) and `cpu_baseline` (the C
-restatement of the reference algorithm, oracle/c, timed on the host cores).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run does only what
+that headline needs: set up, warm up, time the K steps, dump the outputs if asked, print.
+`--full` adds everything measured beside it, all outside the timed region: `cpu_baseline`
+(the C restatement of the reference algorithm, oracle/c, timed on the host cores), the
+per-phase breakdown with `roofline` for the backward-sweep kernel (HIP events on the
+kernel's own stream), the materialised path, the solve to convergence, the c4 MPC shard and
+the other BASELINE configs.
 """
 import argparse
 import json
@@ -429,9 +433,14 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (one rank per GPU); gloo = rehearsal of the N-rank control flow with several ranks "
                          "on ONE card (tests): ranks map to device LOCAL_RANK %% device_count, collectives run on host copies")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-phase-timing", action="store_true")
-    ap.add_argument("--no-solve-extra", action="store_true", help="skip the solve_to_convergence / MPC / configs extras (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="c3: also measure everything reported beside the headline (CPU baseline, phase breakdown and roofline, "
+                         "materialised path, solve to convergence, c4 MPC shard, other configs), outside the timed region")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-phase-timing", action="store_true",
+                    help="--full without the phase breakdown, the materialised path and the extras behind them")
+    ap.add_argument("--no-solve-extra", action="store_true",
+                    help="--full without the solve_to_convergence / MPC / configs extras (profiling runs)")
     ap.add_argument("--exchange", action="store_true",
                     help="N = 1 only: run the inter-GPU status exchange anyway, over a ONE-rank RCCL group")
     ap.add_argument("--exchange-every", type=int, default=0,
@@ -443,6 +452,7 @@ def main():
                     help="write what the timed path computed in its last step as DIR/<name>.npy (rank 0's shard; at most "
                          f"{DUMP_BUDGET_BYTES // 1000000} MB in all: a fixed, seeded sample of the batch beyond that)")
     args = ap.parse_args()
+    phase_timing = args.full and not args.no_phase_timing
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -453,7 +463,7 @@ def main():
     p = problems.ua_double_pendulum(integrator="rk4", N=200)
     # CPU baseline first: its worker processes are forked before this process touches the GPU
     cpu = cpu_all = None
-    if world == 1 and not args.no_cpu_baseline and args.config == "c3":
+    if world == 1 and args.full and not args.no_cpu_baseline and args.config == "c3":
         share, every = host_cores()
         cpu = cpu_baseline(p, args.dtype, share)
         cpu["numpy_restatement_single_core_value"] = numpy_restatement_rate(p, args.dtype)
@@ -556,7 +566,7 @@ def main():
     # dispatch (hipExtLaunchKernelGGL: the dispatch's own begin/end timestamps, no extra stream packets)
     phases = None
     mat = None
-    if not args.no_phase_timing:
+    if phase_timing:
         h.timing_enable(True)
         h.timing_reset()
         for _ in range(args.steps):
@@ -681,7 +691,7 @@ def main():
                 out["gpu_over_cpu_all_cores"] = value / cpu_all["value"]
         if exchange and world == 1:
             out["exchange"] = f"status all-gather over a one-rank RCCL group (side stream) every {every} steps"
-        if world == 1 and not args.no_phase_timing and not args.no_solve_extra:
+        if world == 1 and phase_timing and not args.no_solve_extra:
             # reported beside the throughput figure, outside every timed region above: the same batch
             # solved to convergence with the reference's stopping rules (tol, maxiter 50, line-search failure)
             hs = sysm.make_handle(horizon=N, batch=B, n_alpha=args.n_alpha, n_trials=10, tol=p["tol"], maxiter=50,

@@ -1,7 +1,7 @@
-"""bench.py as the driver runs it, on the one GPU of a test box: the headline line carries `roofline`, the
-materialised path beside the fused one and the per-config extras; `--config c4` / `--config c5` (the launchers an
-8-GPU node runs under torch.distributed.run) run with ONE rank over a one-rank RCCL group; and
-ShardedBatch.mpc_run reproduces the un-sharded device-resident MPC loop bit for bit."""
+"""bench.py as the driver runs it, on the one GPU of a test box: a plain run prints the headline alone; with `--full` the
+line carries `roofline`, the materialised path beside the fused one and the per-config extras; `--config c4` /
+`--config c5` (the launchers an 8-GPU node runs under torch.distributed.run) run with ONE rank
+over a one-rank RCCL group; and ShardedBatch.mpc_run reproduces the un-sharded device-resident MPC loop bit for bit."""
 import json
 import os
 import subprocess
@@ -28,7 +28,7 @@ def _bench(*args, timeout=300):
 
 
 def test_headline_line_small():
-    d = _bench("--steps", "4", "--warmup", "2", "--batch", "2048", "--no-cpu-baseline")     # (> 1024: the two-launch fused path)
+    d = _bench("--steps", "4", "--warmup", "2", "--batch", "2048", "--full", "--no-cpu-baseline")     # (> 1024: the two-launch fused path)
     assert d["unit"] == "iLQR iterations/sec" and d["n_gpus"] == 1 and d["steps"] == 4 and d["all_costs_finite"]
     assert abs(d["value"] - 2048 * 4 / (d["ms_per_step"] * 4e-3)) / d["value"] < 1e-9
     assert "fused" in d["config"]["iteration_path"]
@@ -45,6 +45,15 @@ def test_headline_line_small():
     assert m["all_finite"] and m["host_looped"]["same_result"] and m["host_looped"]["attribution"]["iteration_launches_per_step"] >= 1
     s = d["solve_to_convergence"]
     assert s["converged"] + s["linesearch_failed"] + s["maxiter"] == 2048
+
+
+def test_plain_run_is_the_headline_alone():
+    """Without --full nothing is measured beside the timed steps: the line holds the headline and its configuration."""
+    d = _bench("--steps", "3", "--warmup", "1", "--batch", "256")
+    assert d["unit"] == "iLQR iterations/sec" and d["steps"] == 3 and d["warmup"] == 1 and d["all_costs_finite"]
+    assert abs(d["value"] - 256 * 3 / (d["ms_per_step"] * 3e-3)) / d["value"] < 1e-9
+    assert not set(d) & {"cpu_baseline", "cpu_baseline_all_cores", "phases_us_per_step", "kernels", "roofline",
+                         "roofline_materialised", "materialised", "solve_to_convergence", "mpc_c4_shard", "configs"}
 
 
 def test_headline_under_torch_distributed_run_one_rank():
@@ -94,14 +103,14 @@ def test_two_ranks_rehearsed_on_one_card(extra, unit, total):
 
 def test_headline_small_shard_runs_persistent():
     """A shard of <= 1024 trajectories: the whole iteration is one launch of ilqr_persistent_kernel, and the line says so."""
-    d = _bench("--steps", "3", "--warmup", "1", "--batch", "256", "--no-cpu-baseline", "--no-solve-extra")
+    d = _bench("--steps", "3", "--warmup", "1", "--batch", "256", "--full", "--no-cpu-baseline", "--no-solve-extra")
     assert "persistent" in d["config"]["iteration_path"] and "ilqr_persistent_kernel" in d["roofline"]["kernel"]
     assert d["roofline"]["launches"] == 3 and d["roofline"]["avg_launch_us"] > 0 and d["all_costs_finite"]
     assert any(k.startswith("ilqr_persistent_kernel") for k in d["kernels"])
 
 
 def test_headline_materialised_switch():
-    d = _bench("--steps", "3", "--warmup", "1", "--batch", "256", "--no-cpu-baseline", "--no-solve-extra", "--materialised")
+    d = _bench("--steps", "3", "--warmup", "1", "--batch", "256", "--full", "--no-cpu-baseline", "--no-solve-extra", "--materialised")
     assert "materialised" in d["config"]["iteration_path"] and d["roofline"]["bound"] == "hbm"
 
 
