@@ -147,7 +147,10 @@ typedef enum ilqr_field {
     ILQR_MULTIPLIERS = 13, /* [B][N+1][2 n_x] state-limit multipliers lam_t, upper bounds (x_max) first, row t = 0 and
                               the constraints of infinite bounds 0; handle dtype (get only, see ilqr_set_state_limits) */
     ILQR_VIOLATION = 14,   /* [B]  max over t = 1..N, j of max(0, c) on the accepted X of the last inner solve; handle dtype (get only) */
-    ILQR_OUTER_ITERS = 15  /* [B]  int32 inner solves run by the last state-limited ilqr_solve (get only) */
+    ILQR_OUTER_ITERS = 15, /* [B]  int32 inner solves run by the last state-limited ilqr_solve (get only) */
+    ILQR_MPC_STATUS_LOG = 16 /* [n_steps][B] int32 status word of every step's solve in the last state-limited
+                                ilqr_mpc_run, ILQR_TRAJ_FLAG_INFEASIBLE included; bytes = n_steps * B * 4 of that run;
+                                ILQR_ERR_STATE before any such run (get only, see ilqr_set_mpc_multipliers) */
 } ilqr_field;
 
 /* Phases timed by ilqr_timing_* (HIP events recorded on the handle's stream). */
@@ -314,14 +317,35 @@ int ilqr_set_batch_params(ilqr_handle h, int which, const double* rows, int row_
  *  - composes with control limits, per-trajectory parameters, every integrator and mu > 0.  Every state-limited call
  *    runs linearise -> box sweep -> rollouts -> select as separate launches, whatever cfg->flags say (the fused and
  *    persistent kernels have no state limits);
- *  - ilqr_backward_pass, ilqr_forward_pass, ilqr_backward_tensors (no multipliers) and ilqr_mpc_reset, ilqr_mpc_rearm,
- *    ilqr_mpc_run return ILQR_ERR_UNSUPPORTED while limits are set.
+ *  - ilqr_backward_pass, ilqr_forward_pass and ilqr_backward_tensors (no multipliers) return ILQR_ERR_UNSUPPORTED while
+ *    limits are set; so do ilqr_mpc_reset, ilqr_mpc_rearm and ilqr_mpc_run unless ilqr_set_mpc_multipliers has selected
+ *    a multiplier policy for the MPC loop.
  * Defaults (the Python layer's): ctol = 1e-4, rho0 = 1, rho_factor = 10, rho_max = 1e8, max_outer = 10.
  * Returns ILQR_ERR_UNSUPPORTED for ILQR_SYS_LINEAR and ILQR_SYS_CUSTOM (clearing with NULL, NULL is valid on every
  * handle), ILQR_ERR_INVALID_ARG for a NaN bound, x_min > x_max, exactly one NULL pointer, ctol <= 0, rho0 <= 0,
  * rho_factor < 1, rho_max < rho0 or max_outer < 1. */
 int ilqr_set_state_limits(ilqr_handle h, const double* x_min, const double* x_max, double ctol, double rho0,
                           double rho_factor, double rho_max, int max_outer);
+
+/* ---- state limits in the MPC loop (build extension) -------------------------------------------------------
+ * Selects what the multipliers of every MPC step's solve start from while state limits are set:
+ *  - ILQR_MPC_AL_OFF (the default): ilqr_mpc_reset, ilqr_mpc_rearm and ilqr_mpc_run return ILQR_ERR_UNSUPPORTED while
+ *    state limits are set;
+ *  - ILQR_MPC_AL_COLD: lam = 0, rho = rho0 at every step;
+ *  - ILQR_MPC_AL_WARM: rho = rho0, and lam = the previous step's final multipliers shifted one step along the horizon,
+ *    per trajectory: lam_t <- lam_{t+1} (t = 1..N-1), lam_N <- lam_N (the last row repeated, as the warm start of U),
+ *    lam_0 = 0.  The first step after ilqr_mpc_reset starts from lam = 0, the first after ilqr_mpc_rearm from the
+ *    multipliers of the solve that ran before, unshifted; the first of a later ilqr_mpc_run continues the shift.  Only
+ *    WARM steps write the shift: the first WARM step after COLD steps starts from the last COLD solve's multipliers,
+ *    unshifted (as after ilqr_mpc_rearm).
+ * With state limits set, each MPC step is exactly one state-limited ilqr_solve (x_0 from the plant, U the shifted warm
+ * start, X, K, U_ff carried from the step before), then the step's epilogue as without limits (plant step with
+ * plant_integrator and, where set, the plant rows).  After a state-limited ilqr_mpc_run: cost_out holds the plain J of
+ * every step, ILQR_MULTIPLIERS (unshifted), ILQR_VIOLATION and ILQR_OUTER_ITERS describe the last step's solve, and
+ * ILQR_MPC_STATUS_LOG holds every step's status words.  Without state limits the mode changes nothing.  The mode may be
+ * changed between any two calls.  Returns ILQR_ERR_INVALID_ARG for an unknown mode or a NULL handle. */
+enum { ILQR_MPC_AL_OFF = 0, ILQR_MPC_AL_COLD = 1, ILQR_MPC_AL_WARM = 2 };
+int ilqr_set_mpc_multipliers(ilqr_handle h, int mode);
 
 /* ---- multi-GPU hook -------------------------------------------
  * Writes 4 doubles to DEVICE memory `dev_out4` on the handle's stream:

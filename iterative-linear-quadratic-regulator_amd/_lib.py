@@ -25,7 +25,7 @@ F32, F64 = 0, 1
 SYS_PENDULUM, SYS_UA_DOUBLE_PENDULUM, SYS_DOUBLE_PENDULUM, SYS_LINEAR, SYS_CUSTOM = range(5)
 INTEGRATORS = {"euler": 0, "midpoint": 1, "rk4": 2, "backward_euler": 3, "discrete": 4}
 (X, U, K, UFF, X0, COST, STATUS, ITERS, ALPHA, TRIAL_COSTS, LIN, PLANT_X, PROBE, MULTIPLIERS, VIOLATION,
- OUTER_ITERS) = range(16)
+ OUTER_ITERS, MPC_STATUS_LOG) = range(17)
 TRAJ_ACTIVE, TRAJ_CONVERGED, TRAJ_LINESEARCH_FAILED, TRAJ_MAXITER = range(4)
 TRAJ_FLAG_NON_PD = 0x100
 TRAJ_FLAG_INFEASIBLE = 0x200
@@ -42,7 +42,7 @@ SYMBOLS = (
     "ilqr_initial_rollout", "ilqr_linearize", "ilqr_backward", "ilqr_forward", "ilqr_select", "ilqr_iterate",
     "ilqr_flush", "ilqr_solve", "ilqr_backward_pass", "ilqr_backward_tensors", "ilqr_forward_pass", "ilqr_eval_points", "ilqr_mpc_reset",
     "ilqr_mpc_rearm", "ilqr_mpc_run", "ilqr_status_reduce", "ilqr_timing_enable", "ilqr_timing_reset", "ilqr_timing_get", "ilqr_algorithmic_bytes",
-    "ilqr_set_control_limits", "ilqr_set_batch_params", "ilqr_set_state_limits",
+    "ilqr_set_control_limits", "ilqr_set_batch_params", "ilqr_set_state_limits", "ilqr_set_mpc_multipliers",
 )
 # ilqr_set_batch_params: which rows
 BATCH_MODEL, BATCH_PLANT = 0, 1
@@ -50,6 +50,9 @@ BATCH_MODEL, BATCH_PLANT = 0, 1
 BOX_SYSTEMS = (SYS_PENDULUM, SYS_UA_DOUBLE_PENDULUM, SYS_DOUBLE_PENDULUM)
 # ilqr_set_state_limits: the outer loop's settings when the caller gives none (include/ilqr_hip.h)
 STATE_LIMIT_DEFAULTS = dict(ctol=1e-4, rho0=1.0, rho_factor=10.0, rho_max=1e8, max_outer=10)
+# ilqr_set_mpc_multipliers: what each state-limited MPC step's multipliers start from
+MPC_AL_OFF, MPC_AL_COLD, MPC_AL_WARM = 0, 1, 2
+MPC_MULTIPLIER_MODES = {None: MPC_AL_OFF, "cold": MPC_AL_COLD, "warm": MPC_AL_WARM}
 
 
 class Config(C.Structure):
@@ -131,6 +134,7 @@ def load():
     lib.ilqr_set_control_limits.argtypes = [vp, vp, vp]
     lib.ilqr_set_batch_params.argtypes = [vp, ci, vp, ci]
     lib.ilqr_set_state_limits.argtypes = [vp, vp, vp, cd, cd, cd, cd, ci]
+    lib.ilqr_set_mpc_multipliers.argtypes = [vp, ci]
     if lib.ilqr_abi_version() != ABI_VERSION:
         raise RuntimeError("libilqr_hip.so ABI version mismatch: rebuild the library")
     _lib = lib
@@ -370,6 +374,16 @@ class Handle:
         hi = np.ascontiguousarray(x_max, dtype=np.float64).reshape(self.n_x)
         self._chk(self.lib.ilqr_set_state_limits(self.h, _ptr(lo), _ptr(hi), float(ctol), float(rho0),
                                                  float(rho_factor), float(rho_max), int(max_outer)))
+
+    def set_mpc_multipliers(self, mode):
+        """MPC_AL_OFF / MPC_AL_COLD / MPC_AL_WARM: what every state-limited MPC step's multipliers start from."""
+        self._chk(self.lib.ilqr_set_mpc_multipliers(self.h, int(mode)))
+
+    def mpc_status_log(self, n_steps):
+        """(n_steps, B) int32 status words of every step of the last state-limited mpc_run (of n_steps steps)."""
+        out = np.empty((int(n_steps), self.B), dtype=np.int32)
+        self._chk(self.lib.ilqr_get(self.h, MPC_STATUS_LOG, _ptr(out), out.nbytes))
+        return out
 
     # ---- per-trajectory parameters ----------------------------------------------------------------
     def set_batch_params(self, which, rows):

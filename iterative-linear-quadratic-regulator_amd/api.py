@@ -14,7 +14,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from .iLQR_class import iLQR
+from .iLQR_class import iLQR, mpc_multiplier_mode
 from .systems import (System, MyPendulum, MyUADoublePendulum, MyDoublePendulum, MyLinearSystem)
 
 _KINDS = {"pendulum": MyPendulum, "ua_double_pendulum": MyUADoublePendulum,
@@ -126,11 +126,17 @@ class MPCState:
 
 
 def mpc_init(dynamics, cost, x0, U_init, *, plant_integrator="midpoint", T=None, N=None, tol=1e-5, maxiter=10,
-             n_alpha=None, dtype=np.float64, device=0, u_min=None, u_max=None, batch_params=None, plant_params=None):
+             n_alpha=None, dtype=np.float64, device=0, u_min=None, u_max=None, batch_params=None, plant_params=None,
+             x_min=None, x_max=None, state_limit_options=None, multipliers="warm"):
     """Receding-horizon controller state (run_iLQR_MPC.py:58-106): optimiser model = ``dynamics``,
     plant = the same system with ``plant_integrator``; u_min, u_max: control limits of every solve; batch_params: the
     model's per-trajectory parameters and targets, plant_params: each plant's own system parameters (model mismatch),
-    both dicts for batch_param_rows."""
+    both dicts for batch_param_rows; x_min, x_max, state_limit_options: state limits of every solve (see
+    iLQR.set_state_limits), with ``multipliers`` ("warm" or "cold", see iLQR.set_mpc_multipliers) the policy of their
+    multipliers from step to step."""
+    limited = x_min is not None or x_max is not None
+    if mpc_multiplier_mode(multipliers) == 0 and limited:
+        raise ValueError("mpc_init: state limits need multipliers='warm' or 'cold'")
     system = make_system(dynamics, cost, dtype)
     if isinstance(dynamics, System):
         raise ValueError("mpc_init needs a dynamics description (dict) so it can build the plant twin")
@@ -139,7 +145,9 @@ def mpc_init(dynamics, cost, x0, U_init, *, plant_integrator="midpoint", T=None,
     if N is None and T is None:
         N = U_init.shape[-1]
     s = iLQR(system, T, x0, U_init, tol=tol, maxiter=maxiter, verbose=False, N=N, n_alpha=n_alpha, dtype=dtype,
-             device=device, plant=plant, u_min=u_min, u_max=u_max, batch_params=batch_params, plant_params=plant_params)
+             device=device, plant=plant, u_min=u_min, u_max=u_max, batch_params=batch_params, plant_params=plant_params,
+             x_min=x_min, x_max=x_max, state_limit_options=state_limit_options,
+             mpc_multipliers=multipliers if limited else None)
     s.mpc_reset(x0, U_init)
     return MPCState(solver=s)
 

@@ -273,6 +273,7 @@ int ilqr_set_state_limits(ilqr_handle h, const double* x_min, const double* x_ma
     }
     return h->impl->set_state_limits(x_min, x_max, ctol, rho0, rho_factor, rho_max, max_outer);
 }
+int ilqr_set_mpc_multipliers(ilqr_handle h, int mode) { ILQR_FWD(h, set_mpc_multipliers(mode)); }
 int ilqr_timing_enable(ilqr_handle h, int on) { ILQR_FWD(h, timing_enable(on)); }
 int ilqr_timing_reset(ilqr_handle h) { ILQR_FWD(h, timing_reset()); }
 int ilqr_timing_get(ilqr_handle h, double ms[ILQR_N_PHASES], int64_t launches[ILQR_N_PHASES]) {

@@ -1693,6 +1693,95 @@ __global__ void __launch_bounds__(64 * kMpcChunks) mpc_advance_kernel(MpcArgs<T>
     }
 }
 
+// MPC advance of a state-limited step (include/ilqr_hip.h, ilqr_set_mpc_multipliers): mpc_advance_kernel's work (m.cost
+// points at the plain J, ALArgs::cost_plain), the step's status word into status_log [n_steps][B], and in WARM the
+// multipliers shifted one step along the horizon OUT OF PLACE into lam_next [N+1][2 n_x][B]:
+//   lam_next[0] = 0, lam_next[t] = lam[t + 1] (t = 1..N-1), lam_next[N] = lam[N].
+// Out of place, no row is read after it is written, so the shift needs no barrier and no registers: the 16 slices of a
+// lane's column take the rows round-robin (one coalesced load and store per 64 trajectories and row), and the host swaps
+// the two buffers at the head of the next step.  The U shift and the plant step are mpc_advance_kernel's (a copy: that
+// kernel stays as it is).
+template <typename T> struct MpcALArgs {
+    MpcArgs<T> m;
+    const int* status;    // [B] status words of the step's solve
+    int* status_log;      // [n_steps][B]
+    const T* lam;         // [N+1][2 n_x][B] multipliers of the step's solve
+    T* lam_next;          // [N+1][2 n_x][B] the next step's start (WARM), or nullptr (COLD: no shift)
+};
+
+template <typename T, typename Dyn, bool HET = false>
+__global__ void __launch_bounds__(64 * kMpcChunks) mpc_advance_al_kernel(MpcALArgs<T> s) {
+    constexpr int NX = Dyn::NX, NU = Dyn::NU;
+    constexpr int kMpcSlice = kMpcSliceScalars / NU > 0 ? kMpcSliceScalars / NU : 1;
+    const MpcArgs<T>& a = s.m;
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    const int chunk = threadIdx.y;
+    const size_t B = a.B;
+    const bool inb = b < a.B;
+    const int bb = inb ? b : a.B - 1;
+    T* Uc = a.U + vec_at(B, a.N, NU, a.cur_slot[bb], 0, bb);
+    const size_t sU = B * NU;
+    const int n_shift = a.N - 1;                                   // U[t] <- U[t + 1], t = 0 .. N-2
+    const int per = (n_shift + kMpcChunks - 1) / kMpcChunks;       // time steps per slice
+    const bool sliced = per <= kMpcSlice;
+    T u0[NU];
+    vec_load<T, NU>(Uc, u0);                                       // (before anything is shifted)
+    T keep[kMpcSlice][NU];
+    const int t0 = chunk * per;
+    if (sliced) {
+#pragma unroll
+        for (int q = 0; q < kMpcSlice; ++q)
+            if (q < per && t0 + q < n_shift) vec_load<T, NU>(Uc + (size_t)(t0 + q + 1) * sU, keep[q]);
+    }
+    __syncthreads();
+    if (sliced) {
+        if (inb) {
+#pragma unroll
+            for (int q = 0; q < kMpcSlice; ++q)
+                if (q < per && t0 + q < n_shift) vec_store<T, NU>(Uc + (size_t)(t0 + q) * sU, keep[q]);
+        }
+    }
+    if (!inb) return;
+    if (s.lam_next) {
+        constexpr int Q = 2 * NX;
+        const int rows = (a.N + 1) * Q;                            // row r = t * Q + q
+        for (int r = chunk; r < rows; r += kMpcChunks) {
+            const int t = r / Q;
+            const T v = t == 0 ? T(0) : s.lam[(size_t)(t < a.N ? r + Q : r) * B + b];
+            s.lam_next[(size_t)r * B + b] = v;
+        }
+    }
+    if (chunk != 0) return;
+    T x[NX], xn[NX];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) x[i] = a.plant_x[(size_t)i * B + b];
+    if constexpr (HET) {
+        T pp[Dyn::NSYS];   // the plant's system constants (all a step reads)
+        load_row<Dyn::NSYS>(pp, a.plant_rows, B, b);
+        Stepper<T, Dyn>::step(a.plant_integ, pp, a.dt, x, u0, xn);
+    } else {
+        Stepper<T, Dyn>::step(a.plant_integ, a.params, a.dt, x, u0, xn);
+    }
+#pragma unroll
+    for (int i = 0; i < NX; ++i) {
+        a.plant_x[(size_t)i * B + b] = xn[i];
+        a.x0[(size_t)i * B + b] = xn[i];
+        if (a.x_log) a.x_log[((size_t)a.step * B + b) * NX + i] = xn[i];
+    }
+#pragma unroll
+    for (int j = 0; j < NU; ++j)
+        if (a.u_log) a.u_log[((size_t)a.step * B + b) * NU + j] = u0[j];
+    if (a.cost_log) a.cost_log[(size_t)a.step * B + b] = a.cost[b];
+    s.status_log[(size_t)a.step * B + b] = s.status[b];
+    if (!sliced) {
+        for (int t = 0; t + 1 < a.N; ++t) {
+            T un[NU];
+            vec_load<T, NU>(Uc + (t + 1) * sU, un);
+            vec_store<T, NU>(Uc + t * sU, un);
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------
 // layout conversion between the host layouts of the C-ABI (leading batch axis in
 // front of the reference layout) and the device's batch-innermost slots.

@@ -61,6 +61,7 @@ struct SolverBase {
     virtual int set_batch_params(int which, const double* rows, int row_len) = 0;
     virtual int set_state_limits(const double* x_min, const double* x_max, double ctol, double rho0, double rho_factor,
                                  double rho_max, int max_outer) = 0;
+    virtual int set_mpc_multipliers(int mode) = 0;
 };
 
 int system_dims(int system, int n_x, int n_u);  // 1 if (system, n_x, n_u) is a known combination
@@ -135,6 +136,7 @@ template <typename T> struct Ops {
     void (*forward_al[5])(const KArgs<T>&, hipStream_t) = {};
     void (*al_update)(const KArgs<T>&, const ALArgs<T>&, hipStream_t) = nullptr;
     void (*al_cost)(const KArgs<T>&, const ALArgs<T>&, hipStream_t) = nullptr;
+    void (*mpc_advance_al)(const MpcALArgs<T>&, hipStream_t) = nullptr;   // the epilogue of a state-limited MPC step
 };
 
 // linearize / forward are compiled once per integrator so the integrator switch folds away and each
@@ -456,6 +458,11 @@ template <typename T, typename Dyn> Ops<T> make_ops() {
             if (a.het) { ILQR_LAUNCH((al_cost_kernel<T, Dyn, true>), dim3((a.B + 63) / 64), dim3(64), 0, s, a, al); return; }
             ILQR_LAUNCH((al_cost_kernel<T, Dyn>), dim3((a.B + 63) / 64), dim3(64), 0, s, a, al);
         };
+        o.mpc_advance_al = [](const MpcALArgs<T>& a, hipStream_t s) {
+            const dim3 grid((a.m.B + 63) / 64), block(64, kMpcChunks);
+            if (a.m.plant_rows) { ILQR_LAUNCH((mpc_advance_al_kernel<T, Dyn, true>), grid, block, 0, s, a); return; }
+            ILQR_LAUNCH((mpc_advance_al_kernel<T, Dyn>), grid, block, 0, s, a);
+        };
     }
     o.eval = [](const EvalArgs<T>& a, hipStream_t s) {
         ILQR_LAUNCH((eval_points_kernel<T, Dyn>), dim3((a.npts + 63) / 64), dim3(64), 0, s, a);
@@ -701,6 +708,13 @@ template <typename T> class SolverT : public SolverBase {
     T *al_lam = nullptr, *al_rho = nullptr, *al_viol = nullptr, *al_cost_plain = nullptr;
     int *al_outer = nullptr, *al_live = nullptr, *al_base = nullptr, *al_count = nullptr;
     bool al_cost_valid = false; // al_cost_plain holds the plain J of the last solve's trajectories (ILQR_COST)
+    // state-limited MPC (ilqr_set_mpc_multipliers): the multiplier policy, the WARM shift's second buffer (al_lam_next holds
+    // the next step's start while al_lam_shifted; the two are swapped at the head of that step) and the status log
+    int mpc_al_mode = ILQR_MPC_AL_OFF;
+    T* al_lam_next = nullptr;
+    bool al_lam_shifted = false;
+    int* mpc_status_log = nullptr;     // [n_steps][B] status words of the last state-limited ilqr_mpc_run
+    int mpc_status_cap = 0, mpc_status_steps = 0;
 
     ~SolverT() override {
         if (stream) hipStreamSynchronize(stream);
@@ -711,6 +725,7 @@ template <typename T> class SolverT : public SolverBase {
         hipFree(plant_rows);
         hipFree(al_lam); hipFree(al_rho); hipFree(al_viol); hipFree(al_cost_plain);
         hipFree(al_outer); hipFree(al_live); hipFree(al_base); hipFree(al_count);
+        hipFree(al_lam_next); hipFree(mpc_status_log);
         hipFree(staging);
         hipFree(plant_x);
         hipFree(eval_buf);
@@ -1044,6 +1059,12 @@ template <typename T> class SolverT : public SolverBase {
 
     int get(int field, void* dst, size_t bytes) override {
         if (!dst) { err = "get: NULL pointer"; return ILQR_ERR_INVALID_ARG; }
+        if (field == ILQR_MPC_STATUS_LOG) {
+            if (!mpc_status_steps) { err = "get: no state-limited ilqr_mpc_run has run on this handle"; return ILQR_ERR_STATE; }
+            if (bytes != (size_t)mpc_status_steps * B * sizeof(int32_t)) { err = "get: wrong byte count"; return ILQR_ERR_INVALID_ARG; }
+            ILQR_HIPCHK(hipMemcpyAsync(dst, mpc_status_log, bytes, hipMemcpyDeviceToHost, stream));
+            return sync();
+        }
         const size_t want = field_bytes(field);
         if (want == 0 || bytes != want) { err = "get: unknown field or wrong byte count"; return ILQR_ERR_INVALID_ARG; }
         if (int rf = flush_select()) return rf;
@@ -1479,18 +1500,29 @@ template <typename T> class SolverT : public SolverBase {
         ILQR_HIPCHK(hipMalloc((void**)&al_count, sizeof(int)));
         return ILQR_OK;
     }
-    // lam = 0, rho = rho0, outer counts 0, every trajectory in the outer loop
-    int al_reset() {
-        ILQR_HIPCHK(hipMemsetAsync(al_lam, 0, (size_t)(N + 1) * 2 * NX * B * sizeof(T), stream));
+    // lam = 0 (unless zero_lam is false: a WARM MPC step keeps the lam it starts from), rho = rho0, outer counts 0, every
+    // trajectory in the outer loop.  A pending WARM shift is dropped: lam is what the next solve starts from.
+    int al_reset(bool zero_lam = true) {
+        al_lam_shifted = false;
+        if (zero_lam) ILQR_HIPCHK(hipMemsetAsync(al_lam, 0, (size_t)(N + 1) * 2 * NX * B * sizeof(T), stream));
         ILQR_LAUNCH(al_reset_kernel<T>, dim3((B + 255) / 256), dim3(256), 0, stream, al_args(), B);
         return check_launch();
     }
-    // ilqr_solve with state limits: the head of the solve, then inner solves (the multi-launch loop: fused_ok() is false)
-    // and outer updates until no trajectory is re-armed.  The host reads one count per outer iteration.
+    // ilqr_solve with state limits: the solve itself (solve_al_body), then the copies out and the sync
     int solve_al(int32_t* iters, void* cost) {
         int rc;
+        if ((rc = solve_al_body(true))) return rc;
+        if (iters) ILQR_HIPCHK(hipMemcpyAsync(iters, st.iters, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, stream));
+        if (cost) ILQR_HIPCHK(hipMemcpyAsync(cost, al_cost_plain, (size_t)B * sizeof(T), hipMemcpyDeviceToHost, stream));
+        return sync();
+    }
+    // The head of the solve (lam = 0 when zero_lam, else the lam it finds), then inner solves (the multi-launch loop:
+    // fused_ok() is false) and outer updates until no trajectory is re-armed, then the plain J.  The host reads one count
+    // per outer iteration; the final al_cost_kernel is left enqueued.  Also each step of a state-limited mpc_run.
+    int solve_al_body(bool zero_lam) {
+        int rc;
         if ((rc = flush_select())) return rc;
-        if ((rc = al_reset())) return rc;
+        if ((rc = al_reset(zero_lam))) return rc;
         if ((rc = initial_rollout())) return rc;
         for (int outer = 0;; ++outer) {
             if ((rc = run_iterations())) return rc;
@@ -1511,9 +1543,15 @@ template <typename T> class SolverT : public SolverBase {
         timer.end(stream);
         if ((rc = check_launch())) return rc;
         al_cost_valid = true;
-        if (iters) ILQR_HIPCHK(hipMemcpyAsync(iters, st.iters, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, stream));
-        if (cost) ILQR_HIPCHK(hipMemcpyAsync(cost, al_cost_plain, (size_t)B * sizeof(T), hipMemcpyDeviceToHost, stream));
-        return sync();
+        return ILQR_OK;
+    }
+    int set_mpc_multipliers(int mode) override {
+        if (mode != ILQR_MPC_AL_OFF && mode != ILQR_MPC_AL_COLD && mode != ILQR_MPC_AL_WARM) {
+            err = "set_mpc_multipliers: mode must be ILQR_MPC_AL_OFF, ILQR_MPC_AL_COLD or ILQR_MPC_AL_WARM";
+            return ILQR_ERR_INVALID_ARG;
+        }
+        mpc_al_mode = mode;
+        return ILQR_OK;
     }
     int set_state_limits(const double* x_min, const double* x_max, double ctol, double rho0, double rho_factor,
                          double rho_max, int max_outer) override {
@@ -1774,8 +1812,14 @@ template <typename T> class SolverT : public SolverBase {
     }
 
     // ---- MPC ----------------------------------------------------------------------------
+    // with state limits the MPC calls need a multiplier policy (ilqr_set_mpc_multipliers)
+    int mpc_al_refuse(const char* what) {
+        err = std::string(what) + ": not supported while state limits are set and the MPC multiplier mode is "
+              "ILQR_MPC_AL_OFF (select COLD or WARM with ilqr_set_mpc_multipliers, or clear the limits)";
+        return ILQR_ERR_UNSUPPORTED;
+    }
     int mpc_reset(const void* x0, const void* U) override {
-        if (al_on) return al_refuse("mpc_reset");
+        if (al_on && mpc_al_mode == ILQR_MPC_AL_OFF) return mpc_al_refuse("mpc_reset");
         int rc = set_problem(x0, U);
         if (rc) return rc;
         if ((rc = up_tc(x0, plant_x, NX, 1))) return rc;
@@ -1788,7 +1832,7 @@ template <typename T> class SolverT : public SolverBase {
     // its loop on the same solver object, so step 0's alpha = 0 rollout is u = U_guess + K_warm (x - X_warm)
     // (SURVEY Q1 / Q2); mpc_reset() is the cold start of run_iLQR_UA_MPC.py, whose warm-up is side-effect free.
     int mpc_rearm(const void* x0, const void* U) override {
-        if (al_on) return al_refuse("mpc_rearm");
+        if (al_on && mpc_al_mode == ILQR_MPC_AL_OFF) return mpc_al_refuse("mpc_rearm");
         if (!x0 || !U) { err = "mpc_rearm: NULL pointer"; return ILQR_ERR_INVALID_ARG; }
         if (!have_problem) { err = "mpc_rearm before set_problem / mpc_reset"; return ILQR_ERR_STATE; }
         int rc;
@@ -1797,12 +1841,13 @@ template <typename T> class SolverT : public SolverBase {
         if ((rc = up_tc(x0, st.x0, NX, 1))) return rc;
         if ((rc = up_tc(x0, plant_x, NX, 1))) return rc;
         if ((rc = up_ct(U, st.U, st.cur_slot, NU, N))) return rc;
+        al_lam_shifted = false;      // step 0 starts from the multipliers of the solve that ran before, unshifted
         mpc_ready = true;
         return ILQR_OK;
     }
 
     int mpc_run(int n_steps, void* u_out, void* x_out, void* cost_out) override {
-        if (al_on) return al_refuse("mpc_run");
+        if (al_on && mpc_al_mode == ILQR_MPC_AL_OFF) return mpc_al_refuse("mpc_run");
         if (!mpc_ready) { err = "mpc_run before mpc_reset"; return ILQR_ERR_STATE; }
         if (cfg.plant_integrator < 0) { err = "mpc_run: the handle was created without a plant integrator"; return ILQR_ERR_STATE; }
         if (n_steps < 1) { err = "mpc_run: n_steps < 1"; return ILQR_ERR_INVALID_ARG; }
@@ -1814,7 +1859,10 @@ template <typename T> class SolverT : public SolverBase {
             ILQR_HIPCHK(hipMalloc((void**)&mpc_cost_log, (size_t)n_steps * B * sizeof(T)));
             mpc_log_steps = n_steps;
         }
-        if (persist_ok()) {
+        if (al_on) {
+            int rc = mpc_run_al(n_steps);
+            if (rc) return rc;
+        } else if (persist_ok()) {
             // the whole receding-horizon loop on the device: a workgroup's MPC step lasts as long as ITS slowest instance
             MpcArgs<T> m{};
             m.B = B; m.N = N; m.plant_integ = cfg.plant_integrator; m.step = 0; m.dt = (T)cfg.dt; m.params = params;
@@ -1849,6 +1897,47 @@ template <typename T> class SolverT : public SolverBase {
         if ((rc = fetch(x_out, mpc_x_log, NX))) return rc;
         if ((rc = fetch(cost_out, mpc_cost_log, 1))) return rc;
         return sync();
+    }
+
+    // the steps of a state-limited mpc_run: each one exactly one state-limited solve (COLD: from lam = 0; WARM: from the
+    // previous step's multipliers shifted along the horizon, or after mpc_reset / mpc_rearm from those it finds), then
+    // mpc_advance_al_kernel
+    int mpc_run_al(int n_steps) {
+        const bool warm = mpc_al_mode == ILQR_MPC_AL_WARM;
+        if (!ops.mpc_advance_al) { err = "mpc_run: no state-limited MPC epilogue for this system"; return ILQR_ERR_UNSUPPORTED; }
+        if (n_steps > mpc_status_cap) {
+            ILQR_HIPCHK(hipStreamSynchronize(stream));
+            hipFree(mpc_status_log);
+            mpc_status_log = nullptr;
+            mpc_status_cap = 0;
+            ILQR_HIPCHK(hipMalloc((void**)&mpc_status_log, (size_t)n_steps * B * sizeof(int)));
+            mpc_status_cap = n_steps;
+        }
+        if (warm && !al_lam_next) ILQR_HIPCHK(hipMalloc((void**)&al_lam_next, (size_t)(N + 1) * 2 * NX * B * sizeof(T)));
+        mpc_status_steps = 0;        // (a run that fails part-way leaves no log)
+        for (int k = 0; k < n_steps; ++k) {
+            int rc;
+            if (warm && al_lam_shifted) {
+                if ((rc = flush_select())) return rc;
+                std::swap(al_lam, al_lam_next);
+                if (iter_graph) { hipGraphExecDestroy(iter_graph); iter_graph = nullptr; }   // (captured with the old lam)
+            }
+            if ((rc = solve_al_body(!warm))) return rc;
+            MpcALArgs<T> m{};
+            m.m.B = B; m.m.N = N; m.m.plant_integ = cfg.plant_integrator; m.m.step = k; m.m.dt = (T)cfg.dt; m.m.params = params;
+            m.m.U = st.U; m.m.cur_slot = st.cur_slot; m.m.x0 = st.x0; m.m.plant_x = plant_x;
+            m.m.u_log = mpc_u_log; m.m.x_log = mpc_x_log; m.m.cost_log = mpc_cost_log; m.m.cost = al_cost_plain;
+            m.m.plant_rows = kargs(st).plant_rows;
+            m.status = st.status; m.status_log = mpc_status_log;
+            m.lam = al_lam; m.lam_next = warm ? al_lam_next : nullptr;
+            timer.begin(ILQR_PHASE_OTHER, stream);
+            ops.mpc_advance_al(m, stream);
+            timer.end(stream);
+            if ((rc = check_launch())) return rc;
+            al_lam_shifted = warm;
+        }
+        mpc_status_steps = n_steps;
+        return ILQR_OK;
     }
 
     int debug_set_stream(void* sp) override { stream = (hipStream_t)sp; return ILQR_OK; }

@@ -104,6 +104,15 @@ def state_limits(system, x_min, x_max, options=None):
     return out[0], out[1], opts
 
 
+def mpc_multiplier_mode(mode):
+    """The ``ilqr_set_mpc_multipliers`` code of ``mode``: None (state-limited MPC refuses), "cold" (every step's solve
+    starts from lam = 0) or "warm" (from the previous step's multipliers shifted one step along the horizon).  Raises
+    ValueError for anything else.  Pure host code (no GPU)."""
+    if mode is None or (isinstance(mode, str) and mode in _lib.MPC_MULTIPLIER_MODES):
+        return _lib.MPC_MULTIPLIER_MODES[mode]
+    raise ValueError(f"MPC multipliers must be None, 'cold' or 'warm', got {mode!r}")
+
+
 def batch_param_rows(system, B, params, with_target=True):
     """Per-trajectory parameter rows for ``ilqr_set_batch_params`` as a (B, row_len) float64 array.
 
@@ -150,7 +159,8 @@ class iLQR:
     def __init__(self, system: System, T=None, x_0=None, U_init=None, tol=1e-5, maxiter=100,
                  alpha_factor=0.5, min_alpha=1e-8, verbose=True, *, N=None, n_alpha=None, n_trials=10,
                  dtype=None, device=0, mu=0.0, plant=None, flags=0, stream=None, u_min=None, u_max=None,
-                 batch_params=None, plant_params=None, x_min=None, x_max=None, state_limit_options=None):
+                 batch_params=None, plant_params=None, x_min=None, x_max=None, state_limit_options=None,
+                 mpc_multipliers=None):
         self.system = system
         self.T = T
         self.tol, self.maxiter = tol, maxiter
@@ -188,6 +198,7 @@ class iLQR:
         self.plant = plant
         limits = control_limits(system, u_min, u_max)   # checked before any device is touched
         xlimits = state_limits(system, x_min, x_max, state_limit_options)
+        mpc_mode = mpc_multiplier_mode(mpc_multipliers)
         model_rows = None if batch_params is None else batch_param_rows(system, self.B, batch_params)
         plant_rows = None if plant_params is None else batch_param_rows(system, self.B, plant_params, with_target=False)
         trial_count = 0
@@ -210,6 +221,10 @@ class iLQR:
         self.x_min = self.x_max = self.state_limit_options = None
         if xlimits is not None:
             self._apply_state_limits(xlimits)
+        self.mpc_multipliers = mpc_multipliers
+        if mpc_mode != _lib.MPC_AL_OFF:
+            self._h.set_mpc_multipliers(mpc_mode)
+        self.mpc_status_log = None
         if model_rows is not None:
             self._h.set_batch_params(_lib.BATCH_MODEL, model_rows)
         if plant_rows is not None:
@@ -237,8 +252,18 @@ class iLQR:
         Lagrangian around the inner iLQR solve; options: ctol (1e-4), rho0 (1), rho_factor (10), rho_max (1e8),
         max_outer (10).  optimize_trajectory() then reports the plain cost J, and .multipliers, .violation,
         .outer_iterations; a trajectory still violating by more than ctol after max_outer inner solves has
-        .infeasible set.  The functional passes and the MPC calls refuse while limits are set."""
+        .infeasible set.  The functional passes refuse while limits are set, and so do the MPC calls unless a
+        multiplier policy is set (set_mpc_multipliers)."""
         self._apply_state_limits(state_limits(self.system, x_min, x_max, options))
+
+    def set_mpc_multipliers(self, mode):
+        """What the multipliers of every state-limited MPC step start from (include/ilqr_hip.h,
+        ilqr_set_mpc_multipliers): "cold" (lam = 0 at every step), "warm" (the previous step's multipliers shifted one
+        step along the horizon, the last row repeated) or None (the MPC calls refuse while state limits are set).
+        Without state limits the mode changes nothing."""
+        code = mpc_multiplier_mode(mode)
+        self._h.set_mpc_multipliers(code)
+        self.mpc_multipliers = mode
 
     def _apply_state_limits(self, xlimits):
         if xlimits is None:
@@ -410,10 +435,15 @@ class iLQR:
 
     def mpc_run(self, n_steps):
         """n_steps receding-horizon steps on the device.  Returns (U_sim, X_sim, cost) with shapes
-        (n_steps, [B,] n_u), (n_steps, [B,] n_x) (state AFTER each step) and (n_steps, [B])."""
+        (n_steps, [B,] n_u), (n_steps, [B,] n_x) (state AFTER each step) and (n_steps, [B]).  With state limits (and
+        a multiplier policy, set_mpc_multipliers) every step is one state-limited solve, cost is its plain J, and
+        .mpc_status_log ((n_steps, [B]) int32) holds every step's status word, ILQR_TRAJ_FLAG_INFEASIBLE included."""
         if self.plant is None:
             raise ValueError("construct the solver with plant=<System> to run MPC steps")
         u, x, c = self._h.mpc_run(n_steps)
+        if self.x_min is not None:
+            log = self._h.mpc_status_log(n_steps)
+            self.mpc_status_log = log if self.batched else log[:, 0]
         if not self.batched:
             u, x, c = u[:, 0], x[:, 0], c[:, 0]
         return ready(u), ready(x), ready(c)

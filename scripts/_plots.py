@@ -52,9 +52,10 @@ def open_loop_figure(path, tspan, X_bar, U_bar, x_bounds=None):
     return path
 
 
-def closed_loop_figure(path, tspan_sim, X_sim, U_sim, x_target, u_bounds=None):
+def closed_loop_figure(path, tspan_sim, X_sim, U_sim, x_target, u_bounds=None, x_bounds=None):
     """run_iLQR_MPC.py:150-186.  X_sim (n_x, N_sim+1), U_sim (n_u, N_sim), tspan_sim (N_sim+1).
-    u_bounds: (u_min, u_max) control limits, drawn as dashed lines on the control panel."""
+    u_bounds: (u_min, u_max) control limits, drawn as dashed lines on the control panel; x_bounds: {state index:
+    (lower, upper)} state limits, drawn as dashed lines on that state's panel."""
     X_sim, U_sim = np.asarray(X_sim), np.asarray(U_sim)
     n_x, n_u = X_sim.shape[0], U_sim.shape[0]
     plt, fig = _figure(n_x + 1)
@@ -62,6 +63,9 @@ def closed_loop_figure(path, tspan_sim, X_sim, U_sim, x_target, u_bounds=None):
         ax = plt.subplot(n_x + 1, 1, i + 1)
         ax.plot(tspan_sim, X_sim[i, :], "b-", linewidth=2, label="Closed Loop")
         ax.axhline(x_target[i], color="r", linestyle="--", linewidth=2, label="Target")
+        for k, v in enumerate((x_bounds or {}).get(i, ())):
+            if np.isfinite(v):
+                ax.axhline(v, color="m", linestyle="--", linewidth=1.5, label="State limit" if k == 0 else None)
         if i == 0:
             ax.set_title("Closed-Loop State Trajectories")
             ax.legend()
