@@ -198,14 +198,14 @@ void launch_fused_kernel(const KArgs<T>& a, hipStream_t s) {
     (void)ok;
     static const int force = getenv("ILQR_FUSED_TPW") ? atoi(getenv("ILQR_FUSED_TPW")) : 0;   // A/B switch
     static const int small_max = getenv("ILQR_FUSED_SMALL_MAX") ? atoi(getenv("ILQR_FUSED_SMALL_MAX")) : 1024;
-    // Pair producers (two time steps per lane in packed FP32, bit-identical) are built and tested but OFF by default
-    // in this kernel: with a ring of 4 units they measured the same as the scalar ones (48.6 vs 48.1 us at B = 4096:
-    // the kernel is bound by the sweep waves' chain, and four lone pair waves deliver their first unit later and let
-    // the ring run dry); with 5 slots (133 KB of LDS, the build's value now) 44.7-45.8 against 46.4 us -- one
-    // microsecond, for a third fewer vector instructions in the same time (bench.py's issue-rate fraction would fall
-    // from 0.70 to ~0.6 with nothing else changing).  ILQR_FUSED_PAIRS=1 selects them; the 16-trajectory persistent
-    // kernel always uses them (register budget).
-    static const bool no_pk = getenv("ILQR_FUSED_PAIRS") == nullptr;                          // A/B switch
+    // Pair producers (two time steps per lane in packed FP32, bit-identical) are this kernel's default where they exist.
+    // With a ring of 4 units they measured the same as the scalar ones (48.6 vs 48.1 us at B = 4096: the kernel is
+    // bound by the sweep waves' chain, and four lone pair waves deliver their first unit later and let the ring run
+    // dry); with 5 slots (133 KB of LDS, the build's value) 44.7-45.8 against 46.4 us, and the whole iteration
+    // 0.1360 against 0.1372 ms in alternating runs: a third fewer vector instructions, so the
+    // issue-rate fraction bench.py reports falls while the time does.  ILQR_FUSED_PAIRS=0 selects the scalar
+    // producers; the 16-trajectory persistent kernel always runs the pair ones (register budget).
+    static const bool no_pk = getenv("ILQR_FUSED_PAIRS") != nullptr && atoi(getenv("ILQR_FUSED_PAIRS")) == 0;   // A/B switch
     const bool small = force ? force == 4 : a.B <= small_max;
     if (small) {
         ILQR_LAUNCH((fused_kernel<T, Dyn, I, 4, false, BX, HT>()), dim3((a.B + 3) / 4), dim3(fused_threads<T, 4, false>()),
