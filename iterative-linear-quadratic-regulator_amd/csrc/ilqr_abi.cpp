@@ -171,8 +171,6 @@ int ilqr_create_custom(ilqr_handle* out, const ilqr_config* cfg, const char* plu
     return create_impl(out, cfg, plugin_path);
 }
 
-
-
 int ilqr_destroy(ilqr_handle h) {
     if (!h) return ILQR_OK;
     delete h->impl;  // its code lives in the plugin: destroy before unloading
@@ -229,15 +227,9 @@ int ilqr_mpc_run(ilqr_handle h, int n_steps, void* u_out, void* x_out, void* cos
 }
 int ilqr_status_reduce(ilqr_handle h, void* dev_out4) { ILQR_FWD(h, status_reduce(dev_out4)); }
 /* diagnostic (not in the public header): raw clock-probe buffer, valid when ILQR_CLOCK_PROBE was set */
-int ilqr_debug_probe_dump(ilqr_handle h, long long* dst, size_t n) {
-    if (!h || !h->impl) return ILQR_ERR_INVALID_ARG;
-    return h->impl->probe_dump(dst, n);
-}
+int ilqr_debug_probe_dump(ilqr_handle h, long long* dst, size_t n) { ILQR_FWD(h, probe_dump(dst, n)); }
 /* diagnostic (not in the public header): retarget the handle's launches to another stream (tools/cumask_probe.py) */
-int ilqr_debug_set_stream(ilqr_handle h, void* stream) {
-    if (!h || !h->impl) return ILQR_ERR_INVALID_ARG;
-    return h->impl->debug_set_stream(stream);
-}
+int ilqr_debug_set_stream(ilqr_handle h, void* stream) { ILQR_FWD(h, debug_set_stream(stream)); }
 int ilqr_set_control_limits(ilqr_handle h, const double* u_min, const double* u_max) {
     if (!h || !h->impl) return ILQR_ERR_INVALID_ARG;
     const ilqr_config& c = h->impl->cfg;

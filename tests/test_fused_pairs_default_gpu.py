@@ -1,5 +1,5 @@
 """The fused iteration's default producers in fp32 are the pair producers (two time steps per lane in packed FP32,
-csrc/backward_fused16.hpp; launch_fused_kernel of csrc/solver.hpp).  They must give the bits the scalar producers give:
+csrc/backward_fused16.hpp; launch_fused_kernel of csrc/ops.hpp).  They must give the bits the scalar producers give:
 the same solves run here (default) and in a fresh child process with ILQR_FUSED_PAIRS=0 (the switch is read once per
 process), on the route that launches backward_fused16_kernel in its 16-trajectory form (ILQR_FLAG_NO_PERSIST, B > 1024),
 with and without control limits and per-trajectory parameters, and every output of the solve is compared with
@@ -79,7 +79,7 @@ def _scalar_producers(name, tmp_path):
 
 def test_pairs_are_the_default():
     """launch_fused_kernel: the scalar producers only when ILQR_FUSED_PAIRS is set to 0."""
-    src = open(os.path.join(ROOT, "iterative-linear-quadratic-regulator_amd", "csrc", "solver.hpp")).read()
+    src = open(os.path.join(ROOT, "iterative-linear-quadratic-regulator_amd", "csrc", "ops.hpp")).read()
     assert re.search(r'no_pk = getenv\("ILQR_FUSED_PAIRS"\) != nullptr && atoi\(getenv\("ILQR_FUSED_PAIRS"\)\) == 0;', src)
 
 

@@ -88,8 +88,8 @@ def persist_max_n(tpw):
     return (nt // tpw) * K_KEEP + 1
 
 
-# ---- the A/B switches of solver.hpp change the route: none may be set --------------------------------------------------
-AB_SWITCHES = sorted(set(re.findall(r'getenv\("(ILQR_\w+)"\)', _source("solver.hpp"))))
+# ---- the A/B switches of the host headers (csrc/*.hpp) change the route: none may be set ------------------------------
+AB_SWITCHES = sorted(set(re.findall(r'getenv\("(ILQR_\w+)"\)', "".join(_source(f) for f in sorted(os.listdir(CSRC)) if f.endswith(".hpp")))))
 
 
 @pytest.fixture(autouse=True)
