@@ -275,6 +275,33 @@ ILQR_DEV void al_expand(const KArgs<T>& a, const T* x, const T* lam, T rho, T* g
 }
 
 // ---------------------------------------------------------------------------
+// What the lane sweeps (backward_lane_kernel, backward_box_kernel) read and write, one lane per trajectory.
+// lin [N][E][B]: the E scalars of (b, t) in ILQR_LIN order, f_x f_u l_x l_u l_xx l_ux l_uu; src = the first of them.
+// term [n + n^2][B]: [V_x | V_xx] of the terminal expansion.
+// ---------------------------------------------------------------------------
+template <int E, typename T> ILQR_DEV void load_expansion(const T* src, size_t B, T* tile) {
+#pragma unroll
+    for (int e = 0; e < E; ++e) tile[e] = src[(size_t)e * B];
+}
+template <typename T, int NX> ILQR_DEV void load_terminal(const T* term, size_t B, int b, T* Vx, T (*Vxx)[NX]) {
+#pragma unroll
+    for (int i = 0; i < NX; ++i) Vx[i] = term[(size_t)i * B + b];
+#pragma unroll
+    for (int i = 0; i < NX; ++i)
+#pragma unroll
+        for (int j = 0; j < NX; ++j) Vxx[i][j] = term[(size_t)(NX + i * NX + j) * B + b];
+}
+// [K_t | k_t] into the gain record of (t, b)
+template <typename T, int NX, int NU> ILQR_DEV void store_gains(T* rec, const T (*K)[NX], const T* k) {
+#pragma unroll
+    for (int i = 0; i < NU; ++i)
+#pragma unroll
+        for (int j = 0; j < NX; ++j) rec[i * NX + j] = K[i][j];
+#pragma unroll
+    for (int i = 0; i < NU; ++i) rec[NU * NX + i] = k[i];
+}
+
+// ---------------------------------------------------------------------------
 // linearize: one lane per (b, t) point, t in [0, N]; t == N is the terminal
 // expansion.  Replaces iLQR._get_all_derivatives_for_backward_pass
 // (iLQR_class.py:318-331) + l_f_x / l_f_xx (:136-138), hoisted out of the
@@ -429,7 +456,9 @@ __global__ void __launch_bounds__(TILE16 ? 64 : 256) linearize_kernel(KArgs<T> a
 }
 
 // With state limits: linearize_kernel's generic form ([N][E][B] records, the box sweep's input) of J_A, the terminal at
-// t = N.  A kernel of its own so that linearize_kernel's instantiations stay as they are.
+// t = N.  Its record and terminal stores are linearize_kernel's, written out again: through a shared helper the cost
+// derivatives are evaluated before the Jacobian stores, which costs this kernel up to 93 VGPRs and a lower occupancy bracket
+// in 17 of its 60 instantiations, and changes linearize_kernel's machine code.
 template <typename T, typename Dyn, int INTEG, bool HET = false>
 __global__ void __launch_bounds__(256) linearize_al_kernel(KArgs<T> a) {
     constexpr int NX = Dyn::NX, NU = Dyn::NU;
@@ -752,35 +781,16 @@ __global__ void __launch_bounds__(64) backward_lane_kernel(KArgs<T> a) {
     if (a.reset_slots) a.cur_slot[b] = 0;   // linearize moved this trajectory into slot 0 (see linearize_kernel)
     const size_t B = a.B;
     T Vx[NX], Vxx[NX][NX];
-#pragma unroll
-    for (int i = 0; i < NX; ++i) Vx[i] = a.term[(size_t)i * B + b];
-#pragma unroll
-    for (int i = 0; i < NX; ++i)
-#pragma unroll
-        for (int j = 0; j < NX; ++j) Vxx[i][j] = a.term[(size_t)(NX + i * NX + j) * B + b];
+    load_terminal<T, NX>(a.term, B, b, Vx, Vxx);
     T cur[E], nxt[E];
-    {
-        const T* src = a.lin + ((size_t)(a.N - 1) * E) * B + b;
-#pragma unroll
-        for (int e = 0; e < E; ++e) cur[e] = src[(size_t)e * B];
-    }
+    load_expansion<E>(a.lin + ((size_t)(a.N - 1) * E) * B + b, B, cur);
     bool all_pd = true;
     for (int t = a.N - 1; t >= 0; --t) {
-        if (t > 0) {
-            const T* src = a.lin + ((size_t)(t - 1) * E) * B + b;
-#pragma unroll
-            for (int e = 0; e < E; ++e) nxt[e] = src[(size_t)e * B];
-        }
+        if (t > 0) load_expansion<E>(a.lin + ((size_t)(t - 1) * E) * B + b, B, nxt);
         T K[NU][NX], k[NU];
         all_pd = riccati_step<T, NX, NU>(cur, a.mu, Vx, Vxx, K, k) && all_pd;
         constexpr int R = gain_record(NX, NU);
-        T* rec = a.gains + ((size_t)t * B + b) * R;
-#pragma unroll
-        for (int i = 0; i < NU; ++i)
-#pragma unroll
-            for (int j = 0; j < NX; ++j) rec[i * NX + j] = K[i][j];
-#pragma unroll
-        for (int i = 0; i < NU; ++i) rec[NU * NX + i] = k[i];
+        store_gains<T, NX, NU>(a.gains + ((size_t)t * B + b) * R, K, k);
 #pragma unroll
         for (int e = 0; e < E; ++e) cur[e] = nxt[e];
     }
@@ -862,18 +872,11 @@ __global__ void __launch_bounds__(64) backward_box_kernel(KArgs<T> a) {
     if (a.reset_slots) a.cur_slot[b] = 0;   // linearize moved this trajectory into slot 0 (see linearize_kernel)
     const size_t B = a.B;
     T Vx[NX], Vxx[NX][NX];
-#pragma unroll
-    for (int i = 0; i < NX; ++i) Vx[i] = a.term[(size_t)i * B + b];
-#pragma unroll
-    for (int i = 0; i < NX; ++i)
-#pragma unroll
-        for (int j = 0; j < NX; ++j) Vxx[i][j] = a.term[(size_t)(NX + i * NX + j) * B + b];
+    load_terminal<T, NX>(a.term, B, b, Vx, Vxx);
     bool all_pd = true;
     for (int t = a.N - 1; t >= 0; --t) {
         T tile[E], u[NU];
-        const T* src = a.lin + ((size_t)t * E) * B + b;
-#pragma unroll
-        for (int e = 0; e < E; ++e) tile[e] = src[(size_t)e * B];
+        load_expansion<E>(a.lin + ((size_t)t * E) * B + b, B, tile);
         vec_load<T, NU>(a.U + vec_at(B, a.N, NU, slot, t, b), u);
         T Qx[NX], Qu[NU], Qxx[NX][NX], Qux[NU][NX], Quu[NU][NU], Qr[NU][NU];
         riccati_q<T, NX, NU>(tile, Vx, Vxx, Qx, Qu, Qxx, Qux, Quu);
@@ -892,13 +895,7 @@ __global__ void __launch_bounds__(64) backward_box_kernel(KArgs<T> a) {
         const bool moved = box_gains<T, NX, NU>(Qr, Qux, Qu, lo, hi, pd, K, k);
         riccati_value<T, NX, NU>(moved || a.mu != T(0), Qx, Qu, Qxx, Qux, Quu, K, k, Vx, Vxx);
         constexpr int R = gain_record(NX, NU);
-        T* rec = a.gains + ((size_t)t * B + b) * R;
-#pragma unroll
-        for (int i = 0; i < NU; ++i)
-#pragma unroll
-            for (int j = 0; j < NX; ++j) rec[i * NX + j] = K[i][j];
-#pragma unroll
-        for (int i = 0; i < NU; ++i) rec[NU * NX + i] = k[i];
+        store_gains<T, NX, NU>(a.gains + ((size_t)t * B + b) * R, K, k);
     }
     if (!all_pd) a.status[b] = st | ILQR_TRAJ_FLAG_NON_PD;
 }
@@ -1388,6 +1385,22 @@ template <typename T, typename Dyn, bool HET> struct CostParams {
     }
 };
 
+// The plain J (no phi terms) of the trajectory whose points (0, b) are Xb, Ub, summed in the rollout's order.
+// (al_update_kernel's sum is another one: it adds phi point by point between the stage costs.)
+template <typename T, typename Dyn> ILQR_DEV T plain_cost(const T* p, T dt, const T* Xb, const T* Ub, size_t B, int N) {
+    constexpr int NX = Dyn::NX, NU = Dyn::NU;
+    T cost = T(0);
+    for (int t = 0; t < N; ++t) {
+        T x[NX], u[NU];
+        vec_load<T, NX>(Xb + t * (B * NX), x);
+        vec_load<T, NU>(Ub + t * (B * NU), u);
+        cost += Cost<T, Dyn>::stage(p, dt, x, u);
+    }
+    T x[NX];
+    vec_load<T, NX>(Xb + N * (B * NX), x);
+    return cost + Cost<T, Dyn>::terminal(p, x);
+}
+
 // After an inner solve, for every trajectory still in the outer loop: the violation of its accepted X; done when it is
 // <= ctol, done and ILQR_TRAJ_FLAG_INFEASIBLE after its max_outer-th inner solve, otherwise lam <- max(0, lam + rho c),
 // rho <- min(rho rho_factor, rho_max), cost = cost_prev = J_A of (X, U) under the new multipliers (summed in the
@@ -1479,17 +1492,7 @@ __global__ void __launch_bounds__(64) al_cost_kernel(KArgs<T> a, ALArgs<T> s) {
     const T* Xb = a.X + vec_at(B, N + 1, NX, slot, 0, b);
     const T* Ub = a.U + vec_at(B, N, NU, slot, 0, b);
     const CostParams<T, Dyn, HET> cp(a, b);
-    T cost = T(0);
-    for (int t = 0; t < N; ++t) {
-        T x[NX], u[NU];
-        vec_load<T, NX>(Xb + t * (B * NX), x);
-        vec_load<T, NU>(Ub + t * (B * NU), u);
-        cost += Cost<T, Dyn>::stage(cp.p, a.dt, x, u);
-    }
-    T x[NX];
-    vec_load<T, NX>(Xb + N * (B * NX), x);
-    cost += Cost<T, Dyn>::terminal(cp.p, x);
-    s.cost_plain[b] = cost;
+    s.cost_plain[b] = plain_cost<T, Dyn>(cp.p, a.dt, Xb, Ub, B, N);
     a.iters[b] += s.base[b];
     s.base[b] = 0;
 }
@@ -1631,22 +1634,20 @@ template <typename T> struct MpcArgs {
 // dependent load / store pairs: 66 us of the c4 step, now a few).  Slice 0 also runs the plant step.  Horizons beyond
 // kMpcChunks * (32 / n_u) + 1 steps fall back to the walk.
 constexpr int kMpcChunks = 16, kMpcSliceScalars = 32;   // a slice keeps at most 32 scalars per lane in registers
-// HET: the plant of every trajectory at its own system constants (MpcArgs::plant_rows)
-template <typename T, typename Dyn, bool HET = false>
-__global__ void __launch_bounds__(64 * kMpcChunks) mpc_advance_kernel(MpcArgs<T> a) {
-    constexpr int NX = Dyn::NX, NU = Dyn::NU;
+// The shift of trajectory b's column by the workgroup's slices (every thread of the workgroup calls it: it holds the
+// barrier).  Uc = the column's first vector, u0 = U[0] as it was before the shift; returns whether the horizon fitted
+// the slices (else slice 0 walks the column: mpc_plant_step).
+template <typename T, int NU> ILQR_DEV bool mpc_shift_U(const MpcArgs<T>& a, int b, T*& Uc, T* u0) {
     constexpr int kMpcSlice = kMpcSliceScalars / NU > 0 ? kMpcSliceScalars / NU : 1;
-    const int b = blockIdx.x * 64 + threadIdx.x;
     const int chunk = threadIdx.y;
     const size_t B = a.B;
     const bool inb = b < a.B;
     const int bb = inb ? b : a.B - 1;
-    T* Uc = a.U + vec_at(B, a.N, NU, a.cur_slot[bb], 0, bb);
+    Uc = a.U + vec_at(B, a.N, NU, a.cur_slot[bb], 0, bb);
     const size_t sU = B * NU;
     const int n_shift = a.N - 1;                                   // U[t] <- U[t + 1], t = 0 .. N-2
     const int per = (n_shift + kMpcChunks - 1) / kMpcChunks;       // time steps per slice
     const bool sliced = per <= kMpcSlice;
-    T u0[NU];
     vec_load<T, NU>(Uc, u0);                                       // (before anything is shifted)
     T keep[kMpcSlice][NU];
     const int t0 = chunk * per;
@@ -1663,7 +1664,15 @@ __global__ void __launch_bounds__(64 * kMpcChunks) mpc_advance_kernel(MpcArgs<T>
                 if (q < per && t0 + q < n_shift) vec_store<T, NU>(Uc + (size_t)(t0 + q) * sU, keep[q]);
         }
     }
-    if (chunk != 0 || !inb) return;
+    return sliced;
+}
+
+// Slice 0's work for trajectory b < B: the plant step from u0 (HET: at the plant's own system constants,
+// MpcArgs::plant_rows), the new plant state into plant_x, x0 and the logs, and the walk of a horizon the slices did not fit.
+template <typename T, typename Dyn, bool HET>
+ILQR_DEV void mpc_plant_step(const MpcArgs<T>& a, int b, T* Uc, const T* u0, bool sliced) {
+    constexpr int NX = Dyn::NX, NU = Dyn::NU;
+    const size_t B = a.B, sU = B * NU;
     T x[NX], xn[NX];
 #pragma unroll
     for (int i = 0; i < NX; ++i) x[i] = a.plant_x[(size_t)i * B + b];
@@ -1693,14 +1702,23 @@ __global__ void __launch_bounds__(64 * kMpcChunks) mpc_advance_kernel(MpcArgs<T>
     }
 }
 
+// HET: the plant of every trajectory at its own system constants (MpcArgs::plant_rows)
+template <typename T, typename Dyn, bool HET = false>
+__global__ void __launch_bounds__(64 * kMpcChunks) mpc_advance_kernel(MpcArgs<T> a) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    T *Uc, u0[Dyn::NU];
+    const bool sliced = mpc_shift_U<T, Dyn::NU>(a, b, Uc, u0);
+    if (threadIdx.y != 0 || b >= a.B) return;
+    mpc_plant_step<T, Dyn, HET>(a, b, Uc, u0, sliced);
+}
+
 // MPC advance of a state-limited step (include/ilqr_hip.h, ilqr_set_mpc_multipliers): mpc_advance_kernel's work (m.cost
 // points at the plain J, ALArgs::cost_plain), the step's status word into status_log [n_steps][B], and in WARM the
 // multipliers shifted one step along the horizon OUT OF PLACE into lam_next [N+1][2 n_x][B]:
 //   lam_next[0] = 0, lam_next[t] = lam[t + 1] (t = 1..N-1), lam_next[N] = lam[N].
 // Out of place, no row is read after it is written, so the shift needs no barrier and no registers: the 16 slices of a
 // lane's column take the rows round-robin (one coalesced load and store per 64 trajectories and row), and the host swaps
-// the two buffers at the head of the next step.  The U shift and the plant step are mpc_advance_kernel's (a copy: that
-// kernel stays as it is).
+// the two buffers at the head of the next step.
 template <typename T> struct MpcALArgs {
     MpcArgs<T> m;
     const int* status;    // [B] status words of the step's solve
@@ -1711,39 +1729,15 @@ template <typename T> struct MpcALArgs {
 
 template <typename T, typename Dyn, bool HET = false>
 __global__ void __launch_bounds__(64 * kMpcChunks) mpc_advance_al_kernel(MpcALArgs<T> s) {
-    constexpr int NX = Dyn::NX, NU = Dyn::NU;
-    constexpr int kMpcSlice = kMpcSliceScalars / NU > 0 ? kMpcSliceScalars / NU : 1;
     const MpcArgs<T>& a = s.m;
     const int b = blockIdx.x * 64 + threadIdx.x;
     const int chunk = threadIdx.y;
     const size_t B = a.B;
-    const bool inb = b < a.B;
-    const int bb = inb ? b : a.B - 1;
-    T* Uc = a.U + vec_at(B, a.N, NU, a.cur_slot[bb], 0, bb);
-    const size_t sU = B * NU;
-    const int n_shift = a.N - 1;                                   // U[t] <- U[t + 1], t = 0 .. N-2
-    const int per = (n_shift + kMpcChunks - 1) / kMpcChunks;       // time steps per slice
-    const bool sliced = per <= kMpcSlice;
-    T u0[NU];
-    vec_load<T, NU>(Uc, u0);                                       // (before anything is shifted)
-    T keep[kMpcSlice][NU];
-    const int t0 = chunk * per;
-    if (sliced) {
-#pragma unroll
-        for (int q = 0; q < kMpcSlice; ++q)
-            if (q < per && t0 + q < n_shift) vec_load<T, NU>(Uc + (size_t)(t0 + q + 1) * sU, keep[q]);
-    }
-    __syncthreads();
-    if (sliced) {
-        if (inb) {
-#pragma unroll
-            for (int q = 0; q < kMpcSlice; ++q)
-                if (q < per && t0 + q < n_shift) vec_store<T, NU>(Uc + (size_t)(t0 + q) * sU, keep[q]);
-        }
-    }
-    if (!inb) return;
+    T *Uc, u0[Dyn::NU];
+    const bool sliced = mpc_shift_U<T, Dyn::NU>(a, b, Uc, u0);
+    if (b >= a.B) return;
     if (s.lam_next) {
-        constexpr int Q = 2 * NX;
+        constexpr int Q = 2 * Dyn::NX;
         const int rows = (a.N + 1) * Q;                            // row r = t * Q + q
         for (int r = chunk; r < rows; r += kMpcChunks) {
             const int t = r / Q;
@@ -1752,34 +1746,8 @@ __global__ void __launch_bounds__(64 * kMpcChunks) mpc_advance_al_kernel(MpcALAr
         }
     }
     if (chunk != 0) return;
-    T x[NX], xn[NX];
-#pragma unroll
-    for (int i = 0; i < NX; ++i) x[i] = a.plant_x[(size_t)i * B + b];
-    if constexpr (HET) {
-        T pp[Dyn::NSYS];   // the plant's system constants (all a step reads)
-        load_row<Dyn::NSYS>(pp, a.plant_rows, B, b);
-        Stepper<T, Dyn>::step(a.plant_integ, pp, a.dt, x, u0, xn);
-    } else {
-        Stepper<T, Dyn>::step(a.plant_integ, a.params, a.dt, x, u0, xn);
-    }
-#pragma unroll
-    for (int i = 0; i < NX; ++i) {
-        a.plant_x[(size_t)i * B + b] = xn[i];
-        a.x0[(size_t)i * B + b] = xn[i];
-        if (a.x_log) a.x_log[((size_t)a.step * B + b) * NX + i] = xn[i];
-    }
-#pragma unroll
-    for (int j = 0; j < NU; ++j)
-        if (a.u_log) a.u_log[((size_t)a.step * B + b) * NU + j] = u0[j];
-    if (a.cost_log) a.cost_log[(size_t)a.step * B + b] = a.cost[b];
     s.status_log[(size_t)a.step * B + b] = s.status[b];
-    if (!sliced) {
-        for (int t = 0; t + 1 < a.N; ++t) {
-            T un[NU];
-            vec_load<T, NU>(Uc + (t + 1) * sU, un);
-            vec_store<T, NU>(Uc + t * sU, un);
-        }
-    }
+    mpc_plant_step<T, Dyn, HET>(a, b, Uc, u0, sliced);
 }
 
 // ---------------------------------------------------------------------------
@@ -1787,83 +1755,52 @@ __global__ void __launch_bounds__(64 * kMpcChunks) mpc_advance_al_kernel(MpcALAr
 // front of the reference layout) and the device's batch-innermost slots.
 // dense[b][c][t] (c = component, t = time) <-> slots[slot(b)][t][b][c]
 // ---------------------------------------------------------------------------
-template <typename T>
-__global__ void scatter_ct_kernel(const T* dense, T* slots, const int* cur_slot, int B, int C, int Tn) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (size_t)B * C * Tn) return;
-    const int c = (int)(idx % C);
-    const int b = (int)((idx / C) % B);
-    const int t = (int)(idx / ((size_t)B * C));
-    const int s = cur_slot ? cur_slot[b] : 0;
-    slots[(((size_t)s * Tn + t) * B + b) * C + c] = dense[((size_t)b * C + c) * Tn + t];
+// One kernel per index map, both directions: TO_DEV copies dense -> device layout, else device layout -> dense.
+// The side a direction reads is const: `dense` when TO_DEV, the device tensor otherwise.
+template <typename T, bool READ_ONLY> using layout_ptr = std::conditional_t<READ_ONLY, const T*, T*>;
+template <typename T, bool TO_DEV> ILQR_DEV void layout_copy(layout_ptr<T, TO_DEV> dense, layout_ptr<T, !TO_DEV> dev) {
+    if constexpr (TO_DEV) *dev = *dense;
+    else *dense = *dev;
 }
-template <typename T>
-__global__ void gather_ct_kernel(T* dense, const T* slots, const int* cur_slot, int B, int C, int Tn) {
+template <typename T, bool TO_DEV>
+__global__ void layout_ct_kernel(layout_ptr<T, TO_DEV> dense, layout_ptr<T, !TO_DEV> slots, const int* cur_slot, int B, int C, int Tn) {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (size_t)B * C * Tn) return;
     const int c = (int)(idx % C);
     const int b = (int)((idx / C) % B);
     const int t = (int)(idx / ((size_t)B * C));
     const int s = cur_slot ? cur_slot[b] : 0;
-    dense[((size_t)b * C + c) * Tn + t] = slots[(((size_t)s * Tn + t) * B + b) * C + c];
+    layout_copy<T, TO_DEV>(dense + ((size_t)b * C + c) * Tn + t, slots + (((size_t)s * Tn + t) * B + b) * C + c);
 }
 // dense[b][t][c] <-> dev[t][c][b]   (K, ILQR_LIN, x0 with Tn = 1)
-template <typename T>
-__global__ void scatter_tc_kernel(const T* dense, T* dev, int B, int C, int Tn) {
+template <typename T, bool TO_DEV>
+__global__ void layout_tc_kernel(layout_ptr<T, TO_DEV> dense, layout_ptr<T, !TO_DEV> dev, int B, int C, int Tn) {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (size_t)B * C * Tn) return;
     const int b = (int)(idx % B);
     const int c = (int)((idx / B) % C);
     const int t = (int)(idx / ((size_t)B * C));
-    dev[((size_t)t * C + c) * B + b] = dense[((size_t)b * Tn + t) * C + c];
+    layout_copy<T, TO_DEV>(dense + ((size_t)b * Tn + t) * C + c, dev + ((size_t)t * C + c) * B + b);
 }
-template <typename T>
-__global__ void gather_tc_kernel(T* dense, const T* dev, int B, int C, int Tn) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (size_t)B * C * Tn) return;
-    const int b = (int)(idx % B);
-    const int c = (int)((idx / B) % C);
-    const int t = (int)(idx / ((size_t)B * C));
-    dense[((size_t)b * Tn + t) * C + c] = dev[((size_t)t * C + c) * B + b];
-}
-
 
 // gains[t][b][R] <-> the reference layouts K [B][N][n_u][n_x], U_ff [B][n_u][N]
-template <typename T>
-__global__ void gains_scatter_K_kernel(const T* denseK, T* gains, int B, int N, int MN, int R) {
+template <typename T, bool TO_DEV>
+__global__ void layout_gain_K_kernel(layout_ptr<T, TO_DEV> denseK, layout_ptr<T, !TO_DEV> gains, int B, int N, int MN, int R) {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (size_t)B * N * MN) return;
     const int c = (int)(idx % MN);
     const int t = (int)((idx / MN) % N);
     const int b = (int)(idx / ((size_t)MN * N));
-    gains[((size_t)t * B + b) * R + c] = denseK[idx];
+    layout_copy<T, TO_DEV>(denseK + idx, gains + ((size_t)t * B + b) * R + c);
 }
-template <typename T>
-__global__ void gains_gather_K_kernel(T* denseK, const T* gains, int B, int N, int MN, int R) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (size_t)B * N * MN) return;
-    const int c = (int)(idx % MN);
-    const int t = (int)((idx / MN) % N);
-    const int b = (int)(idx / ((size_t)MN * N));
-    denseK[idx] = gains[((size_t)t * B + b) * R + c];
-}
-template <typename T>
-__global__ void gains_scatter_k_kernel(const T* denseUff, T* gains, int B, int N, int M, int MN, int R) {
+template <typename T, bool TO_DEV>
+__global__ void layout_gain_k_kernel(layout_ptr<T, TO_DEV> denseUff, layout_ptr<T, !TO_DEV> gains, int B, int N, int M, int MN, int R) {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (size_t)B * N * M) return;
     const int t = (int)(idx % N);
     const int j = (int)((idx / N) % M);
     const int b = (int)(idx / ((size_t)M * N));
-    gains[((size_t)t * B + b) * R + MN + j] = denseUff[idx];
-}
-template <typename T>
-__global__ void gains_gather_k_kernel(T* denseUff, const T* gains, int B, int N, int M, int MN, int R) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (size_t)B * N * M) return;
-    const int t = (int)(idx % N);
-    const int j = (int)((idx / N) % M);
-    const int b = (int)(idx / ((size_t)M * N));
-    denseUff[idx] = gains[((size_t)t * B + b) * R + MN + j];
+    layout_copy<T, TO_DEV>(denseUff + idx, gains + ((size_t)t * B + b) * R + MN + j);
 }
 
 }  // namespace ilqr

@@ -214,12 +214,42 @@ template <typename Dyn> constexpr bool box_system() {
 #define ILQR_PERSIST_HET_INTEG_MASK 0x1f
 #endif
 
-// linearise into the tiles of the DPP sweeps (TILE, 64-thread workgroups) or into the generic [N][E][B] expansion (256)
-template <typename T, typename Dyn, bool TILE, int I, bool HETS> void launch_linearize(const KArgs<T>& a, hipStream_t s) {
+// linearise into the tiles of the DPP sweeps (TILE, 64-thread workgroups) or into the generic [N][E][B] expansion (256);
+// AL: the generic expansion of J_A (state limits)
+template <typename T, typename Dyn, bool TILE, int I, bool HETS, bool AL = false>
+void launch_linearize(const KArgs<T>& a, hipStream_t s) {
+    static_assert(!(AL && TILE), "the state-limited expansion has the generic layout only");
     const size_t total = (size_t)a.B * (a.N + 1);
     constexpr int TPB = TILE ? 64 : 256;
-    ILQR_LAUNCH_HET(HETS, a.het, (linearize_kernel<T, Dyn, TILE, I>), (linearize_kernel<T, Dyn, TILE, I, true>),
-                    dim3((unsigned)((total + TPB - 1) / TPB)), dim3(TPB), 0, s, a);
+    const dim3 grid((unsigned)((total + TPB - 1) / TPB)), block(TPB);
+    if constexpr (AL)
+        ILQR_LAUNCH_HET(HETS, a.het, (linearize_al_kernel<T, Dyn, I>), (linearize_al_kernel<T, Dyn, I, true>), grid, block, 0, s, a);
+    else
+        ILQR_LAUNCH_HET(HETS, a.het, (linearize_kernel<T, Dyn, TILE, I>), (linearize_kernel<T, Dyn, TILE, I, true>), grid, block, 0, s, a);
+}
+
+// The rollout of a pass, one lane per (trajectory, alpha): the ring form where it exists for these dimensions and this
+// integrator (RING) and the call's tensors fit its descriptors, else the flat one.  BOX: clamped to the control limits.
+// AL: state limits, the flat clamped rollout with the phi terms -- never the ring form, whose step loop's self-counted
+// loads must not meet the multiplier loads.
+template <typename T, typename Dyn, int I, bool RING, bool BOX, bool AL, bool HETS>
+void launch_forward(const KArgs<T>& a, hipStream_t s) {
+    const dim3 grid((a.B + 63) / 64, a.n_pass), block(64);
+    if constexpr (RING && !AL) {
+        if (ring_rollout_ok(a, Dyn::NX, Dyn::NU)) {
+            if constexpr (BOX)
+                ILQR_LAUNCH_HET(HETS, a.het, (forward_ring_kernel_box<T, Dyn, I>), (forward_ring_kernel_box_het<T, Dyn, I>), grid, block, 0, s, a);
+            else
+                ILQR_LAUNCH_HET(HETS, a.het, (forward_ring_kernel<T, Dyn, I>), (forward_ring_kernel_het<T, Dyn, I>), grid, block, 0, s, a);
+            return;
+        }
+    }
+    if constexpr (AL)
+        ILQR_LAUNCH_HET(HETS, a.het, (forward_kernel_al<T, Dyn, I>), (forward_kernel_al_het<T, Dyn, I>), grid, block, 0, s, a);
+    else if constexpr (BOX)
+        ILQR_LAUNCH_HET(HETS, a.het, (forward_kernel_box<T, Dyn, I>), (forward_kernel_box_het<T, Dyn, I>), grid, block, 0, s, a);
+    else
+        ILQR_LAUNCH_HET(HETS, a.het, (forward_kernel<T, Dyn, I>), (forward_kernel_het<T, Dyn, I>), grid, block, 0, s, a);
 }
 
 template <typename T, typename Dyn, bool TILE, int INTEG> void set_integrator_ops(Ops<T>& o) {
@@ -263,39 +293,14 @@ template <typename T, typename Dyn, bool TILE, int INTEG> void set_integrator_op
         };
         o.persist_any_batch[INTEG] = BIG;
     }
-    o.forward[INTEG] = [](const KArgs<T>& a, hipStream_t s) {
-        const dim3 grid((a.B + 63) / 64, a.n_pass), block(64);
-        if constexpr (RING) {
-            if (ring_rollout_ok(a, Dyn::NX, Dyn::NU)) {
-                ILQR_LAUNCH_HET(HETS, a.het, (forward_ring_kernel<T, Dyn, I>), (forward_ring_kernel_het<T, Dyn, I>), grid, block, 0, s, a);
-                return;
-            }
-        }
-        ILQR_LAUNCH_HET(HETS, a.het, (forward_kernel<T, Dyn, I>), (forward_kernel_het<T, Dyn, I>), grid, block, 0, s, a);
-    };
+    o.forward[INTEG] = launch_forward<T, Dyn, I, RING, false, false, HETS>;
     if constexpr (box_system<Dyn>()) {
         // control limits: linearise into the generic [N][E][B] expansion the box sweep reads, clamped rollouts
         o.linearize_box[INTEG] = launch_linearize<T, Dyn, false, I, true>;
-        o.forward_box[INTEG] = [](const KArgs<T>& a, hipStream_t s) {
-            const dim3 grid((a.B + 63) / 64, a.n_pass), block(64);
-            if constexpr (RING) {
-                if (ring_rollout_ok(a, Dyn::NX, Dyn::NU)) {
-                    ILQR_LAUNCH_HET(true, a.het, (forward_ring_kernel_box<T, Dyn, I>), (forward_ring_kernel_box_het<T, Dyn, I>), grid, block, 0, s, a);
-                    return;
-                }
-            }
-            ILQR_LAUNCH_HET(true, a.het, (forward_kernel_box<T, Dyn, I>), (forward_kernel_box_het<T, Dyn, I>), grid, block, 0, s, a);
-        };
-        // state limits: the box sweep's generic expansion of J_A and the flat clamped rollout with the phi terms (never
-        // the ring form: its step loop's self-counted loads must not meet the multiplier loads)
-        o.linearize_al[INTEG] = [](const KArgs<T>& a, hipStream_t s) {
-            const dim3 grid((unsigned)(((size_t)a.B * (a.N + 1) + 255) / 256)), block(256);
-            ILQR_LAUNCH_HET(true, a.het, (linearize_al_kernel<T, Dyn, I>), (linearize_al_kernel<T, Dyn, I, true>), grid, block, 0, s, a);
-        };
-        o.forward_al[INTEG] = [](const KArgs<T>& a, hipStream_t s) {
-            const dim3 grid((a.B + 63) / 64, a.n_pass), block(64);
-            ILQR_LAUNCH_HET(true, a.het, (forward_kernel_al<T, Dyn, I>), (forward_kernel_al_het<T, Dyn, I>), grid, block, 0, s, a);
-        };
+        o.forward_box[INTEG] = launch_forward<T, Dyn, I, RING, true, false, true>;
+        // state limits: the box sweep's generic expansion of J_A and the clamped rollout with the phi terms
+        o.linearize_al[INTEG] = launch_linearize<T, Dyn, false, I, true, true>;
+        o.forward_al[INTEG] = launch_forward<T, Dyn, I, false, true, true, true>;
     }
 }
 

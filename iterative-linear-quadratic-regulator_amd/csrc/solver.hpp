@@ -464,33 +464,33 @@ template <typename T> class SolverT : public SolverBase {
     }
 #define ILQR_STAGED(kern, ...) [&](dim3 g_, dim3 b_) { hipLaunchKernelGGL(kern, g_, b_, 0, stream, staging.p, __VA_ARGS__); }
     int up_ct(const void* host, T* slots, const int* cur_slot, int C, int Tn) {
-        return stage_up(host, (size_t)B * C * Tn, ILQR_STAGED(scatter_ct_kernel<T>, slots, cur_slot, B, C, Tn));
+        return stage_up(host, (size_t)B * C * Tn, ILQR_STAGED((layout_ct_kernel<T, true>), slots, cur_slot, B, C, Tn));
     }
     int down_ct(void* host, const T* slots, const int* cur_slot, int C, int Tn) {
-        return stage_down(host, (size_t)B * C * Tn, ILQR_STAGED(gather_ct_kernel<T>, slots, cur_slot, B, C, Tn));
+        return stage_down(host, (size_t)B * C * Tn, ILQR_STAGED((layout_ct_kernel<T, false>), slots, cur_slot, B, C, Tn));
     }
     int up_tc(const void* host, T* dev, int C, int Tn) {
-        return stage_up(host, (size_t)B * C * Tn, ILQR_STAGED(scatter_tc_kernel<T>, dev, B, C, Tn));
+        return stage_up(host, (size_t)B * C * Tn, ILQR_STAGED((layout_tc_kernel<T, true>), dev, B, C, Tn));
     }
     int down_tc(void* host, const T* dev, int C, int Tn) {
-        return stage_down(host, (size_t)B * C * Tn, ILQR_STAGED(gather_tc_kernel<T>, dev, B, C, Tn));
+        return stage_down(host, (size_t)B * C * Tn, ILQR_STAGED((layout_tc_kernel<T, false>), dev, B, C, Tn));
     }
     int up_gain_K(const void* host, T* gains) {
-        return stage_up(host, (size_t)B * N * NU * NX, ILQR_STAGED(gains_scatter_K_kernel<T>, gains, B, N, NU * NX, R));
+        return stage_up(host, (size_t)B * N * NU * NX, ILQR_STAGED((layout_gain_K_kernel<T, true>), gains, B, N, NU * NX, R));
     }
     int down_gain_K(void* host, const T* gains) {
-        return stage_down(host, (size_t)B * N * NU * NX, ILQR_STAGED(gains_gather_K_kernel<T>, gains, B, N, NU * NX, R));
+        return stage_down(host, (size_t)B * N * NU * NX, ILQR_STAGED((layout_gain_K_kernel<T, false>), gains, B, N, NU * NX, R));
     }
     int up_gain_k(const void* host, T* gains) {
-        return stage_up(host, (size_t)B * N * NU, ILQR_STAGED(gains_scatter_k_kernel<T>, gains, B, N, NU, NU * NX, R));
+        return stage_up(host, (size_t)B * N * NU, ILQR_STAGED((layout_gain_k_kernel<T, true>), gains, B, N, NU, NU * NX, R));
     }
     int down_gain_k(void* host, const T* gains) {
-        return stage_down(host, (size_t)B * N * NU, ILQR_STAGED(gains_gather_k_kernel<T>, gains, B, N, NU, NU * NX, R));
+        return stage_down(host, (size_t)B * N * NU, ILQR_STAGED((layout_gain_k_kernel<T, false>), gains, B, N, NU, NU * NX, R));
     }
     // the expansion in the layout the backward kernel of this (n_x, n_u) reads -> dense [B][N][E] records
     int down_lin(void* host, const T* lin) {
         const size_t n = (size_t)B * N * E;
-        if (ops.lin_aos) return stage_down(host, n, ILQR_STAGED(gains_gather_K_kernel<T>, lin, B, N, E, E));
+        if (ops.lin_aos) return stage_down(host, n, ILQR_STAGED((layout_gain_K_kernel<T, false>), lin, B, N, E, E));
         if (!ops.tile16) return down_tc(host, lin, E, N);
         if (ops.tile_scalars == kTile16M2) return stage_down(host, n, ILQR_STAGED(tile16m2_gather_dense_kernel<T>, lin, B, N));
         return stage_down(host, n, ILQR_STAGED(tile16_gather_dense_kernel<T>, lin, B, N, NX));
@@ -498,7 +498,7 @@ template <typename T> class SolverT : public SolverBase {
     // and back (the tiles' padding is zeroed first)
     int up_lin(const void* host, T* lin) {
         const size_t n = (size_t)B * N * E;
-        if (ops.lin_aos) return stage_up(host, n, ILQR_STAGED(gains_scatter_K_kernel<T>, lin, B, N, E, E));
+        if (ops.lin_aos) return stage_up(host, n, ILQR_STAGED((layout_gain_K_kernel<T, true>), lin, B, N, E, E));
         if (!ops.tile16) return up_tc(host, lin, E, N);
         return stage_up(host, n, [&](dim3 g, dim3 b) {
             hipMemsetAsync(lin, 0, (size_t)N * B * ops.tile_scalars * sizeof(T), stream);
