@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define ILQR_ABI_VERSION 5
+#define ILQR_ABI_VERSION 5   /* unchanged by ilqr_set_batch_limits: see the note at that entry */
 
 typedef struct ilqr_solver_s* ilqr_handle;
 
@@ -346,6 +346,35 @@ int ilqr_set_state_limits(ilqr_handle h, const double* x_min, const double* x_ma
  * changed between any two calls.  Returns ILQR_ERR_INVALID_ARG for an unknown mode or a NULL handle. */
 enum { ILQR_MPC_AL_OFF = 0, ILQR_MPC_AL_COLD = 1, ILQR_MPC_AL_WARM = 2 };
 int ilqr_set_mpc_multipliers(ilqr_handle h, int mode);
+
+/* ---- per-trajectory limits (build extension) ---------------------------------------------------------------
+ * Every trajectory of the batch may have its own control limits and its own state limits (a fleet whose arms differ in
+ * torque rating or allowed joint speed), alone or next to ilqr_set_batch_params rows.
+ *   which = ILQR_LIMITS_CONTROL: lo, hi [B][n_u] host doubles = u_min, u_max of every trajectory;
+ *           ILQR_LIMITS_STATE:   lo, hi [B][n_x] = x_min, x_max of every trajectory.
+ * +-inf is allowed in every entry.  Rows switch the limits of their kind on exactly as ilqr_set_control_limits /
+ * ilqr_set_state_limits do and everything those entries say holds per trajectory with its own bounds: the same kernels
+ * and the same routing (rows never change the route), in the handle's dtype, so rows that all equal a shared bound
+ * compute exactly what that shared bound computes.  Control rows need no prior call.  State rows use the outer-loop
+ * options (ctol, rho0, rho_factor, rho_max, max_outer) of the last ilqr_set_state_limits with bounds on this handle and
+ * return ILQR_ERR_STATE if there was none; like that call they reset lam = 0, rho = rho0.
+ * State rows and infinite entries: the set of constraints (the columns of ILQR_MULTIPLIERS that can be non-zero) is
+ * shared by the batch -- a constraint exists when the bound is finite for ANY trajectory.  A trajectory whose own bound
+ * is infinite there has c = -inf at every step, so max(0, lam + rho c) = 0: its multiplier stays 0, and it adds exactly
+ * 0 to J_A, to its gradient and Hessian and to the violation; nothing multiplies the infinity by 0 or subtracts it from
+ * itself, so no NaN arises in either dtype.
+ * ilqr_set_control_limits / ilqr_set_state_limits with bounds replace the rows of their kind by shared bounds, and rows
+ * replace shared bounds.  NULL, NULL removes the limits of that kind if they were given as rows (shared bounds stay)
+ * and is valid on every handle.  May be called between any two calls (also between ilqr_mpc_run calls); takes effect
+ * from the next rollout / sweep on.  ilqr_backward_tensors returns ILQR_ERR_UNSUPPORTED while control rows are set.
+ * Returns ILQR_ERR_UNSUPPORTED for ILQR_SYS_LINEAR, ILQR_SYS_CUSTOM and n_x > 4, ILQR_ERR_INVALID_ARG for a bad
+ * `which`, row_len != n_u (n_x), exactly one NULL pointer, or in any entry a NaN, lo > hi, hi = -inf or lo = +inf (a
+ * bound no value can meet; as a state row it would make c = +inf).
+ * ILQR_ABI_VERSION stays 5 with this entry: it is additive, nothing an existing caller passes or reads changed its
+ * layout, and a system plugin carries its own solver and kernel-argument block and is rebuilt whenever a kernel header
+ * changes (its cache key hashes them), so no older binary meets the new entry. */
+enum { ILQR_LIMITS_CONTROL = 0, ILQR_LIMITS_STATE = 1 };
+int ilqr_set_batch_limits(ilqr_handle h, int which, const double* lo, const double* hi, int row_len);
 
 /* ---- multi-GPU hook -------------------------------------------
  * Writes 4 doubles to DEVICE memory `dev_out4` on the handle's stream:

@@ -43,9 +43,12 @@ SYMBOLS = (
     "ilqr_flush", "ilqr_solve", "ilqr_backward_pass", "ilqr_backward_tensors", "ilqr_forward_pass", "ilqr_eval_points", "ilqr_mpc_reset",
     "ilqr_mpc_rearm", "ilqr_mpc_run", "ilqr_status_reduce", "ilqr_timing_enable", "ilqr_timing_reset", "ilqr_timing_get", "ilqr_algorithmic_bytes",
     "ilqr_set_control_limits", "ilqr_set_batch_params", "ilqr_set_state_limits", "ilqr_set_mpc_multipliers",
+    "ilqr_set_batch_limits",
 )
 # ilqr_set_batch_params: which rows
 BATCH_MODEL, BATCH_PLANT = 0, 1
+# ilqr_set_batch_limits: which limits
+LIMITS_CONTROL, LIMITS_STATE = 0, 1
 # the built-in systems that take control limits (ilqr_set_control_limits), and state limits (ilqr_set_state_limits)
 BOX_SYSTEMS = (SYS_PENDULUM, SYS_UA_DOUBLE_PENDULUM, SYS_DOUBLE_PENDULUM)
 # ilqr_set_state_limits: the outer loop's settings when the caller gives none (include/ilqr_hip.h)
@@ -135,6 +138,7 @@ def load():
     lib.ilqr_set_batch_params.argtypes = [vp, ci, vp, ci]
     lib.ilqr_set_state_limits.argtypes = [vp, vp, vp, cd, cd, cd, cd, ci]
     lib.ilqr_set_mpc_multipliers.argtypes = [vp, ci]
+    lib.ilqr_set_batch_limits.argtypes = [vp, ci, vp, vp, ci]
     if lib.ilqr_abi_version() != ABI_VERSION:
         raise RuntimeError("libilqr_hip.so ABI version mismatch: rebuild the library")
     _lib = lib
@@ -396,6 +400,19 @@ class Handle:
         if r.ndim != 2 or r.shape[0] != self.B:
             raise ValueError(f"batch parameter rows must have shape ({self.B}, row_len), but got {r.shape}")
         self._chk(self.lib.ilqr_set_batch_params(self.h, int(which), _ptr(r), int(r.shape[1])))
+
+    # ---- per-trajectory limits --------------------------------------------------------------------
+    def set_batch_limits(self, which, lo, hi):
+        """which = LIMITS_CONTROL: lo, hi (B, n_u) = u_min, u_max of every trajectory; LIMITS_STATE: (B, n_x) = x_min,
+        x_max (after set_state_limits, whose options they use).  (None, None) removes the limits given as rows."""
+        if lo is None and hi is None:
+            self._chk(self.lib.ilqr_set_batch_limits(self.h, int(which), None, None, 0))
+            return
+        lo = np.ascontiguousarray(lo, dtype=np.float64)
+        hi = np.ascontiguousarray(hi, dtype=np.float64)
+        if lo.ndim != 2 or lo.shape[0] != self.B or hi.shape != lo.shape:
+            raise ValueError(f"limit rows must both have shape ({self.B}, row_len), but got {lo.shape} and {hi.shape}")
+        self._chk(self.lib.ilqr_set_batch_limits(self.h, int(which), _ptr(lo), _ptr(hi), int(lo.shape[1])))
 
     # ---- measurement ------------------------------------------------------------------------------
     def timing_enable(self, on=True):

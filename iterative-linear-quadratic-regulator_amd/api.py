@@ -102,9 +102,10 @@ def solve(dynamics, cost, x0, U_init, *, T=None, N=None, tol=1e-5, maxiter=100, 
           min_alpha=1e-8, n_alpha=None, mu=0.0, dtype=np.float64, device=0, verbose=False, u_min=None, u_max=None,
           batch_params=None, x_min=None, x_max=None, state_limit_options=None):
     """Solve one trajectory (x0 (n,), U_init (m, N)) or a batch (x0 (B, n), U_init (B, m, N)).
-    u_min, u_max: control limits (scalars or [n_u], see iLQR.set_control_limits); batch_params: per-trajectory system
-    parameters and x_target (a dict for batch_param_rows); x_min, x_max, state_limit_options: state limits (see
-    iLQR.set_state_limits)."""
+    u_min, u_max: control limits (scalars or [n_u], for a batch also (B, n_u): one row per trajectory; see
+    iLQR.set_control_limits); batch_params: per-trajectory system
+    parameters and x_target (a dict for batch_param_rows); x_min, x_max, state_limit_options: state limits (scalars,
+    [n_x] or for a batch (B, n_x); see iLQR.set_state_limits)."""
     system = make_system(dynamics, cost, dtype)
     U_init = np.asarray(U_init)
     if N is None and T is None:
@@ -129,7 +130,8 @@ def mpc_init(dynamics, cost, x0, U_init, *, plant_integrator="midpoint", T=None,
              n_alpha=None, dtype=np.float64, device=0, u_min=None, u_max=None, batch_params=None, plant_params=None,
              x_min=None, x_max=None, state_limit_options=None, multipliers="warm"):
     """Receding-horizon controller state (run_iLQR_MPC.py:58-106): optimiser model = ``dynamics``,
-    plant = the same system with ``plant_integrator``; u_min, u_max: control limits of every solve; batch_params: the
+    plant = the same system with ``plant_integrator``; u_min, u_max: control limits of every solve (for a batch also
+    (B, n_u), as x_min, x_max (B, n_x): every instance its own); batch_params: the
     model's per-trajectory parameters and targets, plant_params: each plant's own system parameters (model mismatch),
     both dicts for batch_param_rows; x_min, x_max, state_limit_options: state limits of every solve (see
     iLQR.set_state_limits), with ``multipliers`` ("warm" or "cold", see iLQR.set_mpc_multipliers) the policy of their

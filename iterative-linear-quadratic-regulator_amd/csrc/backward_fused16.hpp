@@ -288,7 +288,9 @@ template <typename T, typename Dyn, int INTEG, int TPW, bool PK, bool BOX, bool 
         lc.tr_byte = 4 * ((lane & 48) | (j << 2) | i);
         bool all_pd = true;
         using FS = FusedStep<T, NU>;
-        const T blo = BOX ? a.u_lo[0] : T(0), bhi = BOX ? a.u_hi[0] : T(0);   // (read once: the loop must not reload them)
+        // (read once: the loop must not reload them; with rows every 16-lane group reads its own trajectory's)
+        T blo = T(0), bhi = T(0);
+        if constexpr (BOX) box_bounds<1>(a, b, &blo, &bhi);
         // Two tile buffers used alternately (US is even, so the buffer of a step is a compile-time choice: no copies);
         // the tile of step s + 1 is read from LDS while step s computes.  The flag of the next unit is fetched one step
         // before it is needed, so its LDS round trip is not exposed either.

@@ -266,6 +266,20 @@ int ilqr_set_state_limits(ilqr_handle h, const double* x_min, const double* x_ma
     return h->impl->set_state_limits(x_min, x_max, ctol, rho0, rho_factor, rho_max, max_outer);
 }
 int ilqr_set_mpc_multipliers(ilqr_handle h, int mode) { ILQR_FWD(h, set_mpc_multipliers(mode)); }
+int ilqr_set_batch_limits(ilqr_handle h, int which, const double* lo, const double* hi, int row_len) {
+    if (!h || !h->impl) return ILQR_ERR_INVALID_ARG;
+    const ilqr_config& c = h->impl->cfg;
+    if (which != ILQR_LIMITS_CONTROL && which != ILQR_LIMITS_STATE) {
+        h->impl->err = "set_batch_limits: which must be ILQR_LIMITS_CONTROL or ILQR_LIMITS_STATE";
+        return ILQR_ERR_INVALID_ARG;
+    }
+    // refused where the shared limits are (clearing with NULL, NULL: valid on every handle)
+    if ((lo || hi) && (c.system == ILQR_SYS_LINEAR || c.system == ILQR_SYS_CUSTOM || c.n_x > 4)) {
+        h->impl->err = "set_batch_limits: limits are not supported for linear systems, user-defined systems or n_x > 4";
+        return ILQR_ERR_UNSUPPORTED;
+    }
+    return h->impl->set_batch_limits(which, lo, hi, row_len);
+}
 int ilqr_timing_enable(ilqr_handle h, int on) { ILQR_FWD(h, timing_enable(on)); }
 int ilqr_timing_reset(ilqr_handle h) { ILQR_FWD(h, timing_reset()); }
 int ilqr_timing_get(ilqr_handle h, double ms[ILQR_N_PHASES], int64_t launches[ILQR_N_PHASES]) {

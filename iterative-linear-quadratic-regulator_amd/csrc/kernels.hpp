@@ -85,7 +85,27 @@ template <typename T> struct KArgs {
     int al_mask;
     const T* lam;
     const T* rho;
+    // per-trajectory limits (ilqr_set_batch_limits), batch-innermost like `rows`: u_lo_rows, u_hi_rows [n_u][B] in place of
+    // u_lo / u_hi, x_lo_rows, x_hi_rows [n_x][B] in place of x_lo / x_hi (+-inf where a trajectory has no bound; al_mask
+    // stays shared: a bit is set when ANY trajectory's bound is finite).  nullptr: the shared bounds above.  Read once
+    // per lane before the step loop by the BOX / AL kernels only (box_bounds, ALBounds); appended for the same reason.
+    const T* u_lo_rows;
+    const T* u_hi_rows;
+    const T* x_lo_rows;
+    const T* x_hi_rows;
 };
+
+// The control limits of trajectory b: its row where rows are set (a wave-uniform choice, one coalesced load per entry),
+// else the shared bounds.
+template <int NU, typename T> ILQR_DEV void box_bounds(const KArgs<T>& a, int b, T* lo, T* hi) {
+    const T* __restrict__ rl = a.u_lo_rows;
+    const T* __restrict__ rh = a.u_hi_rows;
+#pragma unroll
+    for (int j = 0; j < NU; ++j) {
+        lo[j] = rl ? rl[(size_t)j * a.B + b] : a.u_lo[j];
+        hi[j] = rl ? rh[(size_t)j * a.B + b] : a.u_hi[j];
+    }
+}
 
 // A HET lane's parameters: its trajectory's row over the first NH = n_sys + n_x entries of its parameter copy, the shared
 // block behind them.  The templates index the copy with compile-time constants, so they run unchanged on per-lane values.
@@ -237,8 +257,25 @@ ILQR_DEV void tile16_pack(P p, T dt, const T* x, const T* u, const T (*fx)[Dyn::
 // phi(c, lam, rho) = (max(0, lam + rho c)^2 - lam^2) / (2 rho), not scaled by dt.  A bound that never binds (lam = 0,
 // c < 0) adds exactly 0 to every cost, gradient and Hessian.
 // ---------------------------------------------------------------------------
-template <typename T, int NX> ILQR_DEV T al_constraint(const KArgs<T>& a, const T* x, int q) {
-    return q < NX ? x[q < NX ? q : 0] - a.x_hi[q < NX ? q : 0] : a.x_lo[q < NX ? 0 : q - NX] - x[q < NX ? 0 : q - NX];
+// The bounds a lane works with: its trajectory's row (KArgs::x_lo_rows, x_hi_rows) or the shared ones, and the shared mask.
+// A row's infinite bound in an unmasked slot gives c = -inf: max(0, lam + rho c) = 0 from lam = 0 on, so the multiplier
+// stays 0, phi and its derivatives are exactly 0 and max(0, c) = 0 -- the constraint is inactive, with no NaN (rho > 0,
+// and -inf is never multiplied by 0 or subtracted from itself).
+template <typename T, int NX> struct ALBounds {
+    T lo[NX], hi[NX];
+    int mask;
+    ILQR_DEV ALBounds(const KArgs<T>& a, int b) : mask(a.al_mask) {
+        const T* __restrict__ rl = a.x_lo_rows;
+        const T* __restrict__ rh = a.x_hi_rows;
+#pragma unroll
+        for (int i = 0; i < NX; ++i) {
+            lo[i] = rl ? rl[(size_t)i * a.B + b] : a.x_lo[i];
+            hi[i] = rl ? rh[(size_t)i * a.B + b] : a.x_hi[i];
+        }
+    }
+};
+template <typename T, int NX> ILQR_DEV T al_constraint(const ALBounds<T, NX>& a, const T* x, int q) {
+    return q < NX ? x[q < NX ? q : 0] - a.hi[q < NX ? q : 0] : a.lo[q < NX ? 0 : q - NX] - x[q < NX ? 0 : q - NX];
 }
 template <typename T> ILQR_DEV T al_pos(T v) { return v > T(0) ? v : T(0); }
 // lam_t of trajectory b; the constraints that do not exist read as 0
@@ -247,11 +284,11 @@ template <typename T, int NX> ILQR_DEV void al_load_lam(const KArgs<T>& a, size_
     for (int q = 0; q < 2 * NX; ++q) lam[q] = ((a.al_mask >> q) & 1) ? a.lam[((size_t)t * 2 * NX + q) * B + b] : T(0);
 }
 // sum of phi over the constraints of one point, in constraint order
-template <typename T, int NX> ILQR_DEV T al_phi(const KArgs<T>& a, const T* x, const T* lam, T rho) {
+template <typename T, int NX> ILQR_DEV T al_phi(const ALBounds<T, NX>& a, const T* x, const T* lam, T rho) {
     T s = T(0);
 #pragma unroll
     for (int q = 0; q < 2 * NX; ++q) {
-        if ((a.al_mask >> q) & 1) {
+        if ((a.mask >> q) & 1) {
             const T m = al_pos(lam[q] + rho * al_constraint<T, NX>(a, x, q));
             s += (m * m - lam[q] * lam[q]) / (T(2) * rho);
         }
@@ -260,10 +297,10 @@ template <typename T, int NX> ILQR_DEV T al_phi(const KArgs<T>& a, const T* x, c
 }
 // d phi / dx into g (+-max(0, lam + rho c)), d2 phi / dx2 into H (rho on the diagonal where lam + rho c > 0)
 template <typename T, int NX>
-ILQR_DEV void al_expand(const KArgs<T>& a, const T* x, const T* lam, T rho, T* g, T (*H)[NX]) {
+ILQR_DEV void al_expand(const ALBounds<T, NX>& a, const T* x, const T* lam, T rho, T* g, T (*H)[NX]) {
 #pragma unroll
     for (int q = 0; q < 2 * NX; ++q) {
-        if ((a.al_mask >> q) & 1) {
+        if ((a.mask >> q) & 1) {
             const int j = q % NX;
             const T v = lam[q] + rho * al_constraint<T, NX>(a, x, q);
             const T m = al_pos(v);
@@ -488,6 +525,7 @@ __global__ void __launch_bounds__(256) linearize_al_kernel(KArgs<T> a) {
 #pragma unroll
         for (int i = 0; i < NU; ++i) u[i] = T(0);
     }
+    const ALBounds<T, NX> xb(a, b);
     T lam[2 * NX], rho = T(0);   // this point's multipliers and the trajectory's penalty (x_0 is given: none at t = 0)
     if (t >= 1) {
         al_load_lam<T, NX>(a, B, b, t, lam);
@@ -497,7 +535,7 @@ __global__ void __launch_bounds__(256) linearize_al_kernel(KArgs<T> a) {
         T g[NX], H[NX][NX];
         Cost<T, Dyn>::l_f_x(p, x, g);
         Cost<T, Dyn>::l_f_xx(p, x, H);
-        al_expand<T, NX>(a, x, lam, rho, g, H);   // the t = N terms go into V_x, V_xx
+        al_expand<T, NX>(xb, x, lam, rho, g, H);   // the t = N terms go into V_x, V_xx
 #pragma unroll
         for (int i = 0; i < NX; ++i) a.term[(size_t)i * B + b] = g[i];
 #pragma unroll
@@ -519,7 +557,7 @@ __global__ void __launch_bounds__(256) linearize_al_kernel(KArgs<T> a) {
     T g[NX], gu[NU], lxx[NX][NX], lux[NU][NX], luu[NU][NU];
     Cost<T, Dyn>::grad(p, a.dt, x, u, g, gu);
     Cost<T, Dyn>::hess(p, a.dt, x, u, lxx, lux, luu);
-    if (t >= 1) al_expand<T, NX>(a, x, lam, rho, g, lxx);
+    if (t >= 1) al_expand<T, NX>(xb, x, lam, rho, g, lxx);
 #pragma unroll
     for (int i = 0; i < NX; ++i) out[(size_t)(e++) * B] = g[i];
 #pragma unroll
@@ -874,6 +912,8 @@ __global__ void __launch_bounds__(64) backward_box_kernel(KArgs<T> a) {
     T Vx[NX], Vxx[NX][NX];
     load_terminal<T, NX>(a.term, B, b, Vx, Vxx);
     bool all_pd = true;
+    T blo[NU], bhi[NU];   // this trajectory's limits
+    box_bounds<NU>(a, b, blo, bhi);
     for (int t = a.N - 1; t >= 0; --t) {
         T tile[E], u[NU];
         load_expansion<E>(a.lin + ((size_t)t * E) * B + b, B, tile);
@@ -889,8 +929,8 @@ __global__ void __launch_bounds__(64) backward_box_kernel(KArgs<T> a) {
         all_pd = all_pd && pd;
 #pragma unroll
         for (int i = 0; i < NU; ++i) {
-            lo[i] = a.u_lo[i] - u[i];
-            hi[i] = a.u_hi[i] - u[i];
+            lo[i] = blo[i] - u[i];
+            hi[i] = bhi[i] - u[i];
         }
         const bool moved = box_gains<T, NX, NU>(Qr, Qux, Qu, lo, hi, pd, K, k);
         riccati_value<T, NX, NU>(moved || a.mu != T(0), Qx, Qu, Qxx, Qux, Quu, K, k, Vx, Vxx);
@@ -957,6 +997,10 @@ ILQR_DEV void forward_body(const KArgs<T>& a) {
     constexpr int NL = AL ? 2 * NX : 1;
     T lam[NL], lam_n[NL];
     const T rho = AL ? a.rho[b] : T(0);
+    T blo[BOX ? NU : 1], bhi[BOX ? NU : 1];   // BOX: this trajectory's control limits; AL: its state limits
+    if constexpr (BOX) box_bounds<NU>(a, b, blo, bhi);
+    struct NoBounds { ILQR_DEV NoBounds(const KArgs<T>&, int) {} };
+    const std::conditional_t<AL, ALBounds<T, NX>, NoBounds> xb(a, b);
     for (int t = 0; t < N; ++t) {
         const int tn = (t + 1 < N) ? t + 1 : t;
         if constexpr (PREFETCH) {
@@ -975,13 +1019,13 @@ ILQR_DEV void forward_body(const KArgs<T>& a) {
             for (int i = 0; i < NX; ++i) fb += g[j * NX + i] * dx[i];
             // u = u_old + alpha * k + K (x - x_old)   (iLQR_class.py:181-182)
             u[j] = uo[j] + alpha * g[NU * NX + j] + fb;
-            if constexpr (BOX) u[j] = clamp_keep_nan(u[j], a.u_lo[j], a.u_hi[j]);
+            if constexpr (BOX) u[j] = clamp_keep_nan(u[j], blo[j], bhi[j]);
         }
         vec_store<T, NX>(Xc + t * sX, x);
         vec_store<T, NU>(Uc + t * sU, u);
         cost += Cost<T, Dyn>::stage(p, a.dt, x, u);
         if constexpr (AL) {
-            if (t > 0) cost += al_phi<T, NX>(a, x, lam, rho);
+            if (t > 0) cost += al_phi<T, NX>(xb, x, lam, rho);
             // lam_{t+1} (row N exists: the terminal's), requested after this step's inputs were used and before its
             // arithmetic: issued at the loop head, the (masked, branchy) loads made the in-order vmcnt wait for them there
             al_load_lam<T, NX>(a, B, b, t + 1, lam_n);
@@ -1011,7 +1055,7 @@ ILQR_DEV void forward_body(const KArgs<T>& a) {
     }
     vec_store<T, NX>(Xc + N * sX, x);
     cost += Cost<T, Dyn>::terminal(p, x);
-    if constexpr (AL) cost += al_phi<T, NX>(a, x, lam, rho);
+    if constexpr (AL) cost += al_phi<T, NX>(xb, x, lam, rho);
     a.costs[(size_t)ai * B + b] = cost;
     cp.stop(a.probe, 1);
 }
@@ -1060,8 +1104,13 @@ ILQR_DEV void rollout_ring(const KArgs<T>& a, int b, int ai, bool in_range, bool
     constexpr int PF_CNT = (63 / (NLD + NST)) + 1 > ILQR_RING_PF_MAX ? ILQR_RING_PF_MAX : (63 / (NLD + NST)) + 1;
     // (the fp64 backward-Euler step -- Newton loop with an LU solve -- needs more registers of its own: one slot fewer)
     // (HET: the trajectory's row -- n_sys + n_x scalars -- lives in VGPRs beside the ring, which is that much shallower)
+    // (BOX, with or without HET: the limits are per-lane values -- a trajectory may have its own, KArgs::u_lo_rows -- where
+    // the shared ones used to sit in SGPRs: 2 n_u scalars of VGPRs beside the ring.  Every BOX instantiation still fits at
+    // its old depth except the fp64 Euler ones that also carry a HET row, which come out two registers short: one slot
+    // fewer for those alone)
     constexpr int RING_CAP = ((sizeof(T) == 8 && INTEG == ILQR_INT_BACKWARD_EULER) ? 104 : 130) -
-                             (HET ? (Dyn::NSYS + NX) * (int)sizeof(T) / 4 : 0);
+                             (HET ? (Dyn::NSYS + NX) * (int)sizeof(T) / 4 : 0) -
+                             ((BOX && HET && sizeof(T) == 8 && INTEG == ILQR_INT_EULER) ? SLOT_REGS : 0);
     constexpr int PF = PF_CNT * SLOT_REGS > RING_CAP ? RING_CAP / SLOT_REGS : PF_CNT;
     static_assert(PF >= 2, "ring too shallow to be worth it");
     // status, accepted flag and slot in one memory round trip (bitwise &: no short-circuit between the loads)
@@ -1081,11 +1130,12 @@ ILQR_DEV void rollout_ring(const KArgs<T>& a, int b, int ai, bool in_range, bool
     // (a local copy: when the argument block is memory -- the persistent kernel's roles -- a read of a.dt inside the step
     // loop is a load hipcc waits for with vmcnt(0), which drains the register ring every step)
     const T dt = a.dt;
-    T lo[NU], hi[NU];   // (BOX: the limits in registers, for the same reason)
+    T lo[NU], hi[NU];   // (BOX: the limits in registers, for the same reason; the trajectory's own where rows are set)
+    if constexpr (BOX) {
+        box_bounds<NU>(a, bb, lo, hi);   // (a dead lane reads trajectory 0's)
+    } else {
 #pragma unroll
-    for (int j = 0; j < NU; ++j) {
-        lo[j] = BOX ? a.u_lo[j] : T(0);
-        hi[j] = BOX ? a.u_hi[j] : T(0);
+        for (int j = 0; j < NU; ++j) lo[j] = hi[j] = T(0);
     }
     // The parameter block is copied into registers once: the asm statements below carry "memory" clobbers
     // (they pin the order of loads and stores the vmcnt arithmetic relies on), and a clobber would otherwise
@@ -1417,6 +1467,7 @@ __global__ void __launch_bounds__(64) al_update_kernel(KArgs<T> a, ALArgs<T> s) 
         const T* Xb = a.X + vec_at(B, N + 1, NX, slot, 0, b);
         const T* Ub = a.U + vec_at(B, N, NU, slot, 0, b);
         const size_t sX = B * NX, sU = B * NU;
+        const ALBounds<T, NX> xb(a, b);
         T v = T(0);
         for (int t = 1; t <= N; ++t) {
             T x[NX];
@@ -1424,7 +1475,7 @@ __global__ void __launch_bounds__(64) al_update_kernel(KArgs<T> a, ALArgs<T> s) 
 #pragma unroll
             for (int q = 0; q < 2 * NX; ++q) {
                 if ((a.al_mask >> q) & 1) {
-                    const T c = al_constraint<T, NX>(a, x, q);
+                    const T c = al_constraint<T, NX>(xb, x, q);
                     v = c > v ? c : v;
                 }
             }
@@ -1460,11 +1511,11 @@ __global__ void __launch_bounds__(64) al_update_kernel(KArgs<T> a, ALArgs<T> s) 
                     lam[q] = T(0);
                     if ((a.al_mask >> q) & 1) {
                         T* l = s.lam + ((size_t)t * 2 * NX + q) * B + b;
-                        lam[q] = al_pos(*l + rho * al_constraint<T, NX>(a, x, q));
+                        lam[q] = al_pos(*l + rho * al_constraint<T, NX>(xb, x, q));
                         *l = lam[q];
                     }
                 }
-                cost += al_phi<T, NX>(a, x, lam, rn);
+                cost += al_phi<T, NX>(xb, x, lam, rn);
             }
             a.cost[b] = cost;
             a.cost_prev[b] = cost;

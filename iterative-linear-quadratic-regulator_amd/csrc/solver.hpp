@@ -56,6 +56,7 @@ struct SolverBase {
     virtual int set_state_limits(const double* x_min, const double* x_max, double ctol, double rho0, double rho_factor,
                                  double rho_max, int max_outer) = 0;
     virtual int set_mpc_multipliers(int mode) = 0;
+    virtual int set_batch_limits(int which, const double* lo, const double* hi, int row_len) = 0;
 };
 
 int system_dims(int system, int n_x, int n_u);  // 1 if (system, n_x, n_u) is a known combination
@@ -251,6 +252,10 @@ template <typename T> struct StateLimits {
     bool lam_shifted = false;
     DevBuf<int> status_log;     // [n_steps][B] status words of the last state-limited ilqr_mpc_run
     int status_steps = 0;
+    // per-trajectory bounds (ilqr_set_batch_limits): [n_x][B] each, +-inf where a trajectory has none; `mask` is then the
+    // union over the batch.  rows_on = false: lo / hi above hold for every trajectory
+    DevBuf<T> lo_rows, hi_rows;
+    bool rows_on = false;
     hipError_t alloc(size_t B, size_t N, size_t NX) {
         if (lam) return hipSuccess;
         hipError_t e;
@@ -291,6 +296,9 @@ template <typename T> class SolverT : public SolverBase {
     // control limits (ilqr_set_control_limits): u_min <= u <= u_max for every control of every trajectory
     bool box_on = false;
     double box_lo[kBoxMaxU] = {0}, box_hi[kBoxMaxU] = {0};
+    // per-trajectory control limits (ilqr_set_batch_limits): [n_u][B] each; box_rows = false: box_lo / box_hi hold for all
+    DevBuf<T> u_lo_rows, u_hi_rows;
+    bool box_rows = false;
     BatchParams<T> het;
     StateLimits<T> al;
 
@@ -406,6 +414,8 @@ template <typename T> class SolverT : public SolverBase {
             a.u_hi[i] = (T)box_hi[i];
         }
         a.box = box_on ? 1 : 0;
+        a.u_lo_rows = box_on && box_rows ? u_lo_rows.p : nullptr;
+        a.u_hi_rows = box_on && box_rows ? u_hi_rows.p : nullptr;
         a.het = het.on() ? 1 : 0;
         a.rows = het.on() ? het.rows.p : nullptr;
         a.plant_rows = het.on() ? (het.plant_set ? het.plant_rows.p : het.rows.p) : nullptr;
@@ -422,6 +432,8 @@ template <typename T> class SolverT : public SolverBase {
                 a.x_hi[i] = (T)al.hi[i];
             }
             a.al_mask = al.mask;
+            a.x_lo_rows = al.rows_on ? al.lo_rows.p : nullptr;
+            a.x_hi_rows = al.rows_on ? al.hi_rows.p : nullptr;
             a.lam = al.lam;
             a.rho = al.rho;
         }
@@ -964,6 +976,7 @@ template <typename T> class SolverT : public SolverBase {
             if (int rf = flush_select()) return rf;
             if (al.on) lin_stale = true;      // the expansion in HBM is J_A's
             al.on = false;
+            al.rows_on = false;
             al.cost_valid = false;
             return ILQR_OK;
         }
@@ -994,6 +1007,7 @@ template <typename T> class SolverT : public SolverBase {
             al.hi[i] = i < NX && !std::isinf(x_max[i]) ? x_max[i] : 0.0;
         }
         al.mask = mask;
+        al.rows_on = false;        // shared bounds replace rows
         al.ctol = ctol; al.rho0 = rho0; al.rho_factor = rho_factor; al.rho_max = rho_max; al.max_outer = max_outer;
         lin_stale = true;          // an expansion in HBM has no (or other) multiplier terms
         al.on = true;
@@ -1017,6 +1031,7 @@ template <typename T> class SolverT : public SolverBase {
             if (int rf = flush_select()) return rf;
             if (box_on) lin_stale = true;     // the expansion in HBM is the box sweep's
             box_on = false;
+            box_rows = false;
             return ILQR_OK;
         }
         if (!u_min || !u_max) { err = "set_control_limits: give both u_min and u_max, or neither"; return ILQR_ERR_INVALID_ARG; }
@@ -1035,7 +1050,73 @@ template <typename T> class SolverT : public SolverBase {
         for (int i = 0; i < NU; ++i) { box_lo[i] = u_min[i]; box_hi[i] = u_max[i]; }
         if (!box_on) lin_stale = true;        // the expansion in HBM is the unconstrained sweep's
         box_on = true;
+        box_rows = false;                     // shared bounds replace rows
         return ILQR_OK;
+    }
+
+    // ---- per-trajectory limits ----------------------------------------------------------
+    // which = ILQR_LIMITS_CONTROL: host lo, hi [B][n_u]; ILQR_LIMITS_STATE: [B][n_x].  Uploaded batch-innermost in the
+    // handle's dtype; they switch the limits of their kind on exactly as the shared setters do (the route is decided by
+    // box_on / al.on alone) and are dropped again by those setters.  NULL, NULL: the limits given as rows are removed.
+    int set_batch_limits(int which, const double* lo, const double* hi, int row_len) override {
+        const bool ctrl = which == ILQR_LIMITS_CONTROL;
+        if (!ctrl && which != ILQR_LIMITS_STATE) { err = "set_batch_limits: which must be ILQR_LIMITS_CONTROL or ILQR_LIMITS_STATE"; return ILQR_ERR_INVALID_ARG; }
+        if (!lo && !hi) {
+            if (ctrl ? !box_rows : !al.rows_on) return ILQR_OK;      // no rows of that kind: shared limits stay as they are
+            return ctrl ? set_control_limits(nullptr, nullptr) : set_state_limits(nullptr, nullptr, 0, 0, 0, 0, 0);
+        }
+        if (!lo || !hi) { err = "set_batch_limits: give both lo and hi, or neither"; return ILQR_ERR_INVALID_ARG; }
+        const int C = ctrl ? NU : NX;
+        const bool have = ctrl ? (ops.backward_box && ops.linearize_box[cfg.integrator] && ops.forward_box[cfg.integrator] && NU <= kBoxMaxU)
+                               : (ops.backward_box && ops.linearize_al[cfg.integrator] && ops.forward_al[cfg.integrator] && ops.al_update &&
+                                  NX <= kALMaxX && NU <= kBoxMaxU);
+        if (!have) {
+            err = "set_batch_limits: limits are supported for the pendulum, UA double pendulum and double pendulum only";
+            return ILQR_ERR_UNSUPPORTED;
+        }
+        if (row_len != C) { err = "set_batch_limits: row_len must be " + std::to_string(C); return ILQR_ERR_INVALID_ARG; }
+        if (!ctrl && al.max_outer < 1) {
+            err = "set_batch_limits: state rows use the options of ilqr_set_state_limits (ctol, rho0, ...): call it first";
+            return ILQR_ERR_STATE;
+        }
+        int mask = 0;
+        for (size_t i = 0; i < (size_t)B * C; ++i) {
+            // (hi = -inf or lo = +inf leaves no admissible value: as a state row it would make c = +inf, then lam, phi = inf and NaN)
+            if (std::isnan(lo[i]) || std::isnan(hi[i]) || lo[i] > hi[i] || hi[i] == -INFINITY || lo[i] == INFINITY) {
+                err = "set_batch_limits: lo and hi must not be NaN, lo <= hi in every entry, and no hi = -inf or lo = +inf";
+                return ILQR_ERR_INVALID_ARG;
+            }
+            if (!std::isinf(hi[i])) mask |= 1 << (int)(i % C);          // finite for any trajectory: the slot exists
+            if (!std::isinf(lo[i])) mask |= 1 << (C + (int)(i % C));
+        }
+        if (int rf = flush_select()) return rf;
+        if (int rb = ensure_box(st)) return rb;
+        DevBuf<T>& dlo = ctrl ? u_lo_rows : al.lo_rows;
+        DevBuf<T>& dhi = ctrl ? u_hi_rows : al.hi_rows;
+        if (!dlo) ILQR_HIPCHK(dlo.alloc((size_t)C * B));
+        if (!dhi) ILQR_HIPCHK(dhi.alloc((size_t)C * B));
+        std::vector<T> soa((size_t)2 * C * B);
+        for (int b = 0; b < B; ++b)
+            for (int q = 0; q < C; ++q) {
+                soa[(size_t)q * B + b] = (T)lo[(size_t)b * C + q];
+                soa[(size_t)(C + q) * B + b] = (T)hi[(size_t)b * C + q];
+            }
+        ILQR_HIPCHK(hipMemcpyAsync(dlo, soa.data(), (size_t)C * B * sizeof(T), hipMemcpyHostToDevice, stream));
+        ILQR_HIPCHK(hipMemcpyAsync(dhi, soa.data() + (size_t)C * B, (size_t)C * B * sizeof(T), hipMemcpyHostToDevice, stream));
+        ILQR_HIPCHK(hipStreamSynchronize(stream));
+        if (ctrl) {
+            if (!box_on) lin_stale = true;    // the expansion in HBM is the unconstrained sweep's
+            box_on = true;
+            box_rows = true;
+            return ILQR_OK;
+        }
+        ILQR_HIPCHK(al.alloc(B, N, NX));
+        al.mask = mask;
+        al.rows_on = true;
+        lin_stale = true;          // an expansion in HBM has no (or other) multiplier terms
+        al.on = true;
+        al.cost_valid = false;
+        return al_reset();
     }
 
     // ---- per-trajectory parameters ------------------------------------------------------

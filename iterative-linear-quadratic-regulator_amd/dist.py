@@ -158,6 +158,18 @@ def shard_params(system, B, params, lo, hi, with_target=True):
     return out
 
 
+def shard_limits(B, value, lo, hi):
+    """Rows lo:hi of a limit given for the global batch as (B, n); a scalar, (n,) or None is shared and passes as it is."""
+    import numpy as np
+    if value is None or np.ndim(value) != 2:
+        return value
+    a = np.asarray(value, dtype=np.float64)
+    if a.shape[0] != B:
+        raise ValueError(f"per-trajectory limits must have one row per trajectory of the global batch ({B}), "
+                         f"but got shape {a.shape}")
+    return a[lo:hi].copy()
+
+
 class ShardedBatch:
     """Splits a global batch (x0 (B, n), U_init (B, m, N)) over the ranks of the default process group
     and solves the local shard with ``iLQR``; ``global_status()`` is the RCCL all-reduce."""
@@ -179,6 +191,9 @@ class ShardedBatch:
         for key, with_target in (("batch_params", True), ("plant_params", False)):
             if ilqr_kw.get(key) is not None:
                 ilqr_kw[key] = shard_params(system, len(x0), ilqr_kw[key], self.lo, self.hi, with_target)
+        for key in ("u_min", "u_max", "x_min", "x_max"):      # per-trajectory limits: this shard's rows as well
+            if key in ilqr_kw:
+                ilqr_kw[key] = shard_limits(len(x0), ilqr_kw[key], self.lo, self.hi)
         self.solver = iLQR(system, None, self._x0, self._U0, device=device, verbose=False, **ilqr_kw)
         self._stats = torch.zeros(4, dtype=torch.float64, device=f"cuda:{device}")
         self._xchg = None

@@ -30,9 +30,35 @@ def horizon_steps(T, dt):
     return len(np.arange(0, T + dt, dt)) - 1
 
 
-def control_limits(system, u_min, u_max):
-    """Validated (u_min, u_max) as float64 [n_u] arrays (a scalar is broadcast), or None for no limits.  Raises
-    ValueError for a wrong shape, NaN, u_min > u_max, one bound without the other, or a system without limits."""
+def _limit_rows(names, values, n, B, prefix=""):
+    """Per-trajectory bounds: each of the two values a scalar, (n,) or (B, n) -> float64 (B, n) arrays, checked as the
+    shared bounds are (shape, NaN, lo > hi per entry)."""
+    out = []
+    for name, v in zip(names, values):
+        a = np.asarray(v, dtype=np.float64)
+        if a.ndim == 0:
+            a = np.full((B, n), float(a))
+        elif a.shape == (n,):
+            a = np.broadcast_to(a, (B, n))
+        if a.shape != (B, n):
+            raise ValueError(f"{prefix}{name} must be a scalar or have shape ({n},) or ({B}, {n}), but got {a.shape}")
+        if np.isnan(a).any():
+            raise ValueError(f"{prefix}{name} must not contain NaN")
+        out.append(np.ascontiguousarray(a))
+    if np.isneginf(out[1]).any() or np.isposinf(out[0]).any():
+        raise ValueError(f"{prefix}{names[1]} must not be -inf and {names[0]} must not be +inf (no value meets such a bound)")
+    bad = np.argwhere(out[0] > out[1])
+    if len(bad):
+        b, j = (int(i) for i in bad[0])
+        raise ValueError(f"{prefix}{names[0]} must be <= {names[1]}, got {out[0][b, j]} > {out[1][b, j]} "
+                         f"(trajectory {b}, component {j})")
+    return out[0], out[1]
+
+
+def control_limits(system, u_min, u_max, B=None):
+    """Validated (u_min, u_max) as float64 [n_u] arrays (a scalar is broadcast), or None for no limits.  With B (a
+    batched solver) and a 2-D bound: per-trajectory limits, both as (B, n_u) arrays.  Raises ValueError for a wrong
+    shape, NaN, u_min > u_max, one bound without the other, or a system without limits."""
     if u_min is None and u_max is None:
         return None
     if u_min is None or u_max is None:
@@ -41,6 +67,8 @@ def control_limits(system, u_min, u_max):
         raise ValueError(f"control limits are supported for the pendulum, UA double pendulum and double pendulum "
                          f"only, not for {type(system).__name__}")
     n_u = system.n_u
+    if B is not None and (np.ndim(u_min) == 2 or np.ndim(u_max) == 2):
+        return _limit_rows(("u_min", "u_max"), (u_min, u_max), n_u, int(B))
     out = []
     for name, v in (("u_min", u_min), ("u_max", u_max)):
         a = np.asarray(v, dtype=np.float64)
@@ -56,10 +84,10 @@ def control_limits(system, u_min, u_max):
     return out[0], out[1]
 
 
-def state_limits(system, x_min, x_max, options=None):
+def state_limits(system, x_min, x_max, options=None, B=None):
     """Validated state limits as (x_min, x_max, options): float64 [n_x] arrays (a scalar is broadcast, +-inf = no
     constraint) and the outer loop's settings (``_lib.STATE_LIMIT_DEFAULTS`` updated by ``options``), or None for no
-    limits.  Raises ValueError, with "state limits" in the message, for a wrong shape, NaN, x_min > x_max, one bound
+    limits.  With B (a batched solver) and a 2-D bound: per-trajectory limits, both as (B, n_x) arrays.  Raises ValueError, with "state limits" in the message, for a wrong shape, NaN, x_min > x_max, one bound
     without the other, an unknown or bad option, or a system without state limits.  Pure host code (no GPU)."""
     if x_min is None and x_max is None:
         if options:
@@ -71,18 +99,21 @@ def state_limits(system, x_min, x_max, options=None):
         raise ValueError(f"state limits are supported for the pendulum, UA double pendulum and double pendulum "
                          f"only, not for {type(system).__name__}")
     n = system.n_x
-    out = []
-    for name, v in (("x_min", x_min), ("x_max", x_max)):
-        a = np.asarray(v, dtype=np.float64)
-        if a.ndim == 0:
-            a = np.full(n, float(a))
-        if a.shape != (n,):
-            raise ValueError(f"state limits: {name} must be a scalar or have shape ({n},), but got {a.shape}")
-        if np.isnan(a).any():
-            raise ValueError(f"state limits: {name} must not contain NaN")
-        out.append(np.ascontiguousarray(a))
-    if (out[0] > out[1]).any():
-        raise ValueError(f"state limits: x_min must be <= x_max, got {out[0]} > {out[1]}")
+    if B is not None and (np.ndim(x_min) == 2 or np.ndim(x_max) == 2):
+        out = list(_limit_rows(("x_min", "x_max"), (x_min, x_max), n, int(B), "state limits: "))
+    else:
+        out = []
+        for name, v in (("x_min", x_min), ("x_max", x_max)):
+            a = np.asarray(v, dtype=np.float64)
+            if a.ndim == 0:
+                a = np.full(n, float(a))
+            if a.shape != (n,):
+                raise ValueError(f"state limits: {name} must be a scalar or have shape ({n},), but got {a.shape}")
+            if np.isnan(a).any():
+                raise ValueError(f"state limits: {name} must not contain NaN")
+            out.append(np.ascontiguousarray(a))
+        if (out[0] > out[1]).any():
+            raise ValueError(f"state limits: x_min must be <= x_max, got {out[0]} > {out[1]}")
     opts = dict(_lib.STATE_LIMIT_DEFAULTS)
     unknown = sorted(set(options or {}) - set(opts))
     if unknown:
@@ -196,8 +227,9 @@ class iLQR:
             raise ValueError("the MPC plant must be the same system with the same parameters "
                              "(only its integrator may differ, run_iLQR_MPC.py:58-75)")
         self.plant = plant
-        limits = control_limits(system, u_min, u_max)   # checked before any device is touched
-        xlimits = state_limits(system, x_min, x_max, state_limit_options)
+        rows_B = self.B if self.batched else None      # a batched solver also takes (B, n) bounds: one row per trajectory
+        limits = control_limits(system, u_min, u_max, rows_B)   # checked before any device is touched
+        xlimits = state_limits(system, x_min, x_max, state_limit_options, rows_B)
         mpc_mode = mpc_multiplier_mode(mpc_multipliers)
         model_rows = None if batch_params is None else batch_param_rows(system, self.B, batch_params)
         plant_rows = None if plant_params is None else batch_param_rows(system, self.B, plant_params, with_target=False)
@@ -215,9 +247,9 @@ class iLQR:
             maxiter=maxiter, alpha_factor=alpha_factor, min_alpha=min_alpha, mu=mu,
             plant_integrator=None if plant is None else plant.integrator, device=device, flags=flags,
             stream=stream)   # stream: a hipStream_t (e.g. torch.cuda.current_stream().cuda_stream); None = a private one
+        self.u_min = self.u_max = None
         if limits is not None:
-            self._h.set_control_limits(*limits)
-        self.u_min, self.u_max = (None, None) if limits is None else limits
+            self._apply_control_limits(limits)
         self.x_min = self.x_max = self.state_limit_options = None
         if xlimits is not None:
             self._apply_state_limits(xlimits)
@@ -236,25 +268,33 @@ class iLQR:
 
     def set_control_limits(self, u_min, u_max):
         """Box constraints u_min <= u <= u_max on every control (control-limited DDP; include/ilqr_hip.h,
-        ilqr_set_control_limits): scalars or [n_u] arrays, +-inf allowed; (None, None) removes them.  Takes effect from
-        the next rollout / backward pass on, also between MPC steps."""
-        limits = control_limits(self.system, u_min, u_max)
+        ilqr_set_control_limits): scalars or [n_u] arrays, +-inf allowed; (None, None) removes them.  On a batched solver
+        also (B, n_u): every trajectory its own limits (ilqr_set_batch_limits).  Takes effect from the next rollout /
+        backward pass on, also between MPC steps."""
+        self._apply_control_limits(control_limits(self.system, u_min, u_max, self.B if self.batched else None))
+
+    def _apply_control_limits(self, limits):
         if limits is None:
             self._h.set_control_limits(None, None)
             self.u_min = self.u_max = None
+            return
+        if limits[0].ndim == 2:
+            self._h.set_batch_limits(_lib.LIMITS_CONTROL, *limits)
         else:
             self._h.set_control_limits(*limits)
-            self.u_min, self.u_max = limits
+        self.u_min, self.u_max = limits
 
     def set_state_limits(self, x_min, x_max, **options):
         """Bounds x_min <= x_t <= x_max on the state, t = 1..N (include/ilqr_hip.h, ilqr_set_state_limits): scalars or
-        [n_x] arrays, +-inf for a side without a limit; (None, None) removes them.  Solved by the PHR augmented
+        [n_x] arrays, +-inf for a side without a limit; (None, None) removes them.  On a batched solver also (B, n_x):
+        every trajectory its own limits (ilqr_set_batch_limits; +-inf where a trajectory has none).  Solved by the PHR
+        augmented
         Lagrangian around the inner iLQR solve; options: ctol (1e-4), rho0 (1), rho_factor (10), rho_max (1e8),
         max_outer (10).  optimize_trajectory() then reports the plain cost J, and .multipliers, .violation,
         .outer_iterations; a trajectory still violating by more than ctol after max_outer inner solves has
         .infeasible set.  The functional passes refuse while limits are set, and so do the MPC calls unless a
         multiplier policy is set (set_mpc_multipliers)."""
-        self._apply_state_limits(state_limits(self.system, x_min, x_max, options))
+        self._apply_state_limits(state_limits(self.system, x_min, x_max, options, self.B if self.batched else None))
 
     def set_mpc_multipliers(self, mode):
         """What the multipliers of every state-limited MPC step start from (include/ilqr_hip.h,
@@ -270,7 +310,13 @@ class iLQR:
             self._h.set_state_limits(None, None)
             self.x_min = self.x_max = self.state_limit_options = None
         else:
-            self._h.set_state_limits(xlimits[0], xlimits[1], **xlimits[2])
+            lo, hi, opts = xlimits
+            if lo.ndim == 2:
+                # the outer loop's options travel with shared bounds (here the batch's widest); the rows then replace them
+                self._h.set_state_limits(lo.min(axis=0), hi.max(axis=0), **opts)
+                self._h.set_batch_limits(_lib.LIMITS_STATE, lo, hi)
+            else:
+                self._h.set_state_limits(lo, hi, **opts)
             self.x_min, self.x_max, self.state_limit_options = xlimits
 
     @property
