@@ -16,6 +16,7 @@
  *    batch axis in front of the reference's own layout:
  *        x0   [B][n_x]            X  [B][n_x][N+1]      U    [B][n_u][N]
  *        U_ff [B][n_u][N]         K  [B][N][n_u][n_x]   cost [B]
+ *    (ilqr_policy_rollout: a second batch axis [S], the samples of a trajectory, behind [B])
  *  - the handle owns every device buffer and its stream; the caller owns every
  *    host pointer; no host pointer is retained after a call returns.
  *  - one handle <-> one device <-> one stream; a handle is not thread-safe,
@@ -38,7 +39,7 @@
 extern "C" {
 #endif
 
-#define ILQR_ABI_VERSION 5   /* unchanged by ilqr_set_batch_limits: see the note at that entry */
+#define ILQR_ABI_VERSION 5   /* unchanged by ilqr_set_batch_limits and ilqr_policy_rollout: see the notes at those entries */
 
 typedef struct ilqr_solver_s* ilqr_handle;
 
@@ -375,6 +376,53 @@ int ilqr_set_mpc_multipliers(ilqr_handle h, int mode);
  * changes (its cache key hashes them), so no older binary meets the new entry. */
 enum { ILQR_LIMITS_CONTROL = 0, ILQR_LIMITS_STATE = 1 };
 int ilqr_set_batch_limits(ilqr_handle h, int which, const double* lo, const double* hi, int row_len);
+
+/* ---- closed-loop policy rollouts (build extension) ----------------------------------------------------------
+ * How good is the policy the handle holds on the fleet it describes?  For every trajectory b of the batch, S samples are
+ * rolled out on the device around its nominal -- X_t, U_t, K_t of its current slot: the state after ilqr_solve,
+ * ilqr_iterate, ilqr_mpc_run or ilqr_set of X / U / K (a pending acceptance step is completed first).  Sample s of b:
+ *   x_0       = x0[b][s]                                (the solver's x_0[b] when x0 == NULL)
+ *   u_t       = U_t + K_t (x_t - X_t)     feedback = 1  (u_t = U_t when feedback = 0; the feed-forward k_t is not used)
+ *   u_t       = clamp(u_t, u_min, u_max)                only while control limits are set (shared, or b's row); NaN stays NaN
+ *   x_{t+1}   = f_plant(x_t, u_t) + w[b][s][t]          t = 0..N-1; w == NULL: no disturbance
+ *   cost      = sum_t l(x_t, u_t) + l_f(x_N)            the model's plain J of trajectory b (its x_target row where model
+ *                                                       rows are set; shared Q, R, Q_f; never J_A), summed in the
+ *                                                       rollout's order
+ *   deviation = max over t = 0..N, i of |x_t[i] - X_t[i]|   (raw difference, angles not wrapped)
+ *   violation = max over t = 1..N, j of max(0, c_j(x_t))    b's state bounds; 0 when no state limits are set
+ * State limits and their multipliers do not change the policy: they are only reported.  deviation and violation are
+ * accumulated as v = (d > v) ? d : v from 0: an infinity propagates, a NaN is skipped -- the marker of a diverged sample
+ * is its non-finite cost.
+ * f_plant is the step of `integrator` (>= 0: as given; < 0: cfg.plant_integrator when that is >= 0, else the model's
+ * integrator) at the sample's plant constants, taken from the first of: plant_rows[b][s] of this call, the
+ * ILQR_BATCH_PLANT rows, the ILQR_BATCH_MODEL rows, the parameter block.  Per-sample rows are derived on the host in
+ * double by the formulas of ilqr_set_batch_params, so a sample whose row equals the block computes exactly what it
+ * computes without rows.
+ * One wave of the GPU runs 64 samples of one trajectory: S a multiple of 64 fills the waves, any S >= 1 is valid.
+ * The call is synchronous and changes nothing another entry reads: X, U, gains, cost, status, slots, the MPC plant state
+ * and the multipliers stay as they were, so a solve or ilqr_mpc_run continued after it gives exactly what it gives
+ * without it.  Its device buffers are allocated at the first call that needs them, grown when a later call needs more and
+ * freed with the handle; the X and U sample buffers exist only once those outputs were requested.
+ * Returns ILQR_ERR_UNSUPPORTED for ILQR_SYS_LINEAR and ILQR_SYS_CUSTOM, ILQR_ERR_STATE before ilqr_set_problem /
+ * ilqr_mpc_reset, ILQR_ERR_INVALID_ARG for a wrong struct_size, n_samples < 1, an unknown integrator, a non-finite
+ * plant_rows entry, or every output NULL.
+ * ILQR_ABI_VERSION stays 5 with this entry, for the reasons given at ilqr_set_batch_limits: it is additive. */
+typedef struct ilqr_policy_rollout_desc {
+    uint32_t struct_size;     /* = sizeof(ilqr_policy_rollout_desc) */
+    int32_t n_samples;        /* S >= 1 */
+    int32_t integrator;       /* ilqr_integrator of the plant, or < 0 (see above) */
+    int32_t feedback;         /* 1: closed loop through K; 0: open loop */
+    const void* x0;           /* [B][S][n_x] handle dtype, or NULL */
+    const void* w;            /* [B][S][N][n_x] handle dtype, or NULL */
+    const double* plant_rows; /* [B][S][n_sys] system parameters in parameter-block order, or NULL */
+    void* cost;               /* [B][S]            any output may be NULL */
+    void* x_final;            /* [B][S][n_x] */
+    void* deviation;          /* [B][S] */
+    void* violation;          /* [B][S] */
+    void* X;                  /* [B][S][n_x][N+1]  the reference's (dim, time) layout behind the two batch axes */
+    void* U;                  /* [B][S][n_u][N] */
+} ilqr_policy_rollout_desc;
+int ilqr_policy_rollout(ilqr_handle h, const ilqr_policy_rollout_desc* d);
 
 /* ---- multi-GPU hook -------------------------------------------
  * Writes 4 doubles to DEVICE memory `dev_out4` on the handle's stream:

@@ -43,7 +43,7 @@ SYMBOLS = (
     "ilqr_flush", "ilqr_solve", "ilqr_backward_pass", "ilqr_backward_tensors", "ilqr_forward_pass", "ilqr_eval_points", "ilqr_mpc_reset",
     "ilqr_mpc_rearm", "ilqr_mpc_run", "ilqr_status_reduce", "ilqr_timing_enable", "ilqr_timing_reset", "ilqr_timing_get", "ilqr_algorithmic_bytes",
     "ilqr_set_control_limits", "ilqr_set_batch_params", "ilqr_set_state_limits", "ilqr_set_mpc_multipliers",
-    "ilqr_set_batch_limits",
+    "ilqr_set_batch_limits", "ilqr_policy_rollout",
 )
 # ilqr_set_batch_params: which rows
 BATCH_MODEL, BATCH_PLANT = 0, 1
@@ -69,6 +69,17 @@ class Config(C.Structure):
         ("mu", C.c_double),
         ("params", C.POINTER(C.c_double)), ("n_params", C.c_int32), ("reserved", C.c_int32),
         ("stream", C.c_void_p),
+    ]
+
+
+class PolicyRolloutDesc(C.Structure):
+    """ilqr_policy_rollout_desc (include/ilqr_hip.h), field for field."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("n_samples", C.c_int32), ("integrator", C.c_int32), ("feedback", C.c_int32),
+        ("x0", C.c_void_p), ("w", C.c_void_p), ("plant_rows", C.POINTER(C.c_double)),
+        ("cost", C.c_void_p), ("x_final", C.c_void_p), ("deviation", C.c_void_p), ("violation", C.c_void_p),
+        ("X", C.c_void_p), ("U", C.c_void_p),
     ]
 
 
@@ -139,6 +150,7 @@ def load():
     lib.ilqr_set_state_limits.argtypes = [vp, vp, vp, cd, cd, cd, cd, ci]
     lib.ilqr_set_mpc_multipliers.argtypes = [vp, ci]
     lib.ilqr_set_batch_limits.argtypes = [vp, ci, vp, vp, ci]
+    lib.ilqr_policy_rollout.argtypes = [vp, C.POINTER(PolicyRolloutDesc)]
     if lib.ilqr_abi_version() != ABI_VERSION:
         raise RuntimeError("libilqr_hip.so ABI version mismatch: rebuild the library")
     _lib = lib
@@ -413,6 +425,41 @@ class Handle:
         if lo.ndim != 2 or lo.shape[0] != self.B or hi.shape != lo.shape:
             raise ValueError(f"limit rows must both have shape ({self.B}, row_len), but got {lo.shape} and {hi.shape}")
         self._chk(self.lib.ilqr_set_batch_limits(self.h, int(which), _ptr(lo), _ptr(hi), int(lo.shape[1])))
+
+    # ---- closed-loop policy rollouts ---------------------------------------------------------------
+    def policy_rollout(self, n_samples, x0=None, w=None, plant_rows=None, integrator=-1, feedback=True,
+                       trajectories=False, outputs=("cost", "x_final", "deviation", "violation")):
+        """S = n_samples rollouts per trajectory around the nominal the handle holds (include/ilqr_hip.h,
+        ilqr_policy_rollout).  x0 (B, S, n_x), w (B, S, N, n_x), plant_rows (B, S, n_sys) float64, each or None.  Returns a
+        dict of the requested summaries ((B, S) each, x_final (B, S, n_x)) and, with trajectories, X (B, S, n_x, N + 1) and
+        U (B, S, n_u, N)."""
+        B, S, n, m, N = self.B, int(n_samples), self.n_x, self.n_u, self.N
+        Sa = max(S, 0)
+        d = PolicyRolloutDesc()
+        d.struct_size = C.sizeof(PolicyRolloutDesc)
+        d.n_samples, d.integrator, d.feedback = S, int(integrator), int(bool(feedback))
+        keep = []
+        if x0 is not None:
+            keep.append(self._in(x0, (B, S, n)))
+            d.x0 = _ptr(keep[-1])
+        if w is not None:
+            keep.append(self._in(w, (B, S, N, n)))
+            d.w = _ptr(keep[-1])
+        if plant_rows is not None:
+            r = np.ascontiguousarray(plant_rows, dtype=np.float64)
+            if r.ndim != 3 or r.shape[:2] != (B, S):
+                raise ValueError(f"plant rows must have shape ({B}, {S}, n_sys), but got {r.shape}")
+            keep.append(r)
+            d.plant_rows = r.ctypes.data_as(C.POINTER(C.c_double))
+        shapes = {"cost": (B, Sa), "x_final": (B, Sa, n), "deviation": (B, Sa), "violation": (B, Sa)}
+        out = {k: np.empty(shapes[k], dtype=self.np_dtype) for k in outputs}
+        if trajectories:
+            out["X"] = np.empty((B, Sa, n, N + 1), dtype=self.np_dtype)
+            out["U"] = np.empty((B, Sa, m, N), dtype=self.np_dtype)
+        for k, a in out.items():
+            setattr(d, k, _ptr(a))
+        self._chk(self.lib.ilqr_policy_rollout(self.h, C.byref(d)))
+        return out
 
     # ---- measurement ------------------------------------------------------------------------------
     def timing_enable(self, on=True):

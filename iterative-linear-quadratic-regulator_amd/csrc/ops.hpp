@@ -14,6 +14,7 @@
 #include "kernels_wave.hpp"
 #include "backward_mfma16.hpp"
 #include "forward_mfma16.hpp"
+#include "policy_rollout.hpp"
 
 namespace ilqr {
 
@@ -112,6 +113,8 @@ template <typename T> struct Ops {
     void (*al_update)(const KArgs<T>&, const ALArgs<T>&, hipStream_t) = nullptr;
     void (*al_cost)(const KArgs<T>&, const ALArgs<T>&, hipStream_t) = nullptr;
     void (*mpc_advance_al)(const MpcALArgs<T>&, hipStream_t) = nullptr;   // the epilogue of a state-limited MPC step
+    // closed-loop policy rollouts (ilqr_policy_rollout, policy_rollout.hpp); null where they are not supported
+    void (*policy)(const PolicyArgs<T>&, hipStream_t) = nullptr;
 };
 
 // linearize / forward are compiled once per integrator so the integrator switch folds away and each
@@ -252,6 +255,14 @@ void launch_forward(const KArgs<T>& a, hipStream_t s) {
         ILQR_LAUNCH_HET(HETS, a.het, (forward_kernel<T, Dyn, I>), (forward_kernel_het<T, Dyn, I>), grid, block, 0, s, a);
 }
 
+// S samples per trajectory, one wave per 64 samples of one trajectory (policy_rollout.hpp); the SROWS instantiation where
+// the call brings per-sample plant constants
+template <typename T, typename Dyn> void launch_policy(const PolicyArgs<T>& a, hipStream_t s) {
+    const dim3 grid((a.S + 63) / 64, a.B), block(64);
+    if (a.srows) ILQR_LAUNCH((policy_rollout_kernel<T, Dyn, true>), grid, block, 0, s, a);
+    else ILQR_LAUNCH((policy_rollout_kernel<T, Dyn, false>), grid, block, 0, s, a);
+}
+
 template <typename T, typename Dyn, bool TILE, int INTEG> void set_integrator_ops(Ops<T>& o) {
     constexpr bool SMALL = all_integrators<Dyn>::value;
     // control limits on the fused and persistent kernels: n_u = 1 (u_t rides the tile's padding, FusedWG)
@@ -366,6 +377,7 @@ template <typename T, typename Dyn> Ops<T> make_ops() {
             ILQR_LAUNCH_HET(true, a.m.plant_rows, (mpc_advance_al_kernel<T, Dyn>), (mpc_advance_al_kernel<T, Dyn, true>),
                             dim3((a.m.B + 63) / 64), dim3(64, kMpcChunks), 0, s, a);
         };
+        o.policy = launch_policy<T, Dyn>;
     }
     o.eval = [](const EvalArgs<T>& a, hipStream_t s) {
         ILQR_LAUNCH((eval_points_kernel<T, Dyn>), dim3((a.npts + 63) / 64), dim3(64), 0, s, a);

@@ -57,6 +57,7 @@ struct SolverBase {
                                  double rho_max, int max_outer) = 0;
     virtual int set_mpc_multipliers(int mode) = 0;
     virtual int set_batch_limits(int which, const double* lo, const double* hi, int row_len) = 0;
+    virtual int policy_rollout(const ilqr_policy_rollout_desc& d) = 0;
 };
 
 int system_dims(int system, int n_x, int n_u);  // 1 if (system, n_x, n_u) is a known combination
@@ -301,6 +302,9 @@ template <typename T> class SolverT : public SolverBase {
     bool box_rows = false;
     BatchParams<T> het;
     StateLimits<T> al;
+    // ilqr_policy_rollout: per-sample inputs and outputs, sample-innermost; allocated at the first call that needs them and
+    // grown, never shrunk (pr_X / pr_U only by calls that ask for the sample trajectories)
+    DevBuf<T> pr_x0, pr_w, pr_rows, pr_sum, pr_X, pr_U;
 
     // (the device buffers free themselves after this body: DevBuf)
     ~SolverT() override {
@@ -1166,6 +1170,119 @@ template <typename T> class SolverT : public SolverBase {
         // a plant without model rows: the model's rows are the block's
         if (het.plant_set && !het.model_set) return upload(het.rows, nh, nullptr, 0);
         return ILQR_OK;
+    }
+
+    // ---- closed-loop policy rollouts (policy_rollout.hpp) ---------------------------------
+    // grow-only: `count` elements, or what the buffer already holds when that is enough (nothing queued uses it: every
+    // call that touches these buffers ends synchronised)
+    template <typename U> int grow(DevBuf<U>& buf, size_t count) {
+        if (count <= buf.n) return ILQR_OK;
+        ILQR_HIPCHK(hipStreamSynchronize(stream));
+        ILQR_HIPCHK(buf.alloc(count));
+        return ILQR_OK;
+    }
+    // S samples per trajectory around the nominal (X, U, K of the current slots) the handle holds.  Reads the solver state
+    // and writes only the pr_* buffers and `staging`: nothing another entry reads changes.
+    int policy_rollout(const ilqr_policy_rollout_desc& d) override {
+        if (!ops.policy) {
+            err = "policy_rollout: supported for the pendulum, UA double pendulum and double pendulum only";
+            return ILQR_ERR_UNSUPPORTED;
+        }
+        if (!have_problem) { err = "policy_rollout before set_problem / mpc_reset"; return ILQR_ERR_STATE; }
+        if (d.n_samples < 1) { err = "policy_rollout: n_samples must be >= 1"; return ILQR_ERR_INVALID_ARG; }
+        if (d.integrator > ILQR_INT_DISCRETE) { err = "policy_rollout: unknown integrator"; return ILQR_ERR_INVALID_ARG; }
+        if (!d.cost && !d.x_final && !d.deviation && !d.violation && !d.X && !d.U) {
+            err = "policy_rollout: every output is NULL";
+            return ILQR_ERR_INVALID_ARG;
+        }
+        const size_t S = (size_t)d.n_samples, L = (size_t)B * S;
+        if (L > (size_t)std::numeric_limits<int>::max()) { err = "policy_rollout: batch * n_samples must be < 2^31"; return ILQR_ERR_INVALID_ARG; }
+        const int ns = (int)het.abi_params.size() - (NX + 2 * NX * NX + NU * NU);   // system parameters of the ABI block
+        if (d.plant_rows) {
+            for (size_t i = 0; i < L * ns; ++i)
+                if (!std::isfinite(d.plant_rows[i])) { err = "policy_rollout: every plant_rows value must be finite"; return ILQR_ERR_INVALID_ARG; }
+        }
+        int rc;
+        if ((rc = flush_select())) return rc;
+        if ((rc = fix_slots(st))) return rc;
+        const size_t nX = L * NX * (size_t)(N + 1), nU = L * NU * (size_t)N, nW = L * NX * (size_t)N;
+        if ((rc = grow(pr_sum, L * (size_t)(3 + NX)))) return rc;
+        if (d.x0 && (rc = grow(pr_x0, L * NX))) return rc;
+        if (d.w && (rc = grow(pr_w, nW))) return rc;
+        if (d.plant_rows && (rc = grow(pr_rows, L * (size_t)ops.n_sys_dev))) return rc;
+        if (d.X && (rc = grow(pr_X, nX))) return rc;
+        if (d.U && (rc = grow(pr_U, nU))) return rc;
+        if ((rc = grow(staging, std::max({L * NX, d.w ? nW : (size_t)0, d.X ? nX : (size_t)0, d.U ? nU : (size_t)0})))) return rc;
+        const int Li = (int)L;
+        // host [B][S][c] / [B][S][N][c] -> [c][L] / [N][c][L]: layout_tc_kernel with the samples as its batch axis
+        auto up = [&](const void* host, T* dev, int Tn) {
+            return stage_up(host, L * NX * (size_t)Tn, [&](dim3 g_, dim3 b_) {
+                hipLaunchKernelGGL((layout_tc_kernel<T, true>), g_, b_, 0, stream, staging.p, dev, Li, NX, Tn);
+            });
+        };
+        if (d.x0 && (rc = up(d.x0, pr_x0, 1))) return rc;
+        if (d.w && (rc = up(d.w, pr_w, N))) return rc;
+        if (d.plant_rows) {
+            // derived in double by the formulas of the block's own constants, as the rows of ilqr_set_batch_params
+            const int nd = ops.n_sys_dev;
+            std::vector<T> soa((size_t)nd * L);
+            std::vector<double> blk = het.abi_params;
+            for (size_t l = 0; l < L; ++l) {
+                std::copy(d.plant_rows + l * ns, d.plant_rows + (l + 1) * ns, blk.begin());
+                const std::vector<double> dp = build_device_params(cfg.system, NX, NU, blk.data());
+                for (int q = 0; q < nd; ++q) soa[(size_t)q * L + l] = (T)dp[q];
+            }
+            ILQR_HIPCHK(hipMemcpyAsync(pr_rows, soa.data(), soa.size() * sizeof(T), hipMemcpyHostToDevice, stream));
+            ILQR_HIPCHK(hipStreamSynchronize(stream));
+        }
+        PolicyArgs<T> a{};
+        a.B = B; a.S = d.n_samples; a.N = N; a.n_slots = st.n_slots;
+        a.integ = d.integrator >= 0 ? d.integrator : cfg.plant_integrator >= 0 ? cfg.plant_integrator : cfg.integrator;
+        a.feedback = d.feedback ? 1 : 0;
+        a.dt = (T)cfg.dt;
+        a.X = st.X; a.U = st.U; a.gains = st.gains; a.cur_slot = st.cur_slot; a.params = params; a.x0 = st.x0;
+        a.rows = het.on() ? het.rows.p : nullptr;
+        a.plant_rows = het.plant_set ? het.plant_rows.p : nullptr;
+        a.x0s = d.x0 ? pr_x0.p : nullptr;
+        a.w = d.w ? pr_w.p : nullptr;
+        a.srows = d.plant_rows ? pr_rows.p : nullptr;
+        for (int j = 0; j < kBoxMaxU; ++j) {
+            a.u_lo[j] = box_on ? (T)box_lo[j] : -std::numeric_limits<T>::infinity();
+            a.u_hi[j] = box_on ? (T)box_hi[j] : std::numeric_limits<T>::infinity();
+        }
+        a.u_lo_rows = box_on && box_rows ? u_lo_rows.p : nullptr;
+        a.u_hi_rows = box_on && box_rows ? u_hi_rows.p : nullptr;
+        if (al.on) {
+            for (int i = 0; i < kALMaxX; ++i) { a.x_lo[i] = (T)al.lo[i]; a.x_hi[i] = (T)al.hi[i]; }
+            a.al_mask = al.mask;
+            a.x_lo_rows = al.rows_on ? al.lo_rows.p : nullptr;
+            a.x_hi_rows = al.rows_on ? al.hi_rows.p : nullptr;
+        }
+        a.cost = pr_sum; a.deviation = pr_sum + L; a.violation = pr_sum + 2 * L; a.x_final = pr_sum + 3 * L;
+        a.Xs = d.X ? pr_X.p : nullptr;
+        a.Us = d.U ? pr_U.p : nullptr;
+        if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.policy(a, stream); }))) return rc;
+        auto fetch = [&](void* host, const T* dev) -> int {
+            if (host) ILQR_HIPCHK(hipMemcpyAsync(host, dev, L * sizeof(T), hipMemcpyDeviceToHost, stream));
+            return ILQR_OK;
+        };
+        if ((rc = fetch(d.cost, a.cost)) || (rc = fetch(d.deviation, a.deviation)) || (rc = fetch(d.violation, a.violation))) return rc;
+        if (d.x_final) {
+            rc = stage_down(d.x_final, L * NX, [&](dim3 g_, dim3 b_) {
+                hipLaunchKernelGGL((layout_tc_kernel<T, false>), g_, b_, 0, stream, staging.p, (const T*)a.x_final, Li, NX, 1);
+            });
+            if (rc) return rc;
+        }
+        // [t][c][L] -> host [B][S][c][t]
+        auto down_traj = [&](void* host, const T* dev, int C, int Tn) {
+            return stage_down(host, L * C * (size_t)Tn, [&](dim3 g_, dim3 b_) {
+                hipLaunchKernelGGL(layout_ctl_gather_kernel<T>, g_, b_, 0, stream, staging.p, dev, L, C, Tn);
+            });
+        };
+        if (d.X && (rc = down_traj(d.X, pr_X, NX, N + 1))) return rc;
+        if (d.U && (rc = down_traj(d.U, pr_U, NU, N))) return rc;
+        ILQR_HIPCHK(hipStreamSynchronize(stream));
+        return check_launch();
     }
 
     // ---- pure functional calls --------------------------------------------------------

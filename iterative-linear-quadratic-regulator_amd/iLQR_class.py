@@ -16,6 +16,8 @@ the backtracking line search rolled out in parallel.
 
 from __future__ import annotations
 
+from collections import namedtuple
+
 import numpy as np
 
 from . import _lib
@@ -184,6 +186,60 @@ def batch_param_rows(system, B, params, with_target=True):
     if not np.isfinite(rows).all():
         raise ValueError("batch parameters must be finite (no NaN or inf)")
     return rows
+
+
+PolicyRollout = namedtuple("PolicyRollout", "cost x_final deviation violation X U", defaults=(None, None))
+PolicyRollout.__doc__ = """Result of iLQR.policy_rollout: cost, deviation, violation ([B,] S), x_final ([B,] S, n_x) and, with
+trajectories=True, X ([B,] S, n_x, N + 1) and U ([B,] S, n_u, N), else None.  A diverged sample has a non-finite cost."""
+
+
+def policy_rollout_args(system, N, B, batched, n_samples, x_0=None, disturbance=None, plant_params=None, integrator=None):
+    """Validated arguments of ``ilqr_policy_rollout`` as (S, x0, w, plant_rows, integrator code): x0 (B, S, n_x), w
+    (B, S, N, n_x) as float64 arrays or None, plant_rows (B, S, n_sys) float64 or None, integrator -1 for the solver's
+    plant (else model) integrator.  Inputs carry (B, S, ...) on a batched solver and (S, ...) on a single one.
+    plant_params is what ``set_plant_params`` takes per trajectory, here per sample: {name: scalar or ([B,] S)}.
+    Raises ValueError for n_samples < 1, a wrong shape, a non-finite plant parameter, an unknown parameter name or
+    integrator, or a system without policy rollouts.  Pure host code (no GPU)."""
+    if getattr(system, "SYSTEM_ID", None) not in _lib.BOX_SYSTEMS:
+        raise ValueError(f"policy rollouts are supported for the pendulum, UA double pendulum and double pendulum "
+                         f"only, not for {type(system).__name__}")
+    if isinstance(n_samples, bool) or int(n_samples) != n_samples or int(n_samples) < 1:
+        raise ValueError(f"n_samples must be an integer >= 1, got {n_samples!r}")
+    S, B, n = int(n_samples), int(B), system.n_x
+    lead = (B, S) if batched else (S,)
+
+    def shaped(name, v, tail):
+        if v is None:
+            return None
+        a = np.asarray(v, dtype=np.float64)
+        if a.shape != lead + tail:
+            raise ValueError(f"{name} must have shape {lead + tail}, but got {a.shape}")
+        return np.ascontiguousarray(a.reshape((B, S) + tail))
+
+    x0 = shaped("x_0", x_0, (n,))
+    w = shaped("disturbance", disturbance, (int(N), n))
+    rows = None
+    if plant_params is not None:
+        flat = {}
+        unknown = sorted(set(plant_params) - set(system.param_names()))
+        if unknown:
+            raise ValueError(f"unknown parameter name(s) {unknown}; expected some of {sorted(system.param_names())}")
+        for k, v in dict(plant_params).items():
+            a = np.asarray(v, dtype=np.float64)
+            if a.ndim != 0:
+                if a.shape != lead:
+                    raise ValueError(f"{k} must be a scalar or have shape {lead}, but got {a.shape}")
+                a = a.reshape(B * S)
+            flat[k] = a
+        # one row per sample: the samples are the batch axis of the per-trajectory rows
+        rows = batch_param_rows(system, B * S, flat, with_target=False).reshape(B, S, -1)
+    if integrator is None:
+        code = -1
+    elif isinstance(integrator, str) and integrator in _lib.INTEGRATORS:
+        code = _lib.INTEGRATORS[integrator]
+    else:
+        raise ValueError(f"Unknown integrator: {integrator!r}. Supported: 'rk4', 'midpoint', 'euler', 'backward_euler'.")
+    return S, x0, w, rows, code
 
 
 class iLQR:
@@ -470,6 +526,22 @@ class iLQR:
             print(f"  Iter {i+1} (alpha={alpha:.2e}): Cost improved to {cost:.4f}")
         if i == self.maxiter - 1:
             print(f"Warning: Reached max iterations ({self.maxiter}) without converging.")
+
+    # ---- closed-loop policy rollouts ----------------------------------------------------------------
+    def policy_rollout(self, n_samples, x_0=None, disturbance=None, plant_params=None, integrator=None, feedback=True,
+                       trajectories=False):
+        """How good is the current policy (X, U, K as the solver holds them) off its nominal?  n_samples rollouts per
+        trajectory on the device (include/ilqr_hip.h, ilqr_policy_rollout): u = U + K (x - X) (feedback=False: u = U),
+        clamped to the control limits if set, through the plant.  x_0 ([B,] S, n_x): the samples' initial states (None:
+        the solver's own); disturbance ([B,] S, N, n_x): added to the state after every step; plant_params: per-sample
+        system parameters, {name: scalar or ([B,] S)} as set_plant_params takes per trajectory (None: the plant rows,
+        else the model's parameters); integrator: the plant's (None: the solver's plant, else its model's).  Returns a
+        PolicyRollout; X and U of every sample only with trajectories=True.  A multiple of 64 samples fills the GPU's
+        waves.  Nothing in the solver changes."""
+        S, x0, w, rows, code = policy_rollout_args(self.system, self.N, self.B, self.batched, n_samples, x_0, disturbance,
+                                                   plant_params, integrator)
+        out = self._h.policy_rollout(S, x0, w, rows, code, feedback, trajectories)
+        return PolicyRollout(**{k: self._out(v) for k, v in out.items()})
 
     # ---- MPC (run_iLQR_MPC.py:116-143), device-resident ---------------------------------------------
     def mpc_reset(self, x_0, U_init, keep_state=False):

@@ -1,0 +1,70 @@
+#!/usr/bin/env python3
+"""Policy robustness: solve a batch of UA double pendulum swing-ups (problems.ua_double_pendulum), then ask how good the
+result is off its nominal.  Every solved trajectory is rolled out S times on the device (iLQR.policy_rollout) with the
+initial state off by a few degrees and the plant's m2 and l2 off by up to 20 %, once closed loop through the gains K_t
+and once open loop (the controls U_t alone).  Per trajectory the script reports the share of samples whose final state is
+within the stated tolerance of the target.
+
+    python scripts/run_iLQR_policy_robustness.py [--batch 256] [--samples 1024] [--horizon 200] [--dtype f64] [--seed 0]
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import ilqr_amd                       # noqa: E402
+from ilqr_amd import problems         # noqa: E402
+
+ANGLE_OFF = np.deg2rad(3.0)   # initial joint angles within +-3 degrees of the solver's
+RATE_OFF = 0.05               # initial joint rates within +-0.05 rad/s
+SPREAD = 0.2                  # plant m2, l2 within +-20 % of the model's
+TOL_ANGLE = 0.1               # rad, both joints
+TOL_RATE = 0.5                # rad/s, both joints
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--samples", type=int, default=1024, help="samples per trajectory (a multiple of 64 fills the waves)")
+    ap.add_argument("--horizon", type=int, default=200)
+    ap.add_argument("--dtype", default="f64", choices=["f64", "f32"])
+    ap.add_argument("--seed", type=int, default=0)
+    a = ap.parse_args(argv)
+    dtype = np.float64 if a.dtype == "f64" else np.float32
+    B, S, N = a.batch, a.samples, a.horizon
+    p = problems.ua_double_pendulum(N=N)
+    system = ilqr_amd.make_system(p["dynamics"], p["cost"], dtype)
+    x0, U0 = problems.ua_batch(B, seed=a.seed, N=N)
+    solver = ilqr_amd.iLQR(system, None, x0, U0, N=N, tol=p["tol"], maxiter=p["maxiter"], verbose=False, dtype=dtype)
+    t0 = time.time()
+    solver.optimize_trajectory()
+    print(f"Solved {B} swing-ups (N = {N}) in {time.time() - t0:.3f} s: "
+          f"{solver.status.count('converged')} converged")
+    rng = np.random.default_rng(a.seed + 1)
+    off = rng.uniform(-1.0, 1.0, (B, S, 4)) * np.array([ANGLE_OFF, ANGLE_OFF, RATE_OFF, RATE_OFF])
+    xs = x0[:, None, :] + off
+    plant_params = {"m2": system.m2 * rng.uniform(1 - SPREAD, 1 + SPREAD, (B, S)),
+                    "l2": system.l2 * rng.uniform(1 - SPREAD, 1 + SPREAD, (B, S))}
+    target = np.asarray(system.x_target, np.float64)
+    shares = {}
+    for label, feedback in (("closed loop", True), ("open loop", False)):
+        t0 = time.time()
+        r = solver.policy_rollout(S, xs, plant_params=plant_params, feedback=feedback)
+        el = time.time() - t0
+        err = np.abs(np.asarray(r.x_final, np.float64) - target)
+        ok = np.isfinite(r.cost) & (err[..., :2].max(axis=-1) <= TOL_ANGLE) & (err[..., 2:].max(axis=-1) <= TOL_RATE)
+        share = ok.mean(axis=1)
+        shares[label] = share
+        print(f"{label}: {B} x {S} rollouts in {el:.3f} s; share of samples within tolerance per trajectory: "
+              f"min {share.min():.3f}, median {np.median(share):.3f}, max {share.max():.3f}; "
+              f"median deviation from the nominal {np.median(r.deviation):.3f}")
+    print(f"(tolerance: |angle error| <= {TOL_ANGLE} rad, |rate error| <= {TOL_RATE} rad/s at t = {N * system.dt:g} s; "
+          f"initial angles off by up to {np.rad2deg(ANGLE_OFF):g} degrees, m2 and l2 by up to {SPREAD:.0%})")
+    return shares
+
+
+if __name__ == "__main__":
+    main()
