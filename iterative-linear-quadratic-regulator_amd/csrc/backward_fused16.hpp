@@ -290,7 +290,7 @@ template <typename T, typename Dyn, int INTEG, int TPW, bool PK, bool BOX, bool 
         using FS = FusedStep<T, NU>;
         // (read once: the loop must not reload them; with rows every 16-lane group reads its own trajectory's)
         T blo = T(0), bhi = T(0);
-        if constexpr (BOX) box_bounds<1>(a, b, &blo, &bhi);
+        if constexpr (BOX) box_bounds<1>(a.lim, a.B, b, &blo, &bhi);
         // Two tile buffers used alternately (US is even, so the buffer of a step is a compile-time choice: no copies);
         // the tile of step s + 1 is read from LDS while step s computes.  The flag of the next unit is fetched one step
         // before it is needed, so its LDS round trip is not exposed either.

@@ -43,6 +43,27 @@ constexpr int kCounterRing = 64;
 constexpr int kBoxMaxU = 2;   // control limits: the built-in systems with n_x <= 4 (n_u <= 2)
 constexpr int kALMaxX = 4;    // state limits: the same systems (n_x <= 4)
 
+// The limits of a launch (ilqr_set_control_limits, ilqr_set_state_limits, ilqr_set_batch_limits): bounds on a vector,
+// shared by the batch or one row per trajectory.  One record for KArgs and PolicyArgs, filled by SolverT::limits().
+template <typename T> struct Limits {
+    // control limits, read by the BOX kernels only (forward_kernel_box, forward_ring_kernel_box, backward_box_kernel, the
+    // BOX fused / persistent kernels) and the policy rollout; +-inf where none are set: a clamp then moves nothing
+    T u_lo[kBoxMaxU], u_hi[kBoxMaxU];
+    // state limits, read by the AL kernels only (linearize_al_kernel, forward_kernel_al*, al_update_kernel, al_cost_kernel)
+    // and the policy rollout.  A finite x_hi[j] is the constraint x_t[j] - x_hi[j] <= 0 (bit j of al_mask), a finite
+    // x_lo[j] is x_lo[j] - x_t[j] <= 0 (bit n_x + j), t = 1..N.  al_mask = 0: no state limits
+    T x_lo[kALMaxX], x_hi[kALMaxX];
+    int al_mask;
+    // per-trajectory limits, batch-innermost like KArgs::rows: u_lo_rows, u_hi_rows [n_u][B] in place of u_lo / u_hi,
+    // x_lo_rows, x_hi_rows [n_x][B] in place of x_lo / x_hi (+-inf where a trajectory has no bound; al_mask stays shared: a
+    // bit is set when ANY trajectory's bound is finite).  nullptr: the shared bounds above.  Read once per lane before
+    // the step loop (box_bounds, ALBounds)
+    const T* u_lo_rows;
+    const T* u_hi_rows;
+    const T* x_lo_rows;
+    const T* x_hi_rows;
+};
+
 template <typename T> struct KArgs {
     int B, N, n_slots, integ, maxiter, flags;
     int n_pass;      // alphas in this pass
@@ -65,45 +86,33 @@ template <typename T> struct KArgs {
     int t_first;       // linearize_wave_kernel: first time step of the launch (0, or N-1 for the sparse form)
     const T* params;
     long long* probe;  // diagnostic: {shader cycles, 100 MHz ticks} of block 0 per kernel, or nullptr
-    // control limits (ilqr_set_control_limits), read by the BOX kernels only (forward_kernel_box,
-    // forward_ring_kernel_box, backward_box_kernel, the BOX fused / persistent kernels); appended so the fields above keep
-    // their offsets
-    T u_lo[kBoxMaxU], u_hi[kBoxMaxU];
-    int box;           // limits are set: the fused / persistent launchers pick their BOX instantiations
+    // Everything below is read by the BOX / HET / AL instantiations only, and sits behind the fields above so that those
+    // keep their offsets in every other kernel.  The two flags are aligned like a T: sizeof(KArgs), and with it the offsets
+    // of the implicit kernel arguments behind it (the block size select_kernel and others read), then stays what it was
+    // before the limits became one record, in fp32 and fp64 alike
+    alignas(sizeof(T)) int box;   // control limits are set: the fused / persistent launchers pick their BOX instantiations
+    alignas(sizeof(T)) int het;   // rows are set: the launchers pick their HET instantiations
     // per-trajectory parameters (ilqr_set_batch_params), read by the HET kernels only (the *_het kernels, the HET fused /
-    // persistent roles); appended after the limits for the same reason.  rows: [n_sys + n_x][B] derived system constants
-    // then x_target of every trajectory (SoA: a wave's load of one entry is coalesced); plant_rows: [n_sys][B] of the MPC
-    // plant (the model's rows when the plant has none of its own)
+    // persistent roles).  rows: [n_sys + n_x][B] derived system constants then x_target of every trajectory (SoA: a wave's
+    // load of one entry is coalesced); plant_rows: [n_sys][B] of the MPC plant (the model's rows when the plant has none
+    // of its own)
     const T* rows;
     const T* plant_rows;
-    int het;           // rows are set: the launchers pick their HET instantiations
-    // state limits (ilqr_set_state_limits), read by the AL kernels only (linearize_al_kernel, forward_kernel_al*,
-    // al_update_kernel, al_cost_kernel); appended after the rows for the same reason.  A finite x_hi[j] is the constraint
-    // x_t[j] - x_hi[j] <= 0 (bit j of al_mask), a finite x_lo[j] is x_lo[j] - x_t[j] <= 0 (bit n_x + j), t = 1..N.
-    // lam: [N+1][2 n_x][B] multipliers (upper bounds first, row t = 0 unused), rho: [B] penalties
-    T x_lo[kALMaxX], x_hi[kALMaxX];
-    int al_mask;
+    // state limits: lam [N+1][2 n_x][B] multipliers (upper bounds first, row t = 0 unused), rho [B] penalties
     const T* lam;
     const T* rho;
-    // per-trajectory limits (ilqr_set_batch_limits), batch-innermost like `rows`: u_lo_rows, u_hi_rows [n_u][B] in place of
-    // u_lo / u_hi, x_lo_rows, x_hi_rows [n_x][B] in place of x_lo / x_hi (+-inf where a trajectory has no bound; al_mask
-    // stays shared: a bit is set when ANY trajectory's bound is finite).  nullptr: the shared bounds above.  Read once
-    // per lane before the step loop by the BOX / AL kernels only (box_bounds, ALBounds); appended for the same reason.
-    const T* u_lo_rows;
-    const T* u_hi_rows;
-    const T* x_lo_rows;
-    const T* x_hi_rows;
+    Limits<T> lim;
 };
 
 // The control limits of trajectory b: its row where rows are set (a wave-uniform choice, one coalesced load per entry),
 // else the shared bounds.
-template <int NU, typename T> ILQR_DEV void box_bounds(const KArgs<T>& a, int b, T* lo, T* hi) {
+template <int NU, typename T> ILQR_DEV void box_bounds(const Limits<T>& a, size_t B, int b, T* lo, T* hi) {
     const T* __restrict__ rl = a.u_lo_rows;
     const T* __restrict__ rh = a.u_hi_rows;
 #pragma unroll
     for (int j = 0; j < NU; ++j) {
-        lo[j] = rl ? rl[(size_t)j * a.B + b] : a.u_lo[j];
-        hi[j] = rl ? rh[(size_t)j * a.B + b] : a.u_hi[j];
+        lo[j] = rl ? rl[(size_t)j * B + b] : a.u_lo[j];
+        hi[j] = rl ? rh[(size_t)j * B + b] : a.u_hi[j];
     }
 }
 
@@ -253,24 +262,24 @@ ILQR_DEV void tile16_pack(P p, T dt, const T* x, const T* u, const T (*fx)[Dyn::
 
 // ---------------------------------------------------------------------------
 // State limits (ilqr_set_state_limits): the PHR augmented Lagrangian.  Constraint q of x_t, t = 1..N:
-// q < n_x: c = x_t[q] - x_hi[q];  q >= n_x: c = x_lo[q - n_x] - x_t[q - n_x];  only the finite bounds (KArgs::al_mask).
+// q < n_x: c = x_t[q] - x_hi[q];  q >= n_x: c = x_lo[q - n_x] - x_t[q - n_x];  only the finite bounds (Limits::al_mask).
 // phi(c, lam, rho) = (max(0, lam + rho c)^2 - lam^2) / (2 rho), not scaled by dt.  A bound that never binds (lam = 0,
 // c < 0) adds exactly 0 to every cost, gradient and Hessian.
 // ---------------------------------------------------------------------------
-// The bounds a lane works with: its trajectory's row (KArgs::x_lo_rows, x_hi_rows) or the shared ones, and the shared mask.
+// The bounds a lane works with: its trajectory's row (Limits::x_lo_rows, x_hi_rows) or the shared ones, and the shared mask.
 // A row's infinite bound in an unmasked slot gives c = -inf: max(0, lam + rho c) = 0 from lam = 0 on, so the multiplier
 // stays 0, phi and its derivatives are exactly 0 and max(0, c) = 0 -- the constraint is inactive, with no NaN (rho > 0,
 // and -inf is never multiplied by 0 or subtracted from itself).
 template <typename T, int NX> struct ALBounds {
     T lo[NX], hi[NX];
     int mask;
-    ILQR_DEV ALBounds(const KArgs<T>& a, int b) : mask(a.al_mask) {
+    ILQR_DEV ALBounds(const Limits<T>& a, size_t B, int b) : mask(a.al_mask) {
         const T* __restrict__ rl = a.x_lo_rows;
         const T* __restrict__ rh = a.x_hi_rows;
 #pragma unroll
         for (int i = 0; i < NX; ++i) {
-            lo[i] = rl ? rl[(size_t)i * a.B + b] : a.x_lo[i];
-            hi[i] = rl ? rh[(size_t)i * a.B + b] : a.x_hi[i];
+            lo[i] = rl ? rl[(size_t)i * B + b] : a.x_lo[i];
+            hi[i] = rl ? rh[(size_t)i * B + b] : a.x_hi[i];
         }
     }
 };
@@ -281,7 +290,7 @@ template <typename T> ILQR_DEV T al_pos(T v) { return v > T(0) ? v : T(0); }
 // lam_t of trajectory b; the constraints that do not exist read as 0
 template <typename T, int NX> ILQR_DEV void al_load_lam(const KArgs<T>& a, size_t B, int b, int t, T* lam) {
 #pragma unroll
-    for (int q = 0; q < 2 * NX; ++q) lam[q] = ((a.al_mask >> q) & 1) ? a.lam[((size_t)t * 2 * NX + q) * B + b] : T(0);
+    for (int q = 0; q < 2 * NX; ++q) lam[q] = ((a.lim.al_mask >> q) & 1) ? a.lam[((size_t)t * 2 * NX + q) * B + b] : T(0);
 }
 // sum of phi over the constraints of one point, in constraint order
 template <typename T, int NX> ILQR_DEV T al_phi(const ALBounds<T, NX>& a, const T* x, const T* lam, T rho) {
@@ -525,7 +534,7 @@ __global__ void __launch_bounds__(256) linearize_al_kernel(KArgs<T> a) {
 #pragma unroll
         for (int i = 0; i < NU; ++i) u[i] = T(0);
     }
-    const ALBounds<T, NX> xb(a, b);
+    const ALBounds<T, NX> xb(a.lim, a.B, b);
     T lam[2 * NX], rho = T(0);   // this point's multipliers and the trajectory's penalty (x_0 is given: none at t = 0)
     if (t >= 1) {
         al_load_lam<T, NX>(a, B, b, t, lam);
@@ -913,7 +922,7 @@ __global__ void __launch_bounds__(64) backward_box_kernel(KArgs<T> a) {
     load_terminal<T, NX>(a.term, B, b, Vx, Vxx);
     bool all_pd = true;
     T blo[NU], bhi[NU];   // this trajectory's limits
-    box_bounds<NU>(a, b, blo, bhi);
+    box_bounds<NU>(a.lim, a.B, b, blo, bhi);
     for (int t = a.N - 1; t >= 0; --t) {
         T tile[E], u[NU];
         load_expansion<E>(a.lin + ((size_t)t * E) * B + b, B, tile);
@@ -998,9 +1007,9 @@ ILQR_DEV void forward_body(const KArgs<T>& a) {
     T lam[NL], lam_n[NL];
     const T rho = AL ? a.rho[b] : T(0);
     T blo[BOX ? NU : 1], bhi[BOX ? NU : 1];   // BOX: this trajectory's control limits; AL: its state limits
-    if constexpr (BOX) box_bounds<NU>(a, b, blo, bhi);
-    struct NoBounds { ILQR_DEV NoBounds(const KArgs<T>&, int) {} };
-    const std::conditional_t<AL, ALBounds<T, NX>, NoBounds> xb(a, b);
+    if constexpr (BOX) box_bounds<NU>(a.lim, a.B, b, blo, bhi);
+    struct NoBounds { ILQR_DEV NoBounds(const Limits<T>&, size_t, int) {} };
+    const std::conditional_t<AL, ALBounds<T, NX>, NoBounds> xb(a.lim, a.B, b);
     for (int t = 0; t < N; ++t) {
         const int tn = (t + 1 < N) ? t + 1 : t;
         if constexpr (PREFETCH) {
@@ -1104,7 +1113,7 @@ ILQR_DEV void rollout_ring(const KArgs<T>& a, int b, int ai, bool in_range, bool
     constexpr int PF_CNT = (63 / (NLD + NST)) + 1 > ILQR_RING_PF_MAX ? ILQR_RING_PF_MAX : (63 / (NLD + NST)) + 1;
     // (the fp64 backward-Euler step -- Newton loop with an LU solve -- needs more registers of its own: one slot fewer)
     // (HET: the trajectory's row -- n_sys + n_x scalars -- lives in VGPRs beside the ring, which is that much shallower)
-    // (BOX, with or without HET: the limits are per-lane values -- a trajectory may have its own, KArgs::u_lo_rows -- where
+    // (BOX, with or without HET: the limits are per-lane values -- a trajectory may have its own, Limits::u_lo_rows -- where
     // the shared ones used to sit in SGPRs: 2 n_u scalars of VGPRs beside the ring.  Every BOX instantiation still fits at
     // its old depth except the fp64 Euler ones that also carry a HET row, which come out two registers short: one slot
     // fewer for those alone)
@@ -1132,7 +1141,7 @@ ILQR_DEV void rollout_ring(const KArgs<T>& a, int b, int ai, bool in_range, bool
     const T dt = a.dt;
     T lo[NU], hi[NU];   // (BOX: the limits in registers, for the same reason; the trajectory's own where rows are set)
     if constexpr (BOX) {
-        box_bounds<NU>(a, bb, lo, hi);   // (a dead lane reads trajectory 0's)
+        box_bounds<NU>(a.lim, a.B, bb, lo, hi);   // (a dead lane reads trajectory 0's)
     } else {
 #pragma unroll
         for (int j = 0; j < NU; ++j) lo[j] = hi[j] = T(0);
@@ -1467,14 +1476,14 @@ __global__ void __launch_bounds__(64) al_update_kernel(KArgs<T> a, ALArgs<T> s) 
         const T* Xb = a.X + vec_at(B, N + 1, NX, slot, 0, b);
         const T* Ub = a.U + vec_at(B, N, NU, slot, 0, b);
         const size_t sX = B * NX, sU = B * NU;
-        const ALBounds<T, NX> xb(a, b);
+        const ALBounds<T, NX> xb(a.lim, a.B, b);
         T v = T(0);
         for (int t = 1; t <= N; ++t) {
             T x[NX];
             vec_load<T, NX>(Xb + t * sX, x);
 #pragma unroll
             for (int q = 0; q < 2 * NX; ++q) {
-                if ((a.al_mask >> q) & 1) {
+                if ((a.lim.al_mask >> q) & 1) {
                     const T c = al_constraint<T, NX>(xb, x, q);
                     v = c > v ? c : v;
                 }
@@ -1509,7 +1518,7 @@ __global__ void __launch_bounds__(64) al_update_kernel(KArgs<T> a, ALArgs<T> s) 
 #pragma unroll
                 for (int q = 0; q < 2 * NX; ++q) {
                     lam[q] = T(0);
-                    if ((a.al_mask >> q) & 1) {
+                    if ((a.lim.al_mask >> q) & 1) {
                         T* l = s.lam + ((size_t)t * 2 * NX + q) * B + b;
                         lam[q] = al_pos(*l + rho * al_constraint<T, NX>(xb, x, q));
                         *l = lam[q];

@@ -34,14 +34,9 @@ template <typename T> struct PolicyArgs {
     const T* __restrict__ x0s;          // [n_x][L], or nullptr
     const T* __restrict__ w;            // [N][n_x][L], or nullptr
     const T* __restrict__ srows;        // [n_sys][L] derived plant constants of every sample (the SROWS instantiation)
-    // control limits (+-inf while none are set: the clamp then moves nothing) and state limits, shared or rows [.][B]
-    T u_lo[kBoxMaxU], u_hi[kBoxMaxU];
-    const T* __restrict__ u_lo_rows;
-    const T* __restrict__ u_hi_rows;
-    T x_lo[kALMaxX], x_hi[kALMaxX];
-    int al_mask;                        // 0: no state limits, the violation is 0
-    const T* __restrict__ x_lo_rows;
-    const T* __restrict__ x_hi_rows;
+    // control limits (+-inf while none are set: the clamp then moves nothing) and state limits (al_mask = 0 while none
+    // are set: the violation is 0), shared or rows [.][B]
+    Limits<T> lim;
     // outputs, sample-innermost; Xs / Us may be nullptr
     T* __restrict__ cost;               // [L]
     T* __restrict__ x_final;            // [n_x][L]
@@ -50,21 +45,6 @@ template <typename T> struct PolicyArgs {
     T* __restrict__ Xs;                 // [N+1][n_x][L]
     T* __restrict__ Us;                 // [N][n_u][L]
 };
-
-// The limits of a call in the argument block box_bounds and ALBounds read (only those fields; the rest stays zero and
-// folds away).
-template <typename T> ILQR_DEV KArgs<T> policy_limits(const PolicyArgs<T>& a) {
-    KArgs<T> k{};
-    k.B = a.B;
-#pragma unroll
-    for (int j = 0; j < kBoxMaxU; ++j) { k.u_lo[j] = a.u_lo[j]; k.u_hi[j] = a.u_hi[j]; }
-#pragma unroll
-    for (int i = 0; i < kALMaxX; ++i) { k.x_lo[i] = a.x_lo[i]; k.x_hi[i] = a.x_hi[i]; }
-    k.al_mask = a.al_mask;
-    k.u_lo_rows = a.u_lo_rows; k.u_hi_rows = a.u_hi_rows;
-    k.x_lo_rows = a.x_lo_rows; k.x_hi_rows = a.x_hi_rows;
-    return k;
-}
 
 // A wave-uniform address of memory the kernel never writes, in the constant address space: the compiler then reads it
 // with scalar loads whatever it can prove about the kernel's stores (an output pointer inside an argument struct does not
@@ -120,10 +100,9 @@ __global__ void __launch_bounds__(64) policy_rollout_kernel(PolicyArgs<T> a) {
 #pragma unroll
         for (int q = 0; q < NSYS; ++q) pp[q] = mr[q];
     }
-    const KArgs<T> lim = policy_limits(a);
     T blo[NU], bhi[NU];
-    box_bounds<NU>(lim, b, blo, bhi);
-    const ALBounds<T, NX> xb(lim, b);
+    box_bounds<NU>(a.lim, B, b, blo, bhi);
+    const ALBounds<T, NX> xb(a.lim, B, b);
 
     const int slot = a.cur_slot[b];
     const T* Xo = a.X + vec_at(B, N + 1, NX, slot, 0, b);

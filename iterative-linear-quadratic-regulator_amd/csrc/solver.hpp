@@ -236,11 +236,20 @@ template <typename T> struct BatchParams {
     }
 };
 
-// state limits (ilqr_set_state_limits): bounds shared by the batch, the outer loop's settings and per-trajectory state
-template <typename T> struct StateLimits {
-    bool on = false;
-    double lo[kALMaxX] = {0}, hi[kALMaxX] = {0};
-    int mask = 0;            // KArgs::al_mask
+// Bounds of one kind -- the controls' (SolverT::box) or the states' (StateLimits) -- shared by the batch or one row per
+// trajectory; SolverT::limits() packs the two into the kernels' Limits record
+constexpr int kMaxBound = kALMaxX > kBoxMaxU ? kALMaxX : kBoxMaxU;
+template <typename T> struct BoundSet {
+    bool on = false;         // limits of this kind are set: the route (BOX / AL kernels) is decided by this alone
+    bool rows_on = false;    // lo_rows / hi_rows hold; false: lo / hi hold for every trajectory
+    double lo[kMaxBound] = {0}, hi[kMaxBound] = {0};
+    int mask = 0;            // the finite bounds: bit j for hi[j], bit C + j for lo[j]; with rows the union over the batch
+                             // (Limits::al_mask; the controls' is not used)
+    DevBuf<T> lo_rows, hi_rows;   // [C][B] each, +-inf where a trajectory has no bound (ilqr_set_batch_limits)
+};
+
+// state limits (ilqr_set_state_limits): the bounds, the outer loop's settings and per-trajectory state
+template <typename T> struct StateLimits : BoundSet<T> {
     double ctol = 0, rho0 = 0, rho_factor = 0, rho_max = 0;
     int max_outer = 0;
     DevBuf<T> lam, rho, viol, cost_plain;
@@ -253,10 +262,6 @@ template <typename T> struct StateLimits {
     bool lam_shifted = false;
     DevBuf<int> status_log;     // [n_steps][B] status words of the last state-limited ilqr_mpc_run
     int status_steps = 0;
-    // per-trajectory bounds (ilqr_set_batch_limits): [n_x][B] each, +-inf where a trajectory has none; `mask` is then the
-    // union over the batch.  rows_on = false: lo / hi above hold for every trajectory
-    DevBuf<T> lo_rows, hi_rows;
-    bool rows_on = false;
     hipError_t alloc(size_t B, size_t N, size_t NX) {
         if (lam) return hipSuccess;
         hipError_t e;
@@ -294,12 +299,7 @@ template <typename T> class SolverT : public SolverBase {
     PhaseTimer timer;
     bool have_problem = false, have_rollout = false, mpc_ready = false;
     int iter_seq = 0;
-    // control limits (ilqr_set_control_limits): u_min <= u <= u_max for every control of every trajectory
-    bool box_on = false;
-    double box_lo[kBoxMaxU] = {0}, box_hi[kBoxMaxU] = {0};
-    // per-trajectory control limits (ilqr_set_batch_limits): [n_u][B] each; box_rows = false: box_lo / box_hi hold for all
-    DevBuf<T> u_lo_rows, u_hi_rows;
-    bool box_rows = false;
+    BoundSet<T> box;        // control limits (ilqr_set_control_limits, ilqr_set_batch_limits): u_min <= u <= u_max
     BatchParams<T> het;
     StateLimits<T> al;
     // ilqr_policy_rollout: per-sample inputs and outputs, sample-innermost; allocated at the first call that needs them and
@@ -404,6 +404,26 @@ template <typename T> class SolverT : public SolverBase {
         return ILQR_OK;
     }
 
+    // The limits as the kernels read them (KArgs::lim, PolicyArgs::lim).  Controls: the bounds while control limits are on,
+    // else +-inf -- the state-limited path always runs the box sweep and the clamped rollout, and the policy rollout always
+    // clamps: with +-inf bounds they move nothing.  States: bounds, mask and rows while state limits are on, else zeros
+    // and mask 0 (no constraint exists).
+    Limits<T> limits() const {
+        Limits<T> l{};
+        const T inf = std::numeric_limits<T>::infinity();
+        for (int j = 0; j < kBoxMaxU; ++j) {
+            l.u_lo[j] = box.on ? (T)box.lo[j] : -inf;
+            l.u_hi[j] = box.on ? (T)box.hi[j] : inf;
+        }
+        if (box.on && box.rows_on) { l.u_lo_rows = box.lo_rows; l.u_hi_rows = box.hi_rows; }
+        if (al.on) {
+            for (int i = 0; i < kALMaxX; ++i) { l.x_lo[i] = (T)al.lo[i]; l.x_hi[i] = (T)al.hi[i]; }
+            l.al_mask = al.mask;
+            if (al.rows_on) { l.x_lo_rows = al.lo_rows; l.x_hi_rows = al.hi_rows; }
+        }
+        return l;
+    }
+
     KArgs<T> kargs(const DeviceState<T>& s) const {
         KArgs<T> a{};
         a.B = B; a.N = N; a.n_slots = s.n_slots; a.integ = cfg.integrator; a.maxiter = cfg.maxiter; a.flags = cfg.flags;
@@ -413,34 +433,15 @@ template <typename T> class SolverT : public SolverBase {
         a.status = s.status; a.iters = s.iters; a.accepted = s.accepted; a.counters = s.counters; a.params = params;
         a.reset_slots = 0;
         a.probe = probe_on ? probe.p : nullptr;
-        for (int i = 0; i < kBoxMaxU; ++i) {
-            a.u_lo[i] = (T)box_lo[i];
-            a.u_hi[i] = (T)box_hi[i];
-        }
-        a.box = box_on ? 1 : 0;
-        a.u_lo_rows = box_on && box_rows ? u_lo_rows.p : nullptr;
-        a.u_hi_rows = box_on && box_rows ? u_hi_rows.p : nullptr;
+        a.box = box.on ? 1 : 0;
         a.het = het.on() ? 1 : 0;
         a.rows = het.on() ? het.rows.p : nullptr;
         a.plant_rows = het.on() ? (het.plant_set ? het.plant_rows.p : het.rows.p) : nullptr;
         if (al.on) {
-            if (!box_on) {
-                // the state-limited path always runs the box sweep and the clamped rollout: with +-inf bounds they move nothing
-                for (int i = 0; i < kBoxMaxU; ++i) {
-                    a.u_lo[i] = -std::numeric_limits<T>::infinity();
-                    a.u_hi[i] = std::numeric_limits<T>::infinity();
-                }
-            }
-            for (int i = 0; i < kALMaxX; ++i) {
-                a.x_lo[i] = (T)al.lo[i];
-                a.x_hi[i] = (T)al.hi[i];
-            }
-            a.al_mask = al.mask;
-            a.x_lo_rows = al.rows_on ? al.lo_rows.p : nullptr;
-            a.x_hi_rows = al.rows_on ? al.hi_rows.p : nullptr;
             a.lam = al.lam;
             a.rho = al.rho;
         }
+        a.lim = limits();
         return a;
     }
 
@@ -595,7 +596,7 @@ template <typename T> class SolverT : public SolverBase {
             case ILQR_X0: return down_tc(dst, st.x0, NX, 1);
             case ILQR_PLANT_X: return down_tc(dst, plant_x, NX, 1);
             case ILQR_LIN:
-                if (box_on || al.on) {   // control / state limits: the box sweep's expansion, in the generic layout
+                if (box.on || al.on) {   // control / state limits: the box sweep's expansion, in the generic layout
                     if (lin_stale || !st.box_lin_valid) {
                         if (int rl = do_linearize(st, true)) return rl;
                     }
@@ -633,7 +634,7 @@ template <typename T> class SolverT : public SolverBase {
         return check_launch();
     }
     // control limits: the generic expansion for the box sweep (ops.linearize_box); state limits: that of J_A
-    bool limits_on() const { return box_on || al.on; }
+    bool limits_on() const { return box.on || al.on; }
     // full = false: the sweep that follows may be the constant-matrix form, which reads the matrices at t = N-1 only
     int do_linearize(DeviceState<T>& s, bool full = false) {
         const bool limits = limits_on();
@@ -647,7 +648,7 @@ template <typename T> class SolverT : public SolverBase {
         KArgs<T> a = kargs(s);
         if (limits) { a.lin = s.box_lin; a.term = s.box_term; }
         a.lin_sparse = sparse ? 1 : 0;
-        const auto launch = al.on ? ops.linearize_al[cfg.integrator] : box_on ? ops.linearize_box[cfg.integrator] : ops.linearize[cfg.integrator];
+        const auto launch = al.on ? ops.linearize_al[cfg.integrator] : box.on ? ops.linearize_box[cfg.integrator] : ops.linearize[cfg.integrator];
         const int rc = timed(ILQR_PHASE_LINEARIZE, [&] { launch(a, stream); });
         s.slots_stale = limits || ops.canonical;   // the sweep that follows resets cur_slot (KArgs::reset_slots)
         s.lin_const = !limits && ops.const_lin;
@@ -688,7 +689,7 @@ template <typename T> class SolverT : public SolverBase {
         a.init_mode = init;     // head of a solve: every trajectory rolls out, counter slot 0 is cleared
         a.counter_idx = 0;
         for (int i = 0; i < n; ++i) a.alphas[i] = (T)alphas[i];
-        const auto launch = al.on ? ops.forward_al[cfg.integrator] : box_on ? ops.forward_box[cfg.integrator] : ops.forward[cfg.integrator];
+        const auto launch = al.on ? ops.forward_al[cfg.integrator] : box.on ? ops.forward_box[cfg.integrator] : ops.forward[cfg.integrator];
         return timed(ILQR_PHASE_FORWARD, [&] { launch(a, stream); });
     }
     int do_select(DeviceState<T>& s, const double* alphas, int n, bool last, bool init, int counter_idx) {
@@ -713,7 +714,7 @@ template <typename T> class SolverT : public SolverBase {
 
     bool fused_ok() const {
         static const bool off = getenv("ILQR_NO_FUSE") != nullptr;   // A/B switch, and bench.py's materialised leg
-        return !off && !al.on && (!box_on || ops.fused_box) && !(cfg.flags & ILQR_FLAG_NO_FUSE) && ops.fused[cfg.integrator] && cfg.mu == 0.0 && (int)trial_alphas.size() <= A &&
+        return !off && !al.on && (!box.on || ops.fused_box) && !(cfg.flags & ILQR_FLAG_NO_FUSE) && ops.fused[cfg.integrator] && cfg.mu == 0.0 && (int)trial_alphas.size() <= A &&
                (size_t)N * B * R * sizeof(T) <= kDescriptorMax;
     }
     // the persistent form (persistent.hpp): same conditions as the fused kernel, plus the ring rollout's 32-bit offsets
@@ -974,52 +975,8 @@ template <typename T> class SolverT : public SolverBase {
         al.mpc_mode = mode;
         return ILQR_OK;
     }
-    int set_state_limits(const double* x_min, const double* x_max, double ctol, double rho0, double rho_factor,
-                         double rho_max, int max_outer) override {
-        if (!x_min && !x_max) {
-            if (int rf = flush_select()) return rf;
-            if (al.on) lin_stale = true;      // the expansion in HBM is J_A's
-            al.on = false;
-            al.rows_on = false;
-            al.cost_valid = false;
-            return ILQR_OK;
-        }
-        if (!x_min || !x_max) { err = "set_state_limits: give both x_min and x_max, or neither"; return ILQR_ERR_INVALID_ARG; }
-        if (!ops.backward_box || !ops.linearize_al[cfg.integrator] || !ops.forward_al[cfg.integrator] || !ops.al_update ||
-            NX > kALMaxX || NU > kBoxMaxU) {
-            err = "set_state_limits: state limits are supported for the pendulum, UA double pendulum and double pendulum only";
-            return ILQR_ERR_UNSUPPORTED;
-        }
-        int mask = 0;
-        for (int i = 0; i < NX; ++i) {
-            if (std::isnan(x_min[i]) || std::isnan(x_max[i]) || x_min[i] > x_max[i]) {
-                err = "set_state_limits: x_min and x_max must not be NaN and x_min <= x_max";
-                return ILQR_ERR_INVALID_ARG;
-            }
-            if (!std::isinf(x_max[i])) mask |= 1 << i;          // an infinite bound is no constraint
-            if (!std::isinf(x_min[i])) mask |= 1 << (NX + i);
-        }
-        if (!(ctol > 0) || !(rho0 > 0) || !(rho_factor >= 1) || !(rho_max >= rho0) || max_outer < 1) {
-            err = "set_state_limits: need ctol > 0, rho0 > 0, rho_factor >= 1, rho_max >= rho0 and max_outer >= 1";
-            return ILQR_ERR_INVALID_ARG;
-        }
-        if (int rf = flush_select()) return rf;
-        if (int rb = ensure_box(st)) return rb;
-        ILQR_HIPCHK(al.alloc(B, N, NX));
-        for (int i = 0; i < kALMaxX; ++i) {
-            al.lo[i] = i < NX && !std::isinf(x_min[i]) ? x_min[i] : 0.0;
-            al.hi[i] = i < NX && !std::isinf(x_max[i]) ? x_max[i] : 0.0;
-        }
-        al.mask = mask;
-        al.rows_on = false;        // shared bounds replace rows
-        al.ctol = ctol; al.rho0 = rho0; al.rho_factor = rho_factor; al.rho_max = rho_max; al.max_outer = max_outer;
-        lin_stale = true;          // an expansion in HBM has no (or other) multiplier terms
-        al.on = true;
-        al.cost_valid = false;
-        return al_reset();
-    }
 
-    // ---- control limits -----------------------------------------------------------------
+    // ---- control and state limits ---------------------------------------------------------
     // the box sweep's generic expansion reuses `lin` / `term` when they are large enough (the DPP tiles: 48 >= E = 22 / 46,
     // 64 >= 58 scalars per (t, b); 20 >= n + n^2 terminal scalars), so limits cost no memory there
     int ensure_box(DeviceState<T>& s) {
@@ -1030,51 +987,124 @@ template <typename T> class SolverT : public SolverBase {
         s.box_term = s.box_term_own ? s.box_term_own.p : s.term.p;
         return ILQR_OK;
     }
-    int set_control_limits(const double* u_min, const double* u_max) override {
-        if (!u_min && !u_max) {
-            if (int rf = flush_select()) return rf;
-            if (box_on) lin_stale = true;     // the expansion in HBM is the box sweep's
-            box_on = false;
-            box_rows = false;
-            return ILQR_OK;
+    BoundSet<T>& bounds(bool ctrl) { return ctrl ? box : al; }
+    // this handle has the kernels of the control-limited (ctrl) or the state-limited route
+    bool limits_supported(bool ctrl) const {
+        if (!ops.backward_box || NU > kBoxMaxU) return false;
+        if (ctrl) return ops.linearize_box[cfg.integrator] && ops.forward_box[cfg.integrator];
+        return ops.linearize_al[cfg.integrator] && ops.forward_al[cfg.integrator] && ops.al_update && NX <= kALMaxX;
+    }
+    // `count` vectors of C bounds each: no NaN and lo <= hi in every entry; refuse_empty: also no hi = -inf and no lo = +inf,
+    // which leave no admissible value (as a state row they would make c = +inf, then lam, phi = inf and NaN).  The rows
+    // refuse them; the shared setters never have, and take such a bound as "no constraint".  *mask: the finite bounds
+    // (BoundSet::mask) -- an infinite bound is no constraint, and one finite for any vector makes the slot exist.
+    static bool check_bounds(const double* lo, const double* hi, size_t count, int C, bool refuse_empty, int* mask) {
+        *mask = 0;
+        for (size_t i = 0; i < count * C; ++i) {
+            if (std::isnan(lo[i]) || std::isnan(hi[i]) || lo[i] > hi[i]) return false;
+            if (refuse_empty && (hi[i] == -INFINITY || lo[i] == INFINITY)) return false;
+            if (!std::isinf(hi[i])) *mask |= 1 << (int)(i % C);
+            if (!std::isinf(lo[i])) *mask |= 1 << (C + (int)(i % C));
         }
-        if (!u_min || !u_max) { err = "set_control_limits: give both u_min and u_max, or neither"; return ILQR_ERR_INVALID_ARG; }
-        if (!ops.backward_box || !ops.linearize_box[cfg.integrator] || !ops.forward_box[cfg.integrator] || NU > kBoxMaxU) {
-            err = "set_control_limits: control limits are supported for the pendulum, UA double pendulum and double pendulum only";
-            return ILQR_ERR_UNSUPPORTED;
-        }
-        for (int i = 0; i < NU; ++i) {
-            if (std::isnan(u_min[i]) || std::isnan(u_max[i]) || u_min[i] > u_max[i]) {
-                err = "set_control_limits: u_min and u_max must not be NaN and u_min <= u_max";
-                return ILQR_ERR_INVALID_ARG;
-            }
-        }
+        return true;
+    }
+    // The checked bounds of one kind take effect and the kind is switched on.  rows: host lo, hi [B][C], uploaded
+    // batch-innermost in the handle's dtype; else C values each for every trajectory, which replace rows (the states' kept as
+    // 0 where infinite: their slot is masked out).
+    int apply_limits(bool ctrl, const double* lo, const double* hi, bool rows, int mask) {
+        BoundSet<T>& s = bounds(ctrl);
+        const int C = ctrl ? NU : NX;
         if (int rf = flush_select()) return rf;
         if (int rb = ensure_box(st)) return rb;
-        for (int i = 0; i < NU; ++i) { box_lo[i] = u_min[i]; box_hi[i] = u_max[i]; }
-        if (!box_on) lin_stale = true;        // the expansion in HBM is the unconstrained sweep's
-        box_on = true;
-        box_rows = false;                     // shared bounds replace rows
+        if (rows) {
+            if (!s.lo_rows) ILQR_HIPCHK(s.lo_rows.alloc((size_t)C * B));
+            if (!s.hi_rows) ILQR_HIPCHK(s.hi_rows.alloc((size_t)C * B));
+            std::vector<T> soa((size_t)2 * C * B);
+            for (int b = 0; b < B; ++b)
+                for (int q = 0; q < C; ++q) {
+                    soa[(size_t)q * B + b] = (T)lo[(size_t)b * C + q];
+                    soa[(size_t)(C + q) * B + b] = (T)hi[(size_t)b * C + q];
+                }
+            ILQR_HIPCHK(hipMemcpyAsync(s.lo_rows, soa.data(), (size_t)C * B * sizeof(T), hipMemcpyHostToDevice, stream));
+            ILQR_HIPCHK(hipMemcpyAsync(s.hi_rows, soa.data() + (size_t)C * B, (size_t)C * B * sizeof(T), hipMemcpyHostToDevice, stream));
+            ILQR_HIPCHK(hipStreamSynchronize(stream));
+        } else {
+            for (int i = 0; i < kMaxBound; ++i) {
+                s.lo[i] = i < C && (ctrl || !std::isinf(lo[i])) ? lo[i] : 0.0;
+                s.hi[i] = i < C && (ctrl || !std::isinf(hi[i])) ? hi[i] : 0.0;
+            }
+        }
+        s.mask = mask;
+        s.rows_on = rows;
+        if (ctrl) {
+            if (!box.on) lin_stale = true;    // the expansion in HBM is the unconstrained sweep's
+            box.on = true;
+            return ILQR_OK;
+        }
+        ILQR_HIPCHK(al.alloc(B, N, NX));
+        lin_stale = true;          // an expansion in HBM has no (or other) multiplier terms
+        al.on = true;
+        al.cost_valid = false;
+        return al_reset();
+    }
+    // limits of one kind off, shared and rows alike
+    int clear_limits(bool ctrl) {
+        BoundSet<T>& s = bounds(ctrl);
+        if (int rf = flush_select()) return rf;
+        if (s.on) lin_stale = true;       // the expansion in HBM is the box sweep's / J_A's
+        s.on = false;
+        s.rows_on = false;
+        if (!ctrl) al.cost_valid = false;
         return ILQR_OK;
     }
 
-    // ---- per-trajectory limits ----------------------------------------------------------
-    // which = ILQR_LIMITS_CONTROL: host lo, hi [B][n_u]; ILQR_LIMITS_STATE: [B][n_x].  Uploaded batch-innermost in the
-    // handle's dtype; they switch the limits of their kind on exactly as the shared setters do (the route is decided by
-    // box_on / al.on alone) and are dropped again by those setters.  NULL, NULL: the limits given as rows are removed.
+    int set_state_limits(const double* x_min, const double* x_max, double ctol, double rho0, double rho_factor,
+                         double rho_max, int max_outer) override {
+        if (!x_min && !x_max) return clear_limits(false);
+        if (!x_min || !x_max) { err = "set_state_limits: give both x_min and x_max, or neither"; return ILQR_ERR_INVALID_ARG; }
+        if (!limits_supported(false)) {
+            err = "set_state_limits: state limits are supported for the pendulum, UA double pendulum and double pendulum only";
+            return ILQR_ERR_UNSUPPORTED;
+        }
+        int mask;
+        if (!check_bounds(x_min, x_max, 1, NX, false, &mask)) {
+            err = "set_state_limits: x_min and x_max must not be NaN and x_min <= x_max";
+            return ILQR_ERR_INVALID_ARG;
+        }
+        if (!(ctol > 0) || !(rho0 > 0) || !(rho_factor >= 1) || !(rho_max >= rho0) || max_outer < 1) {
+            err = "set_state_limits: need ctol > 0, rho0 > 0, rho_factor >= 1, rho_max >= rho0 and max_outer >= 1";
+            return ILQR_ERR_INVALID_ARG;
+        }
+        al.ctol = ctol; al.rho0 = rho0; al.rho_factor = rho_factor; al.rho_max = rho_max; al.max_outer = max_outer;
+        return apply_limits(false, x_min, x_max, false, mask);
+    }
+    int set_control_limits(const double* u_min, const double* u_max) override {
+        if (!u_min && !u_max) return clear_limits(true);
+        if (!u_min || !u_max) { err = "set_control_limits: give both u_min and u_max, or neither"; return ILQR_ERR_INVALID_ARG; }
+        if (!limits_supported(true)) {
+            err = "set_control_limits: control limits are supported for the pendulum, UA double pendulum and double pendulum only";
+            return ILQR_ERR_UNSUPPORTED;
+        }
+        int mask;
+        if (!check_bounds(u_min, u_max, 1, NU, false, &mask)) {
+            err = "set_control_limits: u_min and u_max must not be NaN and u_min <= u_max";
+            return ILQR_ERR_INVALID_ARG;
+        }
+        return apply_limits(true, u_min, u_max, false, mask);
+    }
+    // per-trajectory limits.  which = ILQR_LIMITS_CONTROL: host lo, hi [B][n_u]; ILQR_LIMITS_STATE: [B][n_x].  They switch
+    // the limits of their kind on exactly as the shared setters do and are dropped again by those setters.  NULL, NULL: the
+    // limits given as rows are removed.
     int set_batch_limits(int which, const double* lo, const double* hi, int row_len) override {
         const bool ctrl = which == ILQR_LIMITS_CONTROL;
         if (!ctrl && which != ILQR_LIMITS_STATE) { err = "set_batch_limits: which must be ILQR_LIMITS_CONTROL or ILQR_LIMITS_STATE"; return ILQR_ERR_INVALID_ARG; }
         if (!lo && !hi) {
-            if (ctrl ? !box_rows : !al.rows_on) return ILQR_OK;      // no rows of that kind: shared limits stay as they are
-            return ctrl ? set_control_limits(nullptr, nullptr) : set_state_limits(nullptr, nullptr, 0, 0, 0, 0, 0);
+            if (!bounds(ctrl).rows_on) return ILQR_OK;      // no rows of that kind: shared limits stay as they are
+            return clear_limits(ctrl);
         }
         if (!lo || !hi) { err = "set_batch_limits: give both lo and hi, or neither"; return ILQR_ERR_INVALID_ARG; }
         const int C = ctrl ? NU : NX;
-        const bool have = ctrl ? (ops.backward_box && ops.linearize_box[cfg.integrator] && ops.forward_box[cfg.integrator] && NU <= kBoxMaxU)
-                               : (ops.backward_box && ops.linearize_al[cfg.integrator] && ops.forward_al[cfg.integrator] && ops.al_update &&
-                                  NX <= kALMaxX && NU <= kBoxMaxU);
-        if (!have) {
+        if (!limits_supported(ctrl)) {
             err = "set_batch_limits: limits are supported for the pendulum, UA double pendulum and double pendulum only";
             return ILQR_ERR_UNSUPPORTED;
         }
@@ -1083,54 +1113,38 @@ template <typename T> class SolverT : public SolverBase {
             err = "set_batch_limits: state rows use the options of ilqr_set_state_limits (ctol, rho0, ...): call it first";
             return ILQR_ERR_STATE;
         }
-        int mask = 0;
-        for (size_t i = 0; i < (size_t)B * C; ++i) {
-            // (hi = -inf or lo = +inf leaves no admissible value: as a state row it would make c = +inf, then lam, phi = inf and NaN)
-            if (std::isnan(lo[i]) || std::isnan(hi[i]) || lo[i] > hi[i] || hi[i] == -INFINITY || lo[i] == INFINITY) {
-                err = "set_batch_limits: lo and hi must not be NaN, lo <= hi in every entry, and no hi = -inf or lo = +inf";
-                return ILQR_ERR_INVALID_ARG;
-            }
-            if (!std::isinf(hi[i])) mask |= 1 << (int)(i % C);          // finite for any trajectory: the slot exists
-            if (!std::isinf(lo[i])) mask |= 1 << (C + (int)(i % C));
+        int mask;
+        if (!check_bounds(lo, hi, (size_t)B, C, true, &mask)) {
+            err = "set_batch_limits: lo and hi must not be NaN, lo <= hi in every entry, and no hi = -inf or lo = +inf";
+            return ILQR_ERR_INVALID_ARG;
         }
-        if (int rf = flush_select()) return rf;
-        if (int rb = ensure_box(st)) return rb;
-        DevBuf<T>& dlo = ctrl ? u_lo_rows : al.lo_rows;
-        DevBuf<T>& dhi = ctrl ? u_hi_rows : al.hi_rows;
-        if (!dlo) ILQR_HIPCHK(dlo.alloc((size_t)C * B));
-        if (!dhi) ILQR_HIPCHK(dhi.alloc((size_t)C * B));
-        std::vector<T> soa((size_t)2 * C * B);
-        for (int b = 0; b < B; ++b)
-            for (int q = 0; q < C; ++q) {
-                soa[(size_t)q * B + b] = (T)lo[(size_t)b * C + q];
-                soa[(size_t)(C + q) * B + b] = (T)hi[(size_t)b * C + q];
-            }
-        ILQR_HIPCHK(hipMemcpyAsync(dlo, soa.data(), (size_t)C * B * sizeof(T), hipMemcpyHostToDevice, stream));
-        ILQR_HIPCHK(hipMemcpyAsync(dhi, soa.data() + (size_t)C * B, (size_t)C * B * sizeof(T), hipMemcpyHostToDevice, stream));
-        ILQR_HIPCHK(hipStreamSynchronize(stream));
-        if (ctrl) {
-            if (!box_on) lin_stale = true;    // the expansion in HBM is the unconstrained sweep's
-            box_on = true;
-            box_rows = true;
-            return ILQR_OK;
-        }
-        ILQR_HIPCHK(al.alloc(B, N, NX));
-        al.mask = mask;
-        al.rows_on = true;
-        lin_stale = true;          // an expansion in HBM has no (or other) multiplier terms
-        al.on = true;
-        al.cost_valid = false;
-        return al_reset();
+        return apply_limits(ctrl, lo, hi, true, mask);
     }
 
     // ---- per-trajectory parameters ------------------------------------------------------
+    int n_sys_abi() const { return (int)het.abi_params.size() - (NX + 2 * NX * NX + NU * NU); }   // system parameters of the ABI block
+    // `count` source rows of `len` values each (per trajectory, or per sample of ilqr_policy_rollout), each spliced into the
+    // front of a copy of the block (src = nullptr: the block as it is) -> the first n_out device constants of each row, in the
+    // handle's dtype, row-innermost [n_out][count] at dev
+    int derive_rows(const double* src, int len, size_t count, int n_out, T* dev) {
+        std::vector<T> soa((size_t)n_out * count);
+        std::vector<double> blk = het.abi_params;
+        for (size_t r = 0; r < count; ++r) {
+            if (src) std::copy(src + r * len, src + (r + 1) * len, blk.begin());   // sys params, then x_target
+            const std::vector<double> d = build_device_params(cfg.system, NX, NU, blk.data());
+            for (int q = 0; q < n_out; ++q) soa[(size_t)q * count + r] = (T)d[q];
+        }
+        ILQR_HIPCHK(hipMemcpyAsync(dev, soa.data(), soa.size() * sizeof(T), hipMemcpyHostToDevice, stream));
+        ILQR_HIPCHK(hipStreamSynchronize(stream));
+        return ILQR_OK;
+    }
     // which = ILQR_BATCH_MODEL: host rows [B][n_sys_abi + n_x] (system parameters in the block's order, x_target);
     // ILQR_BATCH_PLANT: [B][n_sys_abi].  Every row is derived by build_device_params on a copy of the block with the row
     // spliced in, and uploaded batch-innermost.  A plant without model rows leaves the model at the block: its rows are
     // then the block's own, broadcast.
     int set_batch_params(int which, const double* host_rows, int row_len) override {
         if (which != ILQR_BATCH_MODEL && which != ILQR_BATCH_PLANT) { err = "set_batch_params: which must be ILQR_BATCH_MODEL or ILQR_BATCH_PLANT"; return ILQR_ERR_INVALID_ARG; }
-        const int ns = (int)het.abi_params.size() - (NX + 2 * NX * NX + NU * NU);   // system parameters of the ABI block
+        const int ns = n_sys_abi();
         const int nh = ops.n_sys_dev + NX;     // device row: derived constants, x_target
         if (host_rows) {
             if (!ops.het) {
@@ -1146,29 +1160,17 @@ template <typename T> class SolverT : public SolverBase {
         lin_stale = true;   // an expansion in HBM was taken at the old parameters
         ILQR_HIPCHK(het.alloc(which == ILQR_BATCH_PLANT && host_rows, nh, ops.n_sys_dev, B));
         // one derived row per trajectory: [nh][B] (model) or [n_sys][B] (plant)
-        auto upload = [&](T* dev, int n_out, const double* src, int len) -> int {
-            std::vector<T> soa((size_t)n_out * B);
-            std::vector<double> blk = het.abi_params;
-            for (int b = 0; b < B; ++b) {
-                if (src) std::copy(src + (size_t)b * len, src + (size_t)(b + 1) * len, blk.begin());   // sys params, then x_target
-                const std::vector<double> d = build_device_params(cfg.system, NX, NU, blk.data());
-                for (int q = 0; q < n_out; ++q) soa[(size_t)q * B + b] = (T)d[q];
-            }
-            ILQR_HIPCHK(hipMemcpyAsync(dev, soa.data(), soa.size() * sizeof(T), hipMemcpyHostToDevice, stream));
-            ILQR_HIPCHK(hipStreamSynchronize(stream));
-            return ILQR_OK;
-        };
         if (which == ILQR_BATCH_MODEL) {
             het.model_set = host_rows != nullptr;
-            if (host_rows) return upload(het.rows, nh, host_rows, row_len);
+            if (host_rows) return derive_rows(host_rows, row_len, B, nh, het.rows);
         } else {
             het.plant_set = host_rows != nullptr;
             if (host_rows) {
-                if (int ru = upload(het.plant_rows, ops.n_sys_dev, host_rows, row_len)) return ru;
+                if (int ru = derive_rows(host_rows, row_len, B, ops.n_sys_dev, het.plant_rows)) return ru;
             }
         }
         // a plant without model rows: the model's rows are the block's
-        if (het.plant_set && !het.model_set) return upload(het.rows, nh, nullptr, 0);
+        if (het.plant_set && !het.model_set) return derive_rows(nullptr, 0, B, nh, het.rows);
         return ILQR_OK;
     }
 
@@ -1197,7 +1199,7 @@ template <typename T> class SolverT : public SolverBase {
         }
         const size_t S = (size_t)d.n_samples, L = (size_t)B * S;
         if (L > (size_t)std::numeric_limits<int>::max()) { err = "policy_rollout: batch * n_samples must be < 2^31"; return ILQR_ERR_INVALID_ARG; }
-        const int ns = (int)het.abi_params.size() - (NX + 2 * NX * NX + NU * NU);   // system parameters of the ABI block
+        const int ns = n_sys_abi();
         if (d.plant_rows) {
             for (size_t i = 0; i < L * ns; ++i)
                 if (!std::isfinite(d.plant_rows[i])) { err = "policy_rollout: every plant_rows value must be finite"; return ILQR_ERR_INVALID_ARG; }
@@ -1222,19 +1224,8 @@ template <typename T> class SolverT : public SolverBase {
         };
         if (d.x0 && (rc = up(d.x0, pr_x0, 1))) return rc;
         if (d.w && (rc = up(d.w, pr_w, N))) return rc;
-        if (d.plant_rows) {
-            // derived in double by the formulas of the block's own constants, as the rows of ilqr_set_batch_params
-            const int nd = ops.n_sys_dev;
-            std::vector<T> soa((size_t)nd * L);
-            std::vector<double> blk = het.abi_params;
-            for (size_t l = 0; l < L; ++l) {
-                std::copy(d.plant_rows + l * ns, d.plant_rows + (l + 1) * ns, blk.begin());
-                const std::vector<double> dp = build_device_params(cfg.system, NX, NU, blk.data());
-                for (int q = 0; q < nd; ++q) soa[(size_t)q * L + l] = (T)dp[q];
-            }
-            ILQR_HIPCHK(hipMemcpyAsync(pr_rows, soa.data(), soa.size() * sizeof(T), hipMemcpyHostToDevice, stream));
-            ILQR_HIPCHK(hipStreamSynchronize(stream));
-        }
+        // derived in double by the formulas of the block's own constants, as the rows of ilqr_set_batch_params
+        if (d.plant_rows && (rc = derive_rows(d.plant_rows, ns, L, ops.n_sys_dev, pr_rows))) return rc;
         PolicyArgs<T> a{};
         a.B = B; a.S = d.n_samples; a.N = N; a.n_slots = st.n_slots;
         a.integ = d.integrator >= 0 ? d.integrator : cfg.plant_integrator >= 0 ? cfg.plant_integrator : cfg.integrator;
@@ -1246,18 +1237,7 @@ template <typename T> class SolverT : public SolverBase {
         a.x0s = d.x0 ? pr_x0.p : nullptr;
         a.w = d.w ? pr_w.p : nullptr;
         a.srows = d.plant_rows ? pr_rows.p : nullptr;
-        for (int j = 0; j < kBoxMaxU; ++j) {
-            a.u_lo[j] = box_on ? (T)box_lo[j] : -std::numeric_limits<T>::infinity();
-            a.u_hi[j] = box_on ? (T)box_hi[j] : std::numeric_limits<T>::infinity();
-        }
-        a.u_lo_rows = box_on && box_rows ? u_lo_rows.p : nullptr;
-        a.u_hi_rows = box_on && box_rows ? u_hi_rows.p : nullptr;
-        if (al.on) {
-            for (int i = 0; i < kALMaxX; ++i) { a.x_lo[i] = (T)al.lo[i]; a.x_hi[i] = (T)al.hi[i]; }
-            a.al_mask = al.mask;
-            a.x_lo_rows = al.rows_on ? al.lo_rows.p : nullptr;
-            a.x_hi_rows = al.rows_on ? al.hi_rows.p : nullptr;
-        }
+        a.lim = limits();
         a.cost = pr_sum; a.deviation = pr_sum + L; a.violation = pr_sum + 2 * L; a.x_final = pr_sum + 3 * L;
         a.Xs = d.X ? pr_X.p : nullptr;
         a.Us = d.U ? pr_U.p : nullptr;
@@ -1317,7 +1297,7 @@ template <typename T> class SolverT : public SolverBase {
     int backward_tensors(const void* lin, const void* term, void* Uff, void* K) override {
         if (al.on) return al_refuse("backward_tensors");
         if (!lin || !term) { err = "backward_tensors: NULL input"; return ILQR_ERR_INVALID_ARG; }
-        if (box_on) { err = "backward_tensors: the box QP needs the controls u_t, which an expansion does not carry (clear the limits)"; return ILQR_ERR_UNSUPPORTED; }
+        if (box.on) { err = "backward_tensors: the box QP needs the controls u_t, which an expansion does not carry (clear the limits)"; return ILQR_ERR_UNSUPPORTED; }
         int rc;
         if ((rc = prepare_fn())) return rc;
         if ((rc = up_lin(lin, fn.lin))) return rc;

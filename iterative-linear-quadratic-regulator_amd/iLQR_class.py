@@ -32,29 +32,35 @@ def horizon_steps(T, dt):
     return len(np.arange(0, T + dt, dt)) - 1
 
 
-def _limit_rows(names, values, n, B, prefix=""):
-    """Per-trajectory bounds: each of the two values a scalar, (n,) or (B, n) -> float64 (B, n) arrays, checked as the
-    shared bounds are (shape, NaN, lo > hi per entry)."""
+def _bounds(names, values, n, B=None, prefix=""):
+    """The two bounds, checked (shape, NaN, lo > hi per entry), as float64 arrays: (n,) shared by the batch (a scalar is
+    broadcast), or with B one row per trajectory, (B, n) (a scalar or (n,) is broadcast).  Rows also refuse hi = -inf and
+    lo = +inf; the shared bounds take them as "no constraint", as the library's own setters do."""
+    shape = (n,) if B is None else (B, n)
+    shapes = f"({n},)" if B is None else f"({n},) or ({B}, {n})"
     out = []
     for name, v in zip(names, values):
         a = np.asarray(v, dtype=np.float64)
         if a.ndim == 0:
-            a = np.full((B, n), float(a))
-        elif a.shape == (n,):
-            a = np.broadcast_to(a, (B, n))
-        if a.shape != (B, n):
-            raise ValueError(f"{prefix}{name} must be a scalar or have shape ({n},) or ({B}, {n}), but got {a.shape}")
+            a = np.full(shape, float(a))
+        elif B is not None and a.shape == (n,):
+            a = np.broadcast_to(a, shape)
+        if a.shape != shape:
+            raise ValueError(f"{prefix}{name} must be a scalar or have shape {shapes}, but got {a.shape}")
         if np.isnan(a).any():
             raise ValueError(f"{prefix}{name} must not contain NaN")
         out.append(np.ascontiguousarray(a))
-    if np.isneginf(out[1]).any() or np.isposinf(out[0]).any():
+    lo, hi = out
+    if B is not None and (np.isneginf(hi).any() or np.isposinf(lo).any()):
         raise ValueError(f"{prefix}{names[1]} must not be -inf and {names[0]} must not be +inf (no value meets such a bound)")
-    bad = np.argwhere(out[0] > out[1])
+    bad = np.argwhere(lo > hi)
+    if len(bad) and B is None:
+        raise ValueError(f"{prefix}{names[0]} must be <= {names[1]}, got {lo} > {hi}")
     if len(bad):
         b, j = (int(i) for i in bad[0])
-        raise ValueError(f"{prefix}{names[0]} must be <= {names[1]}, got {out[0][b, j]} > {out[1][b, j]} "
+        raise ValueError(f"{prefix}{names[0]} must be <= {names[1]}, got {lo[b, j]} > {hi[b, j]} "
                          f"(trajectory {b}, component {j})")
-    return out[0], out[1]
+    return lo, hi
 
 
 def control_limits(system, u_min, u_max, B=None):
@@ -68,22 +74,8 @@ def control_limits(system, u_min, u_max, B=None):
     if getattr(system, "SYSTEM_ID", None) not in _lib.BOX_SYSTEMS:
         raise ValueError(f"control limits are supported for the pendulum, UA double pendulum and double pendulum "
                          f"only, not for {type(system).__name__}")
-    n_u = system.n_u
-    if B is not None and (np.ndim(u_min) == 2 or np.ndim(u_max) == 2):
-        return _limit_rows(("u_min", "u_max"), (u_min, u_max), n_u, int(B))
-    out = []
-    for name, v in (("u_min", u_min), ("u_max", u_max)):
-        a = np.asarray(v, dtype=np.float64)
-        if a.ndim == 0:
-            a = np.full(n_u, float(a))
-        if a.shape != (n_u,):
-            raise ValueError(f"{name} must be a scalar or have shape ({n_u},), but got {a.shape}")
-        if np.isnan(a).any():
-            raise ValueError(f"{name} must not contain NaN")
-        out.append(np.ascontiguousarray(a))
-    if (out[0] > out[1]).any():
-        raise ValueError(f"u_min must be <= u_max, got {out[0]} > {out[1]}")
-    return out[0], out[1]
+    rows = B is not None and (np.ndim(u_min) == 2 or np.ndim(u_max) == 2)
+    return _bounds(("u_min", "u_max"), (u_min, u_max), system.n_u, int(B) if rows else None)
 
 
 def state_limits(system, x_min, x_max, options=None, B=None):
@@ -100,22 +92,8 @@ def state_limits(system, x_min, x_max, options=None, B=None):
     if getattr(system, "SYSTEM_ID", None) not in _lib.BOX_SYSTEMS:
         raise ValueError(f"state limits are supported for the pendulum, UA double pendulum and double pendulum "
                          f"only, not for {type(system).__name__}")
-    n = system.n_x
-    if B is not None and (np.ndim(x_min) == 2 or np.ndim(x_max) == 2):
-        out = list(_limit_rows(("x_min", "x_max"), (x_min, x_max), n, int(B), "state limits: "))
-    else:
-        out = []
-        for name, v in (("x_min", x_min), ("x_max", x_max)):
-            a = np.asarray(v, dtype=np.float64)
-            if a.ndim == 0:
-                a = np.full(n, float(a))
-            if a.shape != (n,):
-                raise ValueError(f"state limits: {name} must be a scalar or have shape ({n},), but got {a.shape}")
-            if np.isnan(a).any():
-                raise ValueError(f"state limits: {name} must not contain NaN")
-            out.append(np.ascontiguousarray(a))
-        if (out[0] > out[1]).any():
-            raise ValueError(f"state limits: x_min must be <= x_max, got {out[0]} > {out[1]}")
+    rows = B is not None and (np.ndim(x_min) == 2 or np.ndim(x_max) == 2)
+    out = _bounds(("x_min", "x_max"), (x_min, x_max), system.n_x, int(B) if rows else None, "state limits: ")
     opts = dict(_lib.STATE_LIMIT_DEFAULTS)
     unknown = sorted(set(options or {}) - set(opts))
     if unknown:
