@@ -16,7 +16,7 @@
  *    batch axis in front of the reference's own layout:
  *        x0   [B][n_x]            X  [B][n_x][N+1]      U    [B][n_u][N]
  *        U_ff [B][n_u][N]         K  [B][N][n_u][n_x]   cost [B]
- *    (ilqr_policy_rollout: a second batch axis [S], the samples of a trajectory, behind [B])
+ *    (ilqr_policy_rollout, ilqr_policy_monte_carlo: a second batch axis [S], the samples of a trajectory, behind [B])
  *  - the handle owns every device buffer and its stream; the caller owns every
  *    host pointer; no host pointer is retained after a call returns.
  *  - one handle <-> one device <-> one stream; a handle is not thread-safe,
@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define ILQR_ABI_VERSION 5   /* unchanged by ilqr_set_batch_limits and ilqr_policy_rollout: see the notes at those entries */
+#define ILQR_ABI_VERSION 5   /* unchanged by ilqr_set_batch_limits, ilqr_policy_rollout and ilqr_policy_monte_carlo: see the notes at those entries */
 
 typedef struct ilqr_solver_s* ilqr_handle;
 
@@ -423,6 +423,60 @@ typedef struct ilqr_policy_rollout_desc {
     void* U;                  /* [B][S][n_u][N] */
 } ilqr_policy_rollout_desc;
 int ilqr_policy_rollout(ilqr_handle h, const ilqr_policy_rollout_desc* d);
+
+/* ---- policy Monte Carlo: device-drawn noise and per-trajectory statistics (build extension) -----------------
+ * ilqr_policy_rollout with the perturbations drawn on the device and the answer reduced there: nothing crosses to the
+ * device but a seed and two rows of n_x standard deviations per trajectory, and what comes back is nine numbers per
+ * trajectory (every per-sample output is optional).  Everything ilqr_policy_rollout says about the policy, the clamp,
+ * the plant, cost, deviation and violation holds; only the source of x_0 and w differs.  Sample s of trajectory b:
+ *   x_0       = x_0[b] + x0_std[b] (.) z(b, s, 0, stream 1)      (the solver's x_0[b] itself when x0_std == NULL)
+ *   w_t       = w_std[b] (.) z(b, s, t, stream 0)   t = 0..N-1   (no disturbance when w_std == NULL)
+ * Each product is rounded to the handle's dtype before it is added (never fused with the add), so ilqr_policy_rollout
+ * called with the returned x0_out and w_out gives the same bits.  With x0_std == w_std == NULL the call computes exactly
+ * what ilqr_policy_rollout computes with x0 == w == NULL.
+ * Generator: Philox4x32-10 (Salmon et al., SC'11; multipliers 0xD2511F53, 0xCD9E8D57, key increments 0x9E3779B9,
+ * 0xBB67AE85) at counter = (s, first_trajectory + b, t, stream), key = (seed & 0xffffffff, seed >> 32): the stream of
+ * sample (b, s) depends neither on B nor on S, and a shard of a fleet draws the fleet's streams through
+ * first_trajectory.  One call gives r0..r3; state component i uses z_i (n_x <= 4), fp32 in both dtypes, converted to the
+ * handle's dtype before the multiply:
+ *   ILQR_NOISE_UNIFORM   k = r_i >> 9;  z_i = 0x1.bb67aep+0f * ((float)(2k + 1 - 2^23) * 2^-23)     (unit variance)
+ *   ILQR_NOISE_GAUSSIAN  pairs (r0, r1), (r2, r3):  u1 = (float)(2 (r_a >> 9) + 1) * 2^-24,  u2 = (float)(r_b >> 8) * 2^-24,
+ *                        rad = sqrt(-2 ln u1),  z_a = rad cos(2 pi u2),  z_b = rad sin(2 pi u2)
+ * (the hardware logarithm, root, sine and cosine: |z - exact| <= 2e-5).
+ * Statistics, on the device over the samples of b with a finite cost (sums in double, two passes, a fixed order):
+ *   stats[b]  = cost mean, cost std (population), cost min, cost max, deviation mean, deviation max, violation max
+ *   counts[b] = n_finite, n_violating (violation > violation_tol among the finite)
+ * With n_finite == 0 the seven statistics are NaN.
+ * Returns ILQR_ERR_UNSUPPORTED for ILQR_SYS_LINEAR and ILQR_SYS_CUSTOM, ILQR_ERR_STATE before ilqr_set_problem /
+ * ilqr_mpc_reset, ILQR_ERR_INVALID_ARG for a NULL handle or desc, a wrong struct_size, n_samples < 1, an unknown
+ * integrator or distribution, first_trajectory < 0, a negative or non-finite standard deviation, a negative or NaN
+ * violation_tol, a non-finite plant_rows entry, or every output NULL.  Synchronous; changes nothing another entry reads.
+ * ILQR_ABI_VERSION stays 5 with this entry, for the reasons given at ilqr_set_batch_limits: it is additive. */
+enum { ILQR_NOISE_GAUSSIAN = 0, ILQR_NOISE_UNIFORM = 1 };
+typedef struct ilqr_monte_carlo_desc {
+    uint32_t struct_size;     /* = sizeof(ilqr_monte_carlo_desc) */
+    int32_t n_samples;        /* S >= 1 */
+    int32_t integrator;       /* as ilqr_policy_rollout */
+    int32_t feedback;         /* as ilqr_policy_rollout */
+    int32_t distribution;     /* ILQR_NOISE_* */
+    int32_t first_trajectory; /* >= 0: global index of this handle's trajectory 0 */
+    uint64_t seed;
+    double violation_tol;     /* >= 0 */
+    const double* x0_std;     /* [B][n_x] >= 0, finite; or NULL */
+    const double* w_std;      /* [B][n_x] >= 0, finite; or NULL */
+    const double* plant_rows; /* [B][S][n_sys] as ilqr_policy_rollout, or NULL */
+    double* stats;            /* [B][7]            any output may be NULL */
+    int32_t* counts;          /* [B][2] */
+    void* cost;               /* per-sample outputs, handle dtype, layouts as ilqr_policy_rollout */
+    void* x_final;
+    void* deviation;
+    void* violation;
+    void* X;
+    void* U;
+    void* x0_out;             /* [B][S][n_x]     the initial states that were used */
+    void* w_out;              /* [B][S][N][n_x]  the disturbances that were added (zeros when w_std == NULL) */
+} ilqr_monte_carlo_desc;
+int ilqr_policy_monte_carlo(ilqr_handle h, const ilqr_monte_carlo_desc* d);
 
 /* ---- multi-GPU hook -------------------------------------------
  * Writes 4 doubles to DEVICE memory `dev_out4` on the handle's stream:

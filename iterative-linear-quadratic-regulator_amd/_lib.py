@@ -43,7 +43,7 @@ SYMBOLS = (
     "ilqr_flush", "ilqr_solve", "ilqr_backward_pass", "ilqr_backward_tensors", "ilqr_forward_pass", "ilqr_eval_points", "ilqr_mpc_reset",
     "ilqr_mpc_rearm", "ilqr_mpc_run", "ilqr_status_reduce", "ilqr_timing_enable", "ilqr_timing_reset", "ilqr_timing_get", "ilqr_algorithmic_bytes",
     "ilqr_set_control_limits", "ilqr_set_batch_params", "ilqr_set_state_limits", "ilqr_set_mpc_multipliers",
-    "ilqr_set_batch_limits", "ilqr_policy_rollout",
+    "ilqr_set_batch_limits", "ilqr_policy_rollout", "ilqr_policy_monte_carlo",
 )
 # ilqr_set_batch_params: which rows
 BATCH_MODEL, BATCH_PLANT = 0, 1
@@ -56,6 +56,11 @@ STATE_LIMIT_DEFAULTS = dict(ctol=1e-4, rho0=1.0, rho_factor=10.0, rho_max=1e8, m
 # ilqr_set_mpc_multipliers: what each state-limited MPC step's multipliers start from
 MPC_AL_OFF, MPC_AL_COLD, MPC_AL_WARM = 0, 1, 2
 MPC_MULTIPLIER_MODES = {None: MPC_AL_OFF, "cold": MPC_AL_COLD, "warm": MPC_AL_WARM}
+# ilqr_policy_monte_carlo: the distribution of the device-drawn noise, and the columns of its statistics
+NOISE_GAUSSIAN, NOISE_UNIFORM = 0, 1
+NOISE_DISTRIBUTIONS = {"gaussian": NOISE_GAUSSIAN, "uniform": NOISE_UNIFORM}
+MONTE_CARLO_STATS = ("cost_mean", "cost_std", "cost_min", "cost_max", "deviation_mean", "deviation_max", "violation_max")
+MONTE_CARLO_COUNTS = ("n_finite", "n_violating")
 
 
 class Config(C.Structure):
@@ -80,6 +85,20 @@ class PolicyRolloutDesc(C.Structure):
         ("x0", C.c_void_p), ("w", C.c_void_p), ("plant_rows", C.POINTER(C.c_double)),
         ("cost", C.c_void_p), ("x_final", C.c_void_p), ("deviation", C.c_void_p), ("violation", C.c_void_p),
         ("X", C.c_void_p), ("U", C.c_void_p),
+    ]
+
+
+class MonteCarloDesc(C.Structure):
+    """ilqr_monte_carlo_desc (include/ilqr_hip.h), field for field."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("n_samples", C.c_int32), ("integrator", C.c_int32), ("feedback", C.c_int32),
+        ("distribution", C.c_int32), ("first_trajectory", C.c_int32),
+        ("seed", C.c_uint64), ("violation_tol", C.c_double),
+        ("x0_std", C.POINTER(C.c_double)), ("w_std", C.POINTER(C.c_double)), ("plant_rows", C.POINTER(C.c_double)),
+        ("stats", C.POINTER(C.c_double)), ("counts", C.POINTER(C.c_int32)),
+        ("cost", C.c_void_p), ("x_final", C.c_void_p), ("deviation", C.c_void_p), ("violation", C.c_void_p),
+        ("X", C.c_void_p), ("U", C.c_void_p), ("x0_out", C.c_void_p), ("w_out", C.c_void_p),
     ]
 
 
@@ -151,6 +170,7 @@ def load():
     lib.ilqr_set_mpc_multipliers.argtypes = [vp, ci]
     lib.ilqr_set_batch_limits.argtypes = [vp, ci, vp, vp, ci]
     lib.ilqr_policy_rollout.argtypes = [vp, C.POINTER(PolicyRolloutDesc)]
+    lib.ilqr_policy_monte_carlo.argtypes = [vp, C.POINTER(MonteCarloDesc)]
     if lib.ilqr_abi_version() != ABI_VERSION:
         raise RuntimeError("libilqr_hip.so ABI version mismatch: rebuild the library")
     _lib = lib
@@ -459,6 +479,59 @@ class Handle:
         for k, a in out.items():
             setattr(d, k, _ptr(a))
         self._chk(self.lib.ilqr_policy_rollout(self.h, C.byref(d)))
+        return out
+
+    def policy_monte_carlo(self, n_samples, seed=0, x0_std=None, w_std=None, distribution=NOISE_GAUSSIAN, plant_rows=None,
+                           integrator=-1, feedback=True, violation_tol=0.0, first_trajectory=0, samples=False,
+                           trajectories=False, noise=False, statistics=True):
+        """policy_rollout with x_0 and the disturbance drawn on the device and per-trajectory statistics computed there
+        (include/ilqr_hip.h, ilqr_policy_monte_carlo).  x0_std, w_std (B, n_x) float64 or None, plant_rows (B, S, n_sys)
+        float64 or None.  Returns a dict: stats (B, 7) float64 and counts (B, 2) int32 (with statistics); cost, x_final,
+        deviation, violation (with samples); X, U (with trajectories); x0_out (B, S, n_x), w_out (B, S, N, n_x) (with
+        noise)."""
+        B, S, n, m, N = self.B, int(n_samples), self.n_x, self.n_u, self.N
+        Sa = max(S, 0)
+        d = MonteCarloDesc()
+        d.struct_size = C.sizeof(MonteCarloDesc)
+        d.n_samples, d.integrator, d.feedback = S, int(integrator), int(bool(feedback))
+        d.distribution, d.first_trajectory = int(distribution), int(first_trajectory)
+        d.seed, d.violation_tol = int(seed) & 0xFFFFFFFFFFFFFFFF, float(violation_tol)
+        keep = []
+
+        def rows(a, shape, what):
+            r = np.ascontiguousarray(a, dtype=np.float64)
+            if r.shape != shape:
+                raise ValueError(f"{what} must have shape {shape}, but got {r.shape}")
+            keep.append(r)
+            return r.ctypes.data_as(C.POINTER(C.c_double))
+
+        if x0_std is not None:
+            d.x0_std = rows(x0_std, (B, n), "x0_std")
+        if w_std is not None:
+            d.w_std = rows(w_std, (B, n), "w_std")
+        if plant_rows is not None:
+            r = np.ascontiguousarray(plant_rows, dtype=np.float64)
+            if r.ndim != 3 or r.shape[:2] != (B, S):
+                raise ValueError(f"plant rows must have shape ({B}, {S}, n_sys), but got {r.shape}")
+            keep.append(r)
+            d.plant_rows = r.ctypes.data_as(C.POINTER(C.c_double))
+        out = {}
+        if statistics:
+            out["stats"] = np.empty((B, 7), dtype=np.float64)
+            out["counts"] = np.empty((B, 2), dtype=np.int32)
+            d.stats = out["stats"].ctypes.data_as(C.POINTER(C.c_double))
+            d.counts = out["counts"].ctypes.data_as(C.POINTER(C.c_int32))
+        shapes = {}
+        if samples:
+            shapes.update(cost=(B, Sa), x_final=(B, Sa, n), deviation=(B, Sa), violation=(B, Sa))
+        if trajectories:
+            shapes.update(X=(B, Sa, n, N + 1), U=(B, Sa, m, N))
+        if noise:
+            shapes.update(x0_out=(B, Sa, n), w_out=(B, Sa, N, n))
+        for k, shape in shapes.items():
+            out[k] = np.empty(shape, dtype=self.np_dtype)
+            setattr(d, k, _ptr(out[k]))
+        self._chk(self.lib.ilqr_policy_monte_carlo(self.h, C.byref(d)))
         return out
 
     # ---- measurement ------------------------------------------------------------------------------

@@ -293,6 +293,19 @@ int ilqr_policy_rollout(ilqr_handle h, const ilqr_policy_rollout_desc* d) {
     }
     return h->impl->policy_rollout(*d);
 }
+int ilqr_policy_monte_carlo(ilqr_handle h, const ilqr_monte_carlo_desc* d) {
+    if (!h || !h->impl) return ILQR_ERR_INVALID_ARG;
+    const ilqr_config& c = h->impl->cfg;
+    if (c.system == ILQR_SYS_LINEAR || c.system == ILQR_SYS_CUSTOM) {
+        h->impl->err = "policy_monte_carlo: not supported for linear or user-defined systems";
+        return ILQR_ERR_UNSUPPORTED;
+    }
+    if (!d || d->struct_size != sizeof(ilqr_monte_carlo_desc)) {
+        h->impl->err = "policy_monte_carlo: desc is NULL or struct_size does not match this library's ilqr_monte_carlo_desc";
+        return ILQR_ERR_INVALID_ARG;
+    }
+    return h->impl->policy_monte_carlo(*d);
+}
 int ilqr_timing_enable(ilqr_handle h, int on) { ILQR_FWD(h, timing_enable(on)); }
 int ilqr_timing_reset(ilqr_handle h) { ILQR_FWD(h, timing_reset()); }
 int ilqr_timing_get(ilqr_handle h, double ms[ILQR_N_PHASES], int64_t launches[ILQR_N_PHASES]) {

@@ -115,6 +115,8 @@ template <typename T> struct Ops {
     void (*mpc_advance_al)(const MpcALArgs<T>&, hipStream_t) = nullptr;   // the epilogue of a state-limited MPC step
     // closed-loop policy rollouts (ilqr_policy_rollout, policy_rollout.hpp); null where they are not supported
     void (*policy)(const PolicyArgs<T>&, hipStream_t) = nullptr;
+    // the same with x_0 and w drawn on the device (ilqr_policy_monte_carlo): set wherever `policy` is
+    void (*policy_noise)(const PolicyArgs<T>&, const NoiseArgs<T>&, hipStream_t) = nullptr;
 };
 
 // linearize / forward are compiled once per integrator so the integrator switch folds away and each
@@ -262,6 +264,12 @@ template <typename T, typename Dyn> void launch_policy(const PolicyArgs<T>& a, h
     if (a.srows) ILQR_LAUNCH((policy_rollout_kernel<T, Dyn, true>), grid, block, 0, s, a);
     else ILQR_LAUNCH((policy_rollout_kernel<T, Dyn, false>), grid, block, 0, s, a);
 }
+// the NOISE instantiations of the same body (ilqr_policy_monte_carlo), same mapping
+template <typename T, typename Dyn> void launch_policy_noise(const PolicyArgs<T>& a, const NoiseArgs<T>& nz, hipStream_t s) {
+    const dim3 grid((a.S + 63) / 64, a.B), block(64);
+    if (a.srows) ILQR_LAUNCH((policy_noise_kernel<T, Dyn, true>), grid, block, 0, s, a, nz);
+    else ILQR_LAUNCH((policy_noise_kernel<T, Dyn, false>), grid, block, 0, s, a, nz);
+}
 
 template <typename T, typename Dyn, bool TILE, int INTEG> void set_integrator_ops(Ops<T>& o) {
     constexpr bool SMALL = all_integrators<Dyn>::value;
@@ -378,6 +386,7 @@ template <typename T, typename Dyn> Ops<T> make_ops() {
                             dim3((a.m.B + 63) / 64), dim3(64, kMpcChunks), 0, s, a);
         };
         o.policy = launch_policy<T, Dyn>;
+        o.policy_noise = launch_policy_noise<T, Dyn>;
     }
     o.eval = [](const EvalArgs<T>& a, hipStream_t s) {
         ILQR_LAUNCH((eval_points_kernel<T, Dyn>), dim3((a.npts + 63) / 64), dim3(64), 0, s, a);

@@ -1,5 +1,5 @@
 // policy_rollout.hpp -- closed-loop rollouts of the policy the handle holds: S perturbed samples per trajectory
-// (include/ilqr_hip.h, ilqr_policy_rollout).
+// (include/ilqr_hip.h, ilqr_policy_rollout; ilqr_policy_monte_carlo: the same rollout with x_0 and w drawn on the device).
 //
 // The nominal of trajectory b -- X_t, U_t and the gain record of its current slot -- is followed by S samples that differ
 // in their initial state, their plant constants and a disturbance added after every step:
@@ -72,8 +72,99 @@ template <typename T, int NH> struct PolicyCostParams {
     ILQR_DEV T operator[](int i) const { return i < NH ? row[i < NH ? i : 0] : block[i]; }
 };
 
-template <typename T, typename Dyn, bool SROWS>
-__global__ void __launch_bounds__(64) policy_rollout_kernel(PolicyArgs<T> a) {
+// ---- device-drawn noise (include/ilqr_hip.h, ilqr_policy_monte_carlo) ------------------------------------------------
+// The NOISE instantiations draw x_0 and w_t themselves: x_0[b][s] = x_0[b] + x0_std[b] (.) z(b, s, 0, stream 1),
+// w[b][s][t] = w_std[b] (.) z(b, s, t, stream 0), z from Philox4x32-10 at counter (s, first + b, t, stream) and key
+// (seed low, seed high): one call gives the step's four 32-bit words, component i takes z_i (n_x <= 4).  Nothing of it
+// depends on the state, so the draw of step t stands at the head of the step, beside the request for step t + 1's
+// nominal, and the scheduler runs it under the step's dependency chain.  Every product std * z is rounded to T on its
+// own (noise_mul below: never contracted with the add that follows), so a call of the plain kernel with the returned
+// x_0 / w computes the same bits.
+template <typename T> struct NoiseArgs {
+    unsigned k0, k1;                    // the key: seed & 0xffffffff, seed >> 32
+    unsigned first;                     // global index of this handle's trajectory 0
+    int dist;                           // ILQR_NOISE_GAUSSIAN / ILQR_NOISE_UNIFORM
+    const T* __restrict__ x0_std;       // [B][n_x], or nullptr: every sample starts at x0[b]
+    const T* __restrict__ w_std;        // [B][n_x], or nullptr: no disturbance
+    T* __restrict__ x0_out;             // [n_x][L] the initial states used, or nullptr
+    T* __restrict__ w_out;              // [N][n_x][L] the disturbances added, or nullptr
+};
+
+// Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11)
+ILQR_DEV void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned (&r)[4]) {
+    constexpr unsigned M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
+#pragma unroll
+    for (int round = 0; round < 10; ++round) {
+        // both halves of a product from one 64-bit multiply (v_mad_u64_u32); the form was picked by measurement against
+        // v_mul_hi_u32 + v_mul_lo_u32: DESIGN.md section 4
+        const unsigned long long p0 = (unsigned long long)M0 * c0, p1 = (unsigned long long)M1 * c2;
+        const unsigned hi0 = (unsigned)(p0 >> 32), lo0 = (unsigned)p0;
+        const unsigned hi1 = (unsigned)(p1 >> 32), lo1 = (unsigned)p1;
+        c0 = hi1 ^ c1 ^ k0;
+        c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1;
+        c3 = lo0;
+        k0 += W0;
+        k1 += W1;
+    }
+    r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
+}
+
+// std * z as a product of its own.  __fmul_rn / __dmul_rn are plain multiplications in this ROCm's headers: what keeps the
+// product from fusing with the add behind it is that contraction is off inside these functions (the pragma) and that the
+// library and the plugins are built with -ffp-contract=on (csrc/Makefile, systems/custom_sys.py), under which the
+// compiler contracts within one source expression only, never across a call.  A build with -ffp-contract=fast would be
+// free to fuse after inlining: the generated-equals-explicit test then fails.
+ILQR_DEV float noise_mul(float a, float b) {
+#pragma clang fp contract(off)
+    return __fmul_rn(a, b);
+}
+ILQR_DEV double noise_mul(double a, double b) {
+#pragma clang fp contract(off)
+    return __dmul_rn(a, b);
+}
+
+// z_0 .. z_{C-1} of one Philox call, fp32 in both precisions.
+// UNIFORM: k = r >> 9, z = sqrt(3) * ((2k + 1 - 2^23) * 2^-23): every step before the one multiply is exact.
+// GAUSSIAN: Box-Muller on the pairs (r0, r1), (r2, r3): u1 = (2 (r_a >> 9) + 1) * 2^-24 in [2^-24, 1 - 2^-24],
+// u2 = (r_b >> 8) * 2^-24, rad = sqrt(-2 ln u1), z_a = rad cos(2 pi u2), z_b = rad sin(2 pi u2).  The logarithm is
+// v_log_f32 (base 2, scaled by -2 ln 2), the root v_sqrt_f32, and v_cos_f32 / v_sin_f32 take u2 as it stands: their
+// argument is in revolutions.
+template <int C> ILQR_DEV void noise_z(int dist, const unsigned (&r)[4], float (&z)[C]) {
+    static_assert(C <= 4, "one Philox call serves at most four state components");
+    if (dist == ILQR_NOISE_UNIFORM) {
+#pragma unroll
+        for (int i = 0; i < C; ++i) {
+            const int k = (int)(r[i] >> 9);
+            z[i] = __fmul_rn(0x1.bb67aep+0f, (float)(2 * k + 1 - (1 << 23)) * 0x1p-23f);
+        }
+    } else {
+#pragma unroll
+        for (int p = 0; p < (C + 1) / 2; ++p) {
+            const float u1 = (float)(2u * (r[2 * p] >> 9) + 1u) * 0x1p-24f;
+            const float u2 = (float)(r[2 * p + 1] >> 8) * 0x1p-24f;
+            const float rad = __builtin_amdgcn_sqrtf(__fmul_rn(-0x1.62e430p+0f, __builtin_amdgcn_logf(u1)));   // -2 ln 2 * log2 u1
+            z[2 * p] = __fmul_rn(rad, __builtin_amdgcn_cosf(u2));
+            if (2 * p + 1 < C) z[2 * p + 1 < C ? 2 * p + 1 : 0] = __fmul_rn(rad, __builtin_amdgcn_sinf(u2));
+        }
+    }
+}
+
+// std[i] * z_i(b, s, t, stream), rounded to T
+template <typename T, int C>
+ILQR_DEV void noise_draw(const NoiseArgs<T>& nz, unsigned s, unsigned b, unsigned t, unsigned stream, const T (&sd)[C], T (&o)[C]) {
+    unsigned r[4];
+    philox4x32_10(s, nz.first + b, t, stream, nz.k0, nz.k1, r);
+    float z[C];
+    noise_z<C>(nz.dist, r, z);
+#pragma unroll
+    for (int i = 0; i < C; ++i) o[i] = noise_mul(sd[i], (T)z[i]);
+}
+
+// The rollout of one sample: the body of policy_rollout_kernel (NOISE = false: x_0 and w are the caller's arrays) and
+// of policy_noise_kernel (NOISE = true: drawn here)
+template <typename T, typename Dyn, bool SROWS, bool NOISE>
+ILQR_DEV void policy_rollout_body(const PolicyArgs<T>& a, const NoiseArgs<T>& nz) {
     constexpr int NX = Dyn::NX, NU = Dyn::NU, NSYS = Dyn::NSYS;
     constexpr int R = gain_record(NX, NU);
     using PL = ParamLayout<NSYS, NX, NU>;
@@ -113,6 +204,22 @@ __global__ void __launch_bounds__(64) policy_rollout_kernel(PolicyArgs<T> a) {
     T x[NX], u[NU];
 #pragma unroll
     for (int i = 0; i < NX; ++i) x[i] = a.x0s ? a.x0s[(size_t)i * L + l] : a.x0[(size_t)i * B + b];
+    T wsd[NX];       // w_std[b], wave-uniform
+    if constexpr (NOISE) {
+        if (nz.x0_std) {
+            T sd[NX], e[NX];
+            uniform_load<T, NX>(nz.x0_std + (size_t)b * NX, sd);
+            noise_draw<T, NX>(nz, (unsigned)s, (unsigned)b, 0u, 1u, sd, e);
+#pragma unroll
+            for (int i = 0; i < NX; ++i) x[i] += e[i];
+        }
+        if (nz.x0_out) {
+#pragma unroll
+            for (int i = 0; i < NX; ++i) nz.x0_out[(size_t)i * L + l] = x[i];
+        }
+        if (nz.w_std) uniform_load<T, NX>(nz.w_std + (size_t)b * NX, wsd);
+    }
+    const bool has_w = NOISE ? nz.w_std != nullptr : a.w != nullptr;
     T xo[NX], uo[NU], g[R], xo_n[NX], uo_n[NU], g_n[R];
     uniform_load<T, NX>(Xo, xo);
     uniform_load<T, NU>(Uo, uo);
@@ -125,7 +232,15 @@ __global__ void __launch_bounds__(64) policy_rollout_kernel(PolicyArgs<T> a) {
         uniform_load<T, NU>(Uo + (size_t)tn * sU, uo_n);
         uniform_load<T, R>(G + (size_t)tn * sG, g_n);
         T wt[NX];
-        if (a.w) {
+        if constexpr (NOISE) {
+            if (has_w) {
+                noise_draw<T, NX>(nz, (unsigned)s, (unsigned)b, (unsigned)t, 0u, wsd, wt);
+                if (nz.w_out) {
+#pragma unroll
+                    for (int i = 0; i < NX; ++i) nz.w_out[((size_t)t * NX + i) * L + l] = wt[i];
+                }
+            }
+        } else if (a.w) {
 #pragma unroll
             for (int i = 0; i < NX; ++i) wt[i] = a.w[((size_t)t * NX + i) * L + l];
         }
@@ -156,7 +271,7 @@ __global__ void __launch_bounds__(64) policy_rollout_kernel(PolicyArgs<T> a) {
         T xn[NX];
         Stepper<T, Dyn>::step(a.integ, pp, a.dt, x, u, xn);
 #pragma unroll
-        for (int i = 0; i < NX; ++i) x[i] = a.w ? xn[i] + wt[i] : xn[i];
+        for (int i = 0; i < NX; ++i) x[i] = has_w ? xn[i] + wt[i] : xn[i];
         // the violation of x_{t+1} (t + 1 = 1..N)
 #pragma unroll
         for (int q = 0; q < 2 * NX; ++q) {
@@ -184,6 +299,79 @@ __global__ void __launch_bounds__(64) policy_rollout_kernel(PolicyArgs<T> a) {
     a.cost[l] = cost;
     a.deviation[l] = dev;
     a.violation[l] = viol;
+}
+
+template <typename T, typename Dyn, bool SROWS>
+__global__ void __launch_bounds__(64) policy_rollout_kernel(PolicyArgs<T> a) {
+    policy_rollout_body<T, Dyn, SROWS, false>(a, NoiseArgs<T>{});
+}
+
+template <typename T, typename Dyn, bool SROWS>
+__global__ void __launch_bounds__(64) policy_noise_kernel(PolicyArgs<T> a, NoiseArgs<T> nz) {
+    policy_rollout_body<T, Dyn, SROWS, true>(a, nz);
+}
+
+// Per-trajectory statistics of a Monte Carlo call: one wave per trajectory over its contiguous [S] rows of the sample
+// summaries, over the samples with a finite cost.  Sums in double, two passes (mean, then squared deviations), each lane
+// over its stride of the row and then a butterfly over the wave: the order is fixed, no atomics.
+//   stats[b] = cost mean, std (population), min, max; deviation mean, max; violation max   (NaN when n_finite == 0)
+//   counts[b] = n_finite, n_violating (violation > tol among the finite)
+ILQR_DEV double wave_sum(double v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+ILQR_DEV double wave_max(double v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) { const double o = __shfl_xor(v, m, 64); v = o > v ? o : v; }
+    return v;
+}
+template <typename T>
+__global__ void __launch_bounds__(64) policy_stats_kernel(const T* __restrict__ cost, const T* __restrict__ deviation,
+                                                          const T* __restrict__ violation, int S, double tol,
+                                                          double* __restrict__ stats, int* __restrict__ counts) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const T* c = cost + (size_t)b * S;
+    const T* d = deviation + (size_t)b * S;
+    const T* v = violation + (size_t)b * S;
+    const double inf = __builtin_huge_val();
+    double n = 0, nv = 0, sc = 0, sd = 0, cmin = inf, cmax = -inf, dmax = -inf, vmax = -inf;
+    for (int s = lane; s < S; s += 64) {
+        const double ci = (double)c[s];
+        if (!(ci - ci == 0.0)) continue;       // NaN or an infinity
+        const double di = (double)d[s], vi = (double)v[s];
+        n += 1.0;
+        nv += vi > tol ? 1.0 : 0.0;
+        sc += ci;
+        sd += di;
+        cmin = ci < cmin ? ci : cmin;
+        cmax = ci > cmax ? ci : cmax;
+        dmax = di > dmax ? di : dmax;
+        vmax = vi > vmax ? vi : vmax;
+    }
+    n = wave_sum(n); nv = wave_sum(nv); sc = wave_sum(sc); sd = wave_sum(sd);
+    cmin = -wave_max(-cmin); cmax = wave_max(cmax); dmax = wave_max(dmax); vmax = wave_max(vmax);
+    const double mean = sc / n;
+    double ss = 0;
+    for (int s = lane; s < S; s += 64) {
+        const double ci = (double)c[s];
+        if (!(ci - ci == 0.0)) continue;
+        ss += (ci - mean) * (ci - mean);
+    }
+    ss = wave_sum(ss);
+    if (lane != 0) return;
+    const double nan = __builtin_nan("");
+    const bool any = n > 0.0;
+    double* o = stats + (size_t)b * 7;
+    o[0] = any ? mean : nan;
+    o[1] = any ? sqrt(ss / n) : nan;
+    o[2] = any ? cmin : nan;
+    o[3] = any ? cmax : nan;
+    o[4] = any ? sd / n : nan;
+    o[5] = any ? dmax : nan;
+    o[6] = any ? vmax : nan;
+    counts[2 * b] = (int)n;
+    counts[2 * b + 1] = (int)nv;
 }
 
 // dense[l][c][t] <- dev[t][c][l]: the sample trajectories in the ABI's (dim, time) layout behind the batch axes

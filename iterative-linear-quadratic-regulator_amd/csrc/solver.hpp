@@ -58,6 +58,7 @@ struct SolverBase {
     virtual int set_mpc_multipliers(int mode) = 0;
     virtual int set_batch_limits(int which, const double* lo, const double* hi, int row_len) = 0;
     virtual int policy_rollout(const ilqr_policy_rollout_desc& d) = 0;
+    virtual int policy_monte_carlo(const ilqr_monte_carlo_desc& d) = 0;
 };
 
 int system_dims(int system, int n_x, int n_u);  // 1 if (system, n_x, n_u) is a known combination
@@ -305,6 +306,11 @@ template <typename T> class SolverT : public SolverBase {
     // ilqr_policy_rollout: per-sample inputs and outputs, sample-innermost; allocated at the first call that needs them and
     // grown, never shrunk (pr_X / pr_U only by calls that ask for the sample trajectories)
     DevBuf<T> pr_x0, pr_w, pr_rows, pr_sum, pr_X, pr_U;
+    // ilqr_policy_monte_carlo: the standard deviations [2][B][n_x] and the per-trajectory statistics [B][7], [B][2]
+    DevBuf<T> pr_std;
+    std::vector<T> pr_std_host;
+    DevBuf<double> pr_stats;
+    DevBuf<int> pr_counts;
 
     // (the device buffers free themselves after this body: DevBuf)
     ~SolverT() override {
@@ -1186,35 +1192,71 @@ template <typename T> class SolverT : public SolverBase {
     // S samples per trajectory around the nominal (X, U, K of the current slots) the handle holds.  Reads the solver state
     // and writes only the pr_* buffers and `staging`: nothing another entry reads changes.
     int policy_rollout(const ilqr_policy_rollout_desc& d) override {
+        PolicyCall c{"policy_rollout", d.n_samples, d.integrator, d.feedback, d.x0, d.w, d.plant_rows,
+                     d.cost, d.x_final, d.deviation, d.violation, d.X, d.U};
+        return policy_call(c, nullptr);
+    }
+    // The same rollout with x_0 and w drawn on the device (policy_noise_kernel) and the per-trajectory statistics of its
+    // sample summaries (policy_stats_kernel).  What crosses to the device is the seed and two [B][n_x] rows of standard
+    // deviations; pr_w is touched only when the disturbances are asked back.  Only what the noise and the statistics add is
+    // checked here: policy_call refuses the rest (no such kernels, no problem set, n_samples, integrator, plant_rows).
+    int policy_monte_carlo(const ilqr_monte_carlo_desc& d) override {
+        const char* who = "policy_monte_carlo";
+        auto bad = [&](const char* what) { err = std::string(who) + ": " + what; return ILQR_ERR_INVALID_ARG; };
+        if (d.distribution != ILQR_NOISE_GAUSSIAN && d.distribution != ILQR_NOISE_UNIFORM) return bad("unknown distribution");
+        if (d.first_trajectory < 0) return bad("first_trajectory must be >= 0");
+        if (!(d.violation_tol >= 0.0)) return bad("violation_tol must be >= 0 (and not NaN)");
+        for (const double* sd : {d.x0_std, d.w_std}) {
+            for (size_t i = 0; sd && i < (size_t)B * NX; ++i)
+                if (!std::isfinite(sd[i]) || sd[i] < 0.0) return bad("every standard deviation must be finite and >= 0");
+        }
+        if (!d.stats && !d.counts && !d.cost && !d.x_final && !d.deviation && !d.violation && !d.X && !d.U && !d.x0_out && !d.w_out)
+            return bad("every output is NULL");
+        PolicyCall c{who, d.n_samples, d.integrator, d.feedback, nullptr, nullptr, d.plant_rows,
+                     d.cost, d.x_final, d.deviation, d.violation, d.X, d.U};
+        return policy_call(c, &d);
+    }
+    // what both entries ask of the rollout (the host pointers of ilqr_policy_rollout_desc)
+    struct PolicyCall {
+        const char* who;
+        int n_samples, integrator, feedback;
+        const void *x0, *w;
+        const double* plant_rows;
+        void *cost, *x_final, *deviation, *violation, *X, *U;
+    };
+    int policy_call(const PolicyCall& d, const ilqr_monte_carlo_desc* mc) {
+        const std::string who = d.who;
         if (!ops.policy) {
-            err = "policy_rollout: supported for the pendulum, UA double pendulum and double pendulum only";
+            err = who + ": supported for the pendulum, UA double pendulum and double pendulum only";
             return ILQR_ERR_UNSUPPORTED;
         }
-        if (!have_problem) { err = "policy_rollout before set_problem / mpc_reset"; return ILQR_ERR_STATE; }
-        if (d.n_samples < 1) { err = "policy_rollout: n_samples must be >= 1"; return ILQR_ERR_INVALID_ARG; }
-        if (d.integrator > ILQR_INT_DISCRETE) { err = "policy_rollout: unknown integrator"; return ILQR_ERR_INVALID_ARG; }
-        if (!d.cost && !d.x_final && !d.deviation && !d.violation && !d.X && !d.U) {
-            err = "policy_rollout: every output is NULL";
+        if (!have_problem) { err = who + " before set_problem / mpc_reset"; return ILQR_ERR_STATE; }
+        if (d.n_samples < 1) { err = who + ": n_samples must be >= 1"; return ILQR_ERR_INVALID_ARG; }
+        if (d.integrator > ILQR_INT_DISCRETE) { err = who + ": unknown integrator"; return ILQR_ERR_INVALID_ARG; }
+        if (!mc && !d.cost && !d.x_final && !d.deviation && !d.violation && !d.X && !d.U) {
+            err = who + ": every output is NULL";
             return ILQR_ERR_INVALID_ARG;
         }
         const size_t S = (size_t)d.n_samples, L = (size_t)B * S;
-        if (L > (size_t)std::numeric_limits<int>::max()) { err = "policy_rollout: batch * n_samples must be < 2^31"; return ILQR_ERR_INVALID_ARG; }
+        if (L > (size_t)std::numeric_limits<int>::max()) { err = who + ": batch * n_samples must be < 2^31"; return ILQR_ERR_INVALID_ARG; }
         const int ns = n_sys_abi();
         if (d.plant_rows) {
             for (size_t i = 0; i < L * ns; ++i)
-                if (!std::isfinite(d.plant_rows[i])) { err = "policy_rollout: every plant_rows value must be finite"; return ILQR_ERR_INVALID_ARG; }
+                if (!std::isfinite(d.plant_rows[i])) { err = who + ": every plant_rows value must be finite"; return ILQR_ERR_INVALID_ARG; }
         }
         int rc;
         if ((rc = flush_select())) return rc;
         if ((rc = fix_slots(st))) return rc;
         const size_t nX = L * NX * (size_t)(N + 1), nU = L * NU * (size_t)N, nW = L * NX * (size_t)N;
+        // the disturbances a Monte Carlo call was asked to return (none are drawn without w_std: those are zeros)
+        const bool w_back = mc && mc->w_out && mc->w_std;
         if ((rc = grow(pr_sum, L * (size_t)(3 + NX)))) return rc;
-        if (d.x0 && (rc = grow(pr_x0, L * NX))) return rc;
-        if (d.w && (rc = grow(pr_w, nW))) return rc;
+        if ((d.x0 || (mc && mc->x0_out)) && (rc = grow(pr_x0, L * NX))) return rc;
+        if ((d.w || w_back) && (rc = grow(pr_w, nW))) return rc;
         if (d.plant_rows && (rc = grow(pr_rows, L * (size_t)ops.n_sys_dev))) return rc;
         if (d.X && (rc = grow(pr_X, nX))) return rc;
         if (d.U && (rc = grow(pr_U, nU))) return rc;
-        if ((rc = grow(staging, std::max({L * NX, d.w ? nW : (size_t)0, d.X ? nX : (size_t)0, d.U ? nU : (size_t)0})))) return rc;
+        if ((rc = grow(staging, std::max({L * NX, (d.w || w_back) ? nW : (size_t)0, d.X ? nX : (size_t)0, d.U ? nU : (size_t)0})))) return rc;
         const int Li = (int)L;
         // host [B][S][c] / [B][S][N][c] -> [c][L] / [N][c][L]: layout_tc_kernel with the samples as its batch axis
         auto up = [&](const void* host, T* dev, int Tn) {
@@ -1241,18 +1283,50 @@ template <typename T> class SolverT : public SolverBase {
         a.cost = pr_sum; a.deviation = pr_sum + L; a.violation = pr_sum + 2 * L; a.x_final = pr_sum + 3 * L;
         a.Xs = d.X ? pr_X.p : nullptr;
         a.Us = d.U ? pr_U.p : nullptr;
-        if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.policy(a, stream); }))) return rc;
+        if (mc) {
+            // the standard deviations in the handle's dtype, [2][B][n_x] (x0_std, w_std), and the statistics
+            const size_t nsd = (size_t)B * NX;
+            if ((rc = grow(pr_std, 2 * nsd)) || (rc = grow(pr_stats, (size_t)B * 7)) || (rc = grow(pr_counts, (size_t)B * 2))) return rc;
+            // (pr_std_host outlives the copy: the call ends synchronised before the next one can write it again)
+            pr_std_host.assign(2 * nsd, T(0));
+            for (size_t i = 0; i < nsd; ++i) {
+                if (mc->x0_std) pr_std_host[i] = (T)mc->x0_std[i];
+                if (mc->w_std) pr_std_host[nsd + i] = (T)mc->w_std[i];
+            }
+            ILQR_HIPCHK(hipMemcpyAsync(pr_std.p, pr_std_host.data(), 2 * nsd * sizeof(T), hipMemcpyHostToDevice, stream));
+            NoiseArgs<T> nz{};
+            nz.k0 = (unsigned)(mc->seed & 0xffffffffull); nz.k1 = (unsigned)(mc->seed >> 32);
+            nz.first = (unsigned)mc->first_trajectory;
+            nz.dist = mc->distribution;
+            nz.x0_std = mc->x0_std ? pr_std.p : nullptr;
+            nz.w_std = mc->w_std ? pr_std.p + nsd : nullptr;
+            nz.x0_out = mc->x0_out ? pr_x0.p : nullptr;
+            nz.w_out = w_back ? pr_w.p : nullptr;
+            if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.policy_noise(a, nz, stream); }))) return rc;
+            if (mc->stats || mc->counts) {
+                hipLaunchKernelGGL(policy_stats_kernel<T>, dim3(B), dim3(64), 0, stream, (const T*)a.cost, (const T*)a.deviation,
+                                   (const T*)a.violation, d.n_samples, mc->violation_tol, pr_stats.p, pr_counts.p);
+                if (mc->stats) ILQR_HIPCHK(hipMemcpyAsync(mc->stats, pr_stats.p, (size_t)B * 7 * sizeof(double), hipMemcpyDeviceToHost, stream));
+                if (mc->counts) ILQR_HIPCHK(hipMemcpyAsync(mc->counts, pr_counts.p, (size_t)B * 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
+            }
+        } else {
+            if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.policy(a, stream); }))) return rc;
+        }
         auto fetch = [&](void* host, const T* dev) -> int {
             if (host) ILQR_HIPCHK(hipMemcpyAsync(host, dev, L * sizeof(T), hipMemcpyDeviceToHost, stream));
             return ILQR_OK;
         };
         if ((rc = fetch(d.cost, a.cost)) || (rc = fetch(d.deviation, a.deviation)) || (rc = fetch(d.violation, a.violation))) return rc;
-        if (d.x_final) {
-            rc = stage_down(d.x_final, L * NX, [&](dim3 g_, dim3 b_) {
-                hipLaunchKernelGGL((layout_tc_kernel<T, false>), g_, b_, 0, stream, staging.p, (const T*)a.x_final, Li, NX, 1);
+        // [t][c][L] -> host [B][S][t][c]
+        auto down_tcl = [&](void* host, const T* dev, int Tn) {
+            return stage_down(host, L * NX * (size_t)Tn, [&](dim3 g_, dim3 b_) {
+                hipLaunchKernelGGL((layout_tc_kernel<T, false>), g_, b_, 0, stream, staging.p, dev, Li, NX, Tn);
             });
-            if (rc) return rc;
-        }
+        };
+        if (d.x_final && (rc = down_tcl(d.x_final, a.x_final, 1))) return rc;
+        if (mc && mc->x0_out && (rc = down_tcl(mc->x0_out, pr_x0, 1))) return rc;
+        if (w_back && (rc = down_tcl(mc->w_out, pr_w, N))) return rc;
+        if (mc && mc->w_out && !w_back) std::memset(mc->w_out, 0, nW * sizeof(T));
         // [t][c][L] -> host [B][S][c][t]
         auto down_traj = [&](void* host, const T* dev, int C, int Tn) {
             return stage_down(host, L * C * (size_t)Tn, [&](dim3 g_, dim3 b_) {

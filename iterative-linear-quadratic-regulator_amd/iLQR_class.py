@@ -220,6 +220,53 @@ def policy_rollout_args(system, N, B, batched, n_samples, x_0=None, disturbance=
     return S, x0, w, rows, code
 
 
+PolicyMonteCarlo = namedtuple(
+    "PolicyMonteCarlo", _lib.MONTE_CARLO_STATS + _lib.MONTE_CARLO_COUNTS +
+    ("cost", "x_final", "deviation", "violation", "X", "U", "x_0", "disturbance"), defaults=(None,) * 8)
+PolicyMonteCarlo.__doc__ = """Result of iLQR.policy_monte_carlo.  Per trajectory ([B] each, scalars on a single solver), over
+the samples with a finite cost: cost_mean, cost_std (population), cost_min, cost_max, deviation_mean, deviation_max,
+violation_max (float64, NaN when n_finite is 0), n_finite, n_violating (int).  With samples=True cost, deviation, violation
+([B,] S) and x_final ([B,] S, n_x); with trajectories=True X ([B,] S, n_x, N + 1) and U ([B,] S, n_u, N); with noise=True
+x_0 ([B,] S, n_x) and disturbance ([B,] S, N, n_x) as they were drawn; else None."""
+
+
+def policy_monte_carlo_args(system, N, B, batched, n_samples, seed=0, x_0_std=None, disturbance_std=None,
+                            distribution="gaussian", plant_params=None, integrator=None, violation_tol=0.0,
+                            first_trajectory=0):
+    """Validated arguments of ``ilqr_policy_monte_carlo`` as (S, seed, x0_std, w_std, distribution code, plant_rows,
+    integrator code, violation_tol, first_trajectory): the standard deviations (B, n_x) float64 or None -- (n_x,) is
+    broadcast over the batch --, plant_rows and the integrator as policy_rollout_args gives them.  Raises ValueError for
+    what policy_rollout_args refuses, a seed outside [0, 2^64), a standard deviation of a wrong shape, negative or not
+    finite, an unknown distribution, a negative or NaN violation_tol, or a negative first_trajectory.  Pure host code
+    (no GPU)."""
+    S, _, _, rows, code = policy_rollout_args(system, N, B, batched, n_samples, None, None, plant_params, integrator)
+    B, n = int(B), system.n_x
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+        raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
+
+    def std(name, v):
+        if v is None:
+            return None
+        a = np.asarray(v, dtype=np.float64)
+        if a.shape == (n,):
+            a = np.broadcast_to(a, (B, n))
+        if a.shape != (B, n):
+            raise ValueError(f"{name} must have shape ({n},) or ({B}, {n}), but got {a.shape}")
+        if not np.isfinite(a).all() or (a < 0).any():
+            raise ValueError(f"{name} must be finite and >= 0")
+        return np.ascontiguousarray(a)
+
+    x0_std, w_std = std("x_0_std", x_0_std), std("disturbance_std", disturbance_std)
+    if not isinstance(distribution, str) or distribution not in _lib.NOISE_DISTRIBUTIONS:
+        raise ValueError(f"Unknown distribution: {distribution!r}. Supported: 'gaussian', 'uniform'.")
+    tol = float(violation_tol)
+    if not tol >= 0.0:
+        raise ValueError(f"violation_tol must be >= 0, got {violation_tol!r}")
+    if isinstance(first_trajectory, bool) or int(first_trajectory) != first_trajectory or not 0 <= int(first_trajectory) < 2 ** 31:
+        raise ValueError(f"first_trajectory must be an integer >= 0, got {first_trajectory!r}")
+    return S, int(seed), x0_std, w_std, _lib.NOISE_DISTRIBUTIONS[distribution], rows, code, tol, int(first_trajectory)
+
+
 class iLQR:
     def __init__(self, system: System, T=None, x_0=None, U_init=None, tol=1e-5, maxiter=100,
                  alpha_factor=0.5, min_alpha=1e-8, verbose=True, *, N=None, n_alpha=None, n_trials=10,
@@ -520,6 +567,31 @@ class iLQR:
                                                    plant_params, integrator)
         out = self._h.policy_rollout(S, x0, w, rows, code, feedback, trajectories)
         return PolicyRollout(**{k: self._out(v) for k, v in out.items()})
+
+    def policy_monte_carlo(self, n_samples, seed=0, x_0_std=None, disturbance_std=None, distribution="gaussian",
+                           plant_params=None, integrator=None, feedback=True, violation_tol=0.0, first_trajectory=0,
+                           samples=False, trajectories=False, noise=False):
+        """policy_rollout under noise drawn on the device, answered per trajectory (include/ilqr_hip.h,
+        ilqr_policy_monte_carlo): sample s of trajectory b starts at x_0[b] + x_0_std[b] * z and receives
+        disturbance_std[b] * z after every step, z of unit variance ("gaussian" or "uniform") from Philox4x32-10 at
+        (seed, first_trajectory + b, s, t): a sample's stream depends neither on the batch nor on n_samples.  The standard
+        deviations are ([B,] n_x), None for no perturbation of that kind; plant_params, integrator and feedback as
+        policy_rollout.  Returns a PolicyMonteCarlo: statistics of cost, deviation and violation over the samples with a
+        finite cost, n_finite, and n_violating (violation > violation_tol); per-sample arrays with samples=True, X and U
+        with trajectories=True, the drawn x_0 and disturbance with noise=True (policy_rollout with those two gives the
+        same bits).  Nothing in the solver changes."""
+        S, seed, x0_std, w_std, dist, rows, code, tol, first = policy_monte_carlo_args(
+            self.system, self.N, self.B, self.batched, n_samples, seed, x_0_std, disturbance_std, distribution, plant_params,
+            integrator, violation_tol, first_trajectory)
+        out = self._h.policy_monte_carlo(S, seed, x0_std, w_std, dist, rows, code, feedback, tol, first, samples,
+                                         trajectories, noise)
+        stats, counts = out.pop("stats"), out.pop("counts")
+        pick = (lambda a: a) if self.batched else (lambda a: a[0])
+        rec = {k: pick(stats[:, i].copy()) for i, k in enumerate(_lib.MONTE_CARLO_STATS)}
+        rec.update({k: pick(counts[:, i].copy()) for i, k in enumerate(_lib.MONTE_CARLO_COUNTS)})
+        names = {"x0_out": "x_0", "w_out": "disturbance"}
+        rec.update({names.get(k, k): self._out(v) for k, v in out.items()})
+        return PolicyMonteCarlo(**rec)
 
     # ---- MPC (run_iLQR_MPC.py:116-143), device-resident ---------------------------------------------
     def mpc_reset(self, x_0, U_init, keep_state=False):

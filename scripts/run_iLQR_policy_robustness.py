@@ -3,9 +3,12 @@
 result is off its nominal.  Every solved trajectory is rolled out S times on the device (iLQR.policy_rollout) with the
 initial state off by a few degrees and the plant's m2 and l2 off by up to 20 %, once closed loop through the gains K_t
 and once open loop (the controls U_t alone).  Per trajectory the script reports the share of samples whose final state is
-within the stated tolerance of the target.
+within the stated tolerance of the target.  With --process-noise SIGMA the closed loop is also run under Gaussian
+process noise of that standard deviation in every state component, drawn on the device (iLQR.policy_monte_carlo), and the
+per-trajectory statistics of its cost and deviation are reported.
 
     python scripts/run_iLQR_policy_robustness.py [--batch 256] [--samples 1024] [--horizon 200] [--dtype f64] [--seed 0]
+                                                 [--process-noise SIGMA]
 """
 import argparse
 import os
@@ -32,6 +35,8 @@ def main(argv=None):
     ap.add_argument("--horizon", type=int, default=200)
     ap.add_argument("--dtype", default="f64", choices=["f64", "f32"])
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--process-noise", type=float, default=None, metavar="SIGMA",
+                    help="also run the closed loop under N(0, SIGMA^2) process noise drawn on the device (off by default)")
     a = ap.parse_args(argv)
     dtype = np.float64 if a.dtype == "f64" else np.float32
     B, S, N = a.batch, a.samples, a.horizon
@@ -63,6 +68,13 @@ def main(argv=None):
               f"median deviation from the nominal {np.median(r.deviation):.3f}")
     print(f"(tolerance: |angle error| <= {TOL_ANGLE} rad, |rate error| <= {TOL_RATE} rad/s at t = {N * system.dt:g} s; "
           f"initial angles off by up to {np.rad2deg(ANGLE_OFF):g} degrees, m2 and l2 by up to {SPREAD:.0%})")
+    if a.process_noise is not None:
+        t0 = time.time()
+        mc = solver.policy_monte_carlo(S, seed=a.seed, disturbance_std=np.full(4, a.process_noise))
+        el = time.time() - t0
+        print(f"process noise sigma = {a.process_noise:g}: {B} x {S} closed-loop rollouts in {el:.3f} s; per trajectory: "
+              f"finite samples min {int(mc.n_finite.min())} of {S}, cost mean median {np.median(mc.cost_mean):.3f}, "
+              f"cost std median {np.median(mc.cost_std):.3f}, worst deviation from the nominal {np.nanmax(mc.deviation_max):.3f}")
     return shares
 
 

@@ -18,7 +18,8 @@ typedef int i4 __attribute__((ext_vector_type(4)));
 enum {
     FMA_IND, FMA_DEP, FMAC_DPP_ROR_IND, FMAC_DPP_QP_IND, ADD_DPP_DEP, MIX_FMA_DPP, RCP_IND, RCP_DEP, SALU_IND,
     LOAD_X4_B2B, LOAD_X1_B2B, LOAD_X4_SPREAD, STORE_X1_B2B, MFMA_F32_IND, MFMA_F32_DEP, MFMA_F64_IND, BPERM_DEP,
-    READLANE_IND, SWAP32_DEP, PKFMA_IND, FMA64_IND, FMA64_DEP, LOAD_X1_SPREAD, STORE_X1_SPREAD, DS_B128_SPREAD, DS_B32_SPREAD, LDSDMA_SPREAD, FMA7_ONLY, N_MODES
+    READLANE_IND, SWAP32_DEP, PKFMA_IND, FMA64_IND, FMA64_DEP, LOAD_X1_SPREAD, STORE_X1_SPREAD, DS_B128_SPREAD, DS_B32_SPREAD, LDSDMA_SPREAD, FMA7_ONLY,
+    FMA_IND128, MULHI_U32_IND, MULLO_U32_IND, MAD_U64_U32_IND, MULHI_U32_DEP, N_MODES
 };
 static const char* kNames[N_MODES] = {
     "v_fma_f32 independent", "v_fma_f32 dependent", "v_fmac_f32_dpp row_ror independent", "v_fmac_f32_dpp quad_perm independent",
@@ -28,9 +29,11 @@ static const char* kNames[N_MODES] = {
     "v_mfma_f32_16x16x4 dependent", "v_mfma_f64_16x16x4 independent", "ds_bpermute_b32 dependent", "v_readlane_b32 independent",
     "v_permlane32_swap + v_add dependent (x2)", "v_pk_fma_f32 independent", "v_fma_f64 independent", "v_fma_f64 dependent",
     "buffer_load_dword + 7 v_fma each", "buffer_store_dword + 7 v_fma each", "ds_read_b128 + 7 v_fma each",
-    "ds_read_b32 + 7 v_fma each", "global_load_lds_dwordx4 + 7 v_fma each", "7 v_fma (the filler alone)"};
+    "ds_read_b32 + 7 v_fma each", "global_load_lds_dwordx4 + 7 v_fma each", "7 v_fma (the filler alone)",
+    "v_fma_f32 independent, 128 per iteration", "v_mul_hi_u32 independent, 128 per iteration", "v_mul_lo_u32 independent, 128 per iteration",
+    "v_mad_u64_u32 (zero addend) independent, 128 per iteration", "v_mul_hi_u32 dependent, 128 per iteration"};
 // instructions per loop iteration, per mode (the loop body is written out 32 or 8 times)
-static const int kPerIter[N_MODES] = {32, 32, 32, 32, 32, 32, 32, 32, 32, 48, 48, 48, 48, 8, 8, 8, 8, 32, 8, 32, 32, 32, 48, 48, 48, 48, 48, 48};
+static const int kPerIter[N_MODES] = {32, 32, 32, 32, 32, 32, 32, 32, 32, 48, 48, 48, 48, 8, 8, 8, 8, 32, 8, 32, 32, 32, 48, 48, 48, 48, 48, 48, 128, 128, 128, 128, 128};
 
 template <int MODE> __global__ void __launch_bounds__(256) rate(float* buf, long long* cyc, int iters) {
     float a[8];
@@ -45,6 +48,11 @@ template <int MODE> __global__ void __launch_bounds__(256) rate(float* buf, long
     f4 ld[8];
     for (int i = 0; i < 8; ++i) ld[i] = f4{0.f, 0.f, 0.f, 0.f};
     int s0 = iters, s1 = 1, s2 = 2, s3 = 3;
+    // the 32-bit integer products of a counter-based generator (Philox: one high and one low half per multiplier and round)
+    unsigned q[8];
+    unsigned long long q64[8];
+    for (int i = 0; i < 8; ++i) { q[i] = threadIdx.x * 2654435761u + i; q64[i] = q[i]; }
+    const unsigned qm = 0xD2511F53u;
     // descriptor over buf (64 KiB, L2-resident)
     i4 srd;
     {
@@ -185,6 +193,32 @@ template <int MODE> __global__ void __launch_bounds__(256) rate(float* buf, long
             if constexpr (MODE == DS_B32_SPREAD) SPREAD_ASM("ds_read_b32 %[d1], %[lo]\n\t", "s_waitcnt lgkmcnt(0)");
             if constexpr (MODE == LDSDMA_SPREAD) SPREAD_ASM("global_load_lds_dwordx4 %[gp], off\n\t", "s_waitcnt vmcnt(0)");
             if constexpr (MODE == FMA7_ONLY) SPREAD_ASM("", "");
+        } else if constexpr (MODE == FMA_IND128) {
+            // the integer rows below in the shape of the first row, but 128 instructions per iteration: the loop's own
+            // overhead, ~1.6 ticks per instruction at 32 per iteration, falls to a quarter
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+#pragma unroll
+                for (int i = 0; i < 8; ++i) asm volatile("v_fma_f32 %0, %0, %1, %2" : "+v"(a[i]) : "v"(m), "v"(c));
+        } else if constexpr (MODE == MULHI_U32_IND) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+#pragma unroll
+                for (int i = 0; i < 8; ++i) asm volatile("v_mul_hi_u32 %0, %0, %1" : "+v"(q[i]) : "v"(qm));
+        } else if constexpr (MODE == MULLO_U32_IND) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+#pragma unroll
+                for (int i = 0; i < 8; ++i) asm volatile("v_mul_lo_u32 %0, %0, %1" : "+v"(q[i]) : "v"(qm));
+        } else if constexpr (MODE == MAD_U64_U32_IND) {
+            // both halves of a 32 x 32 product, zero addend (the form a counter-based generator uses)
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+#pragma unroll
+                for (int i = 0; i < 8; ++i) asm volatile("v_mad_u64_u32 %0, vcc, %1, %2, 0" : "=v"(q64[i]) : "v"(q[i]), "v"(qm) : "vcc");
+        } else if constexpr (MODE == MULHI_U32_DEP) {
+#pragma unroll
+            for (int r = 0; r < 128; ++r) asm volatile("v_mul_hi_u32 %0, %0, %1" : "+v"(q[0]) : "v"(qm));
         } else if constexpr (MODE == FMA64_DEP) {
 #pragma unroll
             for (int r = 0; r < 32; ++r) asm volatile("v_fma_f64 %0, %0, %1, %2" : "+v"(d[0]) : "v"(md), "v"(cd));
@@ -192,7 +226,7 @@ template <int MODE> __global__ void __launch_bounds__(256) rate(float* buf, long
     }
     long long t1 = __builtin_readcyclecounter();
     float s = (float)(s0 + s1 + s2 + s3 + perm);
-    for (int i = 0; i < 8; ++i) s += a[i] + (float)d[i] + ld[i].x;
+    for (int i = 0; i < 8; ++i) s += a[i] + (float)d[i] + ld[i].x + (float)(q[i] + (unsigned)q64[i]);
     for (int i = 0; i < 4; ++i) s += acc[i].x + acc[i].y + acc[i].z + acc[i].w;
     s += (float)(accd[0].x + accd[1].y);
     if (s == 12345.678f) buf[20000 + threadIdx.x] = s;
