@@ -478,6 +478,81 @@ typedef struct ilqr_monte_carlo_desc {
 } ilqr_monte_carlo_desc;
 int ilqr_policy_monte_carlo(ilqr_handle h, const ilqr_monte_carlo_desc* d);
 
+/* ---- sampled control search: best-of-S and MPPI updates of U on the device (build extension) -----------------
+ * A cheap search over control sequences before any Riccati sweep is paid for.  For trajectory b, round r = 0..R-1 draws S
+ * temporally correlated perturbations of the nominal controls, rolls each out open loop through the model and replaces
+ * the nominal by the best sample (ILQR_SAMPLE_BEST) or by the softmin-weighted average of all (ILQR_SAMPLE_SOFTMIN, MPPI).
+ * The nominal of round 0 is U of b's current slot -- the state after ilqr_set_problem, ilqr_solve, ilqr_iterate,
+ * ilqr_mpc_run or ilqr_set(ILQR_U); a pending acceptance step is completed first -- and x_0 is the solver's x_0[b].
+ * Sample 0 of every round is the nominal itself: e = 0, nothing is drawn.  Every other sample s, at step t = 0..N-1:
+ *   n_t[j]    = u_std[b][j] * z_j(b, s, t, stream 2 + first_round + r)   the generator, key and transforms of
+ *                                                       ilqr_policy_monte_carlo at counter (s, first_trajectory + b, t,
+ *                                                       stream); component j takes z_j (n_u <= 2).  Streams 0 and 1
+ *                                                       remain those of ilqr_policy_monte_carlo
+ *   e_0       = n_0,  e_t = beta e_{t-1} + c n_t        beta = smoothing, c = sqrt(1 - beta^2) computed in double, both
+ *                                                       rounded to the handle's dtype; every product (u_std z, beta e,
+ *                                                       c n) is rounded to the dtype on its own and then added, never
+ *                                                       fused, so ILQR_NOISE_UNIFORM is bit-reproducible in both
+ *                                                       precisions.  e_t has the variance of n_t at every t
+ *   u_t       = clamp(U^r_t + e_t, u_min, u_max)        only while control limits are set (shared, or b's row); NaN stays NaN
+ *   x_{t+1}   = f_model(x_t, u_t)                       the model's integrator (cfg.integrator) at b's ILQR_BATCH_MODEL row
+ *                                                       where rows are set, else the parameter block; plant rows are not
+ *                                                       used: this step plans with the model
+ *   J_s       = sum_t l(x_t, u_t) + l_f(x_N)            the model's plain J (b's x_target row, shared Q, R, Q_f), summed in
+ *                                                       the rollout's order
+ * State limits and their multipliers do not enter.  The update runs over the samples with a finite J_s (sample 0 of a
+ * finite nominal is always among them):
+ *   BEST      s* = argmin J_s, the lowest s on ties;  U^{r+1}_t = u_{s*,t}
+ *   SOFTMIN   w_s = exp(-(J_s - J_min) / temperature),  W = sum_s w_s,  U^{r+1}_t[j] = (sum_s w_s u_{s,t}[j]) / W:
+ *             a convex combination of clamped controls.  Weights and sums in double, a fixed order, no floating-point
+ *             atomics; every element is rounded to the dtype once at the end and then clamped to the box, which the
+ *             rounding of the sums and the quotient can leave by an ulp: U_new is inside the box, and a mean recomputed
+ *             from U_samples can differ from it by that ulp
+ *   round_stats[r][b]  = J_0 (the cost of the round's nominal), the minimum finite J_s, the effective sample size
+ *                        W^2 / sum_s w_s^2 (reported as 1 in BEST mode);  round_counts[r][b] = n_finite
+ * With n_finite == 0 the nominal is kept, the minimum is NaN and the effective sample size 0.
+ * After the last round U_new = U^R, and cost_new / X_new come from one more rollout of the sample-0 kind.  In BEST mode
+ * cost_new equals the last round's minimum bit for bit (the same code on the same controls; a clamped control clamps to
+ * itself), so it never exceeds round_stats[0][b][0], the cost the caller started from.  SOFTMIN is NOT monotone: the
+ * average of good control sequences need not be a good one; compare cost_new with round_stats[0][b][0].
+ * The rounds stay on the device, on a private copy of U: no host synchronisation between rounds, one download at the end.
+ * The stream of (b, s, r) depends on neither B nor S, and a call with first_round = k after ilqr_set(ILQR_U, U_new)
+ * continues a k-round call exactly.  cost_samples / U_samples are those of the LAST round; the controls of every sample
+ * are kept on the device in either case ([N][n_u][B * S]: the update reads them), and come to the host only when
+ * U_samples is given.
+ * One wave of the GPU runs 64 samples of one trajectory: S a multiple of 64 fills the waves, any S >= 1 is valid.
+ * The call is synchronous and changes nothing another entry reads, in the sense of ilqr_policy_rollout; its device
+ * buffers are allocated at the first call that needs them, grown when a later call needs more and freed with the handle.
+ * Returns ILQR_ERR_UNSUPPORTED for ILQR_SYS_LINEAR and ILQR_SYS_CUSTOM, ILQR_ERR_STATE before ilqr_set_problem /
+ * ilqr_mpc_reset, ILQR_ERR_INVALID_ARG -- all checked before any device work -- for a NULL handle or desc, a wrong
+ * struct_size, n_samples < 1 or n_rounds < 1, first_round + n_rounds > 2^32 - 2, an unknown mode or distribution,
+ * first_trajectory < 0 or first_round < 0, a NULL or negative u_std or one that is not finite in the handle's dtype,
+ * smoothing outside [0, 1), a temperature
+ * that is not finite and > 0 in SOFTMIN mode, or every output NULL.
+ * ILQR_ABI_VERSION stays 5 with this entry, for the reasons given at ilqr_set_batch_limits: it is additive. */
+enum { ILQR_SAMPLE_BEST = 0, ILQR_SAMPLE_SOFTMIN = 1 };
+typedef struct ilqr_sample_controls_desc {
+    uint32_t struct_size;     /* = sizeof(ilqr_sample_controls_desc) */
+    int32_t n_samples;        /* S >= 1 */
+    int32_t n_rounds;         /* R >= 1 */
+    int32_t mode;             /* ILQR_SAMPLE_* */
+    int32_t distribution;     /* ILQR_NOISE_* */
+    int32_t first_trajectory; /* >= 0, as ilqr_policy_monte_carlo */
+    int32_t first_round;      /* >= 0: global index of this call's round 0 */
+    uint64_t seed;
+    double temperature;       /* lambda > 0, in the cost's units; read in SOFTMIN only */
+    double smoothing;         /* beta in [0, 1) */
+    const double* u_std;      /* [B][n_u] >= 0, finite in the handle's dtype; required */
+    void* U_new;              /* [B][n_u][N]   handle dtype; any output may be NULL, not all */
+    void* cost_new;           /* [B]           plain J of U_new from x_0 */
+    void* X_new;              /* [B][n_x][N+1] */
+    double* round_stats;      /* [R][B][3]: cost of sample 0, min finite cost, effective sample size */
+    int32_t* round_counts;    /* [R][B]: n_finite */
+    void* cost_samples;       /* [B][S]        of the LAST round */
+    void* U_samples;          /* [B][S][n_u][N] of the LAST round, as applied (clamped) */
+} ilqr_sample_controls_desc;
+int ilqr_sample_controls(ilqr_handle h, const ilqr_sample_controls_desc* d);
+
 /* ---- multi-GPU hook -------------------------------------------
  * Writes 4 doubles to DEVICE memory `dev_out4` on the handle's stream:
  *   { min cost, max |cost - cost_prev|, #trajectories still active, #converged }

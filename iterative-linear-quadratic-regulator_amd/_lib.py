@@ -43,7 +43,7 @@ SYMBOLS = (
     "ilqr_flush", "ilqr_solve", "ilqr_backward_pass", "ilqr_backward_tensors", "ilqr_forward_pass", "ilqr_eval_points", "ilqr_mpc_reset",
     "ilqr_mpc_rearm", "ilqr_mpc_run", "ilqr_status_reduce", "ilqr_timing_enable", "ilqr_timing_reset", "ilqr_timing_get", "ilqr_algorithmic_bytes",
     "ilqr_set_control_limits", "ilqr_set_batch_params", "ilqr_set_state_limits", "ilqr_set_mpc_multipliers",
-    "ilqr_set_batch_limits", "ilqr_policy_rollout", "ilqr_policy_monte_carlo",
+    "ilqr_set_batch_limits", "ilqr_policy_rollout", "ilqr_policy_monte_carlo", "ilqr_sample_controls",
 )
 # ilqr_set_batch_params: which rows
 BATCH_MODEL, BATCH_PLANT = 0, 1
@@ -61,6 +61,10 @@ NOISE_GAUSSIAN, NOISE_UNIFORM = 0, 1
 NOISE_DISTRIBUTIONS = {"gaussian": NOISE_GAUSSIAN, "uniform": NOISE_UNIFORM}
 MONTE_CARLO_STATS = ("cost_mean", "cost_std", "cost_min", "cost_max", "deviation_mean", "deviation_max", "violation_max")
 MONTE_CARLO_COUNTS = ("n_finite", "n_violating")
+# ilqr_sample_controls: the update of the nominal, and the columns of a round's statistics
+SAMPLE_BEST, SAMPLE_SOFTMIN = 0, 1
+SAMPLE_MODES = {"best": SAMPLE_BEST, "softmin": SAMPLE_SOFTMIN}
+SAMPLE_ROUND_STATS = ("round_cost_nominal", "round_cost_min", "round_ess")
 
 
 class Config(C.Structure):
@@ -99,6 +103,20 @@ class MonteCarloDesc(C.Structure):
         ("stats", C.POINTER(C.c_double)), ("counts", C.POINTER(C.c_int32)),
         ("cost", C.c_void_p), ("x_final", C.c_void_p), ("deviation", C.c_void_p), ("violation", C.c_void_p),
         ("X", C.c_void_p), ("U", C.c_void_p), ("x0_out", C.c_void_p), ("w_out", C.c_void_p),
+    ]
+
+
+class SampleControlsDesc(C.Structure):
+    """ilqr_sample_controls_desc (include/ilqr_hip.h), field for field."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("n_samples", C.c_int32), ("n_rounds", C.c_int32), ("mode", C.c_int32), ("distribution", C.c_int32),
+        ("first_trajectory", C.c_int32), ("first_round", C.c_int32),
+        ("seed", C.c_uint64), ("temperature", C.c_double), ("smoothing", C.c_double),
+        ("u_std", C.POINTER(C.c_double)),
+        ("U_new", C.c_void_p), ("cost_new", C.c_void_p), ("X_new", C.c_void_p),
+        ("round_stats", C.POINTER(C.c_double)), ("round_counts", C.POINTER(C.c_int32)),
+        ("cost_samples", C.c_void_p), ("U_samples", C.c_void_p),
     ]
 
 
@@ -171,6 +189,7 @@ def load():
     lib.ilqr_set_batch_limits.argtypes = [vp, ci, vp, vp, ci]
     lib.ilqr_policy_rollout.argtypes = [vp, C.POINTER(PolicyRolloutDesc)]
     lib.ilqr_policy_monte_carlo.argtypes = [vp, C.POINTER(MonteCarloDesc)]
+    lib.ilqr_sample_controls.argtypes = [vp, C.POINTER(SampleControlsDesc)]
     if lib.ilqr_abi_version() != ABI_VERSION:
         raise RuntimeError("libilqr_hip.so ABI version mismatch: rebuild the library")
     _lib = lib
@@ -532,6 +551,49 @@ class Handle:
             out[k] = np.empty(shape, dtype=self.np_dtype)
             setattr(d, k, _ptr(out[k]))
         self._chk(self.lib.ilqr_policy_monte_carlo(self.h, C.byref(d)))
+        return out
+
+    # ---- sampled control search --------------------------------------------------------------------
+    def sample_controls(self, n_samples, rounds=1, seed=0, u_std=None, mode=SAMPLE_BEST, temperature=1.0, smoothing=0.0,
+                        distribution=NOISE_GAUSSIAN, first_trajectory=0, first_round=0, samples=False, trajectories=False,
+                        summaries=True):
+        """R = rounds of S = n_samples perturbed open-loop rollouts per trajectory and a best-of-S or softmin update of the
+        controls, on the device (include/ilqr_hip.h, ilqr_sample_controls).  u_std (B, n_u) float64.  Returns a dict: U
+        (B, n_u, N), cost (B,), round_stats (R, B, 3) float64 and round_counts (R, B) int32 (with summaries); X
+        (B, n_x, N + 1) (with trajectories); cost_samples (B, S) and U_samples (B, S, n_u, N) of the last round (with
+        samples)."""
+        B, S, R, n, m, N = self.B, int(n_samples), int(rounds), self.n_x, self.n_u, self.N
+        Sa, Ra = max(S, 0), max(R, 0)
+        d = SampleControlsDesc()
+        d.struct_size = C.sizeof(SampleControlsDesc)
+        d.n_samples, d.n_rounds, d.mode, d.distribution = S, R, int(mode), int(distribution)
+        d.first_trajectory, d.first_round = int(first_trajectory), int(first_round)
+        d.seed, d.temperature, d.smoothing = int(seed) & 0xFFFFFFFFFFFFFFFF, float(temperature), float(smoothing)
+        std = None
+        if u_std is not None:
+            std = np.ascontiguousarray(u_std, dtype=np.float64)
+            if std.shape != (B, m):
+                raise ValueError(f"u_std must have shape {(B, m)}, but got {std.shape}")
+            d.u_std = std.ctypes.data_as(C.POINTER(C.c_double))
+        out = {}
+        if summaries:
+            out["round_stats"] = np.empty((Ra, B, 3), dtype=np.float64)
+            out["round_counts"] = np.empty((Ra, B), dtype=np.int32)
+            d.round_stats = out["round_stats"].ctypes.data_as(C.POINTER(C.c_double))
+            d.round_counts = out["round_counts"].ctypes.data_as(C.POINTER(C.c_int32))
+        shapes = {}
+        if summaries:
+            shapes.update(U_new=(B, m, N), cost_new=(B,))
+        if trajectories:
+            shapes.update(X_new=(B, n, N + 1))
+        if samples:
+            shapes.update(cost_samples=(B, Sa), U_samples=(B, Sa, m, N))
+        names = {"U_new": "U", "cost_new": "cost", "X_new": "X"}
+        for k, shape in shapes.items():
+            a = np.empty(shape, dtype=self.np_dtype)
+            out[names.get(k, k)] = a
+            setattr(d, k, _ptr(a))
+        self._chk(self.lib.ilqr_sample_controls(self.h, C.byref(d)))
         return out
 
     # ---- measurement ------------------------------------------------------------------------------

@@ -306,6 +306,19 @@ int ilqr_policy_monte_carlo(ilqr_handle h, const ilqr_monte_carlo_desc* d) {
     }
     return h->impl->policy_monte_carlo(*d);
 }
+int ilqr_sample_controls(ilqr_handle h, const ilqr_sample_controls_desc* d) {
+    if (!h || !h->impl) return ILQR_ERR_INVALID_ARG;
+    const ilqr_config& c = h->impl->cfg;
+    if (c.system == ILQR_SYS_LINEAR || c.system == ILQR_SYS_CUSTOM) {
+        h->impl->err = "sample_controls: not supported for linear or user-defined systems";
+        return ILQR_ERR_UNSUPPORTED;
+    }
+    if (!d || d->struct_size != sizeof(ilqr_sample_controls_desc)) {
+        h->impl->err = "sample_controls: desc is NULL or struct_size does not match this library's ilqr_sample_controls_desc";
+        return ILQR_ERR_INVALID_ARG;
+    }
+    return h->impl->sample_controls(*d);
+}
 int ilqr_timing_enable(ilqr_handle h, int on) { ILQR_FWD(h, timing_enable(on)); }
 int ilqr_timing_reset(ilqr_handle h) { ILQR_FWD(h, timing_reset()); }
 int ilqr_timing_get(ilqr_handle h, double ms[ILQR_N_PHASES], int64_t launches[ILQR_N_PHASES]) {

@@ -15,6 +15,7 @@
 #include "backward_mfma16.hpp"
 #include "forward_mfma16.hpp"
 #include "policy_rollout.hpp"
+#include "sample_controls.hpp"
 
 namespace ilqr {
 
@@ -117,6 +118,11 @@ template <typename T> struct Ops {
     void (*policy)(const PolicyArgs<T>&, hipStream_t) = nullptr;
     // the same with x_0 and w drawn on the device (ilqr_policy_monte_carlo): set wherever `policy` is
     void (*policy_noise)(const PolicyArgs<T>&, const NoiseArgs<T>&, hipStream_t) = nullptr;
+    // sampled control search (ilqr_sample_controls, sample_controls.hpp), set wherever `policy` is: the private copy of the
+    // nominal, the rollout of a round's samples (S = 1: of the nominal alone), and the round's weights and update of Ub
+    void (*sample_begin)(const SampleArgs<T>&, hipStream_t) = nullptr;
+    void (*sample_rollout)(const SampleArgs<T>&, const NoiseArgs<T>&, hipStream_t) = nullptr;
+    void (*sample_update)(const SampleArgs<T>&, hipStream_t) = nullptr;
 };
 
 // linearize / forward are compiled once per integrator so the integrator switch folds away and each
@@ -271,6 +277,26 @@ template <typename T, typename Dyn> void launch_policy_noise(const PolicyArgs<T>
     else ILQR_LAUNCH((policy_noise_kernel<T, Dyn, false>), grid, block, 0, s, a, nz);
 }
 
+// sampled control search (sample_controls.hpp): the rollout has the policy rollout's mapping; the weights are one wave
+// per trajectory; the update is one lane (BEST) or one wave (SOFTMIN) per (t, j) of a trajectory
+template <typename T, typename Dyn> void launch_sample_begin(const SampleArgs<T>& a, hipStream_t s) {
+    const size_t n = (size_t)a.B * a.N * Dyn::NU;
+    ILQR_LAUNCH((sample_nominal_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.Ub, a.U, a.cur_slot, a.B, a.N, Dyn::NU);
+}
+template <typename T, typename Dyn> void launch_sample_rollout(const SampleArgs<T>& a, const NoiseArgs<T>& nz, hipStream_t s) {
+    ILQR_LAUNCH((sample_rollout_kernel<T, Dyn>), dim3((a.S + 63) / 64, a.B), dim3(64), 0, s, a, nz);
+}
+template <typename T, typename Dyn> void launch_sample_update(const SampleArgs<T>& a, hipStream_t s) {
+    const int rows = a.N * Dyn::NU;
+    // (the phase timer's event pair spans both launches: begin at the weights, end at the update)
+    const LaunchEvents le = launch_events();
+    launch_events() = LaunchEvents{le.a, nullptr};
+    ILQR_LAUNCH((sample_weights_kernel<T>), dim3(a.B), dim3(64), 0, s, a);
+    launch_events() = LaunchEvents{nullptr, le.b};
+    if (a.mode == ILQR_SAMPLE_SOFTMIN) ILQR_LAUNCH((sample_softmin_kernel<T, Dyn::NU>), dim3(a.N, a.B), dim3(64), 0, s, a);
+    else ILQR_LAUNCH((sample_best_kernel<T>), dim3((rows + 63) / 64, a.B), dim3(64), 0, s, a, (int)Dyn::NU);
+}
+
 template <typename T, typename Dyn, bool TILE, int INTEG> void set_integrator_ops(Ops<T>& o) {
     constexpr bool SMALL = all_integrators<Dyn>::value;
     // control limits on the fused and persistent kernels: n_u = 1 (u_t rides the tile's padding, FusedWG)
@@ -387,6 +413,9 @@ template <typename T, typename Dyn> Ops<T> make_ops() {
         };
         o.policy = launch_policy<T, Dyn>;
         o.policy_noise = launch_policy_noise<T, Dyn>;
+        o.sample_begin = launch_sample_begin<T, Dyn>;
+        o.sample_rollout = launch_sample_rollout<T, Dyn>;
+        o.sample_update = launch_sample_update<T, Dyn>;
     }
     o.eval = [](const EvalArgs<T>& a, hipStream_t s) {
         ILQR_LAUNCH((eval_points_kernel<T, Dyn>), dim3((a.npts + 63) / 64), dim3(64), 0, s, a);

@@ -1,0 +1,223 @@
+// sample_controls.hpp -- sampled control search: best-of-S and MPPI updates of U on the device
+// (include/ilqr_hip.h, ilqr_sample_controls).
+//
+// A round perturbs the nominal control sequence Ub of trajectory b with S temporally correlated noise sequences, rolls
+// every one out open loop through the model and replaces Ub by the best sample's controls (BEST) or by the average of
+// all of them weighted by exp(-(J_s - J_min) / lambda) (SOFTMIN):
+//   n_t = u_std[b] (.) z(b, s, t, stream),   e_0 = n_0,   e_t = beta e_{t-1} + c n_t,   c = sqrt(1 - beta^2)
+//   u_t = clamp(Ub_t + e_t),   x_{t+1} = f_model(x_t, u_t),   J_s = sum_t l(x_t, u_t) + l_f(x_N)
+// Sample 0 of every round is the nominal itself (e = 0, nothing drawn).
+// Mapping of the rollout: the policy rollout's (policy_rollout.hpp) -- one wave = 64 samples of ONE trajectory, so Ub_t,
+// the bounds, the model row and u_std are wave-uniform and come through the scalar unit; per-lane outputs are
+// sample-innermost.  The draw and the recurrence stand at the head of the step: nothing of them depends on the state.
+// Three launches per round (rollout, weights, update), all on the handle's stream and on a private copy of U
+// ([N][n_u][B]): no host synchronisation between rounds.
+#pragma once
+#include "policy_rollout.hpp"
+
+namespace ilqr {
+
+template <typename T> struct SampleArgs {
+    int B, S, N;
+    int integ;                          // the model's integrator
+    int mode;                           // ILQR_SAMPLE_BEST / ILQR_SAMPLE_SOFTMIN
+    unsigned stream;                    // the generator's stream of this round: 2 + first_round + r
+    T dt;
+    T beta, c;                          // smoothing and sqrt(1 - smoothing^2), rounded to T on the host
+    double lambda;                      // the temperature (SOFTMIN)
+    // read-only for the rollout
+    const T* __restrict__ U;            // [n_slots][N][B][n_u] the solver's U (sample_nominal_kernel)
+    const int* __restrict__ cur_slot;   // [B]
+    const T* __restrict__ params;       // the parameter block
+    const T* __restrict__ rows;         // [n_sys + n_x][B] model rows, or nullptr
+    const T* __restrict__ x0;           // [n_x][B]
+    const T* __restrict__ u_std;        // [B][n_u]
+    Limits<T> lim;
+    T* __restrict__ Ub;                 // [N][n_u][B] the nominal of the round: read by the rollout, written by the update
+    // per-sample outputs of the rollout, sample-innermost (L = B * S, l = b * S + s)
+    T* __restrict__ cost;               // [L]
+    T* __restrict__ Us;                 // [N][n_u][L] the controls as applied, or nullptr
+    T* __restrict__ Xs;                 // [N+1][n_x][L], or nullptr
+    // the reduction over the samples of a trajectory
+    double* __restrict__ w;             // [L] the weights (SOFTMIN), 0 for a sample with a non-finite cost
+    double* __restrict__ wsum;          // [B] W (0 with no finite sample)
+    int* __restrict__ sel;              // [B] argmin over the finite costs, lowest s on ties; -1 with none
+    double* __restrict__ stats;         // [B][3] of this round: cost of sample 0, min finite cost, effective sample size
+    int* __restrict__ counts;           // [B] of this round: n_finite
+};
+
+// Ub[t][j][b] <- U of b's current slot
+template <typename T>
+__global__ void sample_nominal_kernel(T* __restrict__ Ub, const T* __restrict__ U, const int* __restrict__ cur_slot, int B, int N, int NU) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (size_t)B * N * NU) return;
+    const int b = (int)(idx % B);
+    const int row = (int)(idx / B), t = row / NU, j = row % NU;
+    Ub[idx] = U[vec_at((size_t)B, N, NU, cur_slot[b], t, (size_t)b) + j];
+}
+
+// The rollout of one sample.  Launched with S = 1 it is the rollout of the nominal alone (cost_new / X_new): the same
+// code on the same controls, so the cost of a BEST call's result is the winning sample's cost bit for bit.
+template <typename T, typename Dyn>
+__global__ void __launch_bounds__(64) sample_rollout_kernel(SampleArgs<T> a, NoiseArgs<T> nz) {
+    constexpr int NX = Dyn::NX, NU = Dyn::NU, NSYS = Dyn::NSYS;
+    static_assert(NU <= 2, "component j of a control takes z_j of one generator call's first pair");
+    using PL = ParamLayout<NSYS, NX, NU>;
+    const int b = blockIdx.y;
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= a.S) return;
+    const size_t B = a.B, L = B * (size_t)a.S, l = (size_t)b * a.S + s;
+    const int N = a.N;
+    // wave-uniform: the trajectory's model row (or the block), its limits, its standard deviations
+    T mr[PL::Q];
+    {
+        const uniform_ptr<T> q = a.rows ? as_uniform(a.rows) + b : as_uniform(a.params);
+        const size_t st = a.rows ? B : 1;
+#pragma unroll
+        for (int i = 0; i < PL::Q; ++i) mr[i] = q[(size_t)i * st];
+    }
+    const PolicyCostParams<T, PL::Q> p{mr, as_uniform(a.params)};
+    T blo[NU], bhi[NU], sd[NU];
+#pragma unroll
+    for (int j = 0; j < NU; ++j) {
+        blo[j] = a.lim.u_lo_rows ? as_uniform(a.lim.u_lo_rows)[(size_t)j * B + b] : a.lim.u_lo[j];
+        bhi[j] = a.lim.u_lo_rows ? as_uniform(a.lim.u_hi_rows)[(size_t)j * B + b] : a.lim.u_hi[j];
+    }
+    uniform_load<T, NU>(a.u_std + (size_t)b * NU, sd);
+    const bool nominal = s == 0;
+
+    T x[NX], u[NU], e[NU], ub[NU], ub_n[NU];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) x[i] = as_uniform(a.x0)[(size_t)i * B + b];
+#pragma unroll
+    for (int j = 0; j < NU; ++j) {
+        e[j] = T(0);
+        ub[j] = as_uniform(a.Ub)[(size_t)j * B + b];
+    }
+    T cost = T(0);
+    for (int t = 0; t < N; ++t) {
+        // step t + 1's nominal is requested before step t's arithmetic
+        const int tn = (t + 1 < N) ? t + 1 : t;
+#pragma unroll
+        for (int j = 0; j < NU; ++j) ub_n[j] = as_uniform(a.Ub)[((size_t)tn * NU + j) * B + b];
+        T n[NU];
+        noise_draw<T, NU>(nz, (unsigned)s, (unsigned)b, (unsigned)t, a.stream, sd, n);
+#pragma unroll
+        for (int j = 0; j < NU; ++j) {
+            // two products rounded on their own and one add (noise_mul is never contracted with what follows)
+            const T keep = noise_mul(a.beta, e[j]);
+            const T add = noise_mul(a.c, n[j]);
+            e[j] = t == 0 ? n[j] : keep + add;
+            u[j] = clamp_keep_nan(nominal ? ub[j] : ub[j] + e[j], blo[j], bhi[j]);
+        }
+        if (a.Xs) {
+#pragma unroll
+            for (int i = 0; i < NX; ++i) a.Xs[((size_t)t * NX + i) * L + l] = x[i];
+        }
+        if (a.Us) {
+#pragma unroll
+            for (int j = 0; j < NU; ++j) a.Us[((size_t)t * NU + j) * L + l] = u[j];
+        }
+        cost += Cost<T, Dyn>::stage(p, a.dt, x, u);
+        T xn[NX];
+        Stepper<T, Dyn>::step(a.integ, mr, a.dt, x, u, xn);
+#pragma unroll
+        for (int i = 0; i < NX; ++i) x[i] = xn[i];
+#pragma unroll
+        for (int j = 0; j < NU; ++j) ub[j] = ub_n[j];
+    }
+    if (a.Xs) {
+#pragma unroll
+        for (int i = 0; i < NX; ++i) a.Xs[((size_t)N * NX + i) * L + l] = x[i];
+    }
+    cost += Cost<T, Dyn>::terminal(p, x);
+    a.cost[l] = cost;
+}
+
+// The weights of a round: one wave per trajectory over its contiguous [S] costs, each lane over its stride of the row and
+// then a butterfly over the wave (a fixed order, no atomics), in double.
+//   finite mask, J_min and s* = the lowest s that attains it, w_s = exp(-(J_s - J_min) / lambda) (SOFTMIN; 0 where J_s is
+//   not finite), W = sum w_s, sum w_s^2, n_finite; stats = J_0, J_min, W^2 / sum w_s^2 (BEST: 1; none finite: NaN min, 0)
+template <typename T>
+__global__ void __launch_bounds__(64) sample_weights_kernel(SampleArgs<T> a) {
+    const int b = blockIdx.x, lane = threadIdx.x, S = a.S;
+    const T* c = a.cost + (size_t)b * S;
+    const double inf = __builtin_huge_val();
+    double n = 0, cmin = inf;
+    int smin = 0x7fffffff;
+    for (int s = lane; s < S; s += 64) {
+        const double ci = (double)c[s];
+        if (!(ci - ci == 0.0)) continue;       // NaN or an infinity
+        n += 1.0;
+        if (ci < cmin) { cmin = ci; smin = s; }   // s ascends within a lane: the first of equal costs stays
+    }
+    n = wave_sum(n);
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const double oc = __shfl_xor(cmin, m, 64);
+        const int os = __shfl_xor(smin, m, 64);
+        if (oc < cmin || (oc == cmin && os < smin)) { cmin = oc; smin = os; }
+    }
+    const bool any = n > 0.0;
+    double W = 0, W2 = 0;
+    if (a.mode == ILQR_SAMPLE_SOFTMIN) {
+        double* w = a.w + (size_t)b * S;
+        for (int s = lane; s < S; s += 64) {
+            const double ci = (double)c[s];
+            const double wi = (ci - ci == 0.0) ? exp(-(ci - cmin) / a.lambda) : 0.0;
+            w[s] = wi;
+            W += wi;
+            W2 += wi * wi;
+        }
+        W = wave_sum(W);
+        W2 = wave_sum(W2);
+    }
+    if (lane != 0) return;
+    a.sel[b] = any ? smin : -1;
+    a.wsum[b] = any ? W : 0.0;
+    double* o = a.stats + (size_t)b * 3;
+    o[0] = (double)c[0];
+    o[1] = any ? cmin : __builtin_nan("");
+    o[2] = !any ? 0.0 : a.mode == ILQR_SAMPLE_SOFTMIN ? W * W / W2 : 1.0;
+    a.counts[b] = (int)n;
+}
+
+// BEST: Ub_t <- the winner's controls as applied; one lane per (t, j) of a trajectory.  No finite sample: Ub stays.
+template <typename T>
+__global__ void __launch_bounds__(64) sample_best_kernel(SampleArgs<T> a, int NU) {
+    const int b = blockIdx.y, row = blockIdx.x * 64 + threadIdx.x;
+    if (row >= a.N * NU) return;
+    const int s = a.sel[b];
+    if (s < 0) return;
+    const size_t B = a.B, L = B * (size_t)a.S;
+    a.Ub[(size_t)row * B + b] = a.Us[(size_t)row * L + (size_t)b * a.S + s];
+}
+
+// SOFTMIN: Ub_t[j] <- (sum_s w_s u_{s,t}[j]) / W over the samples with w_s > 0, from the stored controls: one wave per
+// step t of a trajectory, for each j over the contiguous [S] row, each lane over its stride and then a butterfly (a fixed
+// order, no atomics), in double, rounded to T once.  The mean of controls inside the box is inside the box up to the
+// rounding of the sums and the quotient: the clamp takes that last ulp back (a NaN stays NaN).  No finite sample: Ub stays.
+template <typename T, int NU>
+__global__ void __launch_bounds__(64) sample_softmin_kernel(SampleArgs<T> a) {
+    const int b = blockIdx.y, t = blockIdx.x, lane = threadIdx.x, S = a.S;
+    const size_t B = a.B, L = B * (size_t)S;
+    const double W = a.wsum[b];
+    if (!(W > 0.0)) return;
+    const double* w = a.w + (size_t)b * S;
+#pragma unroll
+    for (int j = 0; j < NU; ++j) {
+        const size_t row = (size_t)t * NU + j;
+        const T* u = a.Us + row * L + (size_t)b * S;
+        double acc = 0;
+        for (int s = lane; s < S; s += 64) {
+            const double wi = w[s];
+            if (wi > 0.0) acc += wi * (double)u[s];
+        }
+        acc = wave_sum(acc);
+        const T lo = a.lim.u_lo_rows ? a.lim.u_lo_rows[(size_t)j * B + b] : a.lim.u_lo[j];
+        const T hi = a.lim.u_lo_rows ? a.lim.u_hi_rows[(size_t)j * B + b] : a.lim.u_hi[j];
+        if (lane == 0) a.Ub[row * B + b] = clamp_keep_nan((T)(acc / W), lo, hi);
+    }
+}
+
+}  // namespace ilqr

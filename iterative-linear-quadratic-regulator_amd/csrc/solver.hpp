@@ -59,6 +59,7 @@ struct SolverBase {
     virtual int set_batch_limits(int which, const double* lo, const double* hi, int row_len) = 0;
     virtual int policy_rollout(const ilqr_policy_rollout_desc& d) = 0;
     virtual int policy_monte_carlo(const ilqr_monte_carlo_desc& d) = 0;
+    virtual int sample_controls(const ilqr_sample_controls_desc& d) = 0;
 };
 
 int system_dims(int system, int n_x, int n_u);  // 1 if (system, n_x, n_u) is a known combination
@@ -311,6 +312,13 @@ template <typename T> class SolverT : public SolverBase {
     std::vector<T> pr_std_host;
     DevBuf<double> pr_stats;
     DevBuf<int> pr_counts;
+    // ilqr_sample_controls: the private nominal [N][n_u][B], u_std [B][n_u], the weights [B * S] and W [B], the winners
+    // [B], the rounds' statistics [R][B][3] and counts [R][B]; grown like the pr_* buffers, which hold the per-sample
+    // costs (pr_sum), controls (pr_U) and the final rollout's states (pr_X)
+    DevBuf<T> sc_U, sc_std;
+    std::vector<T> sc_std_host;
+    DevBuf<double> sc_w, sc_stats;
+    DevBuf<int> sc_sel, sc_counts;
 
     // (the device buffers free themselves after this body: DevBuf)
     ~SolverT() override {
@@ -1335,6 +1343,103 @@ template <typename T> class SolverT : public SolverBase {
         };
         if (d.X && (rc = down_traj(d.X, pr_X, NX, N + 1))) return rc;
         if (d.U && (rc = down_traj(d.U, pr_U, NU, N))) return rc;
+        ILQR_HIPCHK(hipStreamSynchronize(stream));
+        return check_launch();
+    }
+
+    // ---- sampled control search (sample_controls.hpp) ---------------------------------------
+    // R rounds of (rollout of S samples, weights, update of the private nominal), then the nominal's own rollout: every
+    // kernel of the search is queued on the stream without a host synchronisation in between.  The downloads follow the
+    // last of them (the staged ones, which convert the layout through `staging`, each end synchronised).  Reads
+    // the solver state and writes only the sc_* / pr_* buffers and `staging`: nothing another entry reads changes.
+    int sample_controls(const ilqr_sample_controls_desc& d) override {
+        const std::string who = "sample_controls";
+        auto bad = [&](const char* what) { err = who + ": " + what; return ILQR_ERR_INVALID_ARG; };
+        if (d.n_samples < 1) return bad("n_samples must be >= 1");
+        if (d.n_rounds < 1) return bad("n_rounds must be >= 1");
+        if (d.mode != ILQR_SAMPLE_BEST && d.mode != ILQR_SAMPLE_SOFTMIN) return bad("unknown mode");
+        if (d.distribution != ILQR_NOISE_GAUSSIAN && d.distribution != ILQR_NOISE_UNIFORM) return bad("unknown distribution");
+        if (d.first_trajectory < 0) return bad("first_trajectory must be >= 0");
+        if (d.first_round < 0) return bad("first_round must be >= 0");
+        // (the streams 2 + first_round + r must fit 32 bits; with two int32 fields the sum is at most 2^32 - 2, so this
+        // cannot fire today: it is the header's clause, kept for the day a field widens)
+        if ((unsigned long long)d.first_round + (unsigned long long)d.n_rounds > 0xfffffffeull)
+            return bad("first_round + n_rounds must be <= 2^32 - 2");
+        if (!d.u_std) return bad("u_std is NULL");
+        for (size_t i = 0; i < (size_t)B * NU; ++i)
+            // (finite as the device holds it: a double beyond the handle's dtype would arrive there as +inf)
+            if (!std::isfinite(d.u_std[i]) || d.u_std[i] < 0.0 || d.u_std[i] > (double)std::numeric_limits<T>::max())
+                return bad("every standard deviation must be finite in the handle's dtype and >= 0");
+        if (!(d.smoothing >= 0.0 && d.smoothing < 1.0)) return bad("smoothing must be in [0, 1)");
+        if (d.mode == ILQR_SAMPLE_SOFTMIN && !(std::isfinite(d.temperature) && d.temperature > 0.0))
+            return bad("temperature must be finite and > 0");
+        if (!d.U_new && !d.cost_new && !d.X_new && !d.round_stats && !d.round_counts && !d.cost_samples && !d.U_samples)
+            return bad("every output is NULL");
+        const size_t S = (size_t)d.n_samples, L = (size_t)B * S, Rn = (size_t)d.n_rounds;
+        if (L > (size_t)std::numeric_limits<int>::max()) return bad("batch * n_samples must be < 2^31");
+        if (!ops.sample_rollout) {
+            err = who + ": supported for the pendulum, UA double pendulum and double pendulum only";
+            return ILQR_ERR_UNSUPPORTED;
+        }
+        if (!have_problem) { err = who + " before set_problem / mpc_reset"; return ILQR_ERR_STATE; }
+        int rc;
+        if ((rc = flush_select())) return rc;
+        if ((rc = fix_slots(st))) return rc;
+        const size_t nU = L * NU * (size_t)N, nUb = (size_t)B * NU * N, nXb = (size_t)B * NX * (N + 1);
+        // (pr_U: the update reads every sample's controls as the rollout stored them)
+        if ((rc = grow(pr_sum, L + (size_t)B)) || (rc = grow(pr_U, nU)) || (rc = grow(sc_U, nUb)) ||
+            (rc = grow(sc_std, (size_t)B * NU)) || (rc = grow(sc_w, L + (size_t)B)) || (rc = grow(sc_sel, (size_t)B)) ||
+            (rc = grow(sc_stats, Rn * B * 3)) || (rc = grow(sc_counts, Rn * B)))
+            return rc;
+        if (d.X_new && (rc = grow(pr_X, nXb))) return rc;
+        if ((rc = grow(staging, std::max({nUb, d.X_new ? nXb : (size_t)0, d.U_samples ? nU : (size_t)0})))) return rc;
+        // (sc_std_host outlives the copy: the call ends synchronised before the next one can write it again)
+        sc_std_host.resize((size_t)B * NU);
+        for (size_t i = 0; i < sc_std_host.size(); ++i) sc_std_host[i] = (T)d.u_std[i];
+        ILQR_HIPCHK(hipMemcpyAsync(sc_std.p, sc_std_host.data(), sc_std_host.size() * sizeof(T), hipMemcpyHostToDevice, stream));
+        SampleArgs<T> a{};
+        a.B = B; a.S = d.n_samples; a.N = N; a.integ = cfg.integrator; a.mode = d.mode;
+        a.dt = (T)cfg.dt;
+        a.beta = (T)d.smoothing; a.c = (T)std::sqrt(1.0 - d.smoothing * d.smoothing);
+        a.lambda = d.temperature;
+        a.U = st.U; a.cur_slot = st.cur_slot; a.params = params; a.x0 = st.x0;
+        a.rows = het.model_set ? het.rows.p : nullptr;
+        a.u_std = sc_std.p;
+        a.lim = limits();
+        a.Ub = sc_U.p;
+        a.cost = pr_sum; a.Us = pr_U.p;
+        a.w = sc_w.p; a.wsum = sc_w.p + L; a.sel = sc_sel.p;
+        NoiseArgs<T> nz{};
+        nz.k0 = (unsigned)(d.seed & 0xffffffffull); nz.k1 = (unsigned)(d.seed >> 32);
+        nz.first = (unsigned)d.first_trajectory;
+        nz.dist = d.distribution;
+        if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sample_begin(a, stream); }))) return rc;
+        for (size_t r = 0; r < Rn; ++r) {
+            a.stream = 2u + (unsigned)d.first_round + (unsigned)r;
+            a.stats = sc_stats.p + r * B * 3;
+            a.counts = sc_counts.p + r * B;
+            if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sample_rollout(a, nz, stream); }))) return rc;
+            if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sample_update(a, stream); }))) return rc;
+        }
+        // the nominal alone: the rollout at S = 1 (sample 0 draws nothing), its cost behind the samples'
+        SampleArgs<T> f = a;
+        f.S = 1; f.cost = pr_sum.p + L; f.Us = nullptr; f.Xs = d.X_new ? pr_X.p : nullptr;
+        if (d.cost_new || d.X_new) {
+            if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sample_rollout(f, nz, stream); }))) return rc;
+        }
+        if (d.round_stats) ILQR_HIPCHK(hipMemcpyAsync(d.round_stats, sc_stats.p, Rn * B * 3 * sizeof(double), hipMemcpyDeviceToHost, stream));
+        if (d.round_counts) ILQR_HIPCHK(hipMemcpyAsync(d.round_counts, sc_counts.p, Rn * B * sizeof(int), hipMemcpyDeviceToHost, stream));
+        if (d.cost_samples) ILQR_HIPCHK(hipMemcpyAsync(d.cost_samples, pr_sum.p, L * sizeof(T), hipMemcpyDeviceToHost, stream));
+        if (d.cost_new) ILQR_HIPCHK(hipMemcpyAsync(d.cost_new, f.cost, (size_t)B * sizeof(T), hipMemcpyDeviceToHost, stream));
+        // [t][c][L] -> host [L][c][t]
+        auto down_traj = [&](void* host, const T* dev, size_t Ln, int C, int Tn) {
+            return stage_down(host, Ln * C * (size_t)Tn, [&](dim3 g_, dim3 b_) {
+                hipLaunchKernelGGL(layout_ctl_gather_kernel<T>, g_, b_, 0, stream, staging.p, dev, Ln, C, Tn);
+            });
+        };
+        if (d.U_samples && (rc = down_traj(d.U_samples, pr_U, L, NU, N))) return rc;
+        if (d.U_new && (rc = down_traj(d.U_new, sc_U, (size_t)B, NU, N))) return rc;
+        if (d.X_new && (rc = down_traj(d.X_new, pr_X, (size_t)B, NX, N + 1))) return rc;
         ILQR_HIPCHK(hipStreamSynchronize(stream));
         return check_launch();
     }

@@ -267,6 +267,66 @@ def policy_monte_carlo_args(system, N, B, batched, n_samples, seed=0, x_0_std=No
     return S, int(seed), x0_std, w_std, _lib.NOISE_DISTRIBUTIONS[distribution], rows, code, tol, int(first_trajectory)
 
 
+SampledControls = namedtuple(
+    "SampledControls", ("U", "cost", "cost_start") + _lib.SAMPLE_ROUND_STATS + ("round_n_finite", "applied", "X", "cost_samples",
+                                                                             "U_samples"), defaults=(None,) * 4)
+SampledControls.__doc__ = """Result of iLQR.sample_controls.  U ([B,] n_u, N): the searched controls; cost ([B]): their plain
+cost from x_0; cost_start ([B]): the cost of the controls the call started from; round_cost_nominal, round_cost_min,
+round_ess (float64) and round_n_finite (int), each (R, [B]): per round the cost of its nominal, the minimum over the
+samples with a finite cost (NaN with none), the effective sample size of the softmin weights (1 in "best" mode) and the
+number of finite samples; applied ([B] bool, None without apply=True): where U became the solver's initial guess; X
+([B,] n_x, N + 1) with trajectories=True; cost_samples ([B,] S) and U_samples ([B,] S, n_u, N) of the last round with
+samples=True; else None."""
+
+
+def sample_controls_args(system, N, B, batched, n_samples, rounds=1, seed=0, u_std=None, mode="best", temperature=None,
+                         smoothing=0.0, distribution="gaussian", first_trajectory=0, first_round=0):
+    """Validated arguments of ``ilqr_sample_controls`` as (S, R, seed, u_std, mode code, temperature, smoothing,
+    distribution code, first_trajectory, first_round): u_std (B, n_u) float64 -- (n_u,) or a scalar is broadcast over the
+    batch.  Raises ValueError for a system without the search, n_samples or rounds that are not integers >= 1, a seed
+    outside [0, 2^64), a missing, misshapen, negative or non-finite u_std, an unknown mode or distribution, a temperature
+    that is not finite and > 0 in "softmin" mode (it is required there), smoothing outside [0, 1), a negative
+    first_trajectory or first_round, or first_round + rounds > 2^32 - 2.  Pure host code (no GPU)."""
+    if getattr(system, "SYSTEM_ID", None) not in _lib.BOX_SYSTEMS:
+        raise ValueError(f"the sampled control search is supported for the pendulum, UA double pendulum and double "
+                         f"pendulum only, not for {type(system).__name__}")
+
+    def count(name, v, lo):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) < 2 ** 31:
+            raise ValueError(f"{name} must be an integer >= {lo}, got {v!r}")
+        return int(v)
+
+    S, R = count("n_samples", n_samples, 1), count("rounds", rounds, 1)
+    B, m = int(B), system.n_u
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+        raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
+    if u_std is None:
+        raise ValueError("u_std is required: the standard deviation of the control perturbation, ([B,] n_u)")
+    std = np.asarray(u_std, dtype=np.float64)
+    if std.shape in ((), (m,)):
+        std = np.broadcast_to(std, (B, m))
+    if std.shape != (B, m):
+        raise ValueError(f"u_std must have shape ({m},) or ({B}, {m}), but got {std.shape}")
+    if not np.isfinite(std).all() or (std < 0).any():
+        raise ValueError("u_std must be finite and >= 0")
+    if not isinstance(mode, str) or mode not in _lib.SAMPLE_MODES:
+        raise ValueError(f"Unknown mode: {mode!r}. Supported: 'best', 'softmin'.")
+    if mode == "softmin":
+        if temperature is None or not (np.isfinite(float(temperature)) and float(temperature) > 0.0):
+            raise ValueError(f"temperature must be finite and > 0 in 'softmin' mode, got {temperature!r}")
+    temp = 1.0 if temperature is None else float(temperature)
+    beta = float(smoothing)
+    if not 0.0 <= beta < 1.0:
+        raise ValueError(f"smoothing must be in [0, 1), got {smoothing!r}")
+    if not isinstance(distribution, str) or distribution not in _lib.NOISE_DISTRIBUTIONS:
+        raise ValueError(f"Unknown distribution: {distribution!r}. Supported: 'gaussian', 'uniform'.")
+    first, first_r = count("first_trajectory", first_trajectory, 0), count("first_round", first_round, 0)
+    if first_r + R > 2 ** 32 - 2:
+        raise ValueError("first_round + rounds must be <= 2^32 - 2")
+    return (S, R, int(seed), np.ascontiguousarray(std), _lib.SAMPLE_MODES[mode], temp, beta,
+            _lib.NOISE_DISTRIBUTIONS[distribution], first, first_r)
+
+
 class iLQR:
     def __init__(self, system: System, T=None, x_0=None, U_init=None, tol=1e-5, maxiter=100,
                  alpha_factor=0.5, min_alpha=1e-8, verbose=True, *, N=None, n_alpha=None, n_trials=10,
@@ -592,6 +652,40 @@ class iLQR:
         names = {"x0_out": "x_0", "w_out": "disturbance"}
         rec.update({names.get(k, k): self._out(v) for k, v in out.items()})
         return PolicyMonteCarlo(**rec)
+
+    # ---- sampled control search ---------------------------------------------------------------------
+    def sample_controls(self, n_samples, rounds=1, seed=0, u_std=None, mode="best", temperature=None, smoothing=0.0,
+                        distribution="gaussian", first_trajectory=0, first_round=0, samples=False, trajectories=False,
+                        apply=False):
+        """A cheap search over control sequences before any Riccati sweep (include/ilqr_hip.h, ilqr_sample_controls):
+        `rounds` times, n_samples perturbations of the solver's current U are rolled out open loop through the model from
+        x_0 and U is replaced by the best sample (mode="best") or by the average weighted by exp(-cost / temperature)
+        (mode="softmin", MPPI; not monotone).  The perturbation of control j is u_std[j] * e_t with e_t = smoothing *
+        e_{t-1} + sqrt(1 - smoothing^2) * z_t, z of unit variance ("gaussian" or "uniform") from Philox4x32-10 at (seed,
+        first_trajectory + b, s, t, round first_round + r); sample 0 of every round is the nominal itself, and controls
+        are clamped to the control limits if set.  u_std is ([B,] n_u) or a scalar.  Returns a SampledControls; the
+        sample costs and controls of the last round with samples=True, X of the result with trajectories=True.  Nothing in
+        the solver changes, unless apply=True: then every trajectory whose searched cost is finite and below the cost it
+        started from takes U as its initial guess, the others keep theirs, and set_problem(x_0, U_sel) makes the next
+        optimize_trajectory() start fresh from it -- no trajectory is made worse."""
+        S, R, seed, std, mcode, temp, beta, dist, first, first_r = sample_controls_args(
+            self.system, self.N, self.B, self.batched, n_samples, rounds, seed, u_std, mode, temperature, smoothing,
+            distribution, first_trajectory, first_round)
+        U_start = self._h.get(_lib.U) if apply else None
+        out = self._h.sample_controls(S, R, seed, std, mcode, temp, beta, dist, first, first_r, samples, trajectories)
+        stats, counts = out.pop("round_stats"), out.pop("round_counts")
+        cost_start = stats[0, :, 0].astype(self.dtype)
+        applied = None
+        if apply:
+            applied = np.isfinite(out["cost"]) & (out["cost"] < cost_start)
+            U_sel = np.where(applied[:, None, None], out["U"], U_start)
+            self._h.set_problem(self._h.get(_lib.X0), U_sel)
+        pick = (lambda a: a) if self.batched else (lambda a: a[0])
+        rpick = (lambda a: a) if self.batched else (lambda a: a[:, 0])
+        rec = {k: rpick(stats[:, :, i].copy()) for i, k in enumerate(_lib.SAMPLE_ROUND_STATS)}
+        rec.update(round_n_finite=rpick(counts), cost_start=pick(cost_start), applied=None if applied is None else pick(applied))
+        rec.update({k: self._out(v) for k, v in out.items()})
+        return SampledControls(**rec)
 
     # ---- MPC (run_iLQR_MPC.py:116-143), device-resident ---------------------------------------------
     def mpc_reset(self, x_0, U_init, keep_state=False):
