@@ -403,7 +403,16 @@ int ilqr_set_batch_limits(ilqr_handle h, int which, const double* lo, const doub
  * and the multipliers stay as they were, so a solve or ilqr_mpc_run continued after it gives exactly what it gives
  * without it.  Its device buffers are allocated at the first call that needs them, grown when a later call needs more and
  * freed with the handle; the X and U sample buffers exist only once those outputs were requested.
- * Returns ILQR_ERR_UNSUPPORTED for ILQR_SYS_LINEAR and ILQR_SYS_CUSTOM, ILQR_ERR_STATE before ilqr_set_problem /
+ * A user-defined system (ILQR_SYS_CUSTOM) is supported when its plugin carries the policy kernels (generated with
+ * policy_kernels=True, systems/custom_sys.py; they are left out by default because they lengthen the plugin's build):
+ *   cost      the user's l and l_f exactly as the solver uses them: the quadratic block form, or the traced cost as written
+ *   f_plant   `integrator` may differ from the model's (a plugin has all four integrators at every n_x); this is the only
+ *             plant / model mismatch such a system has: its constants are part of the generated code, so a non-NULL
+ *             plant_rows returns ILQR_ERR_UNSUPPORTED ("a user-defined system has no parameter rows")
+ *   limits    control and state limits cannot be set on such a handle: the clamp moves nothing and violation is 0
+ * Everything else above holds word for word.
+ * Returns ILQR_ERR_UNSUPPORTED for ILQR_SYS_LINEAR and for an ILQR_SYS_CUSTOM handle whose plugin was generated without the
+ * policy kernels, ILQR_ERR_STATE before ilqr_set_problem /
  * ilqr_mpc_reset, ILQR_ERR_INVALID_ARG for a wrong struct_size, n_samples < 1, an unknown integrator, a non-finite
  * plant_rows entry, or every output NULL.
  * ILQR_ABI_VERSION stays 5 with this entry, for the reasons given at ilqr_set_batch_limits: it is additive. */
@@ -437,17 +446,23 @@ int ilqr_policy_rollout(ilqr_handle h, const ilqr_policy_rollout_desc* d);
  * Generator: Philox4x32-10 (Salmon et al., SC'11; multipliers 0xD2511F53, 0xCD9E8D57, key increments 0x9E3779B9,
  * 0xBB67AE85) at counter = (s, first_trajectory + b, t, stream), key = (seed & 0xffffffff, seed >> 32): the stream of
  * sample (b, s) depends neither on B nor on S, and a shard of a fleet draws the fleet's streams through
- * first_trajectory.  One call gives r0..r3; state component i uses z_i (n_x <= 4), fp32 in both dtypes, converted to the
- * handle's dtype before the multiply:
+ * first_trajectory.  One call gives r0..r3; state component i belongs to group g = i / 4 and uses z_{i mod 4} of the call
+ * whose third counter word is t | (g << 31) (t < N <= 2^31 - 1 leaves bit 31 free; g = 0 is the counter above, so every
+ * n_x <= 4 result is what it was; user-defined systems have n_x <= 6, so g <= 1, and group 1 is drawn only when the system
+ * has a component in it), fp32 in both dtypes, converted to the handle's dtype before the multiply:
  *   ILQR_NOISE_UNIFORM   k = r_i >> 9;  z_i = 0x1.bb67aep+0f * ((float)(2k + 1 - 2^23) * 2^-23)     (unit variance)
- *   ILQR_NOISE_GAUSSIAN  pairs (r0, r1), (r2, r3):  u1 = (float)(2 (r_a >> 9) + 1) * 2^-24,  u2 = (float)(r_b >> 8) * 2^-24,
+ *   ILQR_NOISE_GAUSSIAN  pairs (r0, r1), (r2, r3) of the group's call:  u1 = (float)(2 (r_a >> 9) + 1) * 2^-24,  u2 = (float)(r_b >> 8) * 2^-24,
  *                        rad = sqrt(-2 ln u1),  z_a = rad cos(2 pi u2),  z_b = rad sin(2 pi u2)
  * (the hardware logarithm, root, sine and cosine: |z - exact| <= 2e-5).
  * Statistics, on the device over the samples of b with a finite cost (sums in double, two passes, a fixed order):
  *   stats[b]  = cost mean, cost std (population), cost min, cost max, deviation mean, deviation max, violation max
  *   counts[b] = n_finite, n_violating (violation > violation_tol among the finite)
  * With n_finite == 0 the seven statistics are NaN.
- * Returns ILQR_ERR_UNSUPPORTED for ILQR_SYS_LINEAR and ILQR_SYS_CUSTOM, ILQR_ERR_STATE before ilqr_set_problem /
+ * A user-defined system is supported as in ilqr_policy_rollout (a plugin with the policy kernels; the user's cost; the
+ * plant differs by its integrator only and plant_rows returns ILQR_ERR_UNSUPPORTED; no limits: violation is 0), and
+ * everything above -- the streams' independence of B and S, first_trajectory, the same bits from ilqr_policy_rollout
+ * fed with x0_out and w_out -- holds for it word for word.
+ * Returns ILQR_ERR_UNSUPPORTED for ILQR_SYS_LINEAR and for an ILQR_SYS_CUSTOM handle without the policy kernels, ILQR_ERR_STATE before ilqr_set_problem /
  * ilqr_mpc_reset, ILQR_ERR_INVALID_ARG for a NULL handle or desc, a wrong struct_size, n_samples < 1, an unknown
  * integrator or distribution, first_trajectory < 0, a negative or non-finite standard deviation, a negative or NaN
  * violation_tol, a non-finite plant_rows entry, or every output NULL.  Synchronous; changes nothing another entry reads.
@@ -487,7 +502,8 @@ int ilqr_policy_monte_carlo(ilqr_handle h, const ilqr_monte_carlo_desc* d);
  * Sample 0 of every round is the nominal itself: e = 0, nothing is drawn.  Every other sample s, at step t = 0..N-1:
  *   n_t[j]    = u_std[b][j] * z_j(b, s, t, stream 2 + first_round + r)   the generator, key and transforms of
  *                                                       ilqr_policy_monte_carlo at counter (s, first_trajectory + b, t,
- *                                                       stream); component j takes z_j (n_u <= 2).  Streams 0 and 1
+ *                                                       stream); component j takes z_{j mod 4} of group j / 4, by
+ *                                                       the group rule given there (n_u <= 6).  Streams 0 and 1
  *                                                       remain those of ilqr_policy_monte_carlo
  *   e_0       = n_0,  e_t = beta e_{t-1} + c n_t        beta = smoothing, c = sqrt(1 - beta^2) computed in double, both
  *                                                       rounded to the handle's dtype; every product (u_std z, beta e,
@@ -523,7 +539,12 @@ int ilqr_policy_monte_carlo(ilqr_handle h, const ilqr_monte_carlo_desc* d);
  * One wave of the GPU runs 64 samples of one trajectory: S a multiple of 64 fills the waves, any S >= 1 is valid.
  * The call is synchronous and changes nothing another entry reads, in the sense of ilqr_policy_rollout; its device
  * buffers are allocated at the first call that needs them, grown when a later call needs more and freed with the handle.
- * Returns ILQR_ERR_UNSUPPORTED for ILQR_SYS_LINEAR and ILQR_SYS_CUSTOM, ILQR_ERR_STATE before ilqr_set_problem /
+ * A user-defined system is supported as in ilqr_policy_rollout (a plugin with the policy kernels): J_s is the user's l and
+ * l_f exactly as the solver uses them, f_model is the generated dynamics under cfg.integrator, and since no control limits
+ * can be set on such a handle nothing is clamped.  first_round, first_trajectory and "changes nothing another entry
+ * reads" hold word for word.
+ * Returns ILQR_ERR_UNSUPPORTED for ILQR_SYS_LINEAR and for an ILQR_SYS_CUSTOM handle without the policy kernels,
+ * ILQR_ERR_STATE before ilqr_set_problem /
  * ilqr_mpc_reset, ILQR_ERR_INVALID_ARG -- all checked before any device work -- for a NULL handle or desc, a wrong
  * struct_size, n_samples < 1 or n_rounds < 1, first_round + n_rounds > 2^32 - 2, an unknown mode or distribution,
  * first_trajectory < 0 or first_round < 0, a NULL or negative u_std or one that is not finite in the handle's dtype,

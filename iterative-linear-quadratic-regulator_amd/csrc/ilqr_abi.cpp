@@ -283,7 +283,7 @@ int ilqr_set_batch_limits(ilqr_handle h, int which, const double* lo, const doub
 int ilqr_policy_rollout(ilqr_handle h, const ilqr_policy_rollout_desc* d) {
     if (!h || !h->impl) return ILQR_ERR_INVALID_ARG;
     const ilqr_config& c = h->impl->cfg;
-    if (c.system == ILQR_SYS_LINEAR || c.system == ILQR_SYS_CUSTOM) {
+    if (c.system == ILQR_SYS_LINEAR || (c.system == ILQR_SYS_CUSTOM && !h->impl->policy_kernels)) {
         h->impl->err = "policy_rollout: not supported for linear or user-defined systems";
         return ILQR_ERR_UNSUPPORTED;
     }
@@ -296,7 +296,7 @@ int ilqr_policy_rollout(ilqr_handle h, const ilqr_policy_rollout_desc* d) {
 int ilqr_policy_monte_carlo(ilqr_handle h, const ilqr_monte_carlo_desc* d) {
     if (!h || !h->impl) return ILQR_ERR_INVALID_ARG;
     const ilqr_config& c = h->impl->cfg;
-    if (c.system == ILQR_SYS_LINEAR || c.system == ILQR_SYS_CUSTOM) {
+    if (c.system == ILQR_SYS_LINEAR || (c.system == ILQR_SYS_CUSTOM && !h->impl->policy_kernels)) {
         h->impl->err = "policy_monte_carlo: not supported for linear or user-defined systems";
         return ILQR_ERR_UNSUPPORTED;
     }
@@ -309,7 +309,7 @@ int ilqr_policy_monte_carlo(ilqr_handle h, const ilqr_monte_carlo_desc* d) {
 int ilqr_sample_controls(ilqr_handle h, const ilqr_sample_controls_desc* d) {
     if (!h || !h->impl) return ILQR_ERR_INVALID_ARG;
     const ilqr_config& c = h->impl->cfg;
-    if (c.system == ILQR_SYS_LINEAR || c.system == ILQR_SYS_CUSTOM) {
+    if (c.system == ILQR_SYS_LINEAR || (c.system == ILQR_SYS_CUSTOM && !h->impl->policy_kernels)) {
         h->impl->err = "sample_controls: not supported for linear or user-defined systems";
         return ILQR_ERR_UNSUPPORTED;
     }

@@ -219,6 +219,16 @@ void launch_persist_kernel(const KArgs<T>& a, const PArgs<T>& pa, hipStream_t s)
 template <typename Dyn> constexpr bool box_system() {
     return Dyn::ID == ILQR_SYS_PENDULUM || Dyn::ID == ILQR_SYS_UA_DOUBLE_PENDULUM || Dyn::ID == ILQR_SYS_DOUBLE_PENDULUM;
 }
+// The systems that have the policy kernels (ilqr_policy_rollout, ilqr_policy_monte_carlo, ilqr_sample_controls): the ones
+// above, and a user-defined system whose plugin was generated with them (ILQR_PLUGIN_POLICY at the top of the generated
+// source: systems/custom_sys.py, policy_kernels=True).  Not box_system: limits, state limits and per-trajectory
+// parameters stay with the built-in three.
+#ifndef ILQR_PLUGIN_POLICY
+#define ILQR_PLUGIN_POLICY 0
+#endif
+template <typename Dyn> constexpr bool policy_system() {
+    return box_system<Dyn>() || (Dyn::ID == ILQR_SYS_CUSTOM && ILQR_PLUGIN_POLICY);
+}
 // Bit i set: integrator i gets the persistent kernel's per-trajectory-parameter instantiation (else a solve with rows set
 // takes the fused multi-launch loop).  Independent of ILQR_PERSIST_INTEG_MASK, which keeps the shared-parameter routing.
 #ifndef ILQR_PERSIST_HET_INTEG_MASK
@@ -265,16 +275,28 @@ void launch_forward(const KArgs<T>& a, hipStream_t s) {
 
 // S samples per trajectory, one wave per 64 samples of one trajectory (policy_rollout.hpp); the SROWS instantiation where
 // the call brings per-sample plant constants
+// (a Dyn without system constants has no such rows: its SROWS kernels are never instantiated, and the handle refuses
+// plant_rows before a launch)
 template <typename T, typename Dyn> void launch_policy(const PolicyArgs<T>& a, hipStream_t s) {
     const dim3 grid((a.S + 63) / 64, a.B), block(64);
-    if (a.srows) ILQR_LAUNCH((policy_rollout_kernel<T, Dyn, true>), grid, block, 0, s, a);
-    else ILQR_LAUNCH((policy_rollout_kernel<T, Dyn, false>), grid, block, 0, s, a);
+    if constexpr (Dyn::NSYS > 0) {
+        if (a.srows) {
+            ILQR_LAUNCH((policy_rollout_kernel<T, Dyn, true>), grid, block, 0, s, a);
+            return;
+        }
+    }
+    ILQR_LAUNCH((policy_rollout_kernel<T, Dyn, false>), grid, block, 0, s, a);
 }
 // the NOISE instantiations of the same body (ilqr_policy_monte_carlo), same mapping
 template <typename T, typename Dyn> void launch_policy_noise(const PolicyArgs<T>& a, const NoiseArgs<T>& nz, hipStream_t s) {
     const dim3 grid((a.S + 63) / 64, a.B), block(64);
-    if (a.srows) ILQR_LAUNCH((policy_noise_kernel<T, Dyn, true>), grid, block, 0, s, a, nz);
-    else ILQR_LAUNCH((policy_noise_kernel<T, Dyn, false>), grid, block, 0, s, a, nz);
+    if constexpr (Dyn::NSYS > 0) {
+        if (a.srows) {
+            ILQR_LAUNCH((policy_noise_kernel<T, Dyn, true>), grid, block, 0, s, a, nz);
+            return;
+        }
+    }
+    ILQR_LAUNCH((policy_noise_kernel<T, Dyn, false>), grid, block, 0, s, a, nz);
 }
 
 // sampled control search (sample_controls.hpp): the rollout has the policy rollout's mapping; the weights are one wave
@@ -293,7 +315,7 @@ template <typename T, typename Dyn> void launch_sample_update(const SampleArgs<T
     launch_events() = LaunchEvents{le.a, nullptr};
     ILQR_LAUNCH((sample_weights_kernel<T>), dim3(a.B), dim3(64), 0, s, a);
     launch_events() = LaunchEvents{nullptr, le.b};
-    if (a.mode == ILQR_SAMPLE_SOFTMIN) ILQR_LAUNCH((sample_softmin_kernel<T, Dyn::NU>), dim3(a.N, a.B), dim3(64), 0, s, a);
+    if (a.mode == ILQR_SAMPLE_SOFTMIN) ILQR_LAUNCH((sample_softmin_kernel<T, Dyn::NU, takes_limits<Dyn>()>), dim3(a.N, a.B), dim3(64), 0, s, a);
     else ILQR_LAUNCH((sample_best_kernel<T>), dim3((rows + 63) / 64, a.B), dim3(64), 0, s, a, (int)Dyn::NU);
 }
 
@@ -411,6 +433,8 @@ template <typename T, typename Dyn> Ops<T> make_ops() {
             ILQR_LAUNCH_HET(true, a.m.plant_rows, (mpc_advance_al_kernel<T, Dyn>), (mpc_advance_al_kernel<T, Dyn, true>),
                             dim3((a.m.B + 63) / 64), dim3(64, kMpcChunks), 0, s, a);
         };
+    }
+    if constexpr (policy_system<Dyn>()) {
         o.policy = launch_policy<T, Dyn>;
         o.policy_noise = launch_policy_noise<T, Dyn>;
         o.sample_begin = launch_sample_begin<T, Dyn>;

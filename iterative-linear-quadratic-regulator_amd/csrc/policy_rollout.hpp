@@ -75,7 +75,9 @@ template <typename T, int NH> struct PolicyCostParams {
 // ---- device-drawn noise (include/ilqr_hip.h, ilqr_policy_monte_carlo) ------------------------------------------------
 // The NOISE instantiations draw x_0 and w_t themselves: x_0[b][s] = x_0[b] + x0_std[b] (.) z(b, s, 0, stream 1),
 // w[b][s][t] = w_std[b] (.) z(b, s, t, stream 0), z from Philox4x32-10 at counter (s, first + b, t, stream) and key
-// (seed low, seed high): one call gives the step's four 32-bit words, component i takes z_i (n_x <= 4).  Nothing of it
+// (seed low, seed high): one call gives four 32-bit words, and component i takes z_{i mod 4} of the call of its group
+// g = i / 4, whose third counter word is t | (g << 31) (t < N <= 2^31 - 1 leaves that bit free; g = 0 is the plain
+// counter, so n_x <= 4 draws one call per step as before; a user-defined system has n_x <= 6: g <= 1).  Nothing of it
 // depends on the state, so the draw of step t stands at the head of the step, beside the request for step t + 1's
 // nominal, and the scheduler runs it under the step's dependency chain.  Every product std * z is rounded to T on its
 // own (noise_mul below: never contracted with the add that follows), so a call of the plain kernel with the returned
@@ -150,16 +152,32 @@ template <int C> ILQR_DEV void noise_z(int dist, const unsigned (&r)[4], float (
     }
 }
 
-// std[i] * z_i(b, s, t, stream), rounded to T
+// std[i] * z_i(b, s, t, stream), rounded to T.  Components 0..3 come from the call at counter word t, components 4..7
+// (group 1) from a second call at t | 2^31, made only when C has a component there.
 template <typename T, int C>
 ILQR_DEV void noise_draw(const NoiseArgs<T>& nz, unsigned s, unsigned b, unsigned t, unsigned stream, const T (&sd)[C], T (&o)[C]) {
+    static_assert(C <= 8, "two generator calls (groups 0 and 1) serve at most eight components");
+    constexpr int C0 = C < 4 ? C : 4;
     unsigned r[4];
     philox4x32_10(s, nz.first + b, t, stream, nz.k0, nz.k1, r);
-    float z[C];
-    noise_z<C>(nz.dist, r, z);
+    float z[C0];
+    noise_z<C0>(nz.dist, r, z);
 #pragma unroll
-    for (int i = 0; i < C; ++i) o[i] = noise_mul(sd[i], (T)z[i]);
+    for (int i = 0; i < C0; ++i) o[i] = noise_mul(sd[i], (T)z[i]);
+    if constexpr (C > 4) {
+        unsigned r1[4];
+        philox4x32_10(s, nz.first + b, t | 0x80000000u, stream, nz.k0, nz.k1, r1);
+        float z1[C - 4];
+        noise_z<C - 4>(nz.dist, r1, z1);
+#pragma unroll
+        for (int i = 4; i < C; ++i) o[i] = noise_mul(sd[i], (T)z1[i - 4]);
+    }
 }
+
+// Does the system take control and state limits (ilqr_set_control_limits, ilqr_set_state_limits)?  A user-defined system
+// does not: its handle can hold none, Limits' arrays are sized for the built-in systems (kBoxMaxU, kALMaxX), and the
+// policy kernels of such a Dyn neither read a bound nor clamp -- the violation is 0.
+template <typename Dyn> constexpr bool takes_limits() { return Dyn::ID != ILQR_SYS_CUSTOM; }
 
 // The rollout of one sample: the body of policy_rollout_kernel (NOISE = false: x_0 and w are the caller's arrays) and
 // of policy_noise_kernel (NOISE = true: drawn here)
@@ -167,6 +185,8 @@ template <typename T, typename Dyn, bool SROWS, bool NOISE>
 ILQR_DEV void policy_rollout_body(const PolicyArgs<T>& a, const NoiseArgs<T>& nz) {
     constexpr int NX = Dyn::NX, NU = Dyn::NU, NSYS = Dyn::NSYS;
     constexpr int R = gain_record(NX, NU);
+    constexpr bool LIM = takes_limits<Dyn>();
+    static_assert(!(SROWS && NSYS == 0), "a system without constants has no per-sample plant rows");
     using PL = ParamLayout<NSYS, NX, NU>;
     const int b = blockIdx.y;
     const int s = blockIdx.x * 64 + threadIdx.x;
@@ -182,8 +202,10 @@ ILQR_DEV void policy_rollout_body(const PolicyArgs<T>& a, const NoiseArgs<T>& nz
         for (int q = 0; q < PL::Q; ++q) mr[q] = a.params[q];
     }
     const PolicyCostParams<T, PL::Q> p{mr, as_uniform(a.params)};
-    T pp[NSYS];      // the plant's system constants (all a step reads)
-    if constexpr (SROWS) {
+    T pp[NSYS > 0 ? NSYS : 1];      // the plant's system constants (all a step reads; none with NSYS = 0: never read)
+    if constexpr (NSYS == 0) {
+        pp[0] = T(0);
+    } else if constexpr (SROWS) {
         load_row<NSYS>(pp, a.srows, L, (int)l);
     } else if (a.plant_rows) {
         load_row<NSYS>(pp, a.plant_rows, B, b);
@@ -192,8 +214,8 @@ ILQR_DEV void policy_rollout_body(const PolicyArgs<T>& a, const NoiseArgs<T>& nz
         for (int q = 0; q < NSYS; ++q) pp[q] = mr[q];
     }
     T blo[NU], bhi[NU];
-    box_bounds<NU>(a.lim, B, b, blo, bhi);
-    const ALBounds<T, NX> xb(a.lim, B, b);
+    if constexpr (LIM) box_bounds<NU>(a.lim, B, b, blo, bhi);
+    const ALBounds<T, LIM ? NX : 1> xb(a.lim, B, b);   // (without limits: never read)
 
     const int slot = a.cur_slot[b];
     const T* Xo = a.X + vec_at(B, N + 1, NX, slot, 0, b);
@@ -257,7 +279,7 @@ ILQR_DEV void policy_rollout_body(const PolicyArgs<T>& a, const NoiseArgs<T>& nz
 #pragma unroll
             for (int i = 0; i < NX; ++i) fb += g[j * NX + i] * dx[i];
             u[j] = a.feedback ? uo[j] + fb : uo[j];
-            u[j] = clamp_keep_nan(u[j], blo[j], bhi[j]);
+            if constexpr (LIM) u[j] = clamp_keep_nan(u[j], blo[j], bhi[j]);
         }
         if (a.Xs) {
 #pragma unroll
@@ -273,11 +295,13 @@ ILQR_DEV void policy_rollout_body(const PolicyArgs<T>& a, const NoiseArgs<T>& nz
 #pragma unroll
         for (int i = 0; i < NX; ++i) x[i] = has_w ? xn[i] + wt[i] : xn[i];
         // the violation of x_{t+1} (t + 1 = 1..N)
+        if constexpr (LIM) {
 #pragma unroll
-        for (int q = 0; q < 2 * NX; ++q) {
-            if ((xb.mask >> q) & 1) {
-                const T c = al_constraint<T, NX>(xb, x, q);
-                viol = c > viol ? c : viol;
+            for (int q = 0; q < 2 * NX; ++q) {
+                if ((xb.mask >> q) & 1) {
+                    const T c = al_constraint<T, NX>(xb, x, q);
+                    viol = c > viol ? c : viol;
+                }
             }
         }
 #pragma unroll

@@ -61,7 +61,8 @@ __global__ void sample_nominal_kernel(T* __restrict__ Ub, const T* __restrict__ 
 template <typename T, typename Dyn>
 __global__ void __launch_bounds__(64) sample_rollout_kernel(SampleArgs<T> a, NoiseArgs<T> nz) {
     constexpr int NX = Dyn::NX, NU = Dyn::NU, NSYS = Dyn::NSYS;
-    static_assert(NU <= 2, "component j of a control takes z_j of one generator call's first pair");
+    static_assert(NU <= 8, "component j of a control takes z_{j mod 4} of the generator call of group j / 4 (noise_draw)");
+    constexpr bool LIM = takes_limits<Dyn>();
     using PL = ParamLayout<NSYS, NX, NU>;
     const int b = blockIdx.y;
     const int s = blockIdx.x * 64 + threadIdx.x;
@@ -78,10 +79,12 @@ __global__ void __launch_bounds__(64) sample_rollout_kernel(SampleArgs<T> a, Noi
     }
     const PolicyCostParams<T, PL::Q> p{mr, as_uniform(a.params)};
     T blo[NU], bhi[NU], sd[NU];
+    if constexpr (LIM) {
 #pragma unroll
-    for (int j = 0; j < NU; ++j) {
-        blo[j] = a.lim.u_lo_rows ? as_uniform(a.lim.u_lo_rows)[(size_t)j * B + b] : a.lim.u_lo[j];
-        bhi[j] = a.lim.u_lo_rows ? as_uniform(a.lim.u_hi_rows)[(size_t)j * B + b] : a.lim.u_hi[j];
+        for (int j = 0; j < NU; ++j) {
+            blo[j] = a.lim.u_lo_rows ? as_uniform(a.lim.u_lo_rows)[(size_t)j * B + b] : a.lim.u_lo[j];
+            bhi[j] = a.lim.u_lo_rows ? as_uniform(a.lim.u_hi_rows)[(size_t)j * B + b] : a.lim.u_hi[j];
+        }
     }
     uniform_load<T, NU>(a.u_std + (size_t)b * NU, sd);
     const bool nominal = s == 0;
@@ -108,7 +111,8 @@ __global__ void __launch_bounds__(64) sample_rollout_kernel(SampleArgs<T> a, Noi
             const T keep = noise_mul(a.beta, e[j]);
             const T add = noise_mul(a.c, n[j]);
             e[j] = t == 0 ? n[j] : keep + add;
-            u[j] = clamp_keep_nan(nominal ? ub[j] : ub[j] + e[j], blo[j], bhi[j]);
+            u[j] = nominal ? ub[j] : ub[j] + e[j];
+            if constexpr (LIM) u[j] = clamp_keep_nan(u[j], blo[j], bhi[j]);
         }
         if (a.Xs) {
 #pragma unroll
@@ -197,7 +201,8 @@ __global__ void __launch_bounds__(64) sample_best_kernel(SampleArgs<T> a, int NU
 // step t of a trajectory, for each j over the contiguous [S] row, each lane over its stride and then a butterfly (a fixed
 // order, no atomics), in double, rounded to T once.  The mean of controls inside the box is inside the box up to the
 // rounding of the sums and the quotient: the clamp takes that last ulp back (a NaN stays NaN).  No finite sample: Ub stays.
-template <typename T, int NU>
+// LIM = false (a system that takes no limits, takes_limits): no bound is read and nothing is clamped.
+template <typename T, int NU, bool LIM = true>
 __global__ void __launch_bounds__(64) sample_softmin_kernel(SampleArgs<T> a) {
     const int b = blockIdx.y, t = blockIdx.x, lane = threadIdx.x, S = a.S;
     const size_t B = a.B, L = B * (size_t)S;
@@ -214,9 +219,13 @@ __global__ void __launch_bounds__(64) sample_softmin_kernel(SampleArgs<T> a) {
             if (wi > 0.0) acc += wi * (double)u[s];
         }
         acc = wave_sum(acc);
-        const T lo = a.lim.u_lo_rows ? a.lim.u_lo_rows[(size_t)j * B + b] : a.lim.u_lo[j];
-        const T hi = a.lim.u_lo_rows ? a.lim.u_hi_rows[(size_t)j * B + b] : a.lim.u_hi[j];
-        if (lane == 0) a.Ub[row * B + b] = clamp_keep_nan((T)(acc / W), lo, hi);
+        T v = (T)(acc / W);
+        if constexpr (LIM) {
+            const T lo = a.lim.u_lo_rows ? a.lim.u_lo_rows[(size_t)j * B + b] : a.lim.u_lo[j];
+            const T hi = a.lim.u_lo_rows ? a.lim.u_hi_rows[(size_t)j * B + b] : a.lim.u_hi[j];
+            v = clamp_keep_nan(v, lo, hi);
+        }
+        if (lane == 0) a.Ub[row * B + b] = v;
     }
 }
 

@@ -23,6 +23,9 @@ namespace ilqr {
 struct SolverBase {
     ilqr_config cfg{};
     std::string err;
+    // the launch table has the policy kernels (Ops::policy): the built-in systems that take limits, and a user-defined
+    // system whose plugin was generated with them.  Read by the ABI's gates of the three entries (ilqr_abi.cpp)
+    bool policy_kernels = false;
     virtual ~SolverBase() {}
     virtual int sync() = 0;
     virtual int set_problem(const void* x0, const void* U) = 0;
@@ -378,6 +381,7 @@ template <typename T> class SolverT : public SolverBase {
             err = "no kernels compiled for this (system, n_x, n_u, dtype)";
             return ILQR_ERR_UNSUPPORTED;
         }
+        policy_kernels = ops.policy != nullptr;
         if (ops.tile_scalars == kTile16M2 && (size_t)N * B * kTile16M2 * sizeof(T) > kDescriptorMax) {
             err = "n_x = 4, n_u = 2: horizon * batch too large for the sweep's 32-bit tile offsets (< 2 GiB of tiles)";
             return ILQR_ERR_UNSUPPORTED;
@@ -1236,6 +1240,11 @@ template <typename T> class SolverT : public SolverBase {
         const std::string who = d.who;
         if (!ops.policy) {
             err = who + ": supported for the pendulum, UA double pendulum and double pendulum only";
+            return ILQR_ERR_UNSUPPORTED;
+        }
+        // (its constants are part of the generated code: the plant can differ from the model in its integrator only)
+        if (d.plant_rows && cfg.system == ILQR_SYS_CUSTOM) {
+            err = who + ": a user-defined system has no parameter rows";
             return ILQR_ERR_UNSUPPORTED;
         }
         if (!have_problem) { err = who + " before set_problem / mpc_reset"; return ILQR_ERR_STATE; }

@@ -171,6 +171,13 @@ PolicyRollout.__doc__ = """Result of iLQR.policy_rollout: cost, deviation, viola
 trajectories=True, X ([B,] S, n_x, N + 1) and U ([B,] S, n_u, N), else None.  A diverged sample has a non-finite cost."""
 
 
+def has_policy_kernels(system):
+    """Does the system's native code carry the policy rollout, Monte Carlo and sampled-search kernels?  The pendulum, UA
+    double pendulum and double pendulum always; a user-defined system (SymbolicSystem) built with policy_kernels=True."""
+    return (getattr(system, "SYSTEM_ID", None) in _lib.BOX_SYSTEMS
+            or (getattr(system, "SYSTEM_ID", None) == _lib.SYS_CUSTOM and bool(getattr(system, "policy_kernels", False))))
+
+
 def policy_rollout_args(system, N, B, batched, n_samples, x_0=None, disturbance=None, plant_params=None, integrator=None):
     """Validated arguments of ``ilqr_policy_rollout`` as (S, x0, w, plant_rows, integrator code): x0 (B, S, n_x), w
     (B, S, N, n_x) as float64 arrays or None, plant_rows (B, S, n_sys) float64 or None, integrator -1 for the solver's
@@ -178,7 +185,7 @@ def policy_rollout_args(system, N, B, batched, n_samples, x_0=None, disturbance=
     plant_params is what ``set_plant_params`` takes per trajectory, here per sample: {name: scalar or ([B,] S)}.
     Raises ValueError for n_samples < 1, a wrong shape, a non-finite plant parameter, an unknown parameter name or
     integrator, or a system without policy rollouts.  Pure host code (no GPU)."""
-    if getattr(system, "SYSTEM_ID", None) not in _lib.BOX_SYSTEMS:
+    if not has_policy_kernels(system):
         raise ValueError(f"policy rollouts are supported for the pendulum, UA double pendulum and double pendulum "
                          f"only, not for {type(system).__name__}")
     if isinstance(n_samples, bool) or int(n_samples) != n_samples or int(n_samples) < 1:
@@ -197,6 +204,9 @@ def policy_rollout_args(system, N, B, batched, n_samples, x_0=None, disturbance=
     x0 = shaped("x_0", x_0, (n,))
     w = shaped("disturbance", disturbance, (int(N), n))
     rows = None
+    if plant_params is not None and getattr(system, "SYSTEM_ID", None) not in _lib.BOX_SYSTEMS:
+        raise ValueError("plant_params: a user-defined system has no parameter rows (its constants are part of the "
+                         "generated code); only the plant's integrator can differ from the model's")
     if plant_params is not None:
         flat = {}
         unknown = sorted(set(plant_params) - set(system.param_names()))
@@ -287,7 +297,7 @@ def sample_controls_args(system, N, B, batched, n_samples, rounds=1, seed=0, u_s
     outside [0, 2^64), a missing, misshapen, negative or non-finite u_std, an unknown mode or distribution, a temperature
     that is not finite and > 0 in "softmin" mode (it is required there), smoothing outside [0, 1), a negative
     first_trajectory or first_round, or first_round + rounds > 2^32 - 2.  Pure host code (no GPU)."""
-    if getattr(system, "SYSTEM_ID", None) not in _lib.BOX_SYSTEMS:
+    if not has_policy_kernels(system):
         raise ValueError(f"the sampled control search is supported for the pendulum, UA double pendulum and double "
                          f"pendulum only, not for {type(system).__name__}")
 

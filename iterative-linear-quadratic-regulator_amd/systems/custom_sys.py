@@ -178,7 +178,7 @@ def generate_cost_bodies(l_fcn, l_f_fcn, n_x, n_u):
     return block([("out", l)]), block(d), block([("out", lf)]), block(df)
 
 
-def render_plugin_source(f_cont, n_x, n_u, dtype, l_fcn=None, l_f_fcn=None):
+def render_plugin_source(f_cont, n_x, n_u, dtype, l_fcn=None, l_f_fcn=None, policy_kernels=False):
     f_body, fjac_body = generate_dyn_bodies(f_cont, n_x, n_u)
     if l_fcn is not None:
         cost = generate_cost_bodies(l_fcn, l_f_fcn, n_x, n_u)
@@ -192,6 +192,11 @@ def render_plugin_source(f_cont, n_x, n_u, dtype, l_fcn=None, l_f_fcn=None):
                      ("@LF_DERIVS_BODY@", cost[3]),
                      ("@DTYPE@", "float" if np.dtype(dtype) == np.float32 else "double")):
         src = src.replace(key, val)
+    if policy_kernels:
+        # read by make_ops (csrc/ops.hpp, policy_system): the plugin then carries the policy rollout, Monte Carlo and
+        # sampled-search kernels.  Part of the source text, so part of build_plugin's cache key; without the flag the
+        # source is what it always was
+        src = "#define ILQR_PLUGIN_POLICY 1\n" + src
     return src
 
 
@@ -275,13 +280,19 @@ class SymbolicSystem(System):
     with sympy expressions; they are differentiated twice symbolically and compiled like the dynamics
     (``_l_fcn`` returns the stage cost exactly as written: multiply by ``self.dt`` yourself if you want the
     reference systems' convention, pendulum_sys.py:86).
+
+    ``policy_kernels=True`` builds the plugin with the kernels of ``iLQR.policy_rollout``, ``policy_monte_carlo`` and
+    ``sample_controls`` for this system (the user's cost as the solver uses it, any of the four integrators as the plant).
+    Off by default: each of those kernels inlines all four integrators around the generated dynamics, which lengthens
+    every build of the plugin (DESIGN.md section 4 has the table); a default plugin is refused by the three calls.
     """
 
     SYSTEM_ID = _lib.SYS_CUSTOM
 
     def __init__(self, n_x, n_u, dt, x_target=None, Q=None, R=None, Q_f=None, use_jit=True, integrator="rk4",
-                 dtype=np.float64):
+                 dtype=np.float64, policy_kernels=False):
         super().__init__(n_x, n_u, dt, use_jit=use_jit, integrator=integrator, dtype=dtype)
+        self.policy_kernels = bool(policy_kernels)
         if not (1 <= self.n_x <= 6 and 1 <= self.n_u <= self.n_x):
             raise ValueError("user-defined systems support 1 <= n_u <= n_x <= 6")
         own_l = type(self)._l_fcn is not SymbolicSystem._l_fcn
@@ -322,7 +333,7 @@ class SymbolicSystem(System):
     def plugin_source(self, dtype=None):
         return render_plugin_source(self._f_cont_fcn, self.n_x, self.n_u, self.dtype if dtype is None else dtype,
                                     self._l_fcn if self.custom_cost else None,
-                                    self._l_f_fcn if self.custom_cost else None)
+                                    self._l_f_fcn if self.custom_cost else None, policy_kernels=self.policy_kernels)
 
     def plugin_path(self, dtype=None, verbose=False):
         dt = np.dtype(self.dtype if dtype is None else dtype)

@@ -139,9 +139,12 @@ class ObstacleUnicycle(Unicycle):
         return 50.0 * (x[0] - self.goal[0]) ** 2 + 50.0 * (x[1] - self.goal[1]) ** 2 + 2.0 * (x[2] - 0.5) ** 2
 
 
-def example_problems(dtype=np.float64, integrator="rk4"):
-    """name -> (system, N, x_0): the cases the tests and build() pre-compile."""
+def example_problems(dtype=np.float64, integrator="rk4", policy_kernels=False):
+    """name -> (system, N, x_0): the cases the tests and build() pre-compile.  policy_kernels=True: every plugin carries
+    the policy rollout, Monte Carlo and sampled-search kernels (custom_sys.SymbolicSystem)."""
     kw = dict(dtype=dtype, integrator=integrator)
+    if policy_kernels:
+        kw["policy_kernels"] = True
     pi = np.pi
     return {
         "sym_pendulum": (SymbolicPendulum(0.02, [pi, 0.0], np.diag([0.1, 0.01]), [[0.01]], np.diag([100.0, 10.0]), **kw),
@@ -159,6 +162,20 @@ def example_problems(dtype=np.float64, integrator="rk4"):
                       50, np.array([0.0, 0.0, 0.0, 0, 0, 0])),
         "swingup_cartpole": (SwingUpCartPole(0.02, **kw), 80, np.array([0.0, 0.3, 0, 0])),
         "obstacle_unicycle": (ObstacleUnicycle(0.05, **kw), 60, np.array([0.0, 0.0, 0.3])),
+    }
+
+
+def policy_example_systems(dtype=np.float64, dt=0.01, integrator="rk4", policy_kernels=True):
+    """name -> system: the three examples that between them cover the policy kernels of a user system (n_x = 6: a second
+    group of noise components; a traced cost; an odd n_x with n_u = 2), built with the policy kernels at one step size
+    (policy_kernels=False: their default twins).
+    The GPU tests of those kernels run on them, and build() pre-compiles them."""
+    kw = dict(dtype=dtype, integrator=integrator, policy_kernels=policy_kernels)
+    return {
+        "quadrotor": PlanarQuadrotor(dt, [1.0, 1.0, 0, 0, 0, 0], np.diag([1.0, 1.0, 1.0, 0.1, 0.1, 0.1]), np.diag([0.1, 0.1]),
+                                     np.diag([100.0, 100.0, 10.0, 10.0, 10.0, 1.0]), **kw),
+        "swingup_cartpole": SwingUpCartPole(dt, **kw),
+        "obstacle_unicycle": ObstacleUnicycle(dt, **kw),
     }
 
 
