@@ -465,7 +465,28 @@ class Handle:
             raise ValueError(f"limit rows must both have shape ({self.B}, row_len), but got {lo.shape} and {hi.shape}")
         self._chk(self.lib.ilqr_set_batch_limits(self.h, int(which), _ptr(lo), _ptr(hi), int(lo.shape[1])))
 
-    # ---- closed-loop policy rollouts ---------------------------------------------------------------
+    # ---- the sampling entries: closed-loop policy rollouts, Monte Carlo, sampled control search --------
+    @staticmethod
+    def _rows_in(d, keep, field, a, shape, what):
+        """d.field <- the float64 array ``a`` of ``shape`` (None in it: any length), kept alive in ``keep``; None: unset."""
+        if a is None:
+            return
+        r = np.ascontiguousarray(a, dtype=np.float64)
+        if r.ndim != len(shape) or any(want is not None and got != want for got, want in zip(r.shape, shape)):
+            want = "(" + ", ".join("n_sys" if n is None else str(n) for n in shape) + ")"
+            raise ValueError(f"{what} must have shape {want}, but got {r.shape}")
+        keep.append(r)
+        setattr(d, field, r.ctypes.data_as(C.POINTER(C.c_double)))
+
+    def _outputs(self, d, shapes, dtypes={}, names={}):
+        """Allocate the outputs named by ``shapes`` (the handle's dtype unless ``dtypes`` says otherwise), write them into
+        the descriptor and return them, under ``names`` where the result's key differs from the field."""
+        out = {}
+        for k, shape in shapes.items():
+            a = out[names.get(k, k)] = np.empty(shape, dtype=dtypes.get(k, self.np_dtype))
+            setattr(d, k, a.ctypes.data_as(type(getattr(d, k))) if k in dtypes else _ptr(a))
+        return out
+
     def policy_rollout(self, n_samples, x0=None, w=None, plant_rows=None, integrator=-1, feedback=True,
                        trajectories=False, outputs=("cost", "x_final", "deviation", "violation")):
         """S = n_samples rollouts per trajectory around the nominal the handle holds (include/ilqr_hip.h,
@@ -484,19 +505,12 @@ class Handle:
         if w is not None:
             keep.append(self._in(w, (B, S, N, n)))
             d.w = _ptr(keep[-1])
-        if plant_rows is not None:
-            r = np.ascontiguousarray(plant_rows, dtype=np.float64)
-            if r.ndim != 3 or r.shape[:2] != (B, S):
-                raise ValueError(f"plant rows must have shape ({B}, {S}, n_sys), but got {r.shape}")
-            keep.append(r)
-            d.plant_rows = r.ctypes.data_as(C.POINTER(C.c_double))
+        self._rows_in(d, keep, "plant_rows", plant_rows, (B, S, None), "plant rows")
         shapes = {"cost": (B, Sa), "x_final": (B, Sa, n), "deviation": (B, Sa), "violation": (B, Sa)}
-        out = {k: np.empty(shapes[k], dtype=self.np_dtype) for k in outputs}
+        shapes = {k: shapes[k] for k in outputs}
         if trajectories:
-            out["X"] = np.empty((B, Sa, n, N + 1), dtype=self.np_dtype)
-            out["U"] = np.empty((B, Sa, m, N), dtype=self.np_dtype)
-        for k, a in out.items():
-            setattr(d, k, _ptr(a))
+            shapes.update(X=(B, Sa, n, N + 1), U=(B, Sa, m, N))
+        out = self._outputs(d, shapes)
         self._chk(self.lib.ilqr_policy_rollout(self.h, C.byref(d)))
         return out
 
@@ -516,44 +530,22 @@ class Handle:
         d.distribution, d.first_trajectory = int(distribution), int(first_trajectory)
         d.seed, d.violation_tol = int(seed) & 0xFFFFFFFFFFFFFFFF, float(violation_tol)
         keep = []
-
-        def rows(a, shape, what):
-            r = np.ascontiguousarray(a, dtype=np.float64)
-            if r.shape != shape:
-                raise ValueError(f"{what} must have shape {shape}, but got {r.shape}")
-            keep.append(r)
-            return r.ctypes.data_as(C.POINTER(C.c_double))
-
-        if x0_std is not None:
-            d.x0_std = rows(x0_std, (B, n), "x0_std")
-        if w_std is not None:
-            d.w_std = rows(w_std, (B, n), "w_std")
-        if plant_rows is not None:
-            r = np.ascontiguousarray(plant_rows, dtype=np.float64)
-            if r.ndim != 3 or r.shape[:2] != (B, S):
-                raise ValueError(f"plant rows must have shape ({B}, {S}, n_sys), but got {r.shape}")
-            keep.append(r)
-            d.plant_rows = r.ctypes.data_as(C.POINTER(C.c_double))
-        out = {}
-        if statistics:
-            out["stats"] = np.empty((B, 7), dtype=np.float64)
-            out["counts"] = np.empty((B, 2), dtype=np.int32)
-            d.stats = out["stats"].ctypes.data_as(C.POINTER(C.c_double))
-            d.counts = out["counts"].ctypes.data_as(C.POINTER(C.c_int32))
+        self._rows_in(d, keep, "x0_std", x0_std, (B, n), "x0_std")
+        self._rows_in(d, keep, "w_std", w_std, (B, n), "w_std")
+        self._rows_in(d, keep, "plant_rows", plant_rows, (B, S, None), "plant rows")
         shapes = {}
+        if statistics:
+            shapes.update(stats=(B, 7), counts=(B, 2))
         if samples:
             shapes.update(cost=(B, Sa), x_final=(B, Sa, n), deviation=(B, Sa), violation=(B, Sa))
         if trajectories:
             shapes.update(X=(B, Sa, n, N + 1), U=(B, Sa, m, N))
         if noise:
             shapes.update(x0_out=(B, Sa, n), w_out=(B, Sa, N, n))
-        for k, shape in shapes.items():
-            out[k] = np.empty(shape, dtype=self.np_dtype)
-            setattr(d, k, _ptr(out[k]))
+        out = self._outputs(d, shapes, dtypes={"stats": np.float64, "counts": np.int32})
         self._chk(self.lib.ilqr_policy_monte_carlo(self.h, C.byref(d)))
         return out
 
-    # ---- sampled control search --------------------------------------------------------------------
     def sample_controls(self, n_samples, rounds=1, seed=0, u_std=None, mode=SAMPLE_BEST, temperature=1.0, smoothing=0.0,
                         distribution=NOISE_GAUSSIAN, first_trajectory=0, first_round=0, samples=False, trajectories=False,
                         summaries=True):
@@ -569,30 +561,17 @@ class Handle:
         d.n_samples, d.n_rounds, d.mode, d.distribution = S, R, int(mode), int(distribution)
         d.first_trajectory, d.first_round = int(first_trajectory), int(first_round)
         d.seed, d.temperature, d.smoothing = int(seed) & 0xFFFFFFFFFFFFFFFF, float(temperature), float(smoothing)
-        std = None
-        if u_std is not None:
-            std = np.ascontiguousarray(u_std, dtype=np.float64)
-            if std.shape != (B, m):
-                raise ValueError(f"u_std must have shape {(B, m)}, but got {std.shape}")
-            d.u_std = std.ctypes.data_as(C.POINTER(C.c_double))
-        out = {}
-        if summaries:
-            out["round_stats"] = np.empty((Ra, B, 3), dtype=np.float64)
-            out["round_counts"] = np.empty((Ra, B), dtype=np.int32)
-            d.round_stats = out["round_stats"].ctypes.data_as(C.POINTER(C.c_double))
-            d.round_counts = out["round_counts"].ctypes.data_as(C.POINTER(C.c_int32))
+        keep = []
+        self._rows_in(d, keep, "u_std", u_std, (B, m), "u_std")
         shapes = {}
         if summaries:
-            shapes.update(U_new=(B, m, N), cost_new=(B,))
+            shapes.update(round_stats=(Ra, B, 3), round_counts=(Ra, B), U_new=(B, m, N), cost_new=(B,))
         if trajectories:
             shapes.update(X_new=(B, n, N + 1))
         if samples:
             shapes.update(cost_samples=(B, Sa), U_samples=(B, Sa, m, N))
-        names = {"U_new": "U", "cost_new": "cost", "X_new": "X"}
-        for k, shape in shapes.items():
-            a = np.empty(shape, dtype=self.np_dtype)
-            out[names.get(k, k)] = a
-            setattr(d, k, _ptr(a))
+        out = self._outputs(d, shapes, dtypes={"round_stats": np.float64, "round_counts": np.int32},
+                            names={"U_new": "U", "cost_new": "cost", "X_new": "X"})
         self._chk(self.lib.ilqr_sample_controls(self.h, C.byref(d)))
         return out
 

@@ -46,6 +46,22 @@ static int fail_create(int code, const std::string& msg) {
     return code;
 }
 
+// The sampling entries' common refusals: a null handle, a system without the kernels, a descriptor of another size
+// (ILQR_OK: the entry goes on to the handle)
+template <typename D> static int sampling_entry(ilqr_handle h, const D* d, const char* who, const char* desc_type) {
+    if (!h || !h->impl) return ILQR_ERR_INVALID_ARG;
+    const ilqr_config& c = h->impl->cfg;
+    if (c.system == ILQR_SYS_LINEAR || (c.system == ILQR_SYS_CUSTOM && !h->impl->policy_kernels)) {
+        h->impl->err = std::string(who) + ": not supported for linear or user-defined systems";
+        return ILQR_ERR_UNSUPPORTED;
+    }
+    if (!d || d->struct_size != sizeof(D)) {
+        h->impl->err = std::string(who) + ": desc is NULL or struct_size does not match this library's " + desc_type;
+        return ILQR_ERR_INVALID_ARG;
+    }
+    return ILQR_OK;
+}
+
 extern "C" {
 
 int ilqr_abi_version(void) { return ILQR_ABI_VERSION; }
@@ -281,43 +297,16 @@ int ilqr_set_batch_limits(ilqr_handle h, int which, const double* lo, const doub
     return h->impl->set_batch_limits(which, lo, hi, row_len);
 }
 int ilqr_policy_rollout(ilqr_handle h, const ilqr_policy_rollout_desc* d) {
-    if (!h || !h->impl) return ILQR_ERR_INVALID_ARG;
-    const ilqr_config& c = h->impl->cfg;
-    if (c.system == ILQR_SYS_LINEAR || (c.system == ILQR_SYS_CUSTOM && !h->impl->policy_kernels)) {
-        h->impl->err = "policy_rollout: not supported for linear or user-defined systems";
-        return ILQR_ERR_UNSUPPORTED;
-    }
-    if (!d || d->struct_size != sizeof(ilqr_policy_rollout_desc)) {
-        h->impl->err = "policy_rollout: desc is NULL or struct_size does not match this library's ilqr_policy_rollout_desc";
-        return ILQR_ERR_INVALID_ARG;
-    }
-    return h->impl->policy_rollout(*d);
+    const int rc = sampling_entry(h, d, "policy_rollout", "ilqr_policy_rollout_desc");
+    return rc ? rc : h->impl->policy_rollout(*d);
 }
 int ilqr_policy_monte_carlo(ilqr_handle h, const ilqr_monte_carlo_desc* d) {
-    if (!h || !h->impl) return ILQR_ERR_INVALID_ARG;
-    const ilqr_config& c = h->impl->cfg;
-    if (c.system == ILQR_SYS_LINEAR || (c.system == ILQR_SYS_CUSTOM && !h->impl->policy_kernels)) {
-        h->impl->err = "policy_monte_carlo: not supported for linear or user-defined systems";
-        return ILQR_ERR_UNSUPPORTED;
-    }
-    if (!d || d->struct_size != sizeof(ilqr_monte_carlo_desc)) {
-        h->impl->err = "policy_monte_carlo: desc is NULL or struct_size does not match this library's ilqr_monte_carlo_desc";
-        return ILQR_ERR_INVALID_ARG;
-    }
-    return h->impl->policy_monte_carlo(*d);
+    const int rc = sampling_entry(h, d, "policy_monte_carlo", "ilqr_monte_carlo_desc");
+    return rc ? rc : h->impl->policy_monte_carlo(*d);
 }
 int ilqr_sample_controls(ilqr_handle h, const ilqr_sample_controls_desc* d) {
-    if (!h || !h->impl) return ILQR_ERR_INVALID_ARG;
-    const ilqr_config& c = h->impl->cfg;
-    if (c.system == ILQR_SYS_LINEAR || (c.system == ILQR_SYS_CUSTOM && !h->impl->policy_kernels)) {
-        h->impl->err = "sample_controls: not supported for linear or user-defined systems";
-        return ILQR_ERR_UNSUPPORTED;
-    }
-    if (!d || d->struct_size != sizeof(ilqr_sample_controls_desc)) {
-        h->impl->err = "sample_controls: desc is NULL or struct_size does not match this library's ilqr_sample_controls_desc";
-        return ILQR_ERR_INVALID_ARG;
-    }
-    return h->impl->sample_controls(*d);
+    const int rc = sampling_entry(h, d, "sample_controls", "ilqr_sample_controls_desc");
+    return rc ? rc : h->impl->sample_controls(*d);
 }
 int ilqr_timing_enable(ilqr_handle h, int on) { ILQR_FWD(h, timing_enable(on)); }
 int ilqr_timing_reset(ilqr_handle h) { ILQR_FWD(h, timing_reset()); }

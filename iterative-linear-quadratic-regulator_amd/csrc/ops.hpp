@@ -77,6 +77,19 @@ template <typename T> bool ring_rollout_ok(const KArgs<T>& a, int nx, int nu) {
     return !forward_plain() && std::max(bytes_x, bytes_g) <= kDescriptorMax;
 }
 
+// The sampling entries (ilqr_policy_rollout, ilqr_policy_monte_carlo, ilqr_sample_controls: policy_rollout.hpp,
+// sample_controls.hpp): all set or, where the system does not have them, all null.
+template <typename T> struct SamplingOps {
+    // the closed-loop rollout; [1]: with x_0 and w drawn on the device ([0] does not read its NoiseArgs)
+    void (*policy[2])(const PolicyArgs<T>&, const NoiseArgs<T>&, hipStream_t) = {};
+    // the search: the private copy of the nominal, the rollout of a round's samples (S = 1: of the nominal alone), and the
+    // round's weights and update of Ub
+    void (*begin)(const SampleArgs<T>&, hipStream_t) = nullptr;
+    void (*rollout)(const SampleArgs<T>&, const NoiseArgs<T>&, hipStream_t) = nullptr;
+    void (*update)(const SampleArgs<T>&, hipStream_t) = nullptr;
+    explicit operator bool() const { return rollout != nullptr; }
+};
+
 template <typename T> struct Ops {
     void (*linearize[5])(const KArgs<T>&, hipStream_t) = {};  // indexed by ilqr_integrator
     void (*backward)(const KArgs<T>&, hipStream_t) = nullptr;
@@ -114,15 +127,7 @@ template <typename T> struct Ops {
     void (*al_update)(const KArgs<T>&, const ALArgs<T>&, hipStream_t) = nullptr;
     void (*al_cost)(const KArgs<T>&, const ALArgs<T>&, hipStream_t) = nullptr;
     void (*mpc_advance_al)(const MpcALArgs<T>&, hipStream_t) = nullptr;   // the epilogue of a state-limited MPC step
-    // closed-loop policy rollouts (ilqr_policy_rollout, policy_rollout.hpp); null where they are not supported
-    void (*policy)(const PolicyArgs<T>&, hipStream_t) = nullptr;
-    // the same with x_0 and w drawn on the device (ilqr_policy_monte_carlo): set wherever `policy` is
-    void (*policy_noise)(const PolicyArgs<T>&, const NoiseArgs<T>&, hipStream_t) = nullptr;
-    // sampled control search (ilqr_sample_controls, sample_controls.hpp), set wherever `policy` is: the private copy of the
-    // nominal, the rollout of a round's samples (S = 1: of the nominal alone), and the round's weights and update of Ub
-    void (*sample_begin)(const SampleArgs<T>&, hipStream_t) = nullptr;
-    void (*sample_rollout)(const SampleArgs<T>&, const NoiseArgs<T>&, hipStream_t) = nullptr;
-    void (*sample_update)(const SampleArgs<T>&, hipStream_t) = nullptr;
+    SamplingOps<T> sampling;   // null where the sampling entries are not supported
 };
 
 // linearize / forward are compiled once per integrator so the integrator switch folds away and each
@@ -273,33 +278,23 @@ void launch_forward(const KArgs<T>& a, hipStream_t s) {
         ILQR_LAUNCH_HET(HETS, a.het, (forward_kernel<T, Dyn, I>), (forward_kernel_het<T, Dyn, I>), grid, block, 0, s, a);
 }
 
-// S samples per trajectory, one wave per 64 samples of one trajectory (policy_rollout.hpp); the SROWS instantiation where
-// the call brings per-sample plant constants
-// (a Dyn without system constants has no such rows: its SROWS kernels are never instantiated, and the handle refuses
-// plant_rows before a launch)
-template <typename T, typename Dyn> void launch_policy(const PolicyArgs<T>& a, hipStream_t s) {
+// S samples per trajectory, one wave per 64 samples of one trajectory (sampled_rollout, policy_rollout.hpp) under the
+// feedback law; NOISE: x_0 and w drawn on the device; the SROWS instantiation where the call brings per-sample plant
+// constants (a Dyn without system constants has no such rows: its SROWS kernels are never instantiated, and the handle
+// refuses plant_rows before a launch)
+template <typename T, typename Dyn, bool NOISE> void launch_policy(const PolicyArgs<T>& a, const NoiseArgs<T>& nz, hipStream_t s) {
     const dim3 grid((a.S + 63) / 64, a.B), block(64);
+    auto launch = [&](auto srows) {
+        if constexpr (NOISE) ILQR_LAUNCH((policy_noise_kernel<T, Dyn, decltype(srows)::value>), grid, block, 0, s, a, nz);
+        else ILQR_LAUNCH((policy_rollout_kernel<T, Dyn, decltype(srows)::value>), grid, block, 0, s, a);
+    };
     if constexpr (Dyn::NSYS > 0) {
-        if (a.srows) {
-            ILQR_LAUNCH((policy_rollout_kernel<T, Dyn, true>), grid, block, 0, s, a);
-            return;
-        }
+        if (a.srows) return launch(std::true_type{});
     }
-    ILQR_LAUNCH((policy_rollout_kernel<T, Dyn, false>), grid, block, 0, s, a);
-}
-// the NOISE instantiations of the same body (ilqr_policy_monte_carlo), same mapping
-template <typename T, typename Dyn> void launch_policy_noise(const PolicyArgs<T>& a, const NoiseArgs<T>& nz, hipStream_t s) {
-    const dim3 grid((a.S + 63) / 64, a.B), block(64);
-    if constexpr (Dyn::NSYS > 0) {
-        if (a.srows) {
-            ILQR_LAUNCH((policy_noise_kernel<T, Dyn, true>), grid, block, 0, s, a, nz);
-            return;
-        }
-    }
-    ILQR_LAUNCH((policy_noise_kernel<T, Dyn, false>), grid, block, 0, s, a, nz);
+    launch(std::false_type{});
 }
 
-// sampled control search (sample_controls.hpp): the rollout has the policy rollout's mapping; the weights are one wave
+// sampled control search (sample_controls.hpp): the same rollout under the perturbation law; the weights are one wave
 // per trajectory; the update is one lane (BEST) or one wave (SOFTMIN) per (t, j) of a trajectory
 template <typename T, typename Dyn> void launch_sample_begin(const SampleArgs<T>& a, hipStream_t s) {
     const size_t n = (size_t)a.B * a.N * Dyn::NU;
@@ -435,11 +430,8 @@ template <typename T, typename Dyn> Ops<T> make_ops() {
         };
     }
     if constexpr (policy_system<Dyn>()) {
-        o.policy = launch_policy<T, Dyn>;
-        o.policy_noise = launch_policy_noise<T, Dyn>;
-        o.sample_begin = launch_sample_begin<T, Dyn>;
-        o.sample_rollout = launch_sample_rollout<T, Dyn>;
-        o.sample_update = launch_sample_update<T, Dyn>;
+        o.sampling = {{launch_policy<T, Dyn, false>, launch_policy<T, Dyn, true>}, launch_sample_begin<T, Dyn>,
+                      launch_sample_rollout<T, Dyn>, launch_sample_update<T, Dyn>};
     }
     o.eval = [](const EvalArgs<T>& a, hipStream_t s) {
         ILQR_LAUNCH((eval_points_kernel<T, Dyn>), dim3((a.npts + 63) / 64), dim3(64), 0, s, a);

@@ -176,87 +176,146 @@ ILQR_DEV void noise_draw(const NoiseArgs<T>& nz, unsigned s, unsigned b, unsigne
 
 // Does the system take control and state limits (ilqr_set_control_limits, ilqr_set_state_limits)?  A user-defined system
 // does not: its handle can hold none, Limits' arrays are sized for the built-in systems (kBoxMaxU, kALMaxX), and the
-// policy kernels of such a Dyn neither read a bound nor clamp -- the violation is 0.
+// sampling kernels of such a Dyn neither read a bound nor clamp -- the violation is 0.
 template <typename Dyn> constexpr bool takes_limits() { return Dyn::ID != ILQR_SYS_CUSTOM; }
 
-// The rollout of one sample: the body of policy_rollout_kernel (NOISE = false: x_0 and w are the caller's arrays) and
-// of policy_noise_kernel (NOISE = true: drawn here)
-template <typename T, typename Dyn, bool SROWS, bool NOISE>
-ILQR_DEV void policy_rollout_body(const PolicyArgs<T>& a, const NoiseArgs<T>& nz) {
-    constexpr int NX = Dyn::NX, NU = Dyn::NU, NSYS = Dyn::NSYS;
-    constexpr int R = gain_record(NX, NU);
+// the control bounds of trajectory b, wave-uniform: its rows where limits were given per trajectory, else the shared ones
+template <int NU, typename T> ILQR_DEV void uniform_box_bounds(const Limits<T>& a, size_t B, int b, T* lo, T* hi) {
+#pragma unroll
+    for (int j = 0; j < NU; ++j) {
+        lo[j] = a.u_lo_rows ? as_uniform(a.u_lo_rows)[(size_t)j * B + b] : a.u_lo[j];
+        hi[j] = a.u_lo_rows ? as_uniform(a.u_hi_rows)[(size_t)j * B + b] : a.u_hi[j];
+    }
+}
+
+// sample s of trajectory b: l = b * S + s of the L = B * S samples of a call
+struct SampleAt { int b, s; size_t B, L, l; };
+
+// ---- the sampled rollout: S samples of trajectory b, one wave per 64 of them -----------------------------------------
+// The one rollout of every sampling entry.  It owns what they share -- the lane's sample and the tail guard, the model
+// row (or the block) and the cost's parameters, the control bounds and the clamp, the state from the trajectory's x_0,
+// the Xs / Us stores, the stage cost before the step and the terminal cost last, the cost store -- and asks a control
+// law for the rest: Law(a, nz, k, mr, x) reads the law's wave-uniform inputs and step 0's nominal and may replace or
+// perturb x = x_0[b]; pp is the constants the integrator reads; control(t, tn, x, u) requests step tn = min(t + 1, N - 1)'s
+// nominal and draws step t's noise (nothing of either depends on the state: they stand in front of step t's arithmetic)
+// and forms u_t before the clamp; advance(t, x, xn) moves x and the nominal on to t + 1; finish(x) stores what the law
+// reports beside the cost.  Args (PolicyArgs, SampleArgs) brings B, S, N, integ, dt, params, rows, x0, lim, cost, Xs, Us.
+template <typename T, typename Dyn, typename Law, typename Args>
+ILQR_DEV void sampled_rollout(const Args& a, const NoiseArgs<T>& nz) {
+    constexpr int NX = Dyn::NX, NU = Dyn::NU;
     constexpr bool LIM = takes_limits<Dyn>();
-    static_assert(!(SROWS && NSYS == 0), "a system without constants has no per-sample plant rows");
-    using PL = ParamLayout<NSYS, NX, NU>;
+    using PL = ParamLayout<Dyn::NSYS, NX, NU>;
     const int b = blockIdx.y;
     const int s = blockIdx.x * 64 + threadIdx.x;
     if (s >= a.S) return;
     const size_t B = a.B, L = B * (size_t)a.S, l = (size_t)b * a.S + s;
     const int N = a.N;
-    // wave-uniform: the trajectory's model row (or the block), its plant constants, its limits
+    // wave-uniform: the trajectory's model row (or the block), its limits
     T mr[PL::Q];
-    if (a.rows) {
-        load_row<PL::Q>(mr, a.rows, B, b);
-    } else {
+    const uniform_ptr<T> row = a.rows ? as_uniform(a.rows) + b : as_uniform(a.params);
+    const size_t row_stride = a.rows ? B : 1;
 #pragma unroll
-        for (int q = 0; q < PL::Q; ++q) mr[q] = a.params[q];
-    }
+    for (int i = 0; i < PL::Q; ++i) mr[i] = row[(size_t)i * row_stride];
     const PolicyCostParams<T, PL::Q> p{mr, as_uniform(a.params)};
-    T pp[NSYS > 0 ? NSYS : 1];      // the plant's system constants (all a step reads; none with NSYS = 0: never read)
-    if constexpr (NSYS == 0) {
-        pp[0] = T(0);
-    } else if constexpr (SROWS) {
-        load_row<NSYS>(pp, a.srows, L, (int)l);
-    } else if (a.plant_rows) {
-        load_row<NSYS>(pp, a.plant_rows, B, b);
-    } else {
-#pragma unroll
-        for (int q = 0; q < NSYS; ++q) pp[q] = mr[q];
-    }
     T blo[NU], bhi[NU];
-    if constexpr (LIM) box_bounds<NU>(a.lim, B, b, blo, bhi);
-    const ALBounds<T, LIM ? NX : 1> xb(a.lim, B, b);   // (without limits: never read)
-
-    const int slot = a.cur_slot[b];
-    const T* Xo = a.X + vec_at(B, N + 1, NX, slot, 0, b);
-    const T* Uo = a.U + vec_at(B, N, NU, slot, 0, b);
-    const T* G = a.gains + (size_t)b * R;
-    const size_t sX = B * NX, sU = B * NU, sG = B * R;
+    if constexpr (LIM) uniform_box_bounds<NU>(a.lim, B, b, blo, bhi);
 
     T x[NX], u[NU];
 #pragma unroll
-    for (int i = 0; i < NX; ++i) x[i] = a.x0s ? a.x0s[(size_t)i * L + l] : a.x0[(size_t)i * B + b];
-    T wsd[NX];       // w_std[b], wave-uniform
-    if constexpr (NOISE) {
-        if (nz.x0_std) {
-            T sd[NX], e[NX];
-            uniform_load<T, NX>(nz.x0_std + (size_t)b * NX, sd);
-            noise_draw<T, NX>(nz, (unsigned)s, (unsigned)b, 0u, 1u, sd, e);
+    for (int i = 0; i < NX; ++i) x[i] = as_uniform(a.x0)[(size_t)i * B + b];
+    Law law(a, nz, SampleAt{b, s, B, L, l}, mr, x);
+    T cost = T(0);
+    auto store_x = [&](int t) {
+        if (!a.Xs) return;
 #pragma unroll
-            for (int i = 0; i < NX; ++i) x[i] += e[i];
-        }
-        if (nz.x0_out) {
-#pragma unroll
-            for (int i = 0; i < NX; ++i) nz.x0_out[(size_t)i * L + l] = x[i];
-        }
-        if (nz.w_std) uniform_load<T, NX>(nz.w_std + (size_t)b * NX, wsd);
-    }
-    const bool has_w = NOISE ? nz.w_std != nullptr : a.w != nullptr;
-    T xo[NX], uo[NU], g[R], xo_n[NX], uo_n[NU], g_n[R];
-    uniform_load<T, NX>(Xo, xo);
-    uniform_load<T, NU>(Uo, uo);
-    uniform_load<T, R>(G, g);
-    T cost = T(0), dev = T(0), viol = T(0);
+        for (int i = 0; i < NX; ++i) a.Xs[((size_t)t * NX + i) * L + l] = x[i];
+    };
     for (int t = 0; t < N; ++t) {
-        // step t + 1's nominal is requested before step t's arithmetic (X_{t+1} always exists; U and the gains end at N - 1)
-        const int tn = (t + 1 < N) ? t + 1 : t;
-        uniform_load<T, NX>(Xo + (size_t)(t + 1) * sX, xo_n);
-        uniform_load<T, NU>(Uo + (size_t)tn * sU, uo_n);
-        uniform_load<T, R>(G + (size_t)tn * sG, g_n);
-        T wt[NX];
+        law.control(t, (t + 1 < N) ? t + 1 : t, x, u);
+        if constexpr (LIM) {
+#pragma unroll
+            for (int j = 0; j < NU; ++j) u[j] = clamp_keep_nan(u[j], blo[j], bhi[j]);
+        }
+        store_x(t);
+        if (a.Us) {
+#pragma unroll
+            for (int j = 0; j < NU; ++j) a.Us[((size_t)t * NU + j) * L + l] = u[j];
+        }
+        cost += Cost<T, Dyn>::stage(p, a.dt, x, u);
+        T xn[NX];
+        Stepper<T, Dyn>::step(a.integ, law.pp, a.dt, x, u, xn);
+        law.advance(t, x, xn);
+    }
+    store_x(N);
+    cost += Cost<T, Dyn>::terminal(p, x);
+    a.cost[l] = cost;
+    law.finish(x);
+}
+
+// The feedback law (ilqr_policy_rollout; NOISE: ilqr_policy_monte_carlo, x_0 and w drawn here):
+//   u_t = U_t + K_t (x_t - X_t), or U_t without feedback;  x_{t+1} = f_plant(x_t, u_t) + w_t
+// It reports the largest |x_t - X_t| and the largest state-limit violation of x_1 .. x_N, and x_N.
+template <typename T, typename Dyn, bool SROWS, bool NOISE> struct FeedbackLaw {
+    static constexpr int NX = Dyn::NX, NU = Dyn::NU, NSYS = Dyn::NSYS, R = gain_record(NX, NU);
+    static constexpr bool LIM = takes_limits<Dyn>();
+    static_assert(!(SROWS && NSYS == 0), "a system without constants has no per-sample plant rows");
+    const PolicyArgs<T>& a;
+    const NoiseArgs<T>& nz;
+    const SampleAt k;
+    T pp[NSYS > 0 ? NSYS : 1] = {};   // the plant's system constants (all a step reads; none with NSYS = 0: never read)
+    const ALBounds<T, LIM ? NX : 1> xb;   // (without limits: never read)
+    const T *Xo, *Uo, *G;           // the nominal of b's current slot, wave-uniform
+    T xo[NX], uo[NU], g[R], xo_n[NX], uo_n[NU], g_n[R];
+    T wsd[NX], wt[NX];              // w_std[b] (wave-uniform) and the disturbance of the step
+    bool has_w;
+    T dev = T(0), viol = T(0);
+
+    ILQR_DEV FeedbackLaw(const PolicyArgs<T>& a_, const NoiseArgs<T>& nz_, const SampleAt& k_, T* mr, T (&x)[NX])
+        : a(a_), nz(nz_), k(k_), xb(a_.lim, k_.B, k_.b) {
+        const size_t B = k.B, L = k.L, l = k.l, b = k.b;
+        if constexpr (SROWS) {
+            load_row<NSYS>(pp, a.srows, L, (int)l);
+        } else if (a.plant_rows) {
+            load_row<NSYS>(pp, a.plant_rows, B, k.b);
+        } else {
+#pragma unroll
+            for (int q = 0; q < NSYS; ++q) pp[q] = mr[q];
+        }
+        const int slot = a.cur_slot[b];
+        Xo = a.X + vec_at(B, a.N + 1, NX, slot, 0, b);
+        Uo = a.U + vec_at(B, a.N, NU, slot, 0, b);
+        G = a.gains + (size_t)b * R;
+        if (a.x0s) {
+#pragma unroll
+            for (int i = 0; i < NX; ++i) x[i] = a.x0s[(size_t)i * L + l];
+        }
+        if constexpr (NOISE) {
+            if (nz.x0_std) {
+                T sd[NX], e[NX];
+                uniform_load<T, NX>(nz.x0_std + (size_t)b * NX, sd);
+                noise_draw<T, NX>(nz, (unsigned)k.s, (unsigned)k.b, 0u, 1u, sd, e);
+#pragma unroll
+                for (int i = 0; i < NX; ++i) x[i] += e[i];
+            }
+            if (nz.x0_out) {
+#pragma unroll
+                for (int i = 0; i < NX; ++i) nz.x0_out[(size_t)i * L + l] = x[i];
+            }
+            if (nz.w_std) uniform_load<T, NX>(nz.w_std + (size_t)b * NX, wsd);
+        }
+        has_w = NOISE ? nz.w_std != nullptr : a.w != nullptr;
+        uniform_load<T, NX>(Xo, xo);
+        uniform_load<T, NU>(Uo, uo);
+        uniform_load<T, R>(G, g);
+    }
+    ILQR_DEV void control(int t, int tn, const T (&x)[NX], T (&u)[NU]) {
+        const size_t B = k.B, L = k.L, l = k.l;
+        uniform_load<T, NX>(Xo + (size_t)(t + 1) * (B * NX), xo_n);      // (X_{t+1} always exists)
+        uniform_load<T, NU>(Uo + (size_t)tn * (B * NU), uo_n);
+        uniform_load<T, R>(G + (size_t)tn * (B * R), g_n);
         if constexpr (NOISE) {
             if (has_w) {
-                noise_draw<T, NX>(nz, (unsigned)s, (unsigned)b, (unsigned)t, 0u, wsd, wt);
+                noise_draw<T, NX>(nz, (unsigned)k.s, (unsigned)k.b, (unsigned)t, 0u, wsd, wt);
                 if (nz.w_out) {
 #pragma unroll
                     for (int i = 0; i < NX; ++i) nz.w_out[((size_t)t * NX + i) * L + l] = wt[i];
@@ -279,19 +338,9 @@ ILQR_DEV void policy_rollout_body(const PolicyArgs<T>& a, const NoiseArgs<T>& nz
 #pragma unroll
             for (int i = 0; i < NX; ++i) fb += g[j * NX + i] * dx[i];
             u[j] = a.feedback ? uo[j] + fb : uo[j];
-            if constexpr (LIM) u[j] = clamp_keep_nan(u[j], blo[j], bhi[j]);
         }
-        if (a.Xs) {
-#pragma unroll
-            for (int i = 0; i < NX; ++i) a.Xs[((size_t)t * NX + i) * L + l] = x[i];
-        }
-        if (a.Us) {
-#pragma unroll
-            for (int j = 0; j < NU; ++j) a.Us[((size_t)t * NU + j) * L + l] = u[j];
-        }
-        cost += Cost<T, Dyn>::stage(p, a.dt, x, u);
-        T xn[NX];
-        Stepper<T, Dyn>::step(a.integ, pp, a.dt, x, u, xn);
+    }
+    ILQR_DEV void advance(int, T (&x)[NX], const T (&xn)[NX]) {
 #pragma unroll
         for (int i = 0; i < NX; ++i) x[i] = has_w ? xn[i] + wt[i] : xn[i];
         // the violation of x_{t+1} (t + 1 = 1..N)
@@ -311,28 +360,27 @@ ILQR_DEV void policy_rollout_body(const PolicyArgs<T>& a, const NoiseArgs<T>& nz
 #pragma unroll
         for (int r = 0; r < R; ++r) g[r] = g_n[r];
     }
+    ILQR_DEV void finish(const T (&x)[NX]) {
 #pragma unroll
-    for (int i = 0; i < NX; ++i) {
-        const T e = x[i] - xo[i];        // xo holds X_N
-        const T d = e < T(0) ? -e : e;
-        dev = d > dev ? d : dev;
-        a.x_final[(size_t)i * L + l] = x[i];
-        if (a.Xs) a.Xs[((size_t)N * NX + i) * L + l] = x[i];
+        for (int i = 0; i < NX; ++i) {
+            const T e = x[i] - xo[i];        // xo holds X_N
+            const T d = e < T(0) ? -e : e;
+            dev = d > dev ? d : dev;
+            a.x_final[(size_t)i * k.L + k.l] = x[i];
+        }
+        a.deviation[k.l] = dev;
+        a.violation[k.l] = viol;
     }
-    cost += Cost<T, Dyn>::terminal(p, x);
-    a.cost[l] = cost;
-    a.deviation[l] = dev;
-    a.violation[l] = viol;
-}
+};
 
 template <typename T, typename Dyn, bool SROWS>
 __global__ void __launch_bounds__(64) policy_rollout_kernel(PolicyArgs<T> a) {
-    policy_rollout_body<T, Dyn, SROWS, false>(a, NoiseArgs<T>{});
+    sampled_rollout<T, Dyn, FeedbackLaw<T, Dyn, SROWS, false>>(a, NoiseArgs<T>{});
 }
 
 template <typename T, typename Dyn, bool SROWS>
 __global__ void __launch_bounds__(64) policy_noise_kernel(PolicyArgs<T> a, NoiseArgs<T> nz) {
-    policy_rollout_body<T, Dyn, SROWS, true>(a, nz);
+    sampled_rollout<T, Dyn, FeedbackLaw<T, Dyn, SROWS, true>>(a, nz);
 }
 
 // Per-trajectory statistics of a Monte Carlo call: one wave per trajectory over its contiguous [S] rows of the sample

@@ -7,9 +7,9 @@
 //   n_t = u_std[b] (.) z(b, s, t, stream),   e_0 = n_0,   e_t = beta e_{t-1} + c n_t,   c = sqrt(1 - beta^2)
 //   u_t = clamp(Ub_t + e_t),   x_{t+1} = f_model(x_t, u_t),   J_s = sum_t l(x_t, u_t) + l_f(x_N)
 // Sample 0 of every round is the nominal itself (e = 0, nothing drawn).
-// Mapping of the rollout: the policy rollout's (policy_rollout.hpp) -- one wave = 64 samples of ONE trajectory, so Ub_t,
-// the bounds, the model row and u_std are wave-uniform and come through the scalar unit; per-lane outputs are
-// sample-innermost.  The draw and the recurrence stand at the head of the step: nothing of them depends on the state.
+// The rollout is sampled_rollout (policy_rollout.hpp) under the perturbation law below: one wave = 64 samples of ONE
+// trajectory, so Ub_t, the bounds, the model row and u_std are wave-uniform and come through the scalar unit; per-lane
+// outputs are sample-innermost.
 // Three launches per round (rollout, weights, update), all on the handle's stream and on a private copy of U
 // ([N][n_u][B]): no host synchronisation between rounds.
 #pragma once
@@ -56,86 +56,53 @@ __global__ void sample_nominal_kernel(T* __restrict__ Ub, const T* __restrict__ 
     Ub[idx] = U[vec_at((size_t)B, N, NU, cur_slot[b], t, (size_t)b) + j];
 }
 
-// The rollout of one sample.  Launched with S = 1 it is the rollout of the nominal alone (cost_new / X_new): the same
-// code on the same controls, so the cost of a BEST call's result is the winning sample's cost bit for bit.
-template <typename T, typename Dyn>
-__global__ void __launch_bounds__(64) sample_rollout_kernel(SampleArgs<T> a, NoiseArgs<T> nz) {
-    constexpr int NX = Dyn::NX, NU = Dyn::NU, NSYS = Dyn::NSYS;
+// The perturbation law: e_0 = n_0, e_t = beta e_{t-1} + c n_t, u_t = Ub_t + e_t through the model itself; sample 0 is the
+// nominal (e = 0: its draw is made and dropped).
+template <typename T, typename Dyn> struct PerturbLaw {
+    static constexpr int NX = Dyn::NX, NU = Dyn::NU;
     static_assert(NU <= 8, "component j of a control takes z_{j mod 4} of the generator call of group j / 4 (noise_draw)");
-    constexpr bool LIM = takes_limits<Dyn>();
-    using PL = ParamLayout<NSYS, NX, NU>;
-    const int b = blockIdx.y;
-    const int s = blockIdx.x * 64 + threadIdx.x;
-    if (s >= a.S) return;
-    const size_t B = a.B, L = B * (size_t)a.S, l = (size_t)b * a.S + s;
-    const int N = a.N;
-    // wave-uniform: the trajectory's model row (or the block), its limits, its standard deviations
-    T mr[PL::Q];
-    {
-        const uniform_ptr<T> q = a.rows ? as_uniform(a.rows) + b : as_uniform(a.params);
-        const size_t st = a.rows ? B : 1;
-#pragma unroll
-        for (int i = 0; i < PL::Q; ++i) mr[i] = q[(size_t)i * st];
-    }
-    const PolicyCostParams<T, PL::Q> p{mr, as_uniform(a.params)};
-    T blo[NU], bhi[NU], sd[NU];
-    if constexpr (LIM) {
+    const SampleArgs<T>& a;
+    const NoiseArgs<T>& nz;
+    const SampleAt k;
+    T* const pp;                                  // the model's own constants
+    T sd[NU], e[NU], n[NU], ub[NU], ub_n[NU];     // u_std[b], Ub_t and Ub_{t+1}: wave-uniform
+
+    ILQR_DEV PerturbLaw(const SampleArgs<T>& a_, const NoiseArgs<T>& nz_, const SampleAt& k_, T* mr, T (&)[NX])
+        : a(a_), nz(nz_), k(k_), pp(mr) {
+        uniform_load<T, NU>(a.u_std + (size_t)k.b * NU, sd);
 #pragma unroll
         for (int j = 0; j < NU; ++j) {
-            blo[j] = a.lim.u_lo_rows ? as_uniform(a.lim.u_lo_rows)[(size_t)j * B + b] : a.lim.u_lo[j];
-            bhi[j] = a.lim.u_lo_rows ? as_uniform(a.lim.u_hi_rows)[(size_t)j * B + b] : a.lim.u_hi[j];
+            e[j] = T(0);
+            ub[j] = as_uniform(a.Ub)[(size_t)j * k.B + k.b];
         }
     }
-    uniform_load<T, NU>(a.u_std + (size_t)b * NU, sd);
-    const bool nominal = s == 0;
-
-    T x[NX], u[NU], e[NU], ub[NU], ub_n[NU];
+    ILQR_DEV void control(int t, int tn, const T (&)[NX], T (&u)[NU]) {
 #pragma unroll
-    for (int i = 0; i < NX; ++i) x[i] = as_uniform(a.x0)[(size_t)i * B + b];
-#pragma unroll
-    for (int j = 0; j < NU; ++j) {
-        e[j] = T(0);
-        ub[j] = as_uniform(a.Ub)[(size_t)j * B + b];
-    }
-    T cost = T(0);
-    for (int t = 0; t < N; ++t) {
-        // step t + 1's nominal is requested before step t's arithmetic
-        const int tn = (t + 1 < N) ? t + 1 : t;
-#pragma unroll
-        for (int j = 0; j < NU; ++j) ub_n[j] = as_uniform(a.Ub)[((size_t)tn * NU + j) * B + b];
-        T n[NU];
-        noise_draw<T, NU>(nz, (unsigned)s, (unsigned)b, (unsigned)t, a.stream, sd, n);
+        for (int j = 0; j < NU; ++j) ub_n[j] = as_uniform(a.Ub)[((size_t)tn * NU + j) * k.B + k.b];
+        noise_draw<T, NU>(nz, (unsigned)k.s, (unsigned)k.b, (unsigned)t, a.stream, sd, n);
 #pragma unroll
         for (int j = 0; j < NU; ++j) {
             // two products rounded on their own and one add (noise_mul is never contracted with what follows)
             const T keep = noise_mul(a.beta, e[j]);
             const T add = noise_mul(a.c, n[j]);
             e[j] = t == 0 ? n[j] : keep + add;
-            u[j] = nominal ? ub[j] : ub[j] + e[j];
-            if constexpr (LIM) u[j] = clamp_keep_nan(u[j], blo[j], bhi[j]);
+            u[j] = k.s == 0 ? ub[j] : ub[j] + e[j];     // sample 0 is the nominal
         }
-        if (a.Xs) {
-#pragma unroll
-            for (int i = 0; i < NX; ++i) a.Xs[((size_t)t * NX + i) * L + l] = x[i];
-        }
-        if (a.Us) {
-#pragma unroll
-            for (int j = 0; j < NU; ++j) a.Us[((size_t)t * NU + j) * L + l] = u[j];
-        }
-        cost += Cost<T, Dyn>::stage(p, a.dt, x, u);
-        T xn[NX];
-        Stepper<T, Dyn>::step(a.integ, mr, a.dt, x, u, xn);
+    }
+    ILQR_DEV void advance(int, T (&x)[NX], const T (&xn)[NX]) {
 #pragma unroll
         for (int i = 0; i < NX; ++i) x[i] = xn[i];
 #pragma unroll
         for (int j = 0; j < NU; ++j) ub[j] = ub_n[j];
     }
-    if (a.Xs) {
-#pragma unroll
-        for (int i = 0; i < NX; ++i) a.Xs[((size_t)N * NX + i) * L + l] = x[i];
-    }
-    cost += Cost<T, Dyn>::terminal(p, x);
-    a.cost[l] = cost;
+    ILQR_DEV void finish(const T (&)[NX]) {}
+};
+
+// The rollout of a round's samples.  Launched with S = 1 it is the rollout of the nominal alone (cost_new / X_new): the
+// same code on the same controls, so the cost of a BEST call's result is the winning sample's cost bit for bit.
+template <typename T, typename Dyn>
+__global__ void __launch_bounds__(64) sample_rollout_kernel(SampleArgs<T> a, NoiseArgs<T> nz) {
+    sampled_rollout<T, Dyn, PerturbLaw<T, Dyn>>(a, nz);
 }
 
 // The weights of a round: one wave per trajectory over its contiguous [S] costs, each lane over its stride of the row and
@@ -209,6 +176,8 @@ __global__ void __launch_bounds__(64) sample_softmin_kernel(SampleArgs<T> a) {
     const double W = a.wsum[b];
     if (!(W > 0.0)) return;
     const double* w = a.w + (size_t)b * S;
+    T blo[NU], bhi[NU];
+    if constexpr (LIM) uniform_box_bounds<NU>(a.lim, B, b, blo, bhi);
 #pragma unroll
     for (int j = 0; j < NU; ++j) {
         const size_t row = (size_t)t * NU + j;
@@ -221,9 +190,7 @@ __global__ void __launch_bounds__(64) sample_softmin_kernel(SampleArgs<T> a) {
         acc = wave_sum(acc);
         T v = (T)(acc / W);
         if constexpr (LIM) {
-            const T lo = a.lim.u_lo_rows ? a.lim.u_lo_rows[(size_t)j * B + b] : a.lim.u_lo[j];
-            const T hi = a.lim.u_lo_rows ? a.lim.u_hi_rows[(size_t)j * B + b] : a.lim.u_hi[j];
-            v = clamp_keep_nan(v, lo, hi);
+            v = clamp_keep_nan(v, blo[j], bhi[j]);
         }
         if (lane == 0) a.Ub[row * B + b] = v;
     }

@@ -11,6 +11,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <initializer_list>
 #include <limits>
 #include <string>
 #include <utility>
@@ -227,6 +228,24 @@ template <typename T> struct DeviceState {
     bool box_lin_valid = false;                   // the last linearize wrote box_lin (not lin)
 };
 
+// The workspace of the sampling entries (ilqr_policy_rollout, ilqr_policy_monte_carlo, ilqr_sample_controls), with
+// L = B * S samples, sample-innermost.  A buffer is allocated by the first call that needs it and grown, never shrunk
+// (SolverT::grow); every call that touches one ends synchronised, so the entries share them.
+template <typename T> struct SamplingBufs {
+    // per-sample summaries: cost, deviation, violation [L] each and x_final [n_x][L] (policy); cost [L] and the nominal's
+    // cost [B] behind it (search)
+    DevBuf<T> summaries;
+    DevBuf<T> controls, states;   // Us [N][n_u][L]; Xs [N+1][n_x][L] (search: of the final nominal rollout, [N+1][n_x][B])
+    DevBuf<T> x0, w, plant;       // per-sample inputs [n_x][L], [N][n_x][L], [n_sys][L]; x0 / w also the drawn ones on their way back
+    DevBuf<T> std;                // rows of standard deviations [.][B][C] in the handle's dtype (up_std)
+    std::vector<T> std_host;
+    DevBuf<T> nominal;            // the search's private Ub [N][n_u][B]
+    DevBuf<double> weights;       // the search's w [L] and W [B]
+    DevBuf<int> winners;          // [B]
+    DevBuf<double> stats;         // Monte Carlo [B][7]; search [R][B][3]
+    DevBuf<int> counts;           // Monte Carlo [B][2]; search [R][B]
+};
+
 // per-trajectory parameters (ilqr_set_batch_params): rows [n_sys + n_x][B] of the model (derived constants, x_target),
 // plant_rows [n_sys][B] of the MPC plant; device tensors of the handle's dtype
 template <typename T> struct BatchParams {
@@ -307,21 +326,7 @@ template <typename T> class SolverT : public SolverBase {
     BoundSet<T> box;        // control limits (ilqr_set_control_limits, ilqr_set_batch_limits): u_min <= u <= u_max
     BatchParams<T> het;
     StateLimits<T> al;
-    // ilqr_policy_rollout: per-sample inputs and outputs, sample-innermost; allocated at the first call that needs them and
-    // grown, never shrunk (pr_X / pr_U only by calls that ask for the sample trajectories)
-    DevBuf<T> pr_x0, pr_w, pr_rows, pr_sum, pr_X, pr_U;
-    // ilqr_policy_monte_carlo: the standard deviations [2][B][n_x] and the per-trajectory statistics [B][7], [B][2]
-    DevBuf<T> pr_std;
-    std::vector<T> pr_std_host;
-    DevBuf<double> pr_stats;
-    DevBuf<int> pr_counts;
-    // ilqr_sample_controls: the private nominal [N][n_u][B], u_std [B][n_u], the weights [B * S] and W [B], the winners
-    // [B], the rounds' statistics [R][B][3] and counts [R][B]; grown like the pr_* buffers, which hold the per-sample
-    // costs (pr_sum), controls (pr_U) and the final rollout's states (pr_X)
-    DevBuf<T> sc_U, sc_std;
-    std::vector<T> sc_std_host;
-    DevBuf<double> sc_w, sc_stats;
-    DevBuf<int> sc_sel, sc_counts;
+    SamplingBufs<T> smp;
 
     // (the device buffers free themselves after this body: DevBuf)
     ~SolverT() override {
@@ -381,7 +386,7 @@ template <typename T> class SolverT : public SolverBase {
             err = "no kernels compiled for this (system, n_x, n_u, dtype)";
             return ILQR_ERR_UNSUPPORTED;
         }
-        policy_kernels = ops.policy != nullptr;
+        policy_kernels = (bool)ops.sampling;
         if (ops.tile_scalars == kTile16M2 && (size_t)N * B * kTile16M2 * sizeof(T) > kDescriptorMax) {
             err = "n_x = 4, n_u = 2: horizon * batch too large for the sweep's 32-bit tile offsets (< 2 GiB of tiles)";
             return ILQR_ERR_UNSUPPORTED;
@@ -509,6 +514,17 @@ template <typename T> class SolverT : public SolverBase {
     }
     int down_tc(void* host, const T* dev, int C, int Tn) {
         return stage_down(host, (size_t)B * C * Tn, ILQR_STAGED((layout_tc_kernel<T, false>), dev, B, C, Tn));
+    }
+    // the samples' tensors: [t][n_x][L] <-> host [B][S][t][n_x] (layout_tc_kernel with the samples as its batch axis), and
+    // [t][c][L] -> host [L][c][t]
+    int up_tcl(const void* host, T* dev, size_t L, int Tn) {
+        return stage_up(host, L * NX * (size_t)Tn, ILQR_STAGED((layout_tc_kernel<T, true>), dev, (int)L, NX, Tn));
+    }
+    int down_tcl(void* host, const T* dev, size_t L, int Tn) {
+        return stage_down(host, L * NX * (size_t)Tn, ILQR_STAGED((layout_tc_kernel<T, false>), dev, (int)L, NX, Tn));
+    }
+    int down_traj(void* host, const T* dev, size_t L, int C, int Tn) {
+        return stage_down(host, L * C * (size_t)Tn, ILQR_STAGED(layout_ctl_gather_kernel<T>, dev, L, C, Tn));
     }
     int up_gain_K(const void* host, T* gains) {
         return stage_up(host, (size_t)B * N * NU * NX, ILQR_STAGED((layout_gain_K_kernel<T, true>), gains, B, N, NU * NX, R));
@@ -1192,7 +1208,7 @@ template <typename T> class SolverT : public SolverBase {
         return ILQR_OK;
     }
 
-    // ---- closed-loop policy rollouts (policy_rollout.hpp) ---------------------------------
+    // ---- the sampling entries (policy_rollout.hpp, sample_controls.hpp) ---------------------
     // grow-only: `count` elements, or what the buffer already holds when that is enough (nothing queued uses it: every
     // call that touches these buffers ends synchronised)
     template <typename U> int grow(DevBuf<U>& buf, size_t count) {
@@ -1201,8 +1217,47 @@ template <typename T> class SolverT : public SolverBase {
         ILQR_HIPCHK(buf.alloc(count));
         return ILQR_OK;
     }
+    // The rules every sampling entry shares, one message each.  An entry asks them at the places of its own validation
+    // sequence, so a call that breaks two rules gets the answer it always got: the system has the kernels; a problem is
+    // set; S >= 1; L = B * S < 2^31; then the solver state is settled for reading.
+    int fail(int code, std::string msg) { err = std::move(msg); return code; }
+    int sampling_supported(const std::string& who) {
+        return ops.sampling ? ILQR_OK : fail(ILQR_ERR_UNSUPPORTED, who + ": supported for the pendulum, UA double pendulum and double pendulum only");
+    }
+    int sampling_problem(const std::string& who) { return have_problem ? ILQR_OK : fail(ILQR_ERR_STATE, who + " before set_problem / mpc_reset"); }
+    int sample_count(const std::string& who, int n) { return n >= 1 ? ILQR_OK : fail(ILQR_ERR_INVALID_ARG, who + ": n_samples must be >= 1"); }
+    int sample_total(const std::string& who, int n, size_t* L) {
+        *L = (size_t)B * (size_t)n;
+        return *L <= (size_t)std::numeric_limits<int>::max() ? ILQR_OK : fail(ILQR_ERR_INVALID_ARG, who + ": batch * n_samples must be < 2^31");
+    }
+    int sampling_settle() {
+        const int rc = flush_select();
+        return rc ? rc : fix_slots(st);
+    }
+    static NoiseArgs<T> noise_args(unsigned long long seed, int first_trajectory, int distribution) {
+        NoiseArgs<T> nz{};
+        nz.k0 = (unsigned)(seed & 0xffffffffull); nz.k1 = (unsigned)(seed >> 32);
+        nz.first = (unsigned)first_trajectory;
+        nz.dist = distribution;
+        return nz;
+    }
+    // rows of [B][C] standard deviations (nullptr: zeros), cast to T, one behind the other at smp.std in one copy
+    // (smp.std_host outlives the copy: the call ends synchronised before the next one can write it again)
+    int up_std(std::initializer_list<const double*> rows, int C) {
+        const size_t n = (size_t)B * C;
+        if (int rc = grow(smp.std, rows.size() * n)) return rc;
+        smp.std_host.assign(rows.size() * n, T(0));
+        size_t at = 0;
+        for (const double* r : rows) {
+            for (size_t i = 0; r && i < n; ++i) smp.std_host[at + i] = (T)r[i];
+            at += n;
+        }
+        ILQR_HIPCHK(hipMemcpyAsync(smp.std.p, smp.std_host.data(), smp.std_host.size() * sizeof(T), hipMemcpyHostToDevice, stream));
+        return ILQR_OK;
+    }
+
     // S samples per trajectory around the nominal (X, U, K of the current slots) the handle holds.  Reads the solver state
-    // and writes only the pr_* buffers and `staging`: nothing another entry reads changes.
+    // and writes only `smp` and `staging`: nothing another entry reads changes.
     int policy_rollout(const ilqr_policy_rollout_desc& d) override {
         PolicyCall c{"policy_rollout", d.n_samples, d.integrator, d.feedback, d.x0, d.w, d.plant_rows,
                      d.cost, d.x_final, d.deviation, d.violation, d.X, d.U};
@@ -1210,11 +1265,11 @@ template <typename T> class SolverT : public SolverBase {
     }
     // The same rollout with x_0 and w drawn on the device (policy_noise_kernel) and the per-trajectory statistics of its
     // sample summaries (policy_stats_kernel).  What crosses to the device is the seed and two [B][n_x] rows of standard
-    // deviations; pr_w is touched only when the disturbances are asked back.  Only what the noise and the statistics add is
+    // deviations; smp.w is touched only when the disturbances are asked back.  Only what the noise and the statistics add is
     // checked here: policy_call refuses the rest (no such kernels, no problem set, n_samples, integrator, plant_rows).
     int policy_monte_carlo(const ilqr_monte_carlo_desc& d) override {
         const char* who = "policy_monte_carlo";
-        auto bad = [&](const char* what) { err = std::string(who) + ": " + what; return ILQR_ERR_INVALID_ARG; };
+        auto bad = [&](const char* what) { return fail(ILQR_ERR_INVALID_ARG, std::string(who) + ": " + what); };
         if (d.distribution != ILQR_NOISE_GAUSSIAN && d.distribution != ILQR_NOISE_UNIFORM) return bad("unknown distribution");
         if (d.first_trajectory < 0) return bad("first_trajectory must be >= 0");
         if (!(d.violation_tol >= 0.0)) return bad("violation_tol must be >= 0 (and not NaN)");
@@ -1238,53 +1293,34 @@ template <typename T> class SolverT : public SolverBase {
     };
     int policy_call(const PolicyCall& d, const ilqr_monte_carlo_desc* mc) {
         const std::string who = d.who;
-        if (!ops.policy) {
-            err = who + ": supported for the pendulum, UA double pendulum and double pendulum only";
-            return ILQR_ERR_UNSUPPORTED;
-        }
-        // (its constants are part of the generated code: the plant can differ from the model in its integrator only)
-        if (d.plant_rows && cfg.system == ILQR_SYS_CUSTOM) {
-            err = who + ": a user-defined system has no parameter rows";
-            return ILQR_ERR_UNSUPPORTED;
-        }
-        if (!have_problem) { err = who + " before set_problem / mpc_reset"; return ILQR_ERR_STATE; }
-        if (d.n_samples < 1) { err = who + ": n_samples must be >= 1"; return ILQR_ERR_INVALID_ARG; }
-        if (d.integrator > ILQR_INT_DISCRETE) { err = who + ": unknown integrator"; return ILQR_ERR_INVALID_ARG; }
-        if (!mc && !d.cost && !d.x_final && !d.deviation && !d.violation && !d.X && !d.U) {
-            err = who + ": every output is NULL";
-            return ILQR_ERR_INVALID_ARG;
-        }
-        const size_t S = (size_t)d.n_samples, L = (size_t)B * S;
-        if (L > (size_t)std::numeric_limits<int>::max()) { err = who + ": batch * n_samples must be < 2^31"; return ILQR_ERR_INVALID_ARG; }
-        const int ns = n_sys_abi();
-        if (d.plant_rows) {
-            for (size_t i = 0; i < L * ns; ++i)
-                if (!std::isfinite(d.plant_rows[i])) { err = who + ": every plant_rows value must be finite"; return ILQR_ERR_INVALID_ARG; }
-        }
         int rc;
-        if ((rc = flush_select())) return rc;
-        if ((rc = fix_slots(st))) return rc;
+        size_t L;
+        if ((rc = sampling_supported(who))) return rc;
+        // (its constants are part of the generated code: the plant can differ from the model in its integrator only)
+        if (d.plant_rows && cfg.system == ILQR_SYS_CUSTOM) return fail(ILQR_ERR_UNSUPPORTED, who + ": a user-defined system has no parameter rows");
+        if ((rc = sampling_problem(who)) || (rc = sample_count(who, d.n_samples))) return rc;
+        if (d.integrator > ILQR_INT_DISCRETE) return fail(ILQR_ERR_INVALID_ARG, who + ": unknown integrator");
+        if (!mc && !d.cost && !d.x_final && !d.deviation && !d.violation && !d.X && !d.U)
+            return fail(ILQR_ERR_INVALID_ARG, who + ": every output is NULL");
+        if ((rc = sample_total(who, d.n_samples, &L))) return rc;
+        const int ns = n_sys_abi();
+        for (size_t i = 0; d.plant_rows && i < L * ns; ++i)
+            if (!std::isfinite(d.plant_rows[i])) return fail(ILQR_ERR_INVALID_ARG, who + ": every plant_rows value must be finite");
+        if ((rc = sampling_settle())) return rc;
         const size_t nX = L * NX * (size_t)(N + 1), nU = L * NU * (size_t)N, nW = L * NX * (size_t)N;
         // the disturbances a Monte Carlo call was asked to return (none are drawn without w_std: those are zeros)
         const bool w_back = mc && mc->w_out && mc->w_std;
-        if ((rc = grow(pr_sum, L * (size_t)(3 + NX)))) return rc;
-        if ((d.x0 || (mc && mc->x0_out)) && (rc = grow(pr_x0, L * NX))) return rc;
-        if ((d.w || w_back) && (rc = grow(pr_w, nW))) return rc;
-        if (d.plant_rows && (rc = grow(pr_rows, L * (size_t)ops.n_sys_dev))) return rc;
-        if (d.X && (rc = grow(pr_X, nX))) return rc;
-        if (d.U && (rc = grow(pr_U, nU))) return rc;
+        if ((rc = grow(smp.summaries, L * (size_t)(3 + NX)))) return rc;
+        if ((d.x0 || (mc && mc->x0_out)) && (rc = grow(smp.x0, L * NX))) return rc;
+        if ((d.w || w_back) && (rc = grow(smp.w, nW))) return rc;
+        if (d.plant_rows && (rc = grow(smp.plant, L * (size_t)ops.n_sys_dev))) return rc;
+        if (d.X && (rc = grow(smp.states, nX))) return rc;
+        if (d.U && (rc = grow(smp.controls, nU))) return rc;
         if ((rc = grow(staging, std::max({L * NX, (d.w || w_back) ? nW : (size_t)0, d.X ? nX : (size_t)0, d.U ? nU : (size_t)0})))) return rc;
-        const int Li = (int)L;
-        // host [B][S][c] / [B][S][N][c] -> [c][L] / [N][c][L]: layout_tc_kernel with the samples as its batch axis
-        auto up = [&](const void* host, T* dev, int Tn) {
-            return stage_up(host, L * NX * (size_t)Tn, [&](dim3 g_, dim3 b_) {
-                hipLaunchKernelGGL((layout_tc_kernel<T, true>), g_, b_, 0, stream, staging.p, dev, Li, NX, Tn);
-            });
-        };
-        if (d.x0 && (rc = up(d.x0, pr_x0, 1))) return rc;
-        if (d.w && (rc = up(d.w, pr_w, N))) return rc;
+        if (d.x0 && (rc = up_tcl(d.x0, smp.x0, L, 1))) return rc;
+        if (d.w && (rc = up_tcl(d.w, smp.w, L, N))) return rc;
         // derived in double by the formulas of the block's own constants, as the rows of ilqr_set_batch_params
-        if (d.plant_rows && (rc = derive_rows(d.plant_rows, ns, L, ops.n_sys_dev, pr_rows))) return rc;
+        if (d.plant_rows && (rc = derive_rows(d.plant_rows, ns, L, ops.n_sys_dev, smp.plant))) return rc;
         PolicyArgs<T> a{};
         a.B = B; a.S = d.n_samples; a.N = N; a.n_slots = st.n_slots;
         a.integ = d.integrator >= 0 ? d.integrator : cfg.plant_integrator >= 0 ? cfg.plant_integrator : cfg.integrator;
@@ -1293,78 +1329,56 @@ template <typename T> class SolverT : public SolverBase {
         a.X = st.X; a.U = st.U; a.gains = st.gains; a.cur_slot = st.cur_slot; a.params = params; a.x0 = st.x0;
         a.rows = het.on() ? het.rows.p : nullptr;
         a.plant_rows = het.plant_set ? het.plant_rows.p : nullptr;
-        a.x0s = d.x0 ? pr_x0.p : nullptr;
-        a.w = d.w ? pr_w.p : nullptr;
-        a.srows = d.plant_rows ? pr_rows.p : nullptr;
+        a.x0s = d.x0 ? smp.x0.p : nullptr;
+        a.w = d.w ? smp.w.p : nullptr;
+        a.srows = d.plant_rows ? smp.plant.p : nullptr;
         a.lim = limits();
-        a.cost = pr_sum; a.deviation = pr_sum + L; a.violation = pr_sum + 2 * L; a.x_final = pr_sum + 3 * L;
-        a.Xs = d.X ? pr_X.p : nullptr;
-        a.Us = d.U ? pr_U.p : nullptr;
+        a.cost = smp.summaries; a.deviation = a.cost + L; a.violation = a.cost + 2 * L; a.x_final = a.cost + 3 * L;
+        a.Xs = d.X ? smp.states.p : nullptr;
+        a.Us = d.U ? smp.controls.p : nullptr;
+        NoiseArgs<T> nz{};
         if (mc) {
-            // the standard deviations in the handle's dtype, [2][B][n_x] (x0_std, w_std), and the statistics
+            // the standard deviations [2][B][n_x] (x0_std, w_std), and the statistics
             const size_t nsd = (size_t)B * NX;
-            if ((rc = grow(pr_std, 2 * nsd)) || (rc = grow(pr_stats, (size_t)B * 7)) || (rc = grow(pr_counts, (size_t)B * 2))) return rc;
-            // (pr_std_host outlives the copy: the call ends synchronised before the next one can write it again)
-            pr_std_host.assign(2 * nsd, T(0));
-            for (size_t i = 0; i < nsd; ++i) {
-                if (mc->x0_std) pr_std_host[i] = (T)mc->x0_std[i];
-                if (mc->w_std) pr_std_host[nsd + i] = (T)mc->w_std[i];
-            }
-            ILQR_HIPCHK(hipMemcpyAsync(pr_std.p, pr_std_host.data(), 2 * nsd * sizeof(T), hipMemcpyHostToDevice, stream));
-            NoiseArgs<T> nz{};
-            nz.k0 = (unsigned)(mc->seed & 0xffffffffull); nz.k1 = (unsigned)(mc->seed >> 32);
-            nz.first = (unsigned)mc->first_trajectory;
-            nz.dist = mc->distribution;
-            nz.x0_std = mc->x0_std ? pr_std.p : nullptr;
-            nz.w_std = mc->w_std ? pr_std.p + nsd : nullptr;
-            nz.x0_out = mc->x0_out ? pr_x0.p : nullptr;
-            nz.w_out = w_back ? pr_w.p : nullptr;
-            if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.policy_noise(a, nz, stream); }))) return rc;
-            if (mc->stats || mc->counts) {
-                hipLaunchKernelGGL(policy_stats_kernel<T>, dim3(B), dim3(64), 0, stream, (const T*)a.cost, (const T*)a.deviation,
-                                   (const T*)a.violation, d.n_samples, mc->violation_tol, pr_stats.p, pr_counts.p);
-                if (mc->stats) ILQR_HIPCHK(hipMemcpyAsync(mc->stats, pr_stats.p, (size_t)B * 7 * sizeof(double), hipMemcpyDeviceToHost, stream));
-                if (mc->counts) ILQR_HIPCHK(hipMemcpyAsync(mc->counts, pr_counts.p, (size_t)B * 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
-            }
-        } else {
-            if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.policy(a, stream); }))) return rc;
+            if ((rc = grow(smp.stats, (size_t)B * 7)) || (rc = grow(smp.counts, (size_t)B * 2)) || (rc = up_std({mc->x0_std, mc->w_std}, NX))) return rc;
+            nz = noise_args(mc->seed, mc->first_trajectory, mc->distribution);
+            nz.x0_std = mc->x0_std ? smp.std.p : nullptr;
+            nz.w_std = mc->w_std ? smp.std.p + nsd : nullptr;
+            nz.x0_out = mc->x0_out ? smp.x0.p : nullptr;
+            nz.w_out = w_back ? smp.w.p : nullptr;
+        }
+        if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.policy[mc != nullptr](a, nz, stream); }))) return rc;
+        if (mc && (mc->stats || mc->counts)) {
+            hipLaunchKernelGGL(policy_stats_kernel<T>, dim3(B), dim3(64), 0, stream, (const T*)a.cost, (const T*)a.deviation,
+                               (const T*)a.violation, d.n_samples, mc->violation_tol, smp.stats.p, smp.counts.p);
+            if (mc->stats) ILQR_HIPCHK(hipMemcpyAsync(mc->stats, smp.stats.p, (size_t)B * 7 * sizeof(double), hipMemcpyDeviceToHost, stream));
+            if (mc->counts) ILQR_HIPCHK(hipMemcpyAsync(mc->counts, smp.counts.p, (size_t)B * 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
         }
         auto fetch = [&](void* host, const T* dev) -> int {
             if (host) ILQR_HIPCHK(hipMemcpyAsync(host, dev, L * sizeof(T), hipMemcpyDeviceToHost, stream));
             return ILQR_OK;
         };
         if ((rc = fetch(d.cost, a.cost)) || (rc = fetch(d.deviation, a.deviation)) || (rc = fetch(d.violation, a.violation))) return rc;
-        // [t][c][L] -> host [B][S][t][c]
-        auto down_tcl = [&](void* host, const T* dev, int Tn) {
-            return stage_down(host, L * NX * (size_t)Tn, [&](dim3 g_, dim3 b_) {
-                hipLaunchKernelGGL((layout_tc_kernel<T, false>), g_, b_, 0, stream, staging.p, dev, Li, NX, Tn);
-            });
-        };
-        if (d.x_final && (rc = down_tcl(d.x_final, a.x_final, 1))) return rc;
-        if (mc && mc->x0_out && (rc = down_tcl(mc->x0_out, pr_x0, 1))) return rc;
-        if (w_back && (rc = down_tcl(mc->w_out, pr_w, N))) return rc;
+        if (d.x_final && (rc = down_tcl(d.x_final, a.x_final, L, 1))) return rc;
+        if (mc && mc->x0_out && (rc = down_tcl(mc->x0_out, smp.x0, L, 1))) return rc;
+        if (w_back && (rc = down_tcl(mc->w_out, smp.w, L, N))) return rc;
         if (mc && mc->w_out && !w_back) std::memset(mc->w_out, 0, nW * sizeof(T));
-        // [t][c][L] -> host [B][S][c][t]
-        auto down_traj = [&](void* host, const T* dev, int C, int Tn) {
-            return stage_down(host, L * C * (size_t)Tn, [&](dim3 g_, dim3 b_) {
-                hipLaunchKernelGGL(layout_ctl_gather_kernel<T>, g_, b_, 0, stream, staging.p, dev, L, C, Tn);
-            });
-        };
-        if (d.X && (rc = down_traj(d.X, pr_X, NX, N + 1))) return rc;
-        if (d.U && (rc = down_traj(d.U, pr_U, NU, N))) return rc;
+        if (d.X && (rc = down_traj(d.X, smp.states, L, NX, N + 1))) return rc;
+        if (d.U && (rc = down_traj(d.U, smp.controls, L, NU, N))) return rc;
         ILQR_HIPCHK(hipStreamSynchronize(stream));
         return check_launch();
     }
 
-    // ---- sampled control search (sample_controls.hpp) ---------------------------------------
     // R rounds of (rollout of S samples, weights, update of the private nominal), then the nominal's own rollout: every
     // kernel of the search is queued on the stream without a host synchronisation in between.  The downloads follow the
     // last of them (the staged ones, which convert the layout through `staging`, each end synchronised).  Reads
-    // the solver state and writes only the sc_* / pr_* buffers and `staging`: nothing another entry reads changes.
+    // the solver state and writes only `smp` and `staging`: nothing another entry reads changes.
     int sample_controls(const ilqr_sample_controls_desc& d) override {
         const std::string who = "sample_controls";
-        auto bad = [&](const char* what) { err = who + ": " + what; return ILQR_ERR_INVALID_ARG; };
-        if (d.n_samples < 1) return bad("n_samples must be >= 1");
+        auto bad = [&](const char* what) { return fail(ILQR_ERR_INVALID_ARG, who + ": " + what); };
+        int rc;
+        size_t L;
+        if ((rc = sample_count(who, d.n_samples))) return rc;
         if (d.n_rounds < 1) return bad("n_rounds must be >= 1");
         if (d.mode != ILQR_SAMPLE_BEST && d.mode != ILQR_SAMPLE_SOFTMIN) return bad("unknown mode");
         if (d.distribution != ILQR_NOISE_GAUSSIAN && d.distribution != ILQR_NOISE_UNIFORM) return bad("unknown distribution");
@@ -1384,28 +1398,19 @@ template <typename T> class SolverT : public SolverBase {
             return bad("temperature must be finite and > 0");
         if (!d.U_new && !d.cost_new && !d.X_new && !d.round_stats && !d.round_counts && !d.cost_samples && !d.U_samples)
             return bad("every output is NULL");
-        const size_t S = (size_t)d.n_samples, L = (size_t)B * S, Rn = (size_t)d.n_rounds;
-        if (L > (size_t)std::numeric_limits<int>::max()) return bad("batch * n_samples must be < 2^31");
-        if (!ops.sample_rollout) {
-            err = who + ": supported for the pendulum, UA double pendulum and double pendulum only";
-            return ILQR_ERR_UNSUPPORTED;
-        }
-        if (!have_problem) { err = who + " before set_problem / mpc_reset"; return ILQR_ERR_STATE; }
-        int rc;
-        if ((rc = flush_select())) return rc;
-        if ((rc = fix_slots(st))) return rc;
-        const size_t nU = L * NU * (size_t)N, nUb = (size_t)B * NU * N, nXb = (size_t)B * NX * (N + 1);
-        // (pr_U: the update reads every sample's controls as the rollout stored them)
-        if ((rc = grow(pr_sum, L + (size_t)B)) || (rc = grow(pr_U, nU)) || (rc = grow(sc_U, nUb)) ||
-            (rc = grow(sc_std, (size_t)B * NU)) || (rc = grow(sc_w, L + (size_t)B)) || (rc = grow(sc_sel, (size_t)B)) ||
-            (rc = grow(sc_stats, Rn * B * 3)) || (rc = grow(sc_counts, Rn * B)))
+        if ((rc = sample_total(who, d.n_samples, &L)) || (rc = sampling_supported(who)) || (rc = sampling_problem(who)) ||
+            (rc = sampling_settle()))
             return rc;
-        if (d.X_new && (rc = grow(pr_X, nXb))) return rc;
+        const size_t Rn = (size_t)d.n_rounds;
+        const size_t nU = L * NU * (size_t)N, nUb = (size_t)B * NU * N, nXb = (size_t)B * NX * (N + 1);
+        // (controls: the update reads every sample's controls as the rollout stored them)
+        if ((rc = grow(smp.summaries, L + (size_t)B)) || (rc = grow(smp.controls, nU)) || (rc = grow(smp.nominal, nUb)) ||
+            (rc = grow(smp.weights, L + (size_t)B)) || (rc = grow(smp.winners, (size_t)B)) ||
+            (rc = grow(smp.stats, Rn * B * 3)) || (rc = grow(smp.counts, Rn * B)))
+            return rc;
+        if (d.X_new && (rc = grow(smp.states, nXb))) return rc;
         if ((rc = grow(staging, std::max({nUb, d.X_new ? nXb : (size_t)0, d.U_samples ? nU : (size_t)0})))) return rc;
-        // (sc_std_host outlives the copy: the call ends synchronised before the next one can write it again)
-        sc_std_host.resize((size_t)B * NU);
-        for (size_t i = 0; i < sc_std_host.size(); ++i) sc_std_host[i] = (T)d.u_std[i];
-        ILQR_HIPCHK(hipMemcpyAsync(sc_std.p, sc_std_host.data(), sc_std_host.size() * sizeof(T), hipMemcpyHostToDevice, stream));
+        if ((rc = up_std({d.u_std}, NU))) return rc;
         SampleArgs<T> a{};
         a.B = B; a.S = d.n_samples; a.N = N; a.integ = cfg.integrator; a.mode = d.mode;
         a.dt = (T)cfg.dt;
@@ -1413,42 +1418,33 @@ template <typename T> class SolverT : public SolverBase {
         a.lambda = d.temperature;
         a.U = st.U; a.cur_slot = st.cur_slot; a.params = params; a.x0 = st.x0;
         a.rows = het.model_set ? het.rows.p : nullptr;
-        a.u_std = sc_std.p;
+        a.u_std = smp.std.p;
         a.lim = limits();
-        a.Ub = sc_U.p;
-        a.cost = pr_sum; a.Us = pr_U.p;
-        a.w = sc_w.p; a.wsum = sc_w.p + L; a.sel = sc_sel.p;
-        NoiseArgs<T> nz{};
-        nz.k0 = (unsigned)(d.seed & 0xffffffffull); nz.k1 = (unsigned)(d.seed >> 32);
-        nz.first = (unsigned)d.first_trajectory;
-        nz.dist = d.distribution;
-        if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sample_begin(a, stream); }))) return rc;
+        a.Ub = smp.nominal.p;
+        a.cost = smp.summaries; a.Us = smp.controls.p;
+        a.w = smp.weights.p; a.wsum = smp.weights.p + L; a.sel = smp.winners.p;
+        const NoiseArgs<T> nz = noise_args(d.seed, d.first_trajectory, d.distribution);
+        if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.begin(a, stream); }))) return rc;
         for (size_t r = 0; r < Rn; ++r) {
             a.stream = 2u + (unsigned)d.first_round + (unsigned)r;
-            a.stats = sc_stats.p + r * B * 3;
-            a.counts = sc_counts.p + r * B;
-            if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sample_rollout(a, nz, stream); }))) return rc;
-            if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sample_update(a, stream); }))) return rc;
+            a.stats = smp.stats.p + r * B * 3;
+            a.counts = smp.counts.p + r * B;
+            if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.rollout(a, nz, stream); }))) return rc;
+            if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.update(a, stream); }))) return rc;
         }
-        // the nominal alone: the rollout at S = 1 (sample 0 draws nothing), its cost behind the samples'
+        // the nominal alone: the rollout at S = 1 (sample 0 is the nominal), its cost behind the samples'
         SampleArgs<T> f = a;
-        f.S = 1; f.cost = pr_sum.p + L; f.Us = nullptr; f.Xs = d.X_new ? pr_X.p : nullptr;
+        f.S = 1; f.cost = a.cost + L; f.Us = nullptr; f.Xs = d.X_new ? smp.states.p : nullptr;
         if (d.cost_new || d.X_new) {
-            if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sample_rollout(f, nz, stream); }))) return rc;
+            if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.rollout(f, nz, stream); }))) return rc;
         }
-        if (d.round_stats) ILQR_HIPCHK(hipMemcpyAsync(d.round_stats, sc_stats.p, Rn * B * 3 * sizeof(double), hipMemcpyDeviceToHost, stream));
-        if (d.round_counts) ILQR_HIPCHK(hipMemcpyAsync(d.round_counts, sc_counts.p, Rn * B * sizeof(int), hipMemcpyDeviceToHost, stream));
-        if (d.cost_samples) ILQR_HIPCHK(hipMemcpyAsync(d.cost_samples, pr_sum.p, L * sizeof(T), hipMemcpyDeviceToHost, stream));
+        if (d.round_stats) ILQR_HIPCHK(hipMemcpyAsync(d.round_stats, smp.stats.p, Rn * B * 3 * sizeof(double), hipMemcpyDeviceToHost, stream));
+        if (d.round_counts) ILQR_HIPCHK(hipMemcpyAsync(d.round_counts, smp.counts.p, Rn * B * sizeof(int), hipMemcpyDeviceToHost, stream));
+        if (d.cost_samples) ILQR_HIPCHK(hipMemcpyAsync(d.cost_samples, a.cost, L * sizeof(T), hipMemcpyDeviceToHost, stream));
         if (d.cost_new) ILQR_HIPCHK(hipMemcpyAsync(d.cost_new, f.cost, (size_t)B * sizeof(T), hipMemcpyDeviceToHost, stream));
-        // [t][c][L] -> host [L][c][t]
-        auto down_traj = [&](void* host, const T* dev, size_t Ln, int C, int Tn) {
-            return stage_down(host, Ln * C * (size_t)Tn, [&](dim3 g_, dim3 b_) {
-                hipLaunchKernelGGL(layout_ctl_gather_kernel<T>, g_, b_, 0, stream, staging.p, dev, Ln, C, Tn);
-            });
-        };
-        if (d.U_samples && (rc = down_traj(d.U_samples, pr_U, L, NU, N))) return rc;
-        if (d.U_new && (rc = down_traj(d.U_new, sc_U, (size_t)B, NU, N))) return rc;
-        if (d.X_new && (rc = down_traj(d.X_new, pr_X, (size_t)B, NX, N + 1))) return rc;
+        if (d.U_samples && (rc = down_traj(d.U_samples, smp.controls, L, NU, N))) return rc;
+        if (d.U_new && (rc = down_traj(d.U_new, smp.nominal, (size_t)B, NU, N))) return rc;
+        if (d.X_new && (rc = down_traj(d.X_new, smp.states, (size_t)B, NX, N + 1))) return rc;
         ILQR_HIPCHK(hipStreamSynchronize(stream));
         return check_launch();
     }

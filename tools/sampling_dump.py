@@ -1,0 +1,144 @@
+"""Every output of the three sampling entries (policy_rollout, policy_monte_carlo, sample_controls) at small shapes, as
+one .npz: run it once per build (ILQR_LIB selects the library; a copy of another checkout runs its own package and
+plugins) and compare the two files with --compare.  A refactor of those entries must leave every array identical.
+
+Systems: the built-in policy systems (pendulum, UA double pendulum, double pendulum) and the policy example plugins.
+fp32 and fp64; B = 3, N = 5, S in {1, 65} (a full wave plus a one-lane tail); plant / model integrator rk4 and
+backward_euler.  Variants, every optional output requested: feedback on / off; control limits shared and as rows (both
+clamp); state limits; model rows and plant rows; per-sample plant rows; both distributions; BEST and SOFTMIN; smoothing 0
+and 0.9; two rounds.  (Limits and parameter rows exist for the built-in systems only.)
+
+    python tools/sampling_dump.py out.npz
+    python tools/sampling_dump.py --compare a.npz b.npz [summary.json]
+"""
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import ilqr_amd  # noqa: E402
+from ilqr_amd import problems  # noqa: E402
+from ilqr_amd.systems.examples import policy_example_systems  # noqa: E402
+
+B, N, DT, SEED = 3, 5, 0.01, 0x0123456789ABCDEF
+BUILTIN = {"pendulum": problems.pendulum_mpc, "ua": problems.ua_double_pendulum, "dp": problems.double_pendulum}
+ROWS = {"pendulum": ("l",), "ua": ("m2", "l2"), "dp": ("m2", "l2")}
+
+
+def system(name, dtype, integrator):
+    if name in BUILTIN:
+        p = BUILTIN[name](N=N)
+        return ilqr_amd.make_system({**p["dynamics"], "integrator": integrator, "dt": DT}, p["cost"], dtype)
+    return policy_example_systems(dtype, DT, integrator=integrator)[name]
+
+
+def inputs(n, m, S):
+    """a seeded nominal and sample inputs, rounded to float32 so both dtypes see the same numbers"""
+    rng = np.random.default_rng(17)
+    r32 = lambda a: a.astype(np.float32).astype(np.float64)
+    X, U, K = (r32(rng.standard_normal(s) * c) for s, c in (((B, n, N + 1), 0.3), ((B, m, N), 0.3), ((B, N, m, n), 0.1)))
+    x0 = r32(X[:, None, :, 0] + rng.uniform(-0.05, 0.05, (B, S, n)))
+    w = r32(rng.uniform(-1e-3, 1e-3, (B, S, N, n)))
+    return X, U, K, x0, w
+
+
+def record(out, tag, result):
+    for k, v in result._asdict().items():
+        if v is not None:
+            out[f"{tag}/{k}"] = np.asarray(v)
+
+
+def dump_case(out, name, dtype, integrator, S):
+    tag = f"{name}/{np.dtype(dtype).name}/{integrator}/S{S}"
+    sysm = system(name, dtype, integrator)
+    n, m = sysm.n_x, sysm.n_u
+    X, U, K, x0, w = inputs(n, m, S)
+    rng = np.random.default_rng(5)
+    x0_std, w_std, u_std = rng.uniform(0.01, 0.05, (B, n)), rng.uniform(1e-4, 1e-3, (B, n)), rng.uniform(0.05, 0.2, (B, m))
+    builtin = name in BUILTIN
+    setups = {"plain": {}}
+    if builtin:
+        lo, hi = -np.linspace(0.1, 0.3, B)[:, None] * np.ones((B, m)), np.linspace(0.15, 0.25, B)[:, None] * np.ones((B, m))
+        x_max = np.full(n, np.inf)
+        x_max[0] = 0.1
+        rows = {k: rng.uniform(0.8, 1.2, B) for k in ROWS[name]}
+        setups["limits_shared"] = dict(u_min=-0.2, u_max=0.15, x_min=-x_max, x_max=x_max)
+        setups["limits_rows"] = dict(u_min=lo, u_max=hi)
+        setups["rows"] = dict(batch_params=rows, plant_params={k: v[::-1].copy() for k, v in rows.items()})
+    for setup, kw in setups.items():
+        s = ilqr_amd.iLQR(sysm, None, X[:, :, 0], U, N=N, verbose=False, dtype=dtype, **kw)
+        s.X, s.K = X, K
+        for fb in (True, False):
+            record(out, f"{tag}/{setup}/rollout/fb{int(fb)}",
+                   s.policy_rollout(S, x0, w, integrator=integrator, feedback=fb, trajectories=True))
+            record(out, f"{tag}/{setup}/rollout_own_x0/fb{int(fb)}",
+                   s.policy_rollout(S, integrator=integrator, feedback=fb, trajectories=True))
+        srows = {k: rng.uniform(0.8, 1.2, (B, S)) for k in ROWS[name]} if builtin else None
+        if srows:
+            record(out, f"{tag}/{setup}/rollout_sample_rows", s.policy_rollout(S, x0, w, srows, integrator, trajectories=True))
+        for dist in ("gaussian", "uniform"):
+            for rows_ in ((None, srows) if srows else (None,)):
+                record(out, f"{tag}/{setup}/monte_carlo/{dist}/srows{int(rows_ is not None)}",
+                       s.policy_monte_carlo(S, SEED, x0_std, w_std, dist, rows_, integrator, violation_tol=1e-3,
+                                            first_trajectory=2, samples=True, trajectories=True, noise=True))
+            record(out, f"{tag}/{setup}/monte_carlo/{dist}/no_w",
+                   s.policy_monte_carlo(S, SEED, x0_std, None, dist, integrator=integrator, feedback=False, samples=True, noise=True))
+            for mode, temp in (("best", None), ("softmin", 10.0)):
+                for beta in (0.0, 0.9):
+                    record(out, f"{tag}/{setup}/search/{dist}/{mode}/beta{beta}",
+                           s.sample_controls(S, 2, SEED, u_std, mode, temp, beta, dist, first_trajectory=1, first_round=3,
+                                             samples=True, trajectories=True))
+
+
+def same(a, b):
+    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b, equal_nan=a.dtype.kind == "f")
+
+
+def compare(path_a, path_b, path_json=None):
+    """Array by array (NaN equal to NaN).  The summary has one entry per group of calls that share a system, their
+    arrays' names and shapes and their result: the values each level of the calls' names takes (the group is their
+    product, or lists its calls), the arrays with their shapes, and "identical" when every array of every call is."""
+    a, b = np.load(path_a), np.load(path_b)
+    calls, bad = {}, []
+    for k in sorted(set(a.files) | set(b.files)):
+        call, _, field = k.rpartition("/")
+        ok = k in a.files and k in b.files and same(a[k], b[k])
+        calls.setdefault(call, {})[field] = list(a[k].shape) if ok else "DIFFERENT"
+        if not ok:
+            bad.append(k)
+    groups = {}
+    for call, fields in calls.items():
+        parts = call.split("/")
+        groups.setdefault((parts[0], len(parts), json.dumps(fields)), []).append(parts)
+    table = []
+    for (_, depth, fields), members in groups.items():
+        levels = [sorted({m[i] for m in members}) for i in range(depth)]
+        full = len(members) == int(np.prod([len(v) for v in levels]))
+        fields = json.loads(fields)
+        table.append(dict(calls=len(members), names=levels if full else ["/".join(m) for m in members], arrays=fields,
+                          result="DIFFERENT" if "DIFFERENT" in fields.values() else "identical"))
+    head = dict(arrays=sum(map(len, calls.values())), calls=len(calls), different=bad)
+    if path_json:
+        with open(path_json, "w") as fh:
+            fh.write(json.dumps(head)[:-1] + ', "table": [\n' + ",\n".join(json.dumps(g) for g in table) + "\n]}\n")
+    print(json.dumps(head))
+    return 1 if bad else 0
+
+
+def main():
+    if sys.argv[1] == "--compare":
+        sys.exit(compare(*sys.argv[2:5]))
+    out = {}
+    for name in list(BUILTIN) + list(policy_example_systems()):
+        for dtype in (np.float32, np.float64):
+            for integrator in ("rk4", "backward_euler"):
+                for S in (1, 65):
+                    dump_case(out, name, dtype, integrator, S)
+    np.savez_compressed(sys.argv[1], **out)
+    print(f"{len(out)} arrays -> {sys.argv[1]}")
+
+
+if __name__ == "__main__":
+    main()
