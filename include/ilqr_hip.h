@@ -574,6 +574,55 @@ typedef struct ilqr_sample_controls_desc {
 } ilqr_sample_controls_desc;
 int ilqr_sample_controls(ilqr_handle h, const ilqr_sample_controls_desc* d);
 
+/* ---- sampled MPC: the search above as a receding-horizon controller on the device (build extension) -----------
+ * n_steps steps of MPPI (ILQR_SAMPLE_SOFTMIN) or best-of-S (ILQR_SAMPLE_BEST) control of the plant that ilqr_mpc_reset /
+ * ilqr_mpc_rearm started.  Step k = 0..n_steps-1, for trajectory b:
+ *   1. search   R = n_rounds rounds of ilqr_sample_controls from x_0[b] = the plant state, around the nominal (step 0:
+ *               U of b's current slot; later steps: the previous plan shifted): the same kernels, sample 0 the nominal,
+ *               the model's integrator and ILQR_BATCH_MODEL rows, clamped to the control limits while they are set.
+ *               Round r of step k draws stream 2 + first_round + k R + r
+ *   2. apply    u_0 = plan[0];  x+ = f_plant(x, u_0) + w_k[b]: cfg.plant_integrator at b's ILQR_BATCH_PLANT row where
+ *               rows are set, else the parameter block (a user-defined system: the generated dynamics; it has no rows)
+ *   3. log      plant state and x_0 <- x+;  u_out[k][b] = u_0, x_out[k][b] = x+ (the layouts of ilqr_mpc_run);
+ *               cost_out[k][b] = the cost the search reports for the step's plan, from the state BEFORE the step: the
+ *               last round's minimum (BEST: round_stats[k][R-1][b][1]), J of the averaged plan (SOFTMIN: one more
+ *               rollout of the sample-0 kind, launched only when cost_out is given);  U_plan[k][b] = the plan
+ *   4. shift    plan[t] <- plan[t + 1], the last column repeated, as ilqr_mpc_run shifts its warm start
+ * After the last step the shifted plan becomes U of b's current slot: the handle is in the state
+ * ilqr_mpc_rearm(plant state, shifted plan) leaves it in -- X, K and U_ff are untouched -- so a following ilqr_mpc_run
+ * hands the plant over to the iLQR controller, and a following ilqr_sampled_mpc with first_round advanced by n_steps * R
+ * continues the run exactly.  Nothing synchronises with the host between rounds or steps; the downloads follow the last
+ * step.  round_stats / round_counts hold every round of every step.  Plant rows enter step 2 only: the search plans with
+ * the model.
+ * Returns what ilqr_sample_controls returns, for the same reasons and checked before any device work, with
+ * first_round + n_steps * n_rounds <= 2^32 - 2 (in 64-bit arithmetic) in place of its stream bound, and: ILQR_ERR_INVALID_ARG
+ * for n_steps < 1, a w that is not finite everywhere, or every output NULL; ILQR_ERR_STATE before ilqr_mpc_reset /
+ * ilqr_mpc_rearm or on a handle created without a plant integrator; ILQR_ERR_UNSUPPORTED while state limits are set (the
+ * search's J ignores them).
+ * ILQR_ABI_VERSION stays 5 with this entry, for the reasons given at ilqr_set_batch_limits: it is additive. */
+typedef struct ilqr_sampled_mpc_desc {
+    uint32_t struct_size;     /* = sizeof(ilqr_sampled_mpc_desc) */
+    int32_t n_samples;        /* S >= 1;  this field to u_std: as ilqr_sample_controls_desc */
+    int32_t n_rounds;         /* R >= 1, per step */
+    int32_t mode;             /* ILQR_SAMPLE_* */
+    int32_t distribution;     /* ILQR_NOISE_* */
+    int32_t first_trajectory; /* >= 0 */
+    int32_t first_round;      /* >= 0: global index of step 0's round 0 */
+    int32_t n_steps;          /* >= 1 */
+    uint64_t seed;
+    double temperature;       /* lambda > 0; read in SOFTMIN only */
+    double smoothing;         /* beta in [0, 1) */
+    const double* u_std;      /* [B][n_u] >= 0, finite in the handle's dtype; required */
+    const void* w;            /* [n_steps][B][n_x] handle dtype, finite: added to the plant state after the step; or NULL */
+    void* u_out;              /* [n_steps][B][n_u]    handle dtype; any output may be NULL, not all */
+    void* x_out;              /* [n_steps][B][n_x]    the plant state AFTER the step */
+    void* cost_out;           /* [n_steps][B] */
+    void* U_plan;             /* [n_steps][B][n_u][N] the nominal after the step's rounds, before the shift */
+    double* round_stats;      /* [n_steps][R][B][3] */
+    int32_t* round_counts;    /* [n_steps][R][B] */
+} ilqr_sampled_mpc_desc;
+int ilqr_sampled_mpc(ilqr_handle h, const ilqr_sampled_mpc_desc* d);
+
 /* ---- multi-GPU hook -------------------------------------------
  * Writes 4 doubles to DEVICE memory `dev_out4` on the handle's stream:
  *   { min cost, max |cost - cost_prev|, #trajectories still active, #converged }

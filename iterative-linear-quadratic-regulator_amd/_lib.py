@@ -44,6 +44,7 @@ SYMBOLS = (
     "ilqr_mpc_rearm", "ilqr_mpc_run", "ilqr_status_reduce", "ilqr_timing_enable", "ilqr_timing_reset", "ilqr_timing_get", "ilqr_algorithmic_bytes",
     "ilqr_set_control_limits", "ilqr_set_batch_params", "ilqr_set_state_limits", "ilqr_set_mpc_multipliers",
     "ilqr_set_batch_limits", "ilqr_policy_rollout", "ilqr_policy_monte_carlo", "ilqr_sample_controls",
+    "ilqr_sampled_mpc",
 )
 # ilqr_set_batch_params: which rows
 BATCH_MODEL, BATCH_PLANT = 0, 1
@@ -120,6 +121,19 @@ class SampleControlsDesc(C.Structure):
     ]
 
 
+class SampledMpcDesc(C.Structure):
+    """ilqr_sampled_mpc_desc (include/ilqr_hip.h), field for field."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("n_samples", C.c_int32), ("n_rounds", C.c_int32), ("mode", C.c_int32), ("distribution", C.c_int32),
+        ("first_trajectory", C.c_int32), ("first_round", C.c_int32), ("n_steps", C.c_int32),
+        ("seed", C.c_uint64), ("temperature", C.c_double), ("smoothing", C.c_double),
+        ("u_std", C.POINTER(C.c_double)), ("w", C.c_void_p),
+        ("u_out", C.c_void_p), ("x_out", C.c_void_p), ("cost_out", C.c_void_p), ("U_plan", C.c_void_p),
+        ("round_stats", C.POINTER(C.c_double)), ("round_counts", C.POINTER(C.c_int32)),
+    ]
+
+
 class IlqrError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libilqr_hip error {code}: {msg}")
@@ -190,6 +204,7 @@ def load():
     lib.ilqr_policy_rollout.argtypes = [vp, C.POINTER(PolicyRolloutDesc)]
     lib.ilqr_policy_monte_carlo.argtypes = [vp, C.POINTER(MonteCarloDesc)]
     lib.ilqr_sample_controls.argtypes = [vp, C.POINTER(SampleControlsDesc)]
+    lib.ilqr_sampled_mpc.argtypes = [vp, C.POINTER(SampledMpcDesc)]
     if lib.ilqr_abi_version() != ABI_VERSION:
         raise RuntimeError("libilqr_hip.so ABI version mismatch: rebuild the library")
     _lib = lib
@@ -573,6 +588,32 @@ class Handle:
         out = self._outputs(d, shapes, dtypes={"round_stats": np.float64, "round_counts": np.int32},
                             names={"U_new": "U", "cost_new": "cost", "X_new": "X"})
         self._chk(self.lib.ilqr_sample_controls(self.h, C.byref(d)))
+        return out
+
+    def sampled_mpc(self, n_steps, n_samples, rounds=1, seed=0, u_std=None, mode=SAMPLE_SOFTMIN, temperature=1.0,
+                    smoothing=0.0, distribution=NOISE_GAUSSIAN, first_trajectory=0, first_round=0, w=None, plans=False):
+        """n_steps receding-horizon steps of the sampled search as the controller of the MPC plant, on the device
+        (include/ilqr_hip.h, ilqr_sampled_mpc).  u_std (B, n_u) float64; w (n_steps, B, n_x) or None.  Returns a dict:
+        u (n_steps, B, n_u), x (n_steps, B, n_x), cost (n_steps, B), round_stats (n_steps, R, B, 3) float64 and
+        round_counts (n_steps, R, B) int32; U_plan (n_steps, B, n_u, N) (with plans)."""
+        B, K, S, R, n, m, N = self.B, int(n_steps), int(n_samples), int(rounds), self.n_x, self.n_u, self.N
+        Ka, Ra = max(K, 0), max(R, 0)
+        d = SampledMpcDesc()
+        d.struct_size = C.sizeof(SampledMpcDesc)
+        d.n_samples, d.n_rounds, d.mode, d.distribution = S, R, int(mode), int(distribution)
+        d.first_trajectory, d.first_round, d.n_steps = int(first_trajectory), int(first_round), K
+        d.seed, d.temperature, d.smoothing = int(seed) & 0xFFFFFFFFFFFFFFFF, float(temperature), float(smoothing)
+        keep = []
+        self._rows_in(d, keep, "u_std", u_std, (B, m), "u_std")
+        if w is not None:
+            keep.append(self._in(w, (Ka, B, n)))
+            d.w = _ptr(keep[-1])
+        shapes = dict(u_out=(Ka, B, m), x_out=(Ka, B, n), cost_out=(Ka, B), round_stats=(Ka, Ra, B, 3), round_counts=(Ka, Ra, B))
+        if plans:
+            shapes.update(U_plan=(Ka, B, m, N))
+        out = self._outputs(d, shapes, dtypes={"round_stats": np.float64, "round_counts": np.int32},
+                            names={"u_out": "u", "x_out": "x", "cost_out": "cost"})
+        self._chk(self.lib.ilqr_sampled_mpc(self.h, C.byref(d)))
         return out
 
     # ---- measurement ------------------------------------------------------------------------------

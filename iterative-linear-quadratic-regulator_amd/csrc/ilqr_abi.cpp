@@ -308,6 +308,10 @@ int ilqr_sample_controls(ilqr_handle h, const ilqr_sample_controls_desc* d) {
     const int rc = sampling_entry(h, d, "sample_controls", "ilqr_sample_controls_desc");
     return rc ? rc : h->impl->sample_controls(*d);
 }
+int ilqr_sampled_mpc(ilqr_handle h, const ilqr_sampled_mpc_desc* d) {
+    const int rc = sampling_entry(h, d, "sampled_mpc", "ilqr_sampled_mpc_desc");
+    return rc ? rc : h->impl->sampled_mpc(*d);
+}
 int ilqr_timing_enable(ilqr_handle h, int on) { ILQR_FWD(h, timing_enable(on)); }
 int ilqr_timing_reset(ilqr_handle h) { ILQR_FWD(h, timing_reset()); }
 int ilqr_timing_get(ilqr_handle h, double ms[ILQR_N_PHASES], int64_t launches[ILQR_N_PHASES]) {

@@ -16,6 +16,7 @@
 #include "forward_mfma16.hpp"
 #include "policy_rollout.hpp"
 #include "sample_controls.hpp"
+#include "sampled_mpc.hpp"
 
 namespace ilqr {
 
@@ -77,8 +78,8 @@ template <typename T> bool ring_rollout_ok(const KArgs<T>& a, int nx, int nu) {
     return !forward_plain() && std::max(bytes_x, bytes_g) <= kDescriptorMax;
 }
 
-// The sampling entries (ilqr_policy_rollout, ilqr_policy_monte_carlo, ilqr_sample_controls: policy_rollout.hpp,
-// sample_controls.hpp): all set or, where the system does not have them, all null.
+// The sampling entries (ilqr_policy_rollout, ilqr_policy_monte_carlo, ilqr_sample_controls, ilqr_sampled_mpc:
+// policy_rollout.hpp, sample_controls.hpp, sampled_mpc.hpp): all set or, where the system does not have them, all null.
 template <typename T> struct SamplingOps {
     // the closed-loop rollout; [1]: with x_0 and w drawn on the device ([0] does not read its NoiseArgs)
     void (*policy[2])(const PolicyArgs<T>&, const NoiseArgs<T>&, hipStream_t) = {};
@@ -87,6 +88,9 @@ template <typename T> struct SamplingOps {
     void (*begin)(const SampleArgs<T>&, hipStream_t) = nullptr;
     void (*rollout)(const SampleArgs<T>&, const NoiseArgs<T>&, hipStream_t) = nullptr;
     void (*update)(const SampleArgs<T>&, hipStream_t) = nullptr;
+    // sampled MPC: the epilogue of a step (plant step, logs, shift of Ub), and Ub back into U after the last one
+    void (*advance)(const SampledMpcArgs<T>&, hipStream_t) = nullptr;
+    void (*commit)(const SampleCommitArgs<T>&, hipStream_t) = nullptr;
     explicit operator bool() const { return rollout != nullptr; }
 };
 
@@ -314,6 +318,16 @@ template <typename T, typename Dyn> void launch_sample_update(const SampleArgs<T
     else ILQR_LAUNCH((sample_best_kernel<T>), dim3((rows + 63) / 64, a.B), dim3(64), 0, s, a, (int)Dyn::NU);
 }
 
+// sampled MPC (sampled_mpc.hpp): the workgroup shape of mpc_advance_kernel; HET where the plant has rows of its own
+template <typename T, typename Dyn> void launch_sampled_mpc_advance(const SampledMpcArgs<T>& a, hipStream_t s) {
+    ILQR_LAUNCH_HET(box_system<Dyn>(), a.plant_rows, (sampled_mpc_advance_kernel<T, Dyn>), (sampled_mpc_advance_kernel<T, Dyn, true>),
+                    dim3((a.B + 63) / 64), dim3(64, kMpcChunks), 0, s, a);
+}
+template <typename T, typename Dyn> void launch_sample_commit(const SampleCommitArgs<T>& a, hipStream_t s) {
+    const size_t n = (size_t)a.B * a.N * Dyn::NU;
+    ILQR_LAUNCH((sample_commit_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.U, a.Ub, a.cur_slot, a.B, a.N, Dyn::NU);
+}
+
 template <typename T, typename Dyn, bool TILE, int INTEG> void set_integrator_ops(Ops<T>& o) {
     constexpr bool SMALL = all_integrators<Dyn>::value;
     // control limits on the fused and persistent kernels: n_u = 1 (u_t rides the tile's padding, FusedWG)
@@ -431,7 +445,8 @@ template <typename T, typename Dyn> Ops<T> make_ops() {
     }
     if constexpr (policy_system<Dyn>()) {
         o.sampling = {{launch_policy<T, Dyn, false>, launch_policy<T, Dyn, true>}, launch_sample_begin<T, Dyn>,
-                      launch_sample_rollout<T, Dyn>, launch_sample_update<T, Dyn>};
+                      launch_sample_rollout<T, Dyn>, launch_sample_update<T, Dyn>, launch_sampled_mpc_advance<T, Dyn>,
+                      launch_sample_commit<T, Dyn>};
     }
     o.eval = [](const EvalArgs<T>& a, hipStream_t s) {
         ILQR_LAUNCH((eval_points_kernel<T, Dyn>), dim3((a.npts + 63) / 64), dim3(64), 0, s, a);

@@ -64,6 +64,7 @@ struct SolverBase {
     virtual int policy_rollout(const ilqr_policy_rollout_desc& d) = 0;
     virtual int policy_monte_carlo(const ilqr_monte_carlo_desc& d) = 0;
     virtual int sample_controls(const ilqr_sample_controls_desc& d) = 0;
+    virtual int sampled_mpc(const ilqr_sampled_mpc_desc& d) = 0;
 };
 
 int system_dims(int system, int n_x, int n_u);  // 1 if (system, n_x, n_u) is a known combination
@@ -228,7 +229,7 @@ template <typename T> struct DeviceState {
     bool box_lin_valid = false;                   // the last linearize wrote box_lin (not lin)
 };
 
-// The workspace of the sampling entries (ilqr_policy_rollout, ilqr_policy_monte_carlo, ilqr_sample_controls), with
+// The workspace of the sampling entries (ilqr_policy_rollout, ilqr_policy_monte_carlo, ilqr_sample_controls, ilqr_sampled_mpc), with
 // L = B * S samples, sample-innermost.  A buffer is allocated by the first call that needs it and grown, never shrunk
 // (SolverT::grow); every call that touches one ends synchronised, so the entries share them.
 template <typename T> struct SamplingBufs {
@@ -242,8 +243,9 @@ template <typename T> struct SamplingBufs {
     DevBuf<T> nominal;            // the search's private Ub [N][n_u][B]
     DevBuf<double> weights;       // the search's w [L] and W [B]
     DevBuf<int> winners;          // [B]
-    DevBuf<double> stats;         // Monte Carlo [B][7]; search [R][B][3]
+    DevBuf<double> stats;         // Monte Carlo [B][7]; search [R][B][3] (sampled MPC: [n_steps][R][B][3], counts alike)
     DevBuf<int> counts;           // Monte Carlo [B][2]; search [R][B]
+    DevBuf<T> w_steps, plans;     // sampled MPC: w [n_steps][B][n_x] as the caller gave it; U_plan [n_steps][N][n_u][B]
 };
 
 // per-trajectory parameters (ilqr_set_batch_params): rows [n_sys + n_x][B] of the model (derived constants, x_target),
@@ -1369,6 +1371,47 @@ template <typename T> class SolverT : public SolverBase {
         return check_launch();
     }
 
+    // What the search's descriptors share (ilqr_sample_controls_desc, ilqr_sampled_mpc_desc), refused in the order
+    // ilqr_sample_controls always refused it.  `rounds`: every round the call draws, in 64 bits; `rounds_what`: their name
+    // in the stream bound's message.
+    template <typename D> int search_desc_check(const std::string& who, const D& d, unsigned long long rounds, const char* rounds_what) {
+        auto bad = [&](const std::string& what) { return fail(ILQR_ERR_INVALID_ARG, who + ": " + what); };
+        if (int rc = sample_count(who, d.n_samples)) return rc;
+        if (d.n_rounds < 1) return bad("n_rounds must be >= 1");
+        if (d.mode != ILQR_SAMPLE_BEST && d.mode != ILQR_SAMPLE_SOFTMIN) return bad("unknown mode");
+        if (d.distribution != ILQR_NOISE_GAUSSIAN && d.distribution != ILQR_NOISE_UNIFORM) return bad("unknown distribution");
+        if (d.first_trajectory < 0) return bad("first_trajectory must be >= 0");
+        if (d.first_round < 0) return bad("first_round must be >= 0");
+        // (the streams 2 + first_round + r must fit 32 bits; in ilqr_sample_controls, with two int32 fields, the sum is at
+        // most 2^32 - 2 and this cannot fire: it is the header's clause, kept for the day a field widens)
+        if ((unsigned long long)d.first_round + rounds > 0xfffffffeull)
+            return bad(std::string("first_round + ") + rounds_what + " must be <= 2^32 - 2");
+        if (!d.u_std) return bad("u_std is NULL");
+        for (size_t i = 0; i < (size_t)B * NU; ++i)
+            // (finite as the device holds it: a double beyond the handle's dtype would arrive there as +inf)
+            if (!std::isfinite(d.u_std[i]) || d.u_std[i] < 0.0 || d.u_std[i] > (double)std::numeric_limits<T>::max())
+                return bad("every standard deviation must be finite in the handle's dtype and >= 0");
+        if (!(d.smoothing >= 0.0 && d.smoothing < 1.0)) return bad("smoothing must be in [0, 1)");
+        if (d.mode == ILQR_SAMPLE_SOFTMIN && !(std::isfinite(d.temperature) && d.temperature > 0.0))
+            return bad("temperature must be finite and > 0");
+        return ILQR_OK;
+    }
+    // the search's arguments from the fields its descriptors share; the caller adds stream, stats, counts per round
+    template <typename D> SampleArgs<T> search_args(const D& d, size_t L) {
+        SampleArgs<T> a{};
+        a.B = B; a.S = d.n_samples; a.N = N; a.integ = cfg.integrator; a.mode = d.mode;
+        a.dt = (T)cfg.dt;
+        a.beta = (T)d.smoothing; a.c = (T)std::sqrt(1.0 - d.smoothing * d.smoothing);
+        a.lambda = d.temperature;
+        a.U = st.U; a.cur_slot = st.cur_slot; a.params = params; a.x0 = st.x0;
+        a.rows = het.model_set ? het.rows.p : nullptr;
+        a.u_std = smp.std.p;
+        a.lim = limits();
+        a.Ub = smp.nominal.p;
+        a.cost = smp.summaries; a.Us = smp.controls.p;
+        a.w = smp.weights.p; a.wsum = smp.weights.p + L; a.sel = smp.winners.p;
+        return a;
+    }
     // R rounds of (rollout of S samples, weights, update of the private nominal), then the nominal's own rollout: every
     // kernel of the search is queued on the stream without a host synchronisation in between.  The downloads follow the
     // last of them (the staged ones, which convert the layout through `staging`, each end synchronised).  Reads
@@ -1378,24 +1421,7 @@ template <typename T> class SolverT : public SolverBase {
         auto bad = [&](const char* what) { return fail(ILQR_ERR_INVALID_ARG, who + ": " + what); };
         int rc;
         size_t L;
-        if ((rc = sample_count(who, d.n_samples))) return rc;
-        if (d.n_rounds < 1) return bad("n_rounds must be >= 1");
-        if (d.mode != ILQR_SAMPLE_BEST && d.mode != ILQR_SAMPLE_SOFTMIN) return bad("unknown mode");
-        if (d.distribution != ILQR_NOISE_GAUSSIAN && d.distribution != ILQR_NOISE_UNIFORM) return bad("unknown distribution");
-        if (d.first_trajectory < 0) return bad("first_trajectory must be >= 0");
-        if (d.first_round < 0) return bad("first_round must be >= 0");
-        // (the streams 2 + first_round + r must fit 32 bits; with two int32 fields the sum is at most 2^32 - 2, so this
-        // cannot fire today: it is the header's clause, kept for the day a field widens)
-        if ((unsigned long long)d.first_round + (unsigned long long)d.n_rounds > 0xfffffffeull)
-            return bad("first_round + n_rounds must be <= 2^32 - 2");
-        if (!d.u_std) return bad("u_std is NULL");
-        for (size_t i = 0; i < (size_t)B * NU; ++i)
-            // (finite as the device holds it: a double beyond the handle's dtype would arrive there as +inf)
-            if (!std::isfinite(d.u_std[i]) || d.u_std[i] < 0.0 || d.u_std[i] > (double)std::numeric_limits<T>::max())
-                return bad("every standard deviation must be finite in the handle's dtype and >= 0");
-        if (!(d.smoothing >= 0.0 && d.smoothing < 1.0)) return bad("smoothing must be in [0, 1)");
-        if (d.mode == ILQR_SAMPLE_SOFTMIN && !(std::isfinite(d.temperature) && d.temperature > 0.0))
-            return bad("temperature must be finite and > 0");
+        if ((rc = search_desc_check(who, d, (unsigned long long)d.n_rounds, "n_rounds"))) return rc;
         if (!d.U_new && !d.cost_new && !d.X_new && !d.round_stats && !d.round_counts && !d.cost_samples && !d.U_samples)
             return bad("every output is NULL");
         if ((rc = sample_total(who, d.n_samples, &L)) || (rc = sampling_supported(who)) || (rc = sampling_problem(who)) ||
@@ -1411,18 +1437,7 @@ template <typename T> class SolverT : public SolverBase {
         if (d.X_new && (rc = grow(smp.states, nXb))) return rc;
         if ((rc = grow(staging, std::max({nUb, d.X_new ? nXb : (size_t)0, d.U_samples ? nU : (size_t)0})))) return rc;
         if ((rc = up_std({d.u_std}, NU))) return rc;
-        SampleArgs<T> a{};
-        a.B = B; a.S = d.n_samples; a.N = N; a.integ = cfg.integrator; a.mode = d.mode;
-        a.dt = (T)cfg.dt;
-        a.beta = (T)d.smoothing; a.c = (T)std::sqrt(1.0 - d.smoothing * d.smoothing);
-        a.lambda = d.temperature;
-        a.U = st.U; a.cur_slot = st.cur_slot; a.params = params; a.x0 = st.x0;
-        a.rows = het.model_set ? het.rows.p : nullptr;
-        a.u_std = smp.std.p;
-        a.lim = limits();
-        a.Ub = smp.nominal.p;
-        a.cost = smp.summaries; a.Us = smp.controls.p;
-        a.w = smp.weights.p; a.wsum = smp.weights.p + L; a.sel = smp.winners.p;
+        SampleArgs<T> a = search_args(d, L);
         const NoiseArgs<T> nz = noise_args(d.seed, d.first_trajectory, d.distribution);
         if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.begin(a, stream); }))) return rc;
         for (size_t r = 0; r < Rn; ++r) {
@@ -1445,6 +1460,89 @@ template <typename T> class SolverT : public SolverBase {
         if (d.U_samples && (rc = down_traj(d.U_samples, smp.controls, L, NU, N))) return rc;
         if (d.U_new && (rc = down_traj(d.U_new, smp.nominal, (size_t)B, NU, N))) return rc;
         if (d.X_new && (rc = down_traj(d.X_new, smp.states, (size_t)B, NX, N + 1))) return rc;
+        ILQR_HIPCHK(hipStreamSynchronize(stream));
+        return check_launch();
+    }
+
+    // Sampled MPC (sampled_mpc.hpp): per step R rounds of the search above from x_0 = the plant state and the epilogue
+    // (plant step, logs, shift of the private nominal), then the nominal back into U: queued on the stream in one piece,
+    // the downloads after the last launch.  round_stats / round_counts take n_steps * R rows of smp.stats / smp.counts.
+    // U_plan is written by the epilogue itself, from the registers its shift already holds, into smp.plans in the
+    // nominal's own layout (coalesced, no launch per step); the existing gather kernel converts it at the download.
+    // Leaves the handle as mpc_rearm(plant state, shifted nominal) does: X, K and U_ff are untouched.
+    int sampled_mpc(const ilqr_sampled_mpc_desc& d) override {
+        const std::string who = "sampled_mpc";
+        auto bad = [&](const char* what) { return fail(ILQR_ERR_INVALID_ARG, who + ": " + what); };
+        int rc;
+        size_t L;
+        if (d.n_steps < 1) return bad("n_steps must be >= 1");
+        const unsigned long long rounds = (unsigned long long)d.n_steps * (unsigned long long)std::max(d.n_rounds, 0);
+        if ((rc = search_desc_check(who, d, rounds, "n_steps * n_rounds"))) return rc;
+        const size_t K = (size_t)d.n_steps, Rn = (size_t)d.n_rounds;
+        const T* w_host = (const T*)d.w;
+        for (size_t i = 0; w_host && i < K * B * NX; ++i)
+            if (!std::isfinite(w_host[i])) return bad("every w value must be finite");
+        if (!d.u_out && !d.x_out && !d.cost_out && !d.U_plan && !d.round_stats && !d.round_counts) return bad("every output is NULL");
+        if ((rc = sample_total(who, d.n_samples, &L)) || (rc = sampling_supported(who)) || (rc = sampling_problem(who))) return rc;
+        if (!mpc_ready) return fail(ILQR_ERR_STATE, who + " before mpc_reset / mpc_rearm");
+        if (cfg.plant_integrator < 0) return fail(ILQR_ERR_STATE, who + ": the handle was created without a plant integrator");
+        if (al.on) return al_refuse("sampled_mpc");
+        if ((rc = sampling_settle())) return rc;
+        const size_t nU = L * NU * (size_t)N, nUb = (size_t)B * NU * N;
+        if ((rc = grow(smp.summaries, L + (size_t)B)) || (rc = grow(smp.controls, nU)) || (rc = grow(smp.nominal, nUb)) ||
+            (rc = grow(smp.weights, L + (size_t)B)) || (rc = grow(smp.winners, (size_t)B)) ||
+            (rc = grow(smp.stats, K * Rn * B * 3)) || (rc = grow(smp.counts, K * Rn * B)))
+            return rc;
+        if (d.w && (rc = grow(smp.w_steps, K * B * NX))) return rc;
+        if (d.U_plan && ((rc = grow(smp.plans, K * nUb)) || (rc = grow(staging, nUb)))) return rc;
+        if ((rc = mpc_log_room(d.n_steps)) || (rc = up_std({d.u_std}, NU))) return rc;
+        // (w arrives in the layout the epilogue reads; the caller's buffer outlives the copy: the call ends synchronised)
+        if (d.w) ILQR_HIPCHK(hipMemcpyAsync(smp.w_steps.p, d.w, K * B * NX * sizeof(T), hipMemcpyHostToDevice, stream));
+        SampleArgs<T> a = search_args(d, L);
+        const NoiseArgs<T> nz = noise_args(d.seed, d.first_trajectory, d.distribution);
+        // the nominal alone, for the cost of a SOFTMIN step's plan: the rollout at S = 1, its cost behind the samples'
+        const bool plan_cost = d.cost_out && d.mode == ILQR_SAMPLE_SOFTMIN;
+        SampledMpcArgs<T> m{};
+        m.B = B; m.N = N; m.plant_integ = cfg.plant_integrator; m.dt = (T)cfg.dt; m.params = params;
+        m.plant_rows = kargs(st).plant_rows;
+        m.w = d.w ? smp.w_steps.p : nullptr;
+        m.cost = plan_cost ? a.cost + L : nullptr;
+        m.Ub = a.Ub; m.x0 = st.x0; m.plant_x = plant_x;
+        m.u_log = d.u_out ? mpc_u_log.p : nullptr; m.x_log = d.x_out ? mpc_x_log.p : nullptr;
+        m.cost_log = d.cost_out ? mpc_cost_log.p : nullptr; m.plan_log = d.U_plan ? smp.plans.p : nullptr;
+        if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.begin(a, stream); }))) return rc;
+        for (size_t k = 0; k < K; ++k) {
+            for (size_t r = 0; r < Rn; ++r) {
+                const size_t row = k * Rn + r;
+                a.stream = 2u + (unsigned)d.first_round + (unsigned)row;
+                a.stats = smp.stats.p + row * B * 3;
+                a.counts = smp.counts.p + row * B;
+                if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.rollout(a, nz, stream); }))) return rc;
+                if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.update(a, stream); }))) return rc;
+            }
+            if (plan_cost) {
+                SampleArgs<T> f = a;
+                f.S = 1; f.cost = a.cost + L; f.Us = nullptr;
+                if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.rollout(f, nz, stream); }))) return rc;
+            }
+            m.step = (int)k;
+            m.stats = (d.cost_out && !plan_cost) ? a.stats : nullptr;
+            if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.advance(m, stream); }))) return rc;
+        }
+        const SampleCommitArgs<T> c{B, N, st.U.p, a.Ub, st.cur_slot};
+        if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.commit(c, stream); }))) return rc;
+        al.lam_shifted = false;      // (as mpc_rearm)
+        auto fetch = [&](void* host, const void* dev, size_t bytes) -> int {
+            if (host) ILQR_HIPCHK(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, stream));
+            return ILQR_OK;
+        };
+        if ((rc = fetch(d.u_out, mpc_u_log.p, K * B * NU * sizeof(T))) || (rc = fetch(d.x_out, mpc_x_log.p, K * B * NX * sizeof(T))) ||
+            (rc = fetch(d.cost_out, mpc_cost_log.p, K * B * sizeof(T))) ||
+            (rc = fetch(d.round_stats, smp.stats.p, K * Rn * B * 3 * sizeof(double))) ||
+            (rc = fetch(d.round_counts, smp.counts.p, K * Rn * B * sizeof(int))))
+            return rc;
+        for (size_t k = 0; d.U_plan && k < K; ++k)
+            if ((rc = down_traj((T*)d.U_plan + k * nUb, smp.plans.p + k * nUb, (size_t)B, NU, N))) return rc;
         ILQR_HIPCHK(hipStreamSynchronize(stream));
         return check_launch();
     }
@@ -1610,17 +1708,22 @@ template <typename T> class SolverT : public SolverBase {
         m.plant_rows = kargs(st).plant_rows;
         return m;
     }
+    // the step logs of ilqr_mpc_run and ilqr_sampled_mpc, [n_steps][B][.]: grown, never shrunk (nothing queued uses them:
+    // both calls end synchronised)
+    int mpc_log_room(int n_steps) {
+        if (n_steps <= mpc_log_steps) return ILQR_OK;
+        ILQR_HIPCHK(mpc_u_log.alloc((size_t)n_steps * NU * B));
+        ILQR_HIPCHK(mpc_x_log.alloc((size_t)n_steps * NX * B));
+        ILQR_HIPCHK(mpc_cost_log.alloc((size_t)n_steps * B));
+        mpc_log_steps = n_steps;
+        return ILQR_OK;
+    }
     int mpc_run(int n_steps, void* u_out, void* x_out, void* cost_out) override {
         if (al.on && al.mpc_mode == ILQR_MPC_AL_OFF) return mpc_al_refuse("mpc_run");
         if (!mpc_ready) { err = "mpc_run before mpc_reset"; return ILQR_ERR_STATE; }
         if (cfg.plant_integrator < 0) { err = "mpc_run: the handle was created without a plant integrator"; return ILQR_ERR_STATE; }
         if (n_steps < 1) { err = "mpc_run: n_steps < 1"; return ILQR_ERR_INVALID_ARG; }
-        if (n_steps > mpc_log_steps) {
-            ILQR_HIPCHK(mpc_u_log.alloc((size_t)n_steps * NU * B));
-            ILQR_HIPCHK(mpc_x_log.alloc((size_t)n_steps * NX * B));
-            ILQR_HIPCHK(mpc_cost_log.alloc((size_t)n_steps * B));
-            mpc_log_steps = n_steps;
-        }
+        if (int rl = mpc_log_room(n_steps)) return rl;
         if (al.on) {
             int rc = mpc_run_al(n_steps);
             if (rc) return rc;

@@ -337,6 +337,44 @@ def sample_controls_args(system, N, B, batched, n_samples, rounds=1, seed=0, u_s
             _lib.NOISE_DISTRIBUTIONS[distribution], first, first_r)
 
 
+SampledMPC = namedtuple("SampledMPC", ("U_sim", "X_sim", "cost") + _lib.SAMPLE_ROUND_STATS + ("round_n_finite", "U_plan"),
+                        defaults=(None,))
+SampledMPC.__doc__ = """Result of iLQR.sampled_mpc.  U_sim (n_steps, [B,] n_u): the controls applied; X_sim (n_steps, [B,]
+n_x): the plant state AFTER each step; cost (n_steps, [B]): the cost the search reports for each step's plan, from the
+state before the step (the last round's minimum in "best" mode, the plain cost of the averaged plan in "softmin" mode);
+round_cost_nominal, round_cost_min, round_ess (float64) and round_n_finite (int), each (n_steps, R, [B]): the round
+statistics of SampledControls for every round of every step; U_plan (n_steps, [B,] n_u, N) with plans=True: the plan of
+each step before it is shifted, else None."""
+
+
+def sampled_mpc_args(system, N, B, batched, n_steps, n_samples, rounds=1, seed=0, u_std=None, mode="softmin", temperature=None,
+                     smoothing=0.0, distribution="gaussian", first_trajectory=0, first_round=0, disturbance=None, dtype=None):
+    """Validated arguments of ``ilqr_sampled_mpc`` as (K, S, R, seed, u_std, mode code, temperature, smoothing,
+    distribution code, first_trajectory, first_round, w): everything ``sample_controls_args`` returns and refuses, with
+    n_steps = K an integer >= 1, first_round + n_steps * rounds <= 2^32 - 2 in place of its stream bound, and w the
+    disturbance (n_steps, [B,] n_x) as (K, B, n_x) float64 -- every value finite (in ``dtype`` too, where one is given)
+    -- or None.  Pure host code (no GPU)."""
+    S, R, seed, std, mcode, temp, beta, dist, first, first_r = sample_controls_args(
+        system, N, B, batched, n_samples, rounds, seed, u_std, mode, temperature, smoothing, distribution, first_trajectory,
+        first_round)
+    if isinstance(n_steps, bool) or not isinstance(n_steps, (int, np.integer)) or not 1 <= int(n_steps) < 2 ** 31:
+        raise ValueError(f"n_steps must be an integer >= 1, got {n_steps!r}")
+    K, B, n = int(n_steps), int(B), system.n_x
+    if first_r + K * R > 2 ** 32 - 2:
+        raise ValueError("first_round + n_steps * rounds must be <= 2^32 - 2")
+    w = None
+    if disturbance is not None:
+        w = np.asarray(disturbance, dtype=np.float64)
+        want = (K, B, n) if batched else (K, n)
+        if w.shape != want:
+            raise ValueError(f"disturbance must have shape {want}, but got {w.shape}")
+        w = np.ascontiguousarray(w.reshape(K, B, n))
+        with np.errstate(over="ignore"):
+            if not np.isfinite(w if dtype is None else w.astype(dtype)).all():
+                raise ValueError("disturbance must be finite")
+    return K, S, R, seed, std, mcode, temp, beta, dist, first, first_r, w
+
+
 class iLQR:
     def __init__(self, system: System, T=None, x_0=None, U_init=None, tol=1e-5, maxiter=100,
                  alpha_factor=0.5, min_alpha=1e-8, verbose=True, *, N=None, n_alpha=None, n_trials=10,
@@ -696,6 +734,33 @@ class iLQR:
         rec.update(round_n_finite=rpick(counts), cost_start=pick(cost_start), applied=None if applied is None else pick(applied))
         rec.update({k: self._out(v) for k, v in out.items()})
         return SampledControls(**rec)
+
+    # ---- sampled MPC ---------------------------------------------------------------------------------
+    def sampled_mpc(self, n_steps, n_samples, rounds=1, seed=0, u_std=None, mode="softmin", temperature=None, smoothing=0.0,
+                    distribution="gaussian", first_trajectory=0, first_round=0, disturbance=None, plans=False):
+        """The search of sample_controls as a receding-horizon controller on the device (include/ilqr_hip.h,
+        ilqr_sampled_mpc): MPPI (mode="softmin") or best-of-S (mode="best").  After mpc_reset, each of n_steps steps runs
+        `rounds` rounds of the search from the plant state around the shifted previous plan (step 0: the solver's U),
+        applies the plan's first control to the plant (the solver's plant=, its plant parameters where set), adds
+        disturbance[k] ((n_steps, [B,] n_x), None: nothing) to the new state and shifts the plan, with no host round trip
+        in between.  Round r of step k draws the stream of round first_round + k * rounds + r, so a second call with
+        first_round advanced by n_steps * rounds continues the first exactly; a following mpc_run hands the plant over to
+        the iLQR controller (X, K and U_ff are untouched, U is the shifted plan).  The other arguments are
+        sample_controls'.  Returns a SampledMPC; the plans of every step with plans=True.  Not with state limits."""
+        if self.plant is None:
+            raise ValueError("construct the solver with plant=<System> to run MPC steps")
+        K, S, R, seed, std, mcode, temp, beta, dist, first, first_r, w = sampled_mpc_args(
+            self.system, self.N, self.B, self.batched, n_steps, n_samples, rounds, seed, u_std, mode, temperature, smoothing,
+            distribution, first_trajectory, first_round, disturbance, self.dtype)
+        out = self._h.sampled_mpc(K, S, R, seed, std, mcode, temp, beta, dist, first, first_r, w, plans)
+        stats, counts = out["round_stats"], out["round_counts"]
+        pick = (lambda a: ready(a)) if self.batched else (lambda a: ready(a[..., 0]))
+        rec = {k: pick(stats[..., i].copy()) for i, k in enumerate(_lib.SAMPLE_ROUND_STATS)}
+        rec.update(round_n_finite=pick(counts))
+        step = (lambda a: ready(a)) if self.batched else (lambda a: ready(a[:, 0]))
+        rec.update(U_sim=step(out["u"]), X_sim=step(out["x"]), cost=step(out["cost"]),
+                   U_plan=step(out["U_plan"]) if plans else None)
+        return SampledMPC(**rec)
 
     # ---- MPC (run_iLQR_MPC.py:116-143), device-resident ---------------------------------------------
     def mpc_reset(self, x_0, U_init, keep_state=False):
