@@ -516,7 +516,8 @@ int ilqr_policy_monte_carlo(ilqr_handle h, const ilqr_monte_carlo_desc* d);
  *                                                       used: this step plans with the model
  *   J_s       = sum_t l(x_t, u_t) + l_f(x_N)            the model's plain J (b's x_target row, shared Q, R, Q_f), summed in
  *                                                       the rollout's order
- * State limits and their multipliers do not enter.  The update runs over the samples with a finite J_s (sample 0 of a
+ * State limits and their multipliers do not enter, unless ilqr_set_sample_penalty (below) adds the limits to J_s as a
+ * penalty: every J in this text is then J~ = J + P.  The update runs over the samples with a finite J_s (sample 0 of a
  * finite nominal is always among them):
  *   BEST      s* = argmin J_s, the lowest s on ties;  U^{r+1}_t = u_{s*,t}
  *   SOFTMIN   w_s = exp(-(J_s - J_min) / temperature),  W = sum_s w_s,  U^{r+1}_t[j] = (sum_s w_s u_{s,t}[j]) / W:
@@ -598,7 +599,7 @@ int ilqr_sample_controls(ilqr_handle h, const ilqr_sample_controls_desc* d);
  * first_round + n_steps * n_rounds <= 2^32 - 2 (in 64-bit arithmetic) in place of its stream bound, and: ILQR_ERR_INVALID_ARG
  * for n_steps < 1, a w that is not finite everywhere, or every output NULL; ILQR_ERR_STATE before ilqr_mpc_reset /
  * ilqr_mpc_rearm or on a handle created without a plant integrator; ILQR_ERR_UNSUPPORTED while state limits are set (the
- * search's J ignores them).
+ * search's J ignores them) and no penalty is (ilqr_set_sample_penalty).
  * ILQR_ABI_VERSION stays 5 with this entry, for the reasons given at ilqr_set_batch_limits: it is additive. */
 typedef struct ilqr_sampled_mpc_desc {
     uint32_t struct_size;     /* = sizeof(ilqr_sampled_mpc_desc) */
@@ -622,6 +623,65 @@ typedef struct ilqr_sampled_mpc_desc {
     int32_t* round_counts;    /* [n_steps][R][B] */
 } ilqr_sampled_mpc_desc;
 int ilqr_sampled_mpc(ilqr_handle h, const ilqr_sampled_mpc_desc* d);
+
+/* ---- state limits in the sampled search and sampled MPC: a penalty on the device (build extension) -------------
+ * ilqr_sample_controls and ilqr_sampled_mpc plan with the plain J: the state limits of ilqr_set_state_limits /
+ * ilqr_set_batch_limits do not enter it.  ilqr_set_sample_penalty makes them enter as a constraint cost, the way MPPI
+ * handles state constraints.  For trajectory b with weight[b] = rho_b > 0 and a sample's states x_1 .. x_N (the points
+ * the solver constrains), with c_q the constraints of ilqr_set_state_limits (q < n_x: x[q] - x_max[q]; q >= n_x:
+ * x_min[q - n_x] - x[q - n_x]; only the finite bounds, shared or b's row):
+ *   P_s  = sum_{t=1..N} phi_t,  phi_t = sum_q (max(0, rho_b c_q(x_t))^2) / (2 rho_b)   = (rho_b / 2) sum max(0, c)^2: the
+ *                                      augmented Lagrangian's term at zero multipliers, not scaled by dt.  In the handle's
+ *                                      dtype: phi_t sums q ascending from 0, P sums t ascending from 0
+ *   v_s  = max(0, max_{t, q} c_q(x_t))  the violation as ilqr_policy_rollout reports it (from 0, v = c > v ? c : v)
+ *   J~_s = J_s + P_s                    one add in the handle's dtype, after the terminal cost
+ * With weight[b] = rho0 J~ is the merit the first inner solve of the state-limited ilqr_solve minimises.  While a
+ * penalty is set every cost the two entries report or read is J~: the weights, the argmin, the softmin, round_stats,
+ * cost_new, cost_samples, cost_out, and the non-finite rule (a sample whose P overflows is left out like any other
+ * non-finite cost).  In BEST mode cost_new still equals the last round's minimum bit for bit: the rollout of the nominal
+ * alone is the same penalised code.  A sample with P_s = 0 has J~_s = J_s bit for bit, so while no state limits are set
+ * (no constraint exists: P = 0, v = 0) or no sample reaches a bound every result equals the unpenalised one bit for bit.
+ * weight is [B] doubles, copied to the device in the handle's dtype; NULL clears the penalty (violation_tol is then not
+ * read).  violation_tol is the threshold of round_violating below.  The penalty is read by ilqr_sample_controls and
+ * ilqr_sampled_mpc only: no solve, ilqr_mpc_run or policy entry sees it, and neither multipliers nor rho of the solver
+ * enter or change.  While it is set ilqr_sampled_mpc accepts a handle with state limits (without it: ILQR_ERR_UNSUPPORTED
+ * as before); what ilqr_mpc_reset / ilqr_mpc_rearm ask of such a handle (a multiplier policy) is unchanged, and the
+ * sampled steps change nothing in X, K, U_ff or the multipliers.
+ * Returns ILQR_ERR_INVALID_ARG for a NULL handle, a weight that is not finite in the handle's dtype and > 0 there, or a
+ * violation_tol that is not finite and >= 0 -- checked before any device work, the handle unchanged;
+ * ILQR_ERR_UNSUPPORTED for ILQR_SYS_LINEAR and ILQR_SYS_CUSTOM (a plugin with the policy kernels included: it takes
+ * no state limits).  A successful call invalidates the report below.
+ * ILQR_ABI_VERSION stays 5 with this entry, for the reasons given at ilqr_set_batch_limits: it is additive. */
+int ilqr_set_sample_penalty(ilqr_handle h, const double* weight /* [B], or NULL: clear */, double violation_tol);
+
+/* What the last penalised ilqr_sample_controls / ilqr_sampled_mpc left on the device, with S, R and n_steps of that call
+ * and rounds = R (ilqr_sample_controls) or n_steps * R (ilqr_sampled_mpc, step-major as its round_stats):
+ *   penalty_samples, violation_samples   P_s and v_s of the LAST round (ilqr_sampled_mpc: of the last step's), beside
+ *                                        cost_samples
+ *   penalty_new, violation_new           ilqr_sample_controls: P and v of U_new, from the rollout cost_new comes from
+ *                                        (launched by a penalised call whether or not cost_new was asked for);
+ *                                        ilqr_sampled_mpc: [n_steps][B], of the step's plan from the rollout cost_out
+ *                                        came from (SOFTMIN with cost_out given), otherwise of the last round's s*
+ *   round_penalty[r][b]                  P of sample 0, P of the round's argmin s*, v of s*; all NaN with no finite sample
+ *   round_violating[r][b]                the samples with a finite J~ and v > violation_tol
+ * The reductions run on the device in a fixed order without atomics, behind the round's weights.  The call is
+ * synchronous and changes nothing.
+ * Returns ILQR_ERR_INVALID_ARG for a NULL handle or desc, a wrong struct_size or every output NULL; ILQR_ERR_STATE
+ * unless the handle's most recent sampling call was a penalised ilqr_sample_controls / ilqr_sampled_mpc that succeeded:
+ * an ilqr_policy_rollout / ilqr_policy_monte_carlo, an unpenalised call, or an ilqr_set_sample_penalty after it
+ * invalidates the report.
+ * ILQR_ABI_VERSION stays 5 with this entry: it is additive, and no existing descriptor changes. */
+typedef struct ilqr_sample_penalty_report_desc {
+    uint32_t struct_size;      /* = sizeof(ilqr_sample_penalty_report_desc) */
+    int32_t reserved;          /* 0 */
+    void* penalty_samples;     /* [B][S] handle dtype; any output may be NULL, not all */
+    void* violation_samples;   /* [B][S] */
+    void* penalty_new;         /* [B] (ilqr_sampled_mpc: [n_steps][B]) */
+    void* violation_new;       /* [B] (ilqr_sampled_mpc: [n_steps][B]) */
+    double* round_penalty;     /* [rounds][B][3] */
+    int32_t* round_violating;  /* [rounds][B] */
+} ilqr_sample_penalty_report_desc;
+int ilqr_sample_penalty_report(ilqr_handle h, const ilqr_sample_penalty_report_desc* d);
 
 /* ---- multi-GPU hook -------------------------------------------
  * Writes 4 doubles to DEVICE memory `dev_out4` on the handle's stream:

@@ -44,7 +44,7 @@ SYMBOLS = (
     "ilqr_mpc_rearm", "ilqr_mpc_run", "ilqr_status_reduce", "ilqr_timing_enable", "ilqr_timing_reset", "ilqr_timing_get", "ilqr_algorithmic_bytes",
     "ilqr_set_control_limits", "ilqr_set_batch_params", "ilqr_set_state_limits", "ilqr_set_mpc_multipliers",
     "ilqr_set_batch_limits", "ilqr_policy_rollout", "ilqr_policy_monte_carlo", "ilqr_sample_controls",
-    "ilqr_sampled_mpc",
+    "ilqr_sampled_mpc", "ilqr_set_sample_penalty", "ilqr_sample_penalty_report",
 )
 # ilqr_set_batch_params: which rows
 BATCH_MODEL, BATCH_PLANT = 0, 1
@@ -66,6 +66,8 @@ MONTE_CARLO_COUNTS = ("n_finite", "n_violating")
 SAMPLE_BEST, SAMPLE_SOFTMIN = 0, 1
 SAMPLE_MODES = {"best": SAMPLE_BEST, "softmin": SAMPLE_SOFTMIN}
 SAMPLE_ROUND_STATS = ("round_cost_nominal", "round_cost_min", "round_ess")
+# ilqr_sample_penalty_report: the columns of a round's penalty row
+SAMPLE_PENALTY_STATS = ("round_penalty_start", "round_penalty_best", "round_violation_best")
 
 
 class Config(C.Structure):
@@ -131,6 +133,16 @@ class SampledMpcDesc(C.Structure):
         ("u_std", C.POINTER(C.c_double)), ("w", C.c_void_p),
         ("u_out", C.c_void_p), ("x_out", C.c_void_p), ("cost_out", C.c_void_p), ("U_plan", C.c_void_p),
         ("round_stats", C.POINTER(C.c_double)), ("round_counts", C.POINTER(C.c_int32)),
+    ]
+
+
+class SamplePenaltyReportDesc(C.Structure):
+    """ilqr_sample_penalty_report_desc (include/ilqr_hip.h), field for field."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("reserved", C.c_int32),
+        ("penalty_samples", C.c_void_p), ("violation_samples", C.c_void_p),
+        ("penalty_new", C.c_void_p), ("violation_new", C.c_void_p),
+        ("round_penalty", C.POINTER(C.c_double)), ("round_violating", C.POINTER(C.c_int32)),
     ]
 
 
@@ -205,6 +217,8 @@ def load():
     lib.ilqr_policy_monte_carlo.argtypes = [vp, C.POINTER(MonteCarloDesc)]
     lib.ilqr_sample_controls.argtypes = [vp, C.POINTER(SampleControlsDesc)]
     lib.ilqr_sampled_mpc.argtypes = [vp, C.POINTER(SampledMpcDesc)]
+    lib.ilqr_set_sample_penalty.argtypes = [vp, C.POINTER(cd), cd]
+    lib.ilqr_sample_penalty_report.argtypes = [vp, C.POINTER(SamplePenaltyReportDesc)]
     if lib.ilqr_abi_version() != ABI_VERSION:
         raise RuntimeError("libilqr_hip.so ABI version mismatch: rebuild the library")
     _lib = lib
@@ -614,6 +628,35 @@ class Handle:
         out = self._outputs(d, shapes, dtypes={"round_stats": np.float64, "round_counts": np.int32},
                             names={"u_out": "u", "x_out": "x", "cost_out": "cost"})
         self._chk(self.lib.ilqr_sampled_mpc(self.h, C.byref(d)))
+        return out
+
+    def set_sample_penalty(self, weight, violation_tol=0.0):
+        """The state limits as a penalty in the cost of sample_controls / sampled_mpc (include/ilqr_hip.h,
+        ilqr_set_sample_penalty): weight (B,) float64 > 0, the rho_b of P = (rho_b / 2) sum max(0, c)^2; None clears it.
+        violation_tol: the threshold of the report's round_violating."""
+        if weight is None:
+            self._chk(self.lib.ilqr_set_sample_penalty(self.h, None, 0.0))
+            return
+        w = np.ascontiguousarray(weight, dtype=np.float64)
+        if w.shape != (self.B,):
+            raise ValueError(f"weight must have shape ({self.B},), but got {w.shape}")
+        self._chk(self.lib.ilqr_set_sample_penalty(self.h, w.ctypes.data_as(C.POINTER(C.c_double)), float(violation_tol)))
+
+    def sample_penalty_report(self, n_samples, rounds, n_steps=None, samples=False):
+        """What the last penalised sample_controls (n_steps=None) or sampled_mpc left on the device (include/ilqr_hip.h,
+        ilqr_sample_penalty_report); n_samples, rounds and n_steps are that call's.  Returns a dict: penalty_new and
+        violation_new (B,) -- (n_steps, B) for sampled_mpc --, round_penalty (R, B, 3) float64 and round_violating (R, B)
+        int32 -- (n_steps, R, B[, 3]) for sampled_mpc --; penalty_samples and violation_samples (B, S) (with samples)."""
+        B, S, R = self.B, int(n_samples), int(rounds)
+        lead = () if n_steps is None else (int(n_steps),)
+        d = SamplePenaltyReportDesc()
+        d.struct_size = C.sizeof(SamplePenaltyReportDesc)
+        shapes = dict(penalty_new=lead + (B,), violation_new=lead + (B,), round_penalty=lead + (R, B, 3),
+                      round_violating=lead + (R, B))
+        if samples:
+            shapes.update(penalty_samples=(B, S), violation_samples=(B, S))
+        out = self._outputs(d, shapes, dtypes={"round_penalty": np.float64, "round_violating": np.int32})
+        self._chk(self.lib.ilqr_sample_penalty_report(self.h, C.byref(d)))
         return out
 
     # ---- measurement ------------------------------------------------------------------------------

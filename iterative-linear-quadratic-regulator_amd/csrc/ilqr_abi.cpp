@@ -312,6 +312,25 @@ int ilqr_sampled_mpc(ilqr_handle h, const ilqr_sampled_mpc_desc* d) {
     const int rc = sampling_entry(h, d, "sampled_mpc", "ilqr_sampled_mpc_desc");
     return rc ? rc : h->impl->sampled_mpc(*d);
 }
+int ilqr_set_sample_penalty(ilqr_handle h, const double* weight, double violation_tol) {
+    if (!h || !h->impl) return ILQR_ERR_INVALID_ARG;
+    const ilqr_config& c = h->impl->cfg;
+    // (a plugin with the policy kernels included: a user-defined system takes no state limits)
+    if (c.system == ILQR_SYS_LINEAR || c.system == ILQR_SYS_CUSTOM) {
+        h->impl->err = "set_sample_penalty: supported for the pendulum, UA double pendulum and double pendulum only";
+        return ILQR_ERR_UNSUPPORTED;
+    }
+    return h->impl->set_sample_penalty(weight, violation_tol);
+}
+int ilqr_sample_penalty_report(ilqr_handle h, const ilqr_sample_penalty_report_desc* d) {
+    if (!h || !h->impl) return ILQR_ERR_INVALID_ARG;
+    if (!d || d->struct_size != sizeof(ilqr_sample_penalty_report_desc)) {
+        h->impl->err = "sample_penalty_report: desc is NULL or struct_size does not match this library's "
+                       "ilqr_sample_penalty_report_desc";
+        return ILQR_ERR_INVALID_ARG;
+    }
+    return h->impl->sample_penalty_report(*d);
+}
 int ilqr_timing_enable(ilqr_handle h, int on) { ILQR_FWD(h, timing_enable(on)); }
 int ilqr_timing_reset(ilqr_handle h) { ILQR_FWD(h, timing_reset()); }
 int ilqr_timing_get(ilqr_handle h, double ms[ILQR_N_PHASES], int64_t launches[ILQR_N_PHASES]) {

@@ -91,6 +91,10 @@ template <typename T> struct SamplingOps {
     // sampled MPC: the epilogue of a step (plant step, logs, shift of Ub), and Ub back into U after the last one
     void (*advance)(const SampledMpcArgs<T>&, hipStream_t) = nullptr;
     void (*commit)(const SampleCommitArgs<T>&, hipStream_t) = nullptr;
+    // the state-limit penalty (ilqr_set_sample_penalty): the rollout with J + P as its cost, and the penalty's share of a
+    // round's report; null where the system takes no limits (takes_limits: a generated plugin has neither kernel)
+    void (*rollout_pen)(const SampleArgs<T>&, const NoiseArgs<T>&, hipStream_t) = nullptr;
+    void (*penalty_stats)(const SampleArgs<T>&, hipStream_t) = nullptr;
     explicit operator bool() const { return rollout != nullptr; }
 };
 
@@ -304,8 +308,11 @@ template <typename T, typename Dyn> void launch_sample_begin(const SampleArgs<T>
     const size_t n = (size_t)a.B * a.N * Dyn::NU;
     ILQR_LAUNCH((sample_nominal_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.Ub, a.U, a.cur_slot, a.B, a.N, Dyn::NU);
 }
-template <typename T, typename Dyn> void launch_sample_rollout(const SampleArgs<T>& a, const NoiseArgs<T>& nz, hipStream_t s) {
-    ILQR_LAUNCH((sample_rollout_kernel<T, Dyn>), dim3((a.S + 63) / 64, a.B), dim3(64), 0, s, a, nz);
+template <typename T, typename Dyn, bool PEN = false> void launch_sample_rollout(const SampleArgs<T>& a, const NoiseArgs<T>& nz, hipStream_t s) {
+    ILQR_LAUNCH((sample_rollout_kernel<T, Dyn, PEN>), dim3((a.S + 63) / 64, a.B), dim3(64), 0, s, a, nz);
+}
+template <typename T> void launch_sample_penalty_stats(const SampleArgs<T>& a, hipStream_t s) {
+    ILQR_LAUNCH((sample_penalty_stats_kernel<T>), dim3(a.B), dim3(64), 0, s, a);
 }
 template <typename T, typename Dyn> void launch_sample_update(const SampleArgs<T>& a, hipStream_t s) {
     const int rows = a.N * Dyn::NU;
@@ -447,6 +454,10 @@ template <typename T, typename Dyn> Ops<T> make_ops() {
         o.sampling = {{launch_policy<T, Dyn, false>, launch_policy<T, Dyn, true>}, launch_sample_begin<T, Dyn>,
                       launch_sample_rollout<T, Dyn>, launch_sample_update<T, Dyn>, launch_sampled_mpc_advance<T, Dyn>,
                       launch_sample_commit<T, Dyn>};
+        if constexpr (takes_limits<Dyn>()) {
+            o.sampling.rollout_pen = launch_sample_rollout<T, Dyn, true>;
+            o.sampling.penalty_stats = launch_sample_penalty_stats<T>;
+        }
     }
     o.eval = [](const EvalArgs<T>& a, hipStream_t s) {
         ILQR_LAUNCH((eval_points_kernel<T, Dyn>), dim3((a.npts + 63) / 64), dim3(64), 0, s, a);

@@ -188,6 +188,23 @@ template <int NU, typename T> ILQR_DEV void uniform_box_bounds(const Limits<T>& 
     }
 }
 
+// the state bounds of trajectory b, wave-uniform: its rows where state limits were given per trajectory, else the shared
+// ones (ALBounds' own constructor reads a lane's row with vector loads: here the row's address is made of kernel
+// arguments and blockIdx only)
+template <typename T, int NX> ILQR_DEV ALBounds<T, NX> uniform_al_bounds(const Limits<T>& a, size_t B, int b) {
+    Limits<T> shared = a;
+    shared.x_lo_rows = shared.x_hi_rows = nullptr;
+    ALBounds<T, NX> o(shared, B, b);
+    if (a.x_lo_rows) {
+#pragma unroll
+        for (int i = 0; i < NX; ++i) {
+            o.lo[i] = as_uniform(a.x_lo_rows)[(size_t)i * B + b];
+            o.hi[i] = as_uniform(a.x_hi_rows)[(size_t)i * B + b];
+        }
+    }
+    return o;
+}
+
 // sample s of trajectory b: l = b * S + s of the L = B * S samples of a call
 struct SampleAt { int b, s; size_t B, L, l; };
 
@@ -198,8 +215,9 @@ struct SampleAt { int b, s; size_t B, L, l; };
 // law for the rest: Law(a, nz, k, mr, x) reads the law's wave-uniform inputs and step 0's nominal and may replace or
 // perturb x = x_0[b]; pp is the constants the integrator reads; control(t, tn, x, u) requests step tn = min(t + 1, N - 1)'s
 // nominal and draws step t's noise (nothing of either depends on the state: they stand in front of step t's arithmetic)
-// and forms u_t before the clamp; advance(t, x, xn) moves x and the nominal on to t + 1; finish(x) stores what the law
-// reports beside the cost.  Args (PolicyArgs, SampleArgs) brings B, S, N, integ, dt, params, rows, x0, lim, cost, Xs, Us.
+// and forms u_t before the clamp; advance(t, x, xn) moves x and the nominal on to t + 1; total(cost) is what the law stores
+// as the sample's cost (the cost itself, or the cost plus what the law adds to it in one add); finish(x) stores what the
+// law reports beside the cost.  Args (PolicyArgs, SampleArgs) brings B, S, N, integ, dt, params, rows, x0, lim, cost, Xs, Us.
 template <typename T, typename Dyn, typename Law, typename Args>
 ILQR_DEV void sampled_rollout(const Args& a, const NoiseArgs<T>& nz) {
     constexpr int NX = Dyn::NX, NU = Dyn::NU;
@@ -248,7 +266,7 @@ ILQR_DEV void sampled_rollout(const Args& a, const NoiseArgs<T>& nz) {
     }
     store_x(N);
     cost += Cost<T, Dyn>::terminal(p, x);
-    a.cost[l] = cost;
+    a.cost[l] = law.total(cost);
     law.finish(x);
 }
 
@@ -360,6 +378,7 @@ template <typename T, typename Dyn, bool SROWS, bool NOISE> struct FeedbackLaw {
 #pragma unroll
         for (int r = 0; r < R; ++r) g[r] = g_n[r];
     }
+    ILQR_DEV T total(T cost) const { return cost; }
     ILQR_DEV void finish(const T (&x)[NX]) {
 #pragma unroll
         for (int i = 0; i < NX; ++i) {

@@ -12,6 +12,9 @@
 // outputs are sample-innermost.
 // Three launches per round (rollout, weights, update), all on the handle's stream and on a private copy of U
 // ([N][n_u][B]): no host synchronisation between rounds.
+// While a state-limit penalty is set (ilqr_set_sample_penalty) the rollout is its PEN instantiation -- J_s + P_s in place
+// of J_s, P_s and the violation stored beside it -- and a fourth launch per round reduces the penalty's report; the
+// weights and the update are the same kernels and read the cost as they always did.
 #pragma once
 #include "policy_rollout.hpp"
 
@@ -44,6 +47,49 @@ template <typename T> struct SampleArgs {
     int* __restrict__ sel;              // [B] argmin over the finite costs, lowest s on ties; -1 with none
     double* __restrict__ stats;         // [B][3] of this round: cost of sample 0, min finite cost, effective sample size
     int* __restrict__ counts;           // [B] of this round: n_finite
+    // the state-limit penalty (ilqr_set_sample_penalty): read and written by the PEN instantiation of the rollout and by
+    // sample_penalty_stats_kernel only; all null / 0 while no penalty is set
+    const T* __restrict__ pen_rho;      // [B] the weights rho_b > 0
+    T* __restrict__ pen;                // [L] P_s
+    T* __restrict__ viol;               // [L] v_s
+    double pen_tol;                     // violation_tol
+    double* __restrict__ pen_stats;     // [B][3] of this round: P of sample 0, P and v of s* (NaN with no finite sample)
+    int* __restrict__ pen_counts;       // [B] of this round: the finite samples with v > pen_tol
+};
+
+// The state-limit penalty of a sample (PEN; the empty form costs nothing):
+//   P = sum_{t=1..N} al_phi(bounds_b, x_t, lam = 0, rho_b),   v = max(0, max_{t, q in mask} c_q(x_t))
+// al_phi sums a point's constraints q ascending from 0, and P takes the points t ascending; the sample's cost is
+// J + P in one add after the terminal cost.  Bounds, mask and rho_b are wave-uniform and read once, before the step loop.
+// A row's infinite bound in a masked slot gives c = -inf, max(0, rho c) = 0: nothing is added and v stays (kernels.hpp).
+template <typename T, int NX, bool PEN> struct SamplePenalty {
+    ILQR_DEV SamplePenalty(const SampleArgs<T>&, const SampleAt&) {}
+    ILQR_DEV void add(const T (&)[NX]) {}
+    ILQR_DEV T total(T cost) const { return cost; }
+    ILQR_DEV void store(const SampleArgs<T>&, size_t) const {}
+};
+template <typename T, int NX> struct SamplePenalty<T, NX, true> {
+    const ALBounds<T, NX> xb;
+    const T rho;
+    T P = T(0), v = T(0);
+    ILQR_DEV SamplePenalty(const SampleArgs<T>& a, const SampleAt& k)
+        : xb(uniform_al_bounds<T, NX>(a.lim, k.B, k.b)), rho(as_uniform(a.pen_rho)[k.b]) {}
+    ILQR_DEV void add(const T (&x)[NX]) {
+        const T lam[2 * NX] = {};
+#pragma unroll
+        for (int q = 0; q < 2 * NX; ++q) {
+            if ((xb.mask >> q) & 1) {
+                const T c = al_constraint<T, NX>(xb, x, q);
+                v = c > v ? c : v;
+            }
+        }
+        P += al_phi<T, NX>(xb, x, lam, rho);
+    }
+    ILQR_DEV T total(T cost) const { return cost + P; }
+    ILQR_DEV void store(const SampleArgs<T>& a, size_t l) const {
+        a.pen[l] = P;
+        a.viol[l] = v;
+    }
 };
 
 // Ub[t][j][b] <- U of b's current slot
@@ -57,18 +103,20 @@ __global__ void sample_nominal_kernel(T* __restrict__ Ub, const T* __restrict__ 
 }
 
 // The perturbation law: e_0 = n_0, e_t = beta e_{t-1} + c n_t, u_t = Ub_t + e_t through the model itself; sample 0 is the
-// nominal (e = 0: its draw is made and dropped).
-template <typename T, typename Dyn> struct PerturbLaw {
+// nominal (e = 0: its draw is made and dropped).  PEN: the state-limit penalty of x_1 .. x_N enters the cost.
+template <typename T, typename Dyn, bool PEN = false> struct PerturbLaw {
     static constexpr int NX = Dyn::NX, NU = Dyn::NU;
+    static_assert(!PEN || takes_limits<Dyn>(), "only a system that takes state limits has the penalised rollout");
     static_assert(NU <= 8, "component j of a control takes z_{j mod 4} of the generator call of group j / 4 (noise_draw)");
     const SampleArgs<T>& a;
     const NoiseArgs<T>& nz;
     const SampleAt k;
     T* const pp;                                  // the model's own constants
     T sd[NU], e[NU], n[NU], ub[NU], ub_n[NU];     // u_std[b], Ub_t and Ub_{t+1}: wave-uniform
+    SamplePenalty<T, NX, PEN> pen;
 
     ILQR_DEV PerturbLaw(const SampleArgs<T>& a_, const NoiseArgs<T>& nz_, const SampleAt& k_, T* mr, T (&)[NX])
-        : a(a_), nz(nz_), k(k_), pp(mr) {
+        : a(a_), nz(nz_), k(k_), pp(mr), pen(a_, k_) {
         uniform_load<T, NU>(a.u_std + (size_t)k.b * NU, sd);
 #pragma unroll
         for (int j = 0; j < NU; ++j) {
@@ -94,15 +142,18 @@ template <typename T, typename Dyn> struct PerturbLaw {
         for (int i = 0; i < NX; ++i) x[i] = xn[i];
 #pragma unroll
         for (int j = 0; j < NU; ++j) ub[j] = ub_n[j];
+        pen.add(x);      // the constraints of x_{t+1} (t + 1 = 1..N)
     }
-    ILQR_DEV void finish(const T (&)[NX]) {}
+    ILQR_DEV T total(T cost) const { return pen.total(cost); }
+    ILQR_DEV void finish(const T (&)[NX]) { pen.store(a, k.l); }
 };
 
 // The rollout of a round's samples.  Launched with S = 1 it is the rollout of the nominal alone (cost_new / X_new): the
 // same code on the same controls, so the cost of a BEST call's result is the winning sample's cost bit for bit.
-template <typename T, typename Dyn>
+// PEN (ilqr_set_sample_penalty): cost[l] = J + P, and pen[l] = P, viol[l] = v beside it.
+template <typename T, typename Dyn, bool PEN = false>
 __global__ void __launch_bounds__(64) sample_rollout_kernel(SampleArgs<T> a, NoiseArgs<T> nz) {
-    sampled_rollout<T, Dyn, PerturbLaw<T, Dyn>>(a, nz);
+    sampled_rollout<T, Dyn, PerturbLaw<T, Dyn, PEN>>(a, nz);
 }
 
 // The weights of a round: one wave per trajectory over its contiguous [S] costs, each lane over its stride of the row and
@@ -151,6 +202,33 @@ __global__ void __launch_bounds__(64) sample_weights_kernel(SampleArgs<T> a) {
     o[1] = any ? cmin : __builtin_nan("");
     o[2] = !any ? 0.0 : a.mode == ILQR_SAMPLE_SOFTMIN ? W * W / W2 : 1.0;
     a.counts[b] = (int)n;
+}
+
+// The penalty's share of a round's report, launched behind sample_weights_kernel of a penalised round only: one wave per
+// trajectory over its contiguous [S] rows, each lane over its stride and then a butterfly (a fixed order, no atomics).
+//   pen_stats = P of sample 0, P and v of s* = sel[b] (all NaN with no finite sample)
+//   pen_counts = the samples with a finite cost and v > pen_tol
+template <typename T>
+__global__ void __launch_bounds__(64) sample_penalty_stats_kernel(SampleArgs<T> a) {
+    const int b = blockIdx.x, lane = threadIdx.x, S = a.S;
+    const T* c = a.cost + (size_t)b * S;
+    const T* p = a.pen + (size_t)b * S;
+    const T* v = a.viol + (size_t)b * S;
+    double nv = 0;
+    for (int s = lane; s < S; s += 64) {
+        const double ci = (double)c[s];
+        if (!(ci - ci == 0.0)) continue;       // NaN or an infinity
+        nv += (double)v[s] > a.pen_tol ? 1.0 : 0.0;
+    }
+    nv = wave_sum(nv);
+    if (lane != 0) return;
+    const int s = a.sel[b];
+    const double nan = __builtin_nan("");
+    double* o = a.pen_stats + (size_t)b * 3;
+    o[0] = s >= 0 ? (double)p[0] : nan;
+    o[1] = s >= 0 ? (double)p[s >= 0 ? s : 0] : nan;
+    o[2] = s >= 0 ? (double)v[s >= 0 ? s : 0] : nan;
+    a.pen_counts[b] = (int)nv;
 }
 
 // BEST: Ub_t <- the winner's controls as applied; one lane per (t, j) of a trajectory.  No finite sample: Ub stays.

@@ -65,6 +65,8 @@ struct SolverBase {
     virtual int policy_monte_carlo(const ilqr_monte_carlo_desc& d) = 0;
     virtual int sample_controls(const ilqr_sample_controls_desc& d) = 0;
     virtual int sampled_mpc(const ilqr_sampled_mpc_desc& d) = 0;
+    virtual int set_sample_penalty(const double* weight, double violation_tol) = 0;
+    virtual int sample_penalty_report(const ilqr_sample_penalty_report_desc& d) = 0;
 };
 
 int system_dims(int system, int n_x, int n_u);  // 1 if (system, n_x, n_u) is a known combination
@@ -248,6 +250,22 @@ template <typename T> struct SamplingBufs {
     DevBuf<T> w_steps, plans;     // sampled MPC: w [n_steps][B][n_x] as the caller gave it; U_plan [n_steps][N][n_u][B]
 };
 
+// The state-limit penalty of the sampled search (ilqr_set_sample_penalty) and what its last call left for
+// ilqr_sample_penalty_report.  pen / viol: the samples' [L] and, behind them, the nominal's own rollouts [n_steps][B]
+// (sample_controls: one row).  stats / counts: one row per round, as SamplingBufs::stats / counts.
+template <typename T> struct PenaltyState {
+    bool on = false;
+    double tol = 0;
+    DevBuf<T> rho;                // [B] the weights in the handle's dtype
+    DevBuf<T> pen, viol;
+    DevBuf<double> stats;         // [rounds][B][3]
+    DevBuf<int> counts;           // [rounds][B]
+    // the report: valid while the handle's most recent sampling call was a penalised search that succeeded
+    bool report = false;
+    size_t L = 0, rounds = 0, per_step = 0, steps = 0;   // per_step: R; steps: 1 (sample_controls) or n_steps
+    bool plan_rollout = false;    // pen / viol behind the samples hold every step's plan (else: the last round's s*)
+};
+
 // per-trajectory parameters (ilqr_set_batch_params): rows [n_sys + n_x][B] of the model (derived constants, x_target),
 // plant_rows [n_sys][B] of the MPC plant; device tensors of the handle's dtype
 template <typename T> struct BatchParams {
@@ -329,6 +347,7 @@ template <typename T> class SolverT : public SolverBase {
     BatchParams<T> het;
     StateLimits<T> al;
     SamplingBufs<T> smp;
+    PenaltyState<T> pen;
 
     // (the device buffers free themselves after this body: DevBuf)
     ~SolverT() override {
@@ -1309,6 +1328,7 @@ template <typename T> class SolverT : public SolverBase {
         for (size_t i = 0; d.plant_rows && i < L * ns; ++i)
             if (!std::isfinite(d.plant_rows[i])) return fail(ILQR_ERR_INVALID_ARG, who + ": every plant_rows value must be finite");
         if ((rc = sampling_settle())) return rc;
+        pen.report = false;          // (the most recent sampling call is no penalised search)
         const size_t nX = L * NX * (size_t)(N + 1), nU = L * NU * (size_t)N, nW = L * NX * (size_t)N;
         // the disturbances a Monte Carlo call was asked to return (none are drawn without w_std: those are zeros)
         const bool w_back = mc && mc->w_out && mc->w_std;
@@ -1410,7 +1430,47 @@ template <typename T> class SolverT : public SolverBase {
         a.Ub = smp.nominal.p;
         a.cost = smp.summaries; a.Us = smp.controls.p;
         a.w = smp.weights.p; a.wsum = smp.weights.p + L; a.sel = smp.winners.p;
+        if (pen.on) { a.pen_rho = pen.rho.p; a.pen = pen.pen.p; a.viol = pen.viol.p; a.pen_tol = pen.tol; }
         return a;
+    }
+    // The penalty's buffers for a search of `rounds` rounds and `steps` rollouts of the nominal alone, and the report's
+    // shapes; the report itself becomes valid when the call has succeeded (search_done).
+    int search_begin(size_t L, size_t rounds, size_t per_step, size_t steps) {
+        pen.report = false;
+        if (!pen.on) return ILQR_OK;
+        int rc;
+        if ((rc = grow(pen.pen, L + steps * B)) || (rc = grow(pen.viol, L + steps * B)) ||
+            (rc = grow(pen.stats, rounds * B * 3)) || (rc = grow(pen.counts, rounds * B)))
+            return rc;
+        pen.L = L; pen.rounds = rounds; pen.per_step = per_step; pen.steps = steps;
+        return ILQR_OK;
+    }
+    int search_done(bool plan_rollout) {
+        ILQR_HIPCHK(hipStreamSynchronize(stream));
+        const int rc = check_launch();
+        if (rc == ILQR_OK && pen.on) { pen.report = true; pen.plan_rollout = plan_rollout; }
+        return rc;
+    }
+    // One round: the rollout of the samples (penalised while a penalty is set: SampleArgs::pen), the weights and the
+    // update, and behind them the penalty's share of the round's report.  `a` brings the round's stream and rows.
+    int search_round(SampleArgs<T>& a, const NoiseArgs<T>& nz, size_t row) {
+        int rc;
+        if (a.pen) { a.pen_stats = pen.stats.p + row * B * 3; a.pen_counts = pen.counts.p + row * B; }
+        if ((rc = search_rollout(a, nz))) return rc;
+        if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.update(a, stream); }))) return rc;
+        if (a.pen && (rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.penalty_stats(a, stream); }))) return rc;
+        return ILQR_OK;
+    }
+    int search_rollout(const SampleArgs<T>& a, const NoiseArgs<T>& nz) {
+        return timed(ILQR_PHASE_OTHER, [&] { (a.pen ? ops.sampling.rollout_pen : ops.sampling.rollout)(a, nz, stream); });
+    }
+    // the rollout of the nominal alone (S = 1: sample 0 is the nominal): its cost behind the samples', and while a
+    // penalty is set its P and v behind the samples' too, in row `step` of [steps][B]
+    SampleArgs<T> nominal_args(const SampleArgs<T>& a, size_t L, size_t step) const {
+        SampleArgs<T> f = a;
+        f.S = 1; f.cost = a.cost + L; f.Us = nullptr;
+        if (a.pen) { f.pen = a.pen + L + step * B; f.viol = a.viol + L + step * B; }
+        return f;
     }
     // R rounds of (rollout of S samples, weights, update of the private nominal), then the nominal's own rollout: every
     // kernel of the search is queued on the stream without a host synchronisation in between.  The downloads follow the
@@ -1436,7 +1496,7 @@ template <typename T> class SolverT : public SolverBase {
             return rc;
         if (d.X_new && (rc = grow(smp.states, nXb))) return rc;
         if ((rc = grow(staging, std::max({nUb, d.X_new ? nXb : (size_t)0, d.U_samples ? nU : (size_t)0})))) return rc;
-        if ((rc = up_std({d.u_std}, NU))) return rc;
+        if ((rc = up_std({d.u_std}, NU)) || (rc = search_begin(L, Rn, Rn, 1))) return rc;
         SampleArgs<T> a = search_args(d, L);
         const NoiseArgs<T> nz = noise_args(d.seed, d.first_trajectory, d.distribution);
         if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.begin(a, stream); }))) return rc;
@@ -1444,14 +1504,14 @@ template <typename T> class SolverT : public SolverBase {
             a.stream = 2u + (unsigned)d.first_round + (unsigned)r;
             a.stats = smp.stats.p + r * B * 3;
             a.counts = smp.counts.p + r * B;
-            if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.rollout(a, nz, stream); }))) return rc;
-            if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.update(a, stream); }))) return rc;
+            if ((rc = search_round(a, nz, r))) return rc;
         }
-        // the nominal alone: the rollout at S = 1 (sample 0 is the nominal), its cost behind the samples'
-        SampleArgs<T> f = a;
-        f.S = 1; f.cost = a.cost + L; f.Us = nullptr; f.Xs = d.X_new ? smp.states.p : nullptr;
-        if (d.cost_new || d.X_new) {
-            if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.rollout(f, nz, stream); }))) return rc;
+        // the nominal alone: the rollout at S = 1 (sample 0 is the nominal), its cost behind the samples' (a penalised call
+        // launches it in any case: the report's penalty_new / violation_new come from it)
+        SampleArgs<T> f = nominal_args(a, L, 0);
+        f.Xs = d.X_new ? smp.states.p : nullptr;
+        if (d.cost_new || d.X_new || a.pen) {
+            if ((rc = search_rollout(f, nz))) return rc;
         }
         if (d.round_stats) ILQR_HIPCHK(hipMemcpyAsync(d.round_stats, smp.stats.p, Rn * B * 3 * sizeof(double), hipMemcpyDeviceToHost, stream));
         if (d.round_counts) ILQR_HIPCHK(hipMemcpyAsync(d.round_counts, smp.counts.p, Rn * B * sizeof(int), hipMemcpyDeviceToHost, stream));
@@ -1460,8 +1520,7 @@ template <typename T> class SolverT : public SolverBase {
         if (d.U_samples && (rc = down_traj(d.U_samples, smp.controls, L, NU, N))) return rc;
         if (d.U_new && (rc = down_traj(d.U_new, smp.nominal, (size_t)B, NU, N))) return rc;
         if (d.X_new && (rc = down_traj(d.X_new, smp.states, (size_t)B, NX, N + 1))) return rc;
-        ILQR_HIPCHK(hipStreamSynchronize(stream));
-        return check_launch();
+        return search_done(true);
     }
 
     // Sampled MPC (sampled_mpc.hpp): per step R rounds of the search above from x_0 = the plant state and the epilogue
@@ -1486,7 +1545,8 @@ template <typename T> class SolverT : public SolverBase {
         if ((rc = sample_total(who, d.n_samples, &L)) || (rc = sampling_supported(who)) || (rc = sampling_problem(who))) return rc;
         if (!mpc_ready) return fail(ILQR_ERR_STATE, who + " before mpc_reset / mpc_rearm");
         if (cfg.plant_integrator < 0) return fail(ILQR_ERR_STATE, who + ": the handle was created without a plant integrator");
-        if (al.on) return al_refuse("sampled_mpc");
+        // (the search's J ignores state limits unless the penalty brings them in)
+        if (al.on && !pen.on) return al_refuse("sampled_mpc");
         if ((rc = sampling_settle())) return rc;
         const size_t nU = L * NU * (size_t)N, nUb = (size_t)B * NU * N;
         if ((rc = grow(smp.summaries, L + (size_t)B)) || (rc = grow(smp.controls, nU)) || (rc = grow(smp.nominal, nUb)) ||
@@ -1495,7 +1555,7 @@ template <typename T> class SolverT : public SolverBase {
             return rc;
         if (d.w && (rc = grow(smp.w_steps, K * B * NX))) return rc;
         if (d.U_plan && ((rc = grow(smp.plans, K * nUb)) || (rc = grow(staging, nUb)))) return rc;
-        if ((rc = mpc_log_room(d.n_steps)) || (rc = up_std({d.u_std}, NU))) return rc;
+        if ((rc = mpc_log_room(d.n_steps)) || (rc = up_std({d.u_std}, NU)) || (rc = search_begin(L, K * Rn, Rn, K))) return rc;
         // (w arrives in the layout the epilogue reads; the caller's buffer outlives the copy: the call ends synchronised)
         if (d.w) ILQR_HIPCHK(hipMemcpyAsync(smp.w_steps.p, d.w, K * B * NX * sizeof(T), hipMemcpyHostToDevice, stream));
         SampleArgs<T> a = search_args(d, L);
@@ -1517,13 +1577,10 @@ template <typename T> class SolverT : public SolverBase {
                 a.stream = 2u + (unsigned)d.first_round + (unsigned)row;
                 a.stats = smp.stats.p + row * B * 3;
                 a.counts = smp.counts.p + row * B;
-                if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.rollout(a, nz, stream); }))) return rc;
-                if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.update(a, stream); }))) return rc;
+                if ((rc = search_round(a, nz, row))) return rc;
             }
             if (plan_cost) {
-                SampleArgs<T> f = a;
-                f.S = 1; f.cost = a.cost + L; f.Us = nullptr;
-                if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.rollout(f, nz, stream); }))) return rc;
+                if ((rc = search_rollout(nominal_args(a, L, k), nz))) return rc;
             }
             m.step = (int)k;
             m.stats = (d.cost_out && !plan_cost) ? a.stats : nullptr;
@@ -1543,8 +1600,72 @@ template <typename T> class SolverT : public SolverBase {
             return rc;
         for (size_t k = 0; d.U_plan && k < K; ++k)
             if ((rc = down_traj((T*)d.U_plan + k * nUb, smp.plans.p + k * nUb, (size_t)B, NU, N))) return rc;
+        return search_done(plan_cost);
+    }
+
+    // ---- the state-limit penalty of the search (include/ilqr_hip.h, ilqr_set_sample_penalty) -----------------
+    // Everything is checked before the handle or the device is touched.  The weights cross once, in the handle's dtype.
+    int set_sample_penalty(const double* weight, double violation_tol) override {
+        const std::string who = "set_sample_penalty";
+        if (!ops.sampling.rollout_pen)
+            return fail(ILQR_ERR_UNSUPPORTED, who + ": supported for the pendulum, UA double pendulum and double pendulum only");
+        if (!weight) {
+            pen.on = false;
+            pen.report = false;
+            return ILQR_OK;
+        }
+        if (!(std::isfinite(violation_tol) && violation_tol >= 0.0))
+            return fail(ILQR_ERR_INVALID_ARG, who + ": violation_tol must be finite and >= 0");
+        std::vector<T> w((size_t)B);
+        for (size_t b = 0; b < (size_t)B; ++b) {
+            // (finite and positive as the device holds it: beyond the dtype a double arrives as +inf, below it as 0)
+            if (!std::isfinite(weight[b]) || weight[b] > (double)std::numeric_limits<T>::max() || !((T)weight[b] > T(0)))
+                return fail(ILQR_ERR_INVALID_ARG, who + ": every weight must be finite in the handle's dtype and > 0");
+            w[b] = (T)weight[b];
+        }
+        if (int rc = grow(pen.rho, (size_t)B)) return rc;
+        ILQR_HIPCHK(hipMemcpyAsync(pen.rho.p, w.data(), w.size() * sizeof(T), hipMemcpyHostToDevice, stream));
+        ILQR_HIPCHK(hipStreamSynchronize(stream));      // (w outlives the copy)
+        pen.on = true;
+        pen.tol = violation_tol;
+        pen.report = false;
+        return ILQR_OK;
+    }
+    // Downloads of what the last penalised search left in `pen`; nothing is launched.
+    int sample_penalty_report(const ilqr_sample_penalty_report_desc& d) override {
+        const std::string who = "sample_penalty_report";
+        if (!d.penalty_samples && !d.violation_samples && !d.penalty_new && !d.violation_new && !d.round_penalty && !d.round_violating)
+            return fail(ILQR_ERR_INVALID_ARG, who + ": every output is NULL");
+        if (!pen.report)
+            return fail(ILQR_ERR_STATE, who + ": the handle's most recent sampling call was not a penalised sample_controls / sampled_mpc");
+        const size_t L = pen.L, nB = (size_t)B, n_new = pen.steps * nB;
+        auto fetch = [&](void* host, const void* dev, size_t bytes) -> int {
+            if (host) ILQR_HIPCHK(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, stream));
+            return ILQR_OK;
+        };
+        int rc;
+        if ((rc = fetch(d.penalty_samples, pen.pen.p, L * sizeof(T))) || (rc = fetch(d.violation_samples, pen.viol.p, L * sizeof(T))) ||
+            (rc = fetch(d.round_penalty, pen.stats.p, pen.rounds * nB * 3 * sizeof(double))) ||
+            (rc = fetch(d.round_violating, pen.counts.p, pen.rounds * nB * sizeof(int))))
+            return rc;
+        std::vector<double> rows;
+        if (pen.plan_rollout) {
+            if ((rc = fetch(d.penalty_new, pen.pen.p + L, n_new * sizeof(T))) || (rc = fetch(d.violation_new, pen.viol.p + L, n_new * sizeof(T))))
+                return rc;
+        } else if (d.penalty_new || d.violation_new) {
+            rows.resize(pen.rounds * nB * 3);
+            if ((rc = fetch(rows.data(), pen.stats.p, rows.size() * sizeof(double)))) return rc;
+        }
         ILQR_HIPCHK(hipStreamSynchronize(stream));
-        return check_launch();
+        // the last round's s* of every step: the values are T widened to double on the device, so the way back is exact
+        for (size_t k = 0; !rows.empty() && k < pen.steps; ++k) {
+            const double* last = rows.data() + ((k + 1) * pen.per_step - 1) * nB * 3;
+            for (size_t b = 0; b < nB; ++b) {
+                if (d.penalty_new) ((T*)d.penalty_new)[k * nB + b] = (T)last[b * 3 + 1];
+                if (d.violation_new) ((T*)d.violation_new)[k * nB + b] = (T)last[b * 3 + 2];
+            }
+        }
+        return ILQR_OK;
     }
 
     // ---- pure functional calls --------------------------------------------------------

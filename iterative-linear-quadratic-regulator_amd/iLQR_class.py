@@ -277,16 +277,40 @@ def policy_monte_carlo_args(system, N, B, batched, n_samples, seed=0, x_0_std=No
     return S, int(seed), x0_std, w_std, _lib.NOISE_DISTRIBUTIONS[distribution], rows, code, tol, int(first_trajectory)
 
 
-SampledControls = namedtuple(
+# What SampledControls and SampledMPC gain while a penalty is set (iLQR.set_sample_penalty): attributes beside the tuple's
+# own fields, None without a penalty.  The tuple itself (_fields, unpacking, iteration) stays the unpenalised record.
+PENALTY_FIELDS = ("penalty", "violation") + _lib.SAMPLE_PENALTY_STATS + ("round_n_violating", "penalty_samples",
+                                                                        "violation_samples")
+
+
+def _with_penalty_fields(record):
+    class Record(record):
+        def __new__(cls, *args, **kw):
+            extra = {k: kw.pop(k) for k in PENALTY_FIELDS if k in kw}
+            self = super().__new__(cls, *args, **kw)
+            self.__dict__.update(extra)
+            return self
+
+    for k in PENALTY_FIELDS:
+        setattr(Record, k, None)
+    Record.__name__ = Record.__qualname__ = record.__name__
+    return Record
+
+
+SampledControls = _with_penalty_fields(namedtuple(
     "SampledControls", ("U", "cost", "cost_start") + _lib.SAMPLE_ROUND_STATS + ("round_n_finite", "applied", "X", "cost_samples",
-                                                                             "U_samples"), defaults=(None,) * 4)
-SampledControls.__doc__ = """Result of iLQR.sample_controls.  U ([B,] n_u, N): the searched controls; cost ([B]): their plain
+                                                                             "U_samples"), defaults=(None,) * 4))
+SampledControls.__doc__ ="""Result of iLQR.sample_controls.  U ([B,] n_u, N): the searched controls; cost ([B]): their plain
 cost from x_0; cost_start ([B]): the cost of the controls the call started from; round_cost_nominal, round_cost_min,
 round_ess (float64) and round_n_finite (int), each (R, [B]): per round the cost of its nominal, the minimum over the
 samples with a finite cost (NaN with none), the effective sample size of the softmin weights (1 in "best" mode) and the
 number of finite samples; applied ([B] bool, None without apply=True): where U became the solver's initial guess; X
 ([B,] n_x, N + 1) with trajectories=True; cost_samples ([B,] S) and U_samples ([B,] S, n_u, N) of the last round with
-samples=True; else None."""
+samples=True; else None.  While a penalty is set (set_sample_penalty) every cost above is J + P, and: penalty,
+violation ([B]): P and the largest state-limit violation of U's rollout; round_penalty_start, round_penalty_best,
+round_violation_best (float64) and round_n_violating (int), each (R, [B]): per round P of its nominal, P and the
+violation of its best sample (NaN with no finite sample) and the number of finite samples violating by more than
+violation_tol; penalty_samples, violation_samples ([B,] S) of the last round with samples=True."""
 
 
 def sample_controls_args(system, N, B, batched, n_samples, rounds=1, seed=0, u_std=None, mode="best", temperature=None,
@@ -337,14 +361,17 @@ def sample_controls_args(system, N, B, batched, n_samples, rounds=1, seed=0, u_s
             _lib.NOISE_DISTRIBUTIONS[distribution], first, first_r)
 
 
-SampledMPC = namedtuple("SampledMPC", ("U_sim", "X_sim", "cost") + _lib.SAMPLE_ROUND_STATS + ("round_n_finite", "U_plan"),
-                        defaults=(None,))
+SampledMPC = _with_penalty_fields(namedtuple(
+    "SampledMPC", ("U_sim", "X_sim", "cost") + _lib.SAMPLE_ROUND_STATS + ("round_n_finite", "U_plan"), defaults=(None,)))
 SampledMPC.__doc__ = """Result of iLQR.sampled_mpc.  U_sim (n_steps, [B,] n_u): the controls applied; X_sim (n_steps, [B,]
 n_x): the plant state AFTER each step; cost (n_steps, [B]): the cost the search reports for each step's plan, from the
 state before the step (the last round's minimum in "best" mode, the plain cost of the averaged plan in "softmin" mode);
 round_cost_nominal, round_cost_min, round_ess (float64) and round_n_finite (int), each (n_steps, R, [B]): the round
 statistics of SampledControls for every round of every step; U_plan (n_steps, [B,] n_u, N) with plans=True: the plan of
-each step before it is shifted, else None."""
+each step before it is shifted, else None.  While a penalty is set (set_sample_penalty) cost is J + P, and: penalty,
+violation (n_steps, [B]): P and the violation of each step's plan ("best" mode: of the last round's best sample);
+round_penalty_start, round_penalty_best, round_violation_best, round_n_violating (n_steps, R, [B]) as SampledControls';
+penalty_samples, violation_samples ([B,] S) of the last step's last round with samples=True."""
 
 
 def sampled_mpc_args(system, N, B, batched, n_steps, n_samples, rounds=1, seed=0, u_std=None, mode="softmin", temperature=None,
@@ -373,6 +400,31 @@ def sampled_mpc_args(system, N, B, batched, n_steps, n_samples, rounds=1, seed=0
             if not np.isfinite(w if dtype is None else w.astype(dtype)).all():
                 raise ValueError("disturbance must be finite")
     return K, S, R, seed, std, mcode, temp, beta, dist, first, first_r, w
+
+
+def sample_penalty_args(system, B, weight, violation_tol=0.0, dtype=None):
+    """Validated arguments of ``ilqr_set_sample_penalty`` as (weight, violation_tol): weight (B,) float64 -- a scalar is
+    broadcast over the batch -- or None (clear).  Raises ValueError for a system without state limits (linear and
+    user-defined systems), a misshapen weight, one that is not finite (in ``dtype`` too, where one is given) and > 0, or a
+    violation_tol that is not finite and >= 0.  Pure host code (no GPU)."""
+    if getattr(system, "SYSTEM_ID", None) not in _lib.BOX_SYSTEMS:
+        raise ValueError(f"the sample penalty is supported for the pendulum, UA double pendulum and double pendulum "
+                         f"only, not for {type(system).__name__}")
+    if weight is None:
+        return None, 0.0
+    w = np.asarray(weight, dtype=np.float64)
+    if w.shape == ():
+        w = np.broadcast_to(w, (int(B),))
+    if w.shape != (int(B),):
+        raise ValueError(f"weight must be a scalar or have shape ({int(B)},), but got {w.shape}")
+    with np.errstate(over="ignore", under="ignore"):
+        held = w if dtype is None else w.astype(dtype)
+    if not np.isfinite(held).all() or not (held > 0).all():
+        raise ValueError("weight must be finite and > 0")
+    tol = float(violation_tol)
+    if not (np.isfinite(tol) and tol >= 0.0):
+        raise ValueError(f"violation_tol must be finite and >= 0, got {violation_tol!r}")
+    return np.ascontiguousarray(w), tol
 
 
 class iLQR:
@@ -452,6 +504,7 @@ class iLQR:
             self._h.set_batch_params(_lib.BATCH_PLANT, plant_rows)
         self.batch_params, self.plant_params = model_rows, plant_rows
         self._h.set_problem(x_0.reshape(self.B, self.n_x), U_init.reshape(self.B, self.n_u, self.N))
+        self.sample_penalty = None
         self.status = None
         self.iterations = None
 
@@ -701,6 +754,32 @@ class iLQR:
         rec.update({names.get(k, k): self._out(v) for k, v in out.items()})
         return PolicyMonteCarlo(**rec)
 
+    # ---- state limits in the sampled search -----------------------------------------------------------
+    def set_sample_penalty(self, weight, violation_tol=0.0):
+        """Bring the state limits into sample_controls and sampled_mpc as a penalty (include/ilqr_hip.h,
+        ilqr_set_sample_penalty): the cost of a sample becomes J + P, P = (weight / 2) * sum over x_1 .. x_N and the
+        finite bounds of max(0, c)^2 -- the augmented Lagrangian's term at zero multipliers; with weight = rho0 the merit
+        the first inner solve of the state-limited optimize_trajectory() minimises.  weight is a scalar or (B,), > 0;
+        None clears the penalty.  violation_tol: a sample counts into round_n_violating when it violates by more.  Only
+        the two sampling calls read it; without state limits it adds exactly 0.  With it sampled_mpc accepts a solver
+        with state limits."""
+        w, tol = sample_penalty_args(self.system, self.B, weight, violation_tol, self.dtype)
+        self._h.set_sample_penalty(w, tol)
+        self.sample_penalty = None if w is None else (w if self.batched else w[0], tol)
+
+    def _penalty_record(self, S, R, n_steps, samples):
+        """The penalty's attributes of a SampledControls / SampledMPC, {} while no penalty is set."""
+        if self.sample_penalty is None:
+            return {}
+        rep = self._h.sample_penalty_report(S, R, n_steps, samples)
+        col = (lambda a: ready(a)) if self.batched else (lambda a: ready(a[..., 0]))
+        rows = rep["round_penalty"]
+        rec = {k: col(rows[..., i].copy()) for i, k in enumerate(_lib.SAMPLE_PENALTY_STATS)}
+        rec.update(round_n_violating=col(rep["round_violating"]), penalty=col(rep["penalty_new"]), violation=col(rep["violation_new"]))
+        if samples:
+            rec.update(penalty_samples=self._out(rep["penalty_samples"]), violation_samples=self._out(rep["violation_samples"]))
+        return rec
+
     # ---- sampled control search ---------------------------------------------------------------------
     def sample_controls(self, n_samples, rounds=1, seed=0, u_std=None, mode="best", temperature=None, smoothing=0.0,
                         distribution="gaussian", first_trajectory=0, first_round=0, samples=False, trajectories=False,
@@ -715,12 +794,17 @@ class iLQR:
         sample costs and controls of the last round with samples=True, X of the result with trajectories=True.  Nothing in
         the solver changes, unless apply=True: then every trajectory whose searched cost is finite and below the cost it
         started from takes U as its initial guess, the others keep theirs, and set_problem(x_0, U_sel) makes the next
-        optimize_trajectory() start fresh from it -- no trajectory is made worse."""
+        optimize_trajectory() start fresh from it -- no trajectory is made worse.  State limits enter only after
+        set_sample_penalty: every cost here and in the record is then J + P (P the penalty of the violated limits), the
+        record carries penalty, violation, round_penalty_start, round_penalty_best, round_violation_best and
+        round_n_violating (penalty_samples, violation_samples with samples=True), and apply=True compares the penalised
+        costs: no trajectory is made worse in the penalised sense."""
         S, R, seed, std, mcode, temp, beta, dist, first, first_r = sample_controls_args(
             self.system, self.N, self.B, self.batched, n_samples, rounds, seed, u_std, mode, temperature, smoothing,
             distribution, first_trajectory, first_round)
         U_start = self._h.get(_lib.U) if apply else None
         out = self._h.sample_controls(S, R, seed, std, mcode, temp, beta, dist, first, first_r, samples, trajectories)
+        penalty = self._penalty_record(S, R, None, samples)      # (before apply=True touches the handle again)
         stats, counts = out.pop("round_stats"), out.pop("round_counts")
         cost_start = stats[0, :, 0].astype(self.dtype)
         applied = None
@@ -733,11 +817,11 @@ class iLQR:
         rec = {k: rpick(stats[:, :, i].copy()) for i, k in enumerate(_lib.SAMPLE_ROUND_STATS)}
         rec.update(round_n_finite=rpick(counts), cost_start=pick(cost_start), applied=None if applied is None else pick(applied))
         rec.update({k: self._out(v) for k, v in out.items()})
-        return SampledControls(**rec)
+        return SampledControls(**rec, **penalty)
 
     # ---- sampled MPC ---------------------------------------------------------------------------------
     def sampled_mpc(self, n_steps, n_samples, rounds=1, seed=0, u_std=None, mode="softmin", temperature=None, smoothing=0.0,
-                    distribution="gaussian", first_trajectory=0, first_round=0, disturbance=None, plans=False):
+                    distribution="gaussian", first_trajectory=0, first_round=0, disturbance=None, plans=False, samples=False):
         """The search of sample_controls as a receding-horizon controller on the device (include/ilqr_hip.h,
         ilqr_sampled_mpc): MPPI (mode="softmin") or best-of-S (mode="best").  After mpc_reset, each of n_steps steps runs
         `rounds` rounds of the search from the plant state around the shifted previous plan (step 0: the solver's U),
@@ -746,7 +830,10 @@ class iLQR:
         in between.  Round r of step k draws the stream of round first_round + k * rounds + r, so a second call with
         first_round advanced by n_steps * rounds continues the first exactly; a following mpc_run hands the plant over to
         the iLQR controller (X, K and U_ff are untouched, U is the shifted plan).  The other arguments are
-        sample_controls'.  Returns a SampledMPC; the plans of every step with plans=True.  Not with state limits."""
+        sample_controls'.  Returns a SampledMPC; the plans of every step with plans=True.  With state limits only after
+        set_sample_penalty: every cost is then J + P, the record carries penalty, violation and the round_penalty_* /
+        round_n_violating rows of every step, and with samples=True penalty_samples and violation_samples of the last
+        step's last round.  The multipliers of the state-limited solver are neither read nor changed."""
         if self.plant is None:
             raise ValueError("construct the solver with plant=<System> to run MPC steps")
         K, S, R, seed, std, mcode, temp, beta, dist, first, first_r, w = sampled_mpc_args(
@@ -760,7 +847,7 @@ class iLQR:
         step = (lambda a: ready(a)) if self.batched else (lambda a: ready(a[:, 0]))
         rec.update(U_sim=step(out["u"]), X_sim=step(out["x"]), cost=step(out["cost"]),
                    U_plan=step(out["U_plan"]) if plans else None)
-        return SampledMPC(**rec)
+        return SampledMPC(**rec, **self._penalty_record(S, R, K, samples))
 
     # ---- MPC (run_iLQR_MPC.py:116-143), device-resident ---------------------------------------------
     def mpc_reset(self, x_0, U_init, keep_state=False):
