@@ -109,14 +109,15 @@ class MonteCarloDesc(C.Structure):
     ]
 
 
+# what the two descriptors of the sampled search open with (sampled MPC counts its steps in between)
+_SEARCH_COUNTS = [("struct_size", C.c_uint32), ("n_samples", C.c_int32), ("n_rounds", C.c_int32), ("mode", C.c_int32),
+                  ("distribution", C.c_int32), ("first_trajectory", C.c_int32), ("first_round", C.c_int32)]
+_SEARCH_NOISE = [("seed", C.c_uint64), ("temperature", C.c_double), ("smoothing", C.c_double), ("u_std", C.POINTER(C.c_double))]
+
+
 class SampleControlsDesc(C.Structure):
     """ilqr_sample_controls_desc (include/ilqr_hip.h), field for field."""
-    _fields_ = [
-        ("struct_size", C.c_uint32),
-        ("n_samples", C.c_int32), ("n_rounds", C.c_int32), ("mode", C.c_int32), ("distribution", C.c_int32),
-        ("first_trajectory", C.c_int32), ("first_round", C.c_int32),
-        ("seed", C.c_uint64), ("temperature", C.c_double), ("smoothing", C.c_double),
-        ("u_std", C.POINTER(C.c_double)),
+    _fields_ = _SEARCH_COUNTS + _SEARCH_NOISE + [
         ("U_new", C.c_void_p), ("cost_new", C.c_void_p), ("X_new", C.c_void_p),
         ("round_stats", C.POINTER(C.c_double)), ("round_counts", C.POINTER(C.c_int32)),
         ("cost_samples", C.c_void_p), ("U_samples", C.c_void_p),
@@ -125,12 +126,8 @@ class SampleControlsDesc(C.Structure):
 
 class SampledMpcDesc(C.Structure):
     """ilqr_sampled_mpc_desc (include/ilqr_hip.h), field for field."""
-    _fields_ = [
-        ("struct_size", C.c_uint32),
-        ("n_samples", C.c_int32), ("n_rounds", C.c_int32), ("mode", C.c_int32), ("distribution", C.c_int32),
-        ("first_trajectory", C.c_int32), ("first_round", C.c_int32), ("n_steps", C.c_int32),
-        ("seed", C.c_uint64), ("temperature", C.c_double), ("smoothing", C.c_double),
-        ("u_std", C.POINTER(C.c_double)), ("w", C.c_void_p),
+    _fields_ = _SEARCH_COUNTS + [("n_steps", C.c_int32)] + _SEARCH_NOISE + [
+        ("w", C.c_void_p),
         ("u_out", C.c_void_p), ("x_out", C.c_void_p), ("cost_out", C.c_void_p), ("U_plan", C.c_void_p),
         ("round_stats", C.POINTER(C.c_double)), ("round_counts", C.POINTER(C.c_int32)),
     ]
@@ -507,6 +504,17 @@ class Handle:
         keep.append(r)
         setattr(d, field, r.ctypes.data_as(C.POINTER(C.c_double)))
 
+    @staticmethod
+    def _desc(cls, **scalars):
+        """A descriptor of type ``cls`` with its struct_size and the given scalar fields, each converted as its C type asks
+        (int32: int(), double: float(), the uint64 seed: its low 64 bits), and the list that keeps its input arrays alive."""
+        d, types = cls(), dict(cls._fields_)
+        d.struct_size = C.sizeof(cls)
+        convert = {C.c_double: float, C.c_uint64: lambda v: int(v) & 0xFFFFFFFFFFFFFFFF}
+        for k, v in scalars.items():
+            setattr(d, k, convert.get(types[k], int)(v))
+        return d, []
+
     def _outputs(self, d, shapes, dtypes={}, names={}):
         """Allocate the outputs named by ``shapes`` (the handle's dtype unless ``dtypes`` says otherwise), write them into
         the descriptor and return them, under ``names`` where the result's key differs from the field."""
@@ -524,10 +532,7 @@ class Handle:
         U (B, S, n_u, N)."""
         B, S, n, m, N = self.B, int(n_samples), self.n_x, self.n_u, self.N
         Sa = max(S, 0)
-        d = PolicyRolloutDesc()
-        d.struct_size = C.sizeof(PolicyRolloutDesc)
-        d.n_samples, d.integrator, d.feedback = S, int(integrator), int(bool(feedback))
-        keep = []
+        d, keep = self._desc(PolicyRolloutDesc, n_samples=S, integrator=integrator, feedback=bool(feedback))
         if x0 is not None:
             keep.append(self._in(x0, (B, S, n)))
             d.x0 = _ptr(keep[-1])
@@ -553,12 +558,9 @@ class Handle:
         noise)."""
         B, S, n, m, N = self.B, int(n_samples), self.n_x, self.n_u, self.N
         Sa = max(S, 0)
-        d = MonteCarloDesc()
-        d.struct_size = C.sizeof(MonteCarloDesc)
-        d.n_samples, d.integrator, d.feedback = S, int(integrator), int(bool(feedback))
-        d.distribution, d.first_trajectory = int(distribution), int(first_trajectory)
-        d.seed, d.violation_tol = int(seed) & 0xFFFFFFFFFFFFFFFF, float(violation_tol)
-        keep = []
+        d, keep = self._desc(MonteCarloDesc, n_samples=S, integrator=integrator, feedback=bool(feedback),
+                             distribution=distribution, first_trajectory=first_trajectory, seed=seed,
+                             violation_tol=violation_tol)
         self._rows_in(d, keep, "x0_std", x0_std, (B, n), "x0_std")
         self._rows_in(d, keep, "w_std", w_std, (B, n), "w_std")
         self._rows_in(d, keep, "plant_rows", plant_rows, (B, S, None), "plant rows")
@@ -585,12 +587,9 @@ class Handle:
         samples)."""
         B, S, R, n, m, N = self.B, int(n_samples), int(rounds), self.n_x, self.n_u, self.N
         Sa, Ra = max(S, 0), max(R, 0)
-        d = SampleControlsDesc()
-        d.struct_size = C.sizeof(SampleControlsDesc)
-        d.n_samples, d.n_rounds, d.mode, d.distribution = S, R, int(mode), int(distribution)
-        d.first_trajectory, d.first_round = int(first_trajectory), int(first_round)
-        d.seed, d.temperature, d.smoothing = int(seed) & 0xFFFFFFFFFFFFFFFF, float(temperature), float(smoothing)
-        keep = []
+        d, keep = self._desc(SampleControlsDesc, n_samples=S, n_rounds=R, mode=mode, distribution=distribution,
+                             first_trajectory=first_trajectory, first_round=first_round, seed=seed, temperature=temperature,
+                             smoothing=smoothing)
         self._rows_in(d, keep, "u_std", u_std, (B, m), "u_std")
         shapes = {}
         if summaries:
@@ -612,12 +611,9 @@ class Handle:
         round_counts (n_steps, R, B) int32; U_plan (n_steps, B, n_u, N) (with plans)."""
         B, K, S, R, n, m, N = self.B, int(n_steps), int(n_samples), int(rounds), self.n_x, self.n_u, self.N
         Ka, Ra = max(K, 0), max(R, 0)
-        d = SampledMpcDesc()
-        d.struct_size = C.sizeof(SampledMpcDesc)
-        d.n_samples, d.n_rounds, d.mode, d.distribution = S, R, int(mode), int(distribution)
-        d.first_trajectory, d.first_round, d.n_steps = int(first_trajectory), int(first_round), K
-        d.seed, d.temperature, d.smoothing = int(seed) & 0xFFFFFFFFFFFFFFFF, float(temperature), float(smoothing)
-        keep = []
+        d, keep = self._desc(SampledMpcDesc, n_samples=S, n_rounds=R, mode=mode, distribution=distribution,
+                             first_trajectory=first_trajectory, first_round=first_round, n_steps=K, seed=seed,
+                             temperature=temperature, smoothing=smoothing)
         self._rows_in(d, keep, "u_std", u_std, (B, m), "u_std")
         if w is not None:
             keep.append(self._in(w, (Ka, B, n)))
@@ -649,8 +645,7 @@ class Handle:
         int32 -- (n_steps, R, B[, 3]) for sampled_mpc --; penalty_samples and violation_samples (B, S) (with samples)."""
         B, S, R = self.B, int(n_samples), int(rounds)
         lead = () if n_steps is None else (int(n_steps),)
-        d = SamplePenaltyReportDesc()
-        d.struct_size = C.sizeof(SamplePenaltyReportDesc)
+        d, _ = self._desc(SamplePenaltyReportDesc)
         shapes = dict(penalty_new=lead + (B,), violation_new=lead + (B,), round_penalty=lead + (R, B, 3),
                       round_violating=lead + (R, B))
         if samples:

@@ -16,11 +16,14 @@ the backtracking line search rolled out in parallel.
 
 from __future__ import annotations
 
-from collections import namedtuple
-
 import numpy as np
 
 from . import _lib
+# (the names of the two modules beside this file stay importable from here)
+from .setter_args import _bounds, batch_param_rows, control_limits, mpc_multiplier_mode, state_limits  # noqa: F401
+from .sampling import (PENALTY_FIELDS, PolicyMonteCarlo, PolicyRollout, SampledControls, SampledMPC,  # noqa: F401
+                       _with_penalty_fields, has_policy_kernels, policy_monte_carlo_args, policy_rollout_args,
+                       sample_controls_args, sample_penalty_args, sampled_mpc_args, table_columns, unbatch)
 from .systems.system_base import System, ready
 
 STATUS_NAMES = {_lib.TRAJ_ACTIVE: "active", _lib.TRAJ_CONVERGED: "converged",
@@ -30,401 +33,6 @@ STATUS_NAMES = {_lib.TRAJ_ACTIVE: "active", _lib.TRAJ_CONVERGED: "converged",
 def horizon_steps(T, dt):
     """N = len(arange(0, T + dt, dt)) - 1   (iLQR_class.py:46-47)."""
     return len(np.arange(0, T + dt, dt)) - 1
-
-
-def _bounds(names, values, n, B=None, prefix=""):
-    """The two bounds, checked (shape, NaN, lo > hi per entry), as float64 arrays: (n,) shared by the batch (a scalar is
-    broadcast), or with B one row per trajectory, (B, n) (a scalar or (n,) is broadcast).  Rows also refuse hi = -inf and
-    lo = +inf; the shared bounds take them as "no constraint", as the library's own setters do."""
-    shape = (n,) if B is None else (B, n)
-    shapes = f"({n},)" if B is None else f"({n},) or ({B}, {n})"
-    out = []
-    for name, v in zip(names, values):
-        a = np.asarray(v, dtype=np.float64)
-        if a.ndim == 0:
-            a = np.full(shape, float(a))
-        elif B is not None and a.shape == (n,):
-            a = np.broadcast_to(a, shape)
-        if a.shape != shape:
-            raise ValueError(f"{prefix}{name} must be a scalar or have shape {shapes}, but got {a.shape}")
-        if np.isnan(a).any():
-            raise ValueError(f"{prefix}{name} must not contain NaN")
-        out.append(np.ascontiguousarray(a))
-    lo, hi = out
-    if B is not None and (np.isneginf(hi).any() or np.isposinf(lo).any()):
-        raise ValueError(f"{prefix}{names[1]} must not be -inf and {names[0]} must not be +inf (no value meets such a bound)")
-    bad = np.argwhere(lo > hi)
-    if len(bad) and B is None:
-        raise ValueError(f"{prefix}{names[0]} must be <= {names[1]}, got {lo} > {hi}")
-    if len(bad):
-        b, j = (int(i) for i in bad[0])
-        raise ValueError(f"{prefix}{names[0]} must be <= {names[1]}, got {lo[b, j]} > {hi[b, j]} "
-                         f"(trajectory {b}, component {j})")
-    return lo, hi
-
-
-def control_limits(system, u_min, u_max, B=None):
-    """Validated (u_min, u_max) as float64 [n_u] arrays (a scalar is broadcast), or None for no limits.  With B (a
-    batched solver) and a 2-D bound: per-trajectory limits, both as (B, n_u) arrays.  Raises ValueError for a wrong
-    shape, NaN, u_min > u_max, one bound without the other, or a system without limits."""
-    if u_min is None and u_max is None:
-        return None
-    if u_min is None or u_max is None:
-        raise ValueError("give both u_min and u_max (use +-inf for a side without a limit)")
-    if getattr(system, "SYSTEM_ID", None) not in _lib.BOX_SYSTEMS:
-        raise ValueError(f"control limits are supported for the pendulum, UA double pendulum and double pendulum "
-                         f"only, not for {type(system).__name__}")
-    rows = B is not None and (np.ndim(u_min) == 2 or np.ndim(u_max) == 2)
-    return _bounds(("u_min", "u_max"), (u_min, u_max), system.n_u, int(B) if rows else None)
-
-
-def state_limits(system, x_min, x_max, options=None, B=None):
-    """Validated state limits as (x_min, x_max, options): float64 [n_x] arrays (a scalar is broadcast, +-inf = no
-    constraint) and the outer loop's settings (``_lib.STATE_LIMIT_DEFAULTS`` updated by ``options``), or None for no
-    limits.  With B (a batched solver) and a 2-D bound: per-trajectory limits, both as (B, n_x) arrays.  Raises ValueError, with "state limits" in the message, for a wrong shape, NaN, x_min > x_max, one bound
-    without the other, an unknown or bad option, or a system without state limits.  Pure host code (no GPU)."""
-    if x_min is None and x_max is None:
-        if options:
-            raise ValueError("state limits: options were given without x_min / x_max")
-        return None
-    if x_min is None or x_max is None:
-        raise ValueError("state limits: give both x_min and x_max (use +-inf for a side without a limit)")
-    if getattr(system, "SYSTEM_ID", None) not in _lib.BOX_SYSTEMS:
-        raise ValueError(f"state limits are supported for the pendulum, UA double pendulum and double pendulum "
-                         f"only, not for {type(system).__name__}")
-    rows = B is not None and (np.ndim(x_min) == 2 or np.ndim(x_max) == 2)
-    out = _bounds(("x_min", "x_max"), (x_min, x_max), system.n_x, int(B) if rows else None, "state limits: ")
-    opts = dict(_lib.STATE_LIMIT_DEFAULTS)
-    unknown = sorted(set(options or {}) - set(opts))
-    if unknown:
-        raise ValueError(f"state limits: unknown option(s) {unknown}; expected some of {sorted(opts)}")
-    opts.update(options or {})
-    try:
-        for k in ("ctol", "rho0", "rho_factor", "rho_max"):
-            opts[k] = float(opts[k])
-        mo = opts["max_outer"]
-        if isinstance(mo, bool) or int(mo) != mo:
-            raise ValueError
-        opts["max_outer"] = int(mo)
-    except (TypeError, ValueError):
-        raise ValueError(f"state limits: options must be numbers (max_outer an integer), got {options}") from None
-    if not (opts["ctol"] > 0 and opts["rho0"] > 0 and opts["rho_factor"] >= 1 and opts["rho_max"] >= opts["rho0"]
-            and opts["max_outer"] >= 1) or not all(np.isfinite(opts[k]) for k in ("ctol", "rho0", "rho_factor")):
-        raise ValueError(f"state limits: need ctol > 0, rho0 > 0, rho_factor >= 1, rho_max >= rho0 and max_outer >= 1, "
-                         f"got {opts}")
-    return out[0], out[1], opts
-
-
-def mpc_multiplier_mode(mode):
-    """The ``ilqr_set_mpc_multipliers`` code of ``mode``: None (state-limited MPC refuses), "cold" (every step's solve
-    starts from lam = 0) or "warm" (from the previous step's multipliers shifted one step along the horizon).  Raises
-    ValueError for anything else.  Pure host code (no GPU)."""
-    if mode is None or (isinstance(mode, str) and mode in _lib.MPC_MULTIPLIER_MODES):
-        return _lib.MPC_MULTIPLIER_MODES[mode]
-    raise ValueError(f"MPC multipliers must be None, 'cold' or 'warm', got {mode!r}")
-
-
-def batch_param_rows(system, B, params, with_target=True):
-    """Per-trajectory parameter rows for ``ilqr_set_batch_params`` as a (B, row_len) float64 array.
-
-    params: {name: scalar or (B,)} for the system parameters (``system.param_names()``) and, with with_target,
-    ``"x_target"``: (n_x,) or (B, n_x).  Every name not given takes the system's own value.  Columns: the system
-    parameters in parameter-block order, then x_target (with_target).  Raises ValueError for an unknown name, a wrong
-    shape, a non-finite value, or a system without per-trajectory parameters.  Pure host code (no GPU)."""
-    if getattr(system, "SYSTEM_ID", None) not in _lib.BOX_SYSTEMS or getattr(system, "PARAM_NAMES", None) is None:
-        raise ValueError(f"per-trajectory parameters are supported for the pendulum, UA double pendulum and double "
-                         f"pendulum only, not for {type(system).__name__}")
-    B = int(B)
-    if B < 1:
-        raise ValueError(f"B must be >= 1, got {B}")
-    params = {} if params is None else dict(params)
-    names = system.param_names()
-    allowed = set(names) | ({"x_target"} if with_target else set())
-    unknown = sorted(set(params) - allowed)
-    if unknown:
-        raise ValueError(f"unknown parameter name(s) {unknown}; expected some of {sorted(allowed)}")
-    n_sys = len(names)
-    block = system.param_block()
-    n = system.n_x
-    rows = np.empty((B, n_sys + (n if with_target else 0)), dtype=np.float64)
-    for j, name in enumerate(names):
-        v = np.asarray(params.get(name, block[j]), dtype=np.float64)
-        if v.ndim == 0:
-            v = np.full(B, float(v))
-        if v.shape != (B,):
-            raise ValueError(f"{name} must be a scalar or have shape ({B},), but got {v.shape}")
-        rows[:, j] = v
-    if with_target:
-        xt = np.asarray(params.get("x_target", block[n_sys:n_sys + n]), dtype=np.float64)
-        if xt.shape == (n,):
-            xt = np.broadcast_to(xt, (B, n))
-        if xt.shape != (B, n):
-            raise ValueError(f"x_target must have shape ({n},) or ({B}, {n}), but got {xt.shape}")
-        rows[:, n_sys:] = xt
-    if not np.isfinite(rows).all():
-        raise ValueError("batch parameters must be finite (no NaN or inf)")
-    return rows
-
-
-PolicyRollout = namedtuple("PolicyRollout", "cost x_final deviation violation X U", defaults=(None, None))
-PolicyRollout.__doc__ = """Result of iLQR.policy_rollout: cost, deviation, violation ([B,] S), x_final ([B,] S, n_x) and, with
-trajectories=True, X ([B,] S, n_x, N + 1) and U ([B,] S, n_u, N), else None.  A diverged sample has a non-finite cost."""
-
-
-def has_policy_kernels(system):
-    """Does the system's native code carry the policy rollout, Monte Carlo and sampled-search kernels?  The pendulum, UA
-    double pendulum and double pendulum always; a user-defined system (SymbolicSystem) built with policy_kernels=True."""
-    return (getattr(system, "SYSTEM_ID", None) in _lib.BOX_SYSTEMS
-            or (getattr(system, "SYSTEM_ID", None) == _lib.SYS_CUSTOM and bool(getattr(system, "policy_kernels", False))))
-
-
-def policy_rollout_args(system, N, B, batched, n_samples, x_0=None, disturbance=None, plant_params=None, integrator=None):
-    """Validated arguments of ``ilqr_policy_rollout`` as (S, x0, w, plant_rows, integrator code): x0 (B, S, n_x), w
-    (B, S, N, n_x) as float64 arrays or None, plant_rows (B, S, n_sys) float64 or None, integrator -1 for the solver's
-    plant (else model) integrator.  Inputs carry (B, S, ...) on a batched solver and (S, ...) on a single one.
-    plant_params is what ``set_plant_params`` takes per trajectory, here per sample: {name: scalar or ([B,] S)}.
-    Raises ValueError for n_samples < 1, a wrong shape, a non-finite plant parameter, an unknown parameter name or
-    integrator, or a system without policy rollouts.  Pure host code (no GPU)."""
-    if not has_policy_kernels(system):
-        raise ValueError(f"policy rollouts are supported for the pendulum, UA double pendulum and double pendulum "
-                         f"only, not for {type(system).__name__}")
-    if isinstance(n_samples, bool) or int(n_samples) != n_samples or int(n_samples) < 1:
-        raise ValueError(f"n_samples must be an integer >= 1, got {n_samples!r}")
-    S, B, n = int(n_samples), int(B), system.n_x
-    lead = (B, S) if batched else (S,)
-
-    def shaped(name, v, tail):
-        if v is None:
-            return None
-        a = np.asarray(v, dtype=np.float64)
-        if a.shape != lead + tail:
-            raise ValueError(f"{name} must have shape {lead + tail}, but got {a.shape}")
-        return np.ascontiguousarray(a.reshape((B, S) + tail))
-
-    x0 = shaped("x_0", x_0, (n,))
-    w = shaped("disturbance", disturbance, (int(N), n))
-    rows = None
-    if plant_params is not None and getattr(system, "SYSTEM_ID", None) not in _lib.BOX_SYSTEMS:
-        raise ValueError("plant_params: a user-defined system has no parameter rows (its constants are part of the "
-                         "generated code); only the plant's integrator can differ from the model's")
-    if plant_params is not None:
-        flat = {}
-        unknown = sorted(set(plant_params) - set(system.param_names()))
-        if unknown:
-            raise ValueError(f"unknown parameter name(s) {unknown}; expected some of {sorted(system.param_names())}")
-        for k, v in dict(plant_params).items():
-            a = np.asarray(v, dtype=np.float64)
-            if a.ndim != 0:
-                if a.shape != lead:
-                    raise ValueError(f"{k} must be a scalar or have shape {lead}, but got {a.shape}")
-                a = a.reshape(B * S)
-            flat[k] = a
-        # one row per sample: the samples are the batch axis of the per-trajectory rows
-        rows = batch_param_rows(system, B * S, flat, with_target=False).reshape(B, S, -1)
-    if integrator is None:
-        code = -1
-    elif isinstance(integrator, str) and integrator in _lib.INTEGRATORS:
-        code = _lib.INTEGRATORS[integrator]
-    else:
-        raise ValueError(f"Unknown integrator: {integrator!r}. Supported: 'rk4', 'midpoint', 'euler', 'backward_euler'.")
-    return S, x0, w, rows, code
-
-
-PolicyMonteCarlo = namedtuple(
-    "PolicyMonteCarlo", _lib.MONTE_CARLO_STATS + _lib.MONTE_CARLO_COUNTS +
-    ("cost", "x_final", "deviation", "violation", "X", "U", "x_0", "disturbance"), defaults=(None,) * 8)
-PolicyMonteCarlo.__doc__ = """Result of iLQR.policy_monte_carlo.  Per trajectory ([B] each, scalars on a single solver), over
-the samples with a finite cost: cost_mean, cost_std (population), cost_min, cost_max, deviation_mean, deviation_max,
-violation_max (float64, NaN when n_finite is 0), n_finite, n_violating (int).  With samples=True cost, deviation, violation
-([B,] S) and x_final ([B,] S, n_x); with trajectories=True X ([B,] S, n_x, N + 1) and U ([B,] S, n_u, N); with noise=True
-x_0 ([B,] S, n_x) and disturbance ([B,] S, N, n_x) as they were drawn; else None."""
-
-
-def policy_monte_carlo_args(system, N, B, batched, n_samples, seed=0, x_0_std=None, disturbance_std=None,
-                            distribution="gaussian", plant_params=None, integrator=None, violation_tol=0.0,
-                            first_trajectory=0):
-    """Validated arguments of ``ilqr_policy_monte_carlo`` as (S, seed, x0_std, w_std, distribution code, plant_rows,
-    integrator code, violation_tol, first_trajectory): the standard deviations (B, n_x) float64 or None -- (n_x,) is
-    broadcast over the batch --, plant_rows and the integrator as policy_rollout_args gives them.  Raises ValueError for
-    what policy_rollout_args refuses, a seed outside [0, 2^64), a standard deviation of a wrong shape, negative or not
-    finite, an unknown distribution, a negative or NaN violation_tol, or a negative first_trajectory.  Pure host code
-    (no GPU)."""
-    S, _, _, rows, code = policy_rollout_args(system, N, B, batched, n_samples, None, None, plant_params, integrator)
-    B, n = int(B), system.n_x
-    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
-        raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
-
-    def std(name, v):
-        if v is None:
-            return None
-        a = np.asarray(v, dtype=np.float64)
-        if a.shape == (n,):
-            a = np.broadcast_to(a, (B, n))
-        if a.shape != (B, n):
-            raise ValueError(f"{name} must have shape ({n},) or ({B}, {n}), but got {a.shape}")
-        if not np.isfinite(a).all() or (a < 0).any():
-            raise ValueError(f"{name} must be finite and >= 0")
-        return np.ascontiguousarray(a)
-
-    x0_std, w_std = std("x_0_std", x_0_std), std("disturbance_std", disturbance_std)
-    if not isinstance(distribution, str) or distribution not in _lib.NOISE_DISTRIBUTIONS:
-        raise ValueError(f"Unknown distribution: {distribution!r}. Supported: 'gaussian', 'uniform'.")
-    tol = float(violation_tol)
-    if not tol >= 0.0:
-        raise ValueError(f"violation_tol must be >= 0, got {violation_tol!r}")
-    if isinstance(first_trajectory, bool) or int(first_trajectory) != first_trajectory or not 0 <= int(first_trajectory) < 2 ** 31:
-        raise ValueError(f"first_trajectory must be an integer >= 0, got {first_trajectory!r}")
-    return S, int(seed), x0_std, w_std, _lib.NOISE_DISTRIBUTIONS[distribution], rows, code, tol, int(first_trajectory)
-
-
-# What SampledControls and SampledMPC gain while a penalty is set (iLQR.set_sample_penalty): attributes beside the tuple's
-# own fields, None without a penalty.  The tuple itself (_fields, unpacking, iteration) stays the unpenalised record.
-PENALTY_FIELDS = ("penalty", "violation") + _lib.SAMPLE_PENALTY_STATS + ("round_n_violating", "penalty_samples",
-                                                                        "violation_samples")
-
-
-def _with_penalty_fields(record):
-    class Record(record):
-        def __new__(cls, *args, **kw):
-            extra = {k: kw.pop(k) for k in PENALTY_FIELDS if k in kw}
-            self = super().__new__(cls, *args, **kw)
-            self.__dict__.update(extra)
-            return self
-
-    for k in PENALTY_FIELDS:
-        setattr(Record, k, None)
-    Record.__name__ = Record.__qualname__ = record.__name__
-    return Record
-
-
-SampledControls = _with_penalty_fields(namedtuple(
-    "SampledControls", ("U", "cost", "cost_start") + _lib.SAMPLE_ROUND_STATS + ("round_n_finite", "applied", "X", "cost_samples",
-                                                                             "U_samples"), defaults=(None,) * 4))
-SampledControls.__doc__ ="""Result of iLQR.sample_controls.  U ([B,] n_u, N): the searched controls; cost ([B]): their plain
-cost from x_0; cost_start ([B]): the cost of the controls the call started from; round_cost_nominal, round_cost_min,
-round_ess (float64) and round_n_finite (int), each (R, [B]): per round the cost of its nominal, the minimum over the
-samples with a finite cost (NaN with none), the effective sample size of the softmin weights (1 in "best" mode) and the
-number of finite samples; applied ([B] bool, None without apply=True): where U became the solver's initial guess; X
-([B,] n_x, N + 1) with trajectories=True; cost_samples ([B,] S) and U_samples ([B,] S, n_u, N) of the last round with
-samples=True; else None.  While a penalty is set (set_sample_penalty) every cost above is J + P, and: penalty,
-violation ([B]): P and the largest state-limit violation of U's rollout; round_penalty_start, round_penalty_best,
-round_violation_best (float64) and round_n_violating (int), each (R, [B]): per round P of its nominal, P and the
-violation of its best sample (NaN with no finite sample) and the number of finite samples violating by more than
-violation_tol; penalty_samples, violation_samples ([B,] S) of the last round with samples=True."""
-
-
-def sample_controls_args(system, N, B, batched, n_samples, rounds=1, seed=0, u_std=None, mode="best", temperature=None,
-                         smoothing=0.0, distribution="gaussian", first_trajectory=0, first_round=0):
-    """Validated arguments of ``ilqr_sample_controls`` as (S, R, seed, u_std, mode code, temperature, smoothing,
-    distribution code, first_trajectory, first_round): u_std (B, n_u) float64 -- (n_u,) or a scalar is broadcast over the
-    batch.  Raises ValueError for a system without the search, n_samples or rounds that are not integers >= 1, a seed
-    outside [0, 2^64), a missing, misshapen, negative or non-finite u_std, an unknown mode or distribution, a temperature
-    that is not finite and > 0 in "softmin" mode (it is required there), smoothing outside [0, 1), a negative
-    first_trajectory or first_round, or first_round + rounds > 2^32 - 2.  Pure host code (no GPU)."""
-    if not has_policy_kernels(system):
-        raise ValueError(f"the sampled control search is supported for the pendulum, UA double pendulum and double "
-                         f"pendulum only, not for {type(system).__name__}")
-
-    def count(name, v, lo):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) < 2 ** 31:
-            raise ValueError(f"{name} must be an integer >= {lo}, got {v!r}")
-        return int(v)
-
-    S, R = count("n_samples", n_samples, 1), count("rounds", rounds, 1)
-    B, m = int(B), system.n_u
-    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
-        raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
-    if u_std is None:
-        raise ValueError("u_std is required: the standard deviation of the control perturbation, ([B,] n_u)")
-    std = np.asarray(u_std, dtype=np.float64)
-    if std.shape in ((), (m,)):
-        std = np.broadcast_to(std, (B, m))
-    if std.shape != (B, m):
-        raise ValueError(f"u_std must have shape ({m},) or ({B}, {m}), but got {std.shape}")
-    if not np.isfinite(std).all() or (std < 0).any():
-        raise ValueError("u_std must be finite and >= 0")
-    if not isinstance(mode, str) or mode not in _lib.SAMPLE_MODES:
-        raise ValueError(f"Unknown mode: {mode!r}. Supported: 'best', 'softmin'.")
-    if mode == "softmin":
-        if temperature is None or not (np.isfinite(float(temperature)) and float(temperature) > 0.0):
-            raise ValueError(f"temperature must be finite and > 0 in 'softmin' mode, got {temperature!r}")
-    temp = 1.0 if temperature is None else float(temperature)
-    beta = float(smoothing)
-    if not 0.0 <= beta < 1.0:
-        raise ValueError(f"smoothing must be in [0, 1), got {smoothing!r}")
-    if not isinstance(distribution, str) or distribution not in _lib.NOISE_DISTRIBUTIONS:
-        raise ValueError(f"Unknown distribution: {distribution!r}. Supported: 'gaussian', 'uniform'.")
-    first, first_r = count("first_trajectory", first_trajectory, 0), count("first_round", first_round, 0)
-    if first_r + R > 2 ** 32 - 2:
-        raise ValueError("first_round + rounds must be <= 2^32 - 2")
-    return (S, R, int(seed), np.ascontiguousarray(std), _lib.SAMPLE_MODES[mode], temp, beta,
-            _lib.NOISE_DISTRIBUTIONS[distribution], first, first_r)
-
-
-SampledMPC = _with_penalty_fields(namedtuple(
-    "SampledMPC", ("U_sim", "X_sim", "cost") + _lib.SAMPLE_ROUND_STATS + ("round_n_finite", "U_plan"), defaults=(None,)))
-SampledMPC.__doc__ = """Result of iLQR.sampled_mpc.  U_sim (n_steps, [B,] n_u): the controls applied; X_sim (n_steps, [B,]
-n_x): the plant state AFTER each step; cost (n_steps, [B]): the cost the search reports for each step's plan, from the
-state before the step (the last round's minimum in "best" mode, the plain cost of the averaged plan in "softmin" mode);
-round_cost_nominal, round_cost_min, round_ess (float64) and round_n_finite (int), each (n_steps, R, [B]): the round
-statistics of SampledControls for every round of every step; U_plan (n_steps, [B,] n_u, N) with plans=True: the plan of
-each step before it is shifted, else None.  While a penalty is set (set_sample_penalty) cost is J + P, and: penalty,
-violation (n_steps, [B]): P and the violation of each step's plan ("best" mode: of the last round's best sample);
-round_penalty_start, round_penalty_best, round_violation_best, round_n_violating (n_steps, R, [B]) as SampledControls';
-penalty_samples, violation_samples ([B,] S) of the last step's last round with samples=True."""
-
-
-def sampled_mpc_args(system, N, B, batched, n_steps, n_samples, rounds=1, seed=0, u_std=None, mode="softmin", temperature=None,
-                     smoothing=0.0, distribution="gaussian", first_trajectory=0, first_round=0, disturbance=None, dtype=None):
-    """Validated arguments of ``ilqr_sampled_mpc`` as (K, S, R, seed, u_std, mode code, temperature, smoothing,
-    distribution code, first_trajectory, first_round, w): everything ``sample_controls_args`` returns and refuses, with
-    n_steps = K an integer >= 1, first_round + n_steps * rounds <= 2^32 - 2 in place of its stream bound, and w the
-    disturbance (n_steps, [B,] n_x) as (K, B, n_x) float64 -- every value finite (in ``dtype`` too, where one is given)
-    -- or None.  Pure host code (no GPU)."""
-    S, R, seed, std, mcode, temp, beta, dist, first, first_r = sample_controls_args(
-        system, N, B, batched, n_samples, rounds, seed, u_std, mode, temperature, smoothing, distribution, first_trajectory,
-        first_round)
-    if isinstance(n_steps, bool) or not isinstance(n_steps, (int, np.integer)) or not 1 <= int(n_steps) < 2 ** 31:
-        raise ValueError(f"n_steps must be an integer >= 1, got {n_steps!r}")
-    K, B, n = int(n_steps), int(B), system.n_x
-    if first_r + K * R > 2 ** 32 - 2:
-        raise ValueError("first_round + n_steps * rounds must be <= 2^32 - 2")
-    w = None
-    if disturbance is not None:
-        w = np.asarray(disturbance, dtype=np.float64)
-        want = (K, B, n) if batched else (K, n)
-        if w.shape != want:
-            raise ValueError(f"disturbance must have shape {want}, but got {w.shape}")
-        w = np.ascontiguousarray(w.reshape(K, B, n))
-        with np.errstate(over="ignore"):
-            if not np.isfinite(w if dtype is None else w.astype(dtype)).all():
-                raise ValueError("disturbance must be finite")
-    return K, S, R, seed, std, mcode, temp, beta, dist, first, first_r, w
-
-
-def sample_penalty_args(system, B, weight, violation_tol=0.0, dtype=None):
-    """Validated arguments of ``ilqr_set_sample_penalty`` as (weight, violation_tol): weight (B,) float64 -- a scalar is
-    broadcast over the batch -- or None (clear).  Raises ValueError for a system without state limits (linear and
-    user-defined systems), a misshapen weight, one that is not finite (in ``dtype`` too, where one is given) and > 0, or a
-    violation_tol that is not finite and >= 0.  Pure host code (no GPU)."""
-    if getattr(system, "SYSTEM_ID", None) not in _lib.BOX_SYSTEMS:
-        raise ValueError(f"the sample penalty is supported for the pendulum, UA double pendulum and double pendulum "
-                         f"only, not for {type(system).__name__}")
-    if weight is None:
-        return None, 0.0
-    w = np.asarray(weight, dtype=np.float64)
-    if w.shape == ():
-        w = np.broadcast_to(w, (int(B),))
-    if w.shape != (int(B),):
-        raise ValueError(f"weight must be a scalar or have shape ({int(B)},), but got {w.shape}")
-    with np.errstate(over="ignore", under="ignore"):
-        held = w if dtype is None else w.astype(dtype)
-    if not np.isfinite(held).all() or not (held > 0).all():
-        raise ValueError("weight must be finite and > 0")
-    tol = float(violation_tol)
-    if not (np.isfinite(tol) and tol >= 0.0):
-        raise ValueError(f"violation_tol must be finite and >= 0, got {violation_tol!r}")
-    return np.ascontiguousarray(w), tol
 
 
 class iLQR:
@@ -724,9 +332,9 @@ class iLQR:
         else the model's parameters); integrator: the plant's (None: the solver's plant, else its model's).  Returns a
         PolicyRollout; X and U of every sample only with trajectories=True.  A multiple of 64 samples fills the GPU's
         waves.  Nothing in the solver changes."""
-        S, x0, w, rows, code = policy_rollout_args(self.system, self.N, self.B, self.batched, n_samples, x_0, disturbance,
-                                                   plant_params, integrator)
-        out = self._h.policy_rollout(S, x0, w, rows, code, feedback, trajectories)
+        a = policy_rollout_args(self.system, self.N, self.B, self.batched, n_samples, x_0, disturbance, plant_params,
+                                integrator)
+        out = self._h.policy_rollout(**a._asdict(), feedback=feedback, trajectories=trajectories)
         return PolicyRollout(**{k: self._out(v) for k, v in out.items()})
 
     def policy_monte_carlo(self, n_samples, seed=0, x_0_std=None, disturbance_std=None, distribution="gaussian",
@@ -741,15 +349,12 @@ class iLQR:
         finite cost, n_finite, and n_violating (violation > violation_tol); per-sample arrays with samples=True, X and U
         with trajectories=True, the drawn x_0 and disturbance with noise=True (policy_rollout with those two gives the
         same bits).  Nothing in the solver changes."""
-        S, seed, x0_std, w_std, dist, rows, code, tol, first = policy_monte_carlo_args(
-            self.system, self.N, self.B, self.batched, n_samples, seed, x_0_std, disturbance_std, distribution, plant_params,
-            integrator, violation_tol, first_trajectory)
-        out = self._h.policy_monte_carlo(S, seed, x0_std, w_std, dist, rows, code, feedback, tol, first, samples,
-                                         trajectories, noise)
-        stats, counts = out.pop("stats"), out.pop("counts")
-        pick = (lambda a: a) if self.batched else (lambda a: a[0])
-        rec = {k: pick(stats[:, i].copy()) for i, k in enumerate(_lib.MONTE_CARLO_STATS)}
-        rec.update({k: pick(counts[:, i].copy()) for i, k in enumerate(_lib.MONTE_CARLO_COUNTS)})
+        a = policy_monte_carlo_args(self.system, self.N, self.B, self.batched, n_samples, seed, x_0_std, disturbance_std,
+                                    distribution, plant_params, integrator, violation_tol, first_trajectory)
+        out = self._h.policy_monte_carlo(**a._asdict(), feedback=feedback, samples=samples, trajectories=trajectories,
+                                         noise=noise)
+        rec = table_columns(out.pop("stats"), _lib.MONTE_CARLO_STATS, self.batched)
+        rec.update(table_columns(out.pop("counts"), _lib.MONTE_CARLO_COUNTS, self.batched))
         names = {"x0_out": "x_0", "w_out": "disturbance"}
         rec.update({names.get(k, k): self._out(v) for k, v in out.items()})
         return PolicyMonteCarlo(**rec)
@@ -763,19 +368,18 @@ class iLQR:
         None clears the penalty.  violation_tol: a sample counts into round_n_violating when it violates by more.  Only
         the two sampling calls read it; without state limits it adds exactly 0.  With it sampled_mpc accepts a solver
         with state limits."""
-        w, tol = sample_penalty_args(self.system, self.B, weight, violation_tol, self.dtype)
-        self._h.set_sample_penalty(w, tol)
-        self.sample_penalty = None if w is None else (w if self.batched else w[0], tol)
+        a = sample_penalty_args(self.system, self.B, weight, violation_tol, self.dtype)
+        self._h.set_sample_penalty(**a._asdict())
+        self.sample_penalty = None if a.weight is None else (unbatch(a.weight, self.batched), a.violation_tol)
 
     def _penalty_record(self, S, R, n_steps, samples):
         """The penalty's attributes of a SampledControls / SampledMPC, {} while no penalty is set."""
         if self.sample_penalty is None:
             return {}
         rep = self._h.sample_penalty_report(S, R, n_steps, samples)
-        col = (lambda a: ready(a)) if self.batched else (lambda a: ready(a[..., 0]))
-        rows = rep["round_penalty"]
-        rec = {k: col(rows[..., i].copy()) for i, k in enumerate(_lib.SAMPLE_PENALTY_STATS)}
-        rec.update(round_n_violating=col(rep["round_violating"]), penalty=col(rep["penalty_new"]), violation=col(rep["violation_new"]))
+        rec = table_columns(rep["round_penalty"], _lib.SAMPLE_PENALTY_STATS, self.batched, wrap=True)
+        for k, src in (("round_n_violating", "round_violating"), ("penalty", "penalty_new"), ("violation", "violation_new")):
+            rec[k] = unbatch(rep[src], self.batched, wrap=True)
         if samples:
             rec.update(penalty_samples=self._out(rep["penalty_samples"]), violation_samples=self._out(rep["violation_samples"]))
         return rec
@@ -799,12 +403,11 @@ class iLQR:
         record carries penalty, violation, round_penalty_start, round_penalty_best, round_violation_best and
         round_n_violating (penalty_samples, violation_samples with samples=True), and apply=True compares the penalised
         costs: no trajectory is made worse in the penalised sense."""
-        S, R, seed, std, mcode, temp, beta, dist, first, first_r = sample_controls_args(
-            self.system, self.N, self.B, self.batched, n_samples, rounds, seed, u_std, mode, temperature, smoothing,
-            distribution, first_trajectory, first_round)
+        a = sample_controls_args(self.system, self.N, self.B, self.batched, n_samples, rounds, seed, u_std, mode, temperature,
+                                 smoothing, distribution, first_trajectory, first_round)
         U_start = self._h.get(_lib.U) if apply else None
-        out = self._h.sample_controls(S, R, seed, std, mcode, temp, beta, dist, first, first_r, samples, trajectories)
-        penalty = self._penalty_record(S, R, None, samples)      # (before apply=True touches the handle again)
+        out = self._h.sample_controls(**a._asdict(), samples=samples, trajectories=trajectories)
+        penalty = self._penalty_record(a.n_samples, a.rounds, None, samples)      # (before apply=True touches the handle again)
         stats, counts = out.pop("round_stats"), out.pop("round_counts")
         cost_start = stats[0, :, 0].astype(self.dtype)
         applied = None
@@ -812,10 +415,9 @@ class iLQR:
             applied = np.isfinite(out["cost"]) & (out["cost"] < cost_start)
             U_sel = np.where(applied[:, None, None], out["U"], U_start)
             self._h.set_problem(self._h.get(_lib.X0), U_sel)
-        pick = (lambda a: a) if self.batched else (lambda a: a[0])
-        rpick = (lambda a: a) if self.batched else (lambda a: a[:, 0])
-        rec = {k: rpick(stats[:, :, i].copy()) for i, k in enumerate(_lib.SAMPLE_ROUND_STATS)}
-        rec.update(round_n_finite=rpick(counts), cost_start=pick(cost_start), applied=None if applied is None else pick(applied))
+        rec = table_columns(stats, _lib.SAMPLE_ROUND_STATS, self.batched)
+        rec.update(round_n_finite=unbatch(counts, self.batched), cost_start=unbatch(cost_start, self.batched),
+                   applied=None if applied is None else unbatch(applied, self.batched))
         rec.update({k: self._out(v) for k, v in out.items()})
         return SampledControls(**rec, **penalty)
 
@@ -836,18 +438,14 @@ class iLQR:
         step's last round.  The multipliers of the state-limited solver are neither read nor changed."""
         if self.plant is None:
             raise ValueError("construct the solver with plant=<System> to run MPC steps")
-        K, S, R, seed, std, mcode, temp, beta, dist, first, first_r, w = sampled_mpc_args(
-            self.system, self.N, self.B, self.batched, n_steps, n_samples, rounds, seed, u_std, mode, temperature, smoothing,
-            distribution, first_trajectory, first_round, disturbance, self.dtype)
-        out = self._h.sampled_mpc(K, S, R, seed, std, mcode, temp, beta, dist, first, first_r, w, plans)
-        stats, counts = out["round_stats"], out["round_counts"]
-        pick = (lambda a: ready(a)) if self.batched else (lambda a: ready(a[..., 0]))
-        rec = {k: pick(stats[..., i].copy()) for i, k in enumerate(_lib.SAMPLE_ROUND_STATS)}
-        rec.update(round_n_finite=pick(counts))
-        step = (lambda a: ready(a)) if self.batched else (lambda a: ready(a[:, 0]))
-        rec.update(U_sim=step(out["u"]), X_sim=step(out["x"]), cost=step(out["cost"]),
-                   U_plan=step(out["U_plan"]) if plans else None)
-        return SampledMPC(**rec, **self._penalty_record(S, R, K, samples))
+        a = sampled_mpc_args(self.system, self.N, self.B, self.batched, n_steps, n_samples, rounds, seed, u_std, mode,
+                             temperature, smoothing, distribution, first_trajectory, first_round, disturbance, self.dtype)
+        out = self._h.sampled_mpc(**a._asdict(), plans=plans)
+        rec = table_columns(out["round_stats"], _lib.SAMPLE_ROUND_STATS, self.batched, wrap=True)
+        rec.update(round_n_finite=unbatch(out["round_counts"], self.batched, wrap=True), U_plan=None)
+        names = {"u": "U_sim", "x": "X_sim", "cost": "cost", "U_plan": "U_plan"}      # (n_steps, B, ...) each; U_plan with plans
+        rec.update({names[k]: unbatch(v, self.batched, axis=1, wrap=True) for k, v in out.items() if k in names})
+        return SampledMPC(**rec, **self._penalty_record(a.n_samples, a.rounds, a.n_steps, samples))
 
     # ---- MPC (run_iLQR_MPC.py:116-143), device-resident ---------------------------------------------
     def mpc_reset(self, x_0, U_init, keep_state=False):
@@ -867,7 +465,5 @@ class iLQR:
         u, x, c = self._h.mpc_run(n_steps)
         if self.x_min is not None:
             log = self._h.mpc_status_log(n_steps)
-            self.mpc_status_log = log if self.batched else log[:, 0]
-        if not self.batched:
-            u, x, c = u[:, 0], x[:, 0], c[:, 0]
-        return ready(u), ready(x), ready(c)
+            self.mpc_status_log = unbatch(log, self.batched, axis=1)
+        return tuple(unbatch(a, self.batched, axis=1, wrap=True) for a in (u, x, c))

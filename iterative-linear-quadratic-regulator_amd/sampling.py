@@ -1,0 +1,318 @@
+"""The host side of the sampling calls of ``iLQR``: their result records, one validator per call, all built from one set of
+checks, and the unpacking of the statistics tables the library fills.  Pure host code (no GPU); every refusal is a
+ValueError.  The validators are not equally strict (a count may be 5.0 for one call and must be an int for another): a
+check takes such a difference as a parameter, so that every call accepts exactly what it did when it was written
+(tests/test_sampling_args_cpu.py holds the table)."""
+
+from __future__ import annotations
+
+from collections import namedtuple
+from typing import NamedTuple, Optional
+
+import numpy as np
+
+from . import _lib
+from .setter_args import batch_param_rows, refuse_unsupported
+from .systems.system_base import ready
+
+# What a validator returns: a typing.NamedTuple whose fields are, in this order, the leading keyword arguments of the
+# matching ``_lib.Handle`` method (``handle.sampled_mpc(**args._asdict(), plans=plans)``).
+ROWS = Optional[np.ndarray]
+
+
+# ---- the checks ------------------------------------------------------------------------------------------------------
+def has_policy_kernels(system):
+    """Does the system's native code carry the policy rollout, Monte Carlo and sampled-search kernels?  The pendulum, UA
+    double pendulum and double pendulum always; a user-defined system (SymbolicSystem) built with policy_kernels=True."""
+    return (getattr(system, "SYSTEM_ID", None) in _lib.BOX_SYSTEMS
+            or (getattr(system, "SYSTEM_ID", None) == _lib.SYS_CUSTOM and bool(getattr(system, "policy_kernels", False))))
+
+
+def _count(name, v, lo, integer_type=True, below_2_31=True):
+    """v as an int >= lo.  integer_type: an int or a NumPy integer, else anything equal to its int() (5.0); below_2_31: what
+    an int32 field of a descriptor holds.  A bool is no count."""
+    if (isinstance(v, bool) or not (isinstance(v, (int, np.integer)) if integer_type else int(v) == v)
+            or int(v) < lo or (below_2_31 and int(v) >= 2 ** 31)):
+        raise ValueError(f"{name} must be an integer >= {lo}, got {v!r}")
+    return int(v)
+
+
+def _seed(seed):
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+        raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
+    return int(seed)
+
+
+def _std_rows(name, v, B, width, scalar=False, required=None):
+    """A row of standard deviations per trajectory as (B, width) float64: (width,) -- with ``scalar`` a scalar too -- is
+    broadcast over the batch.  None stays None, unless ``required`` says why the call needs one."""
+    if v is None:
+        if required:
+            raise ValueError(f"{name} is required: {required}")
+        return None
+    a = np.asarray(v, dtype=np.float64)
+    if a.shape == (width,) or (scalar and a.shape == ()):
+        a = np.broadcast_to(a, (B, width))
+    if a.shape != (B, width):
+        raise ValueError(f"{name} must have shape ({width},) or ({B}, {width}), but got {a.shape}")
+    if not np.isfinite(a).all() or (a < 0).any():
+        raise ValueError(f"{name} must be finite and >= 0")
+    return np.ascontiguousarray(a)
+
+
+def _choice(what, v, table):
+    """The code of the name v in table (a distribution, a mode); a code itself is not a name."""
+    if not isinstance(v, str) or v not in table:
+        raise ValueError(f"Unknown {what}: {v!r}. Supported: {', '.join(map(repr, table))}.")
+    return table[v]
+
+
+def _integrator_code(integrator):
+    """-1 (the solver's plant, else model, integrator) for None, else the code of the name."""
+    if integrator is None:
+        return -1
+    if isinstance(integrator, str) and integrator in _lib.INTEGRATORS:
+        return _lib.INTEGRATORS[integrator]
+    raise ValueError(f"Unknown integrator: {integrator!r}. Supported: 'rk4', 'midpoint', 'euler', 'backward_euler'.")
+
+
+# ---- policy rollouts -------------------------------------------------------------------------------------------------
+PolicyRollout = namedtuple("PolicyRollout", "cost x_final deviation violation X U", defaults=(None, None))
+PolicyRollout.__doc__ = """Result of iLQR.policy_rollout: cost, deviation, violation ([B,] S), x_final ([B,] S, n_x) and, with
+trajectories=True, X ([B,] S, n_x, N + 1) and U ([B,] S, n_u, N), else None.  A diverged sample has a non-finite cost."""
+
+PolicyRolloutArgs = NamedTuple("PolicyRolloutArgs", [("n_samples", int), ("x0", ROWS), ("w", ROWS), ("plant_rows", ROWS),
+                                                     ("integrator", int)])
+
+
+def policy_rollout_args(system, N, B, batched, n_samples, x_0=None, disturbance=None, plant_params=None, integrator=None):
+    """Validated arguments of ``ilqr_policy_rollout`` as (S, x0, w, plant_rows, integrator code): x0 (B, S, n_x), w
+    (B, S, N, n_x) as float64 arrays or None, plant_rows (B, S, n_sys) float64 or None, integrator -1 for the solver's
+    plant (else model) integrator.  Inputs carry (B, S, ...) on a batched solver and (S, ...) on a single one.
+    plant_params is what ``set_plant_params`` takes per trajectory, here per sample: {name: scalar or ([B,] S)}.
+    Raises ValueError for n_samples < 1, a wrong shape, a non-finite plant parameter, an unknown parameter name or
+    integrator, or a system without policy rollouts.  Pure host code (no GPU)."""
+    refuse_unsupported(system, "policy rollouts are", has_policy_kernels(system))
+    S = _count("n_samples", n_samples, 1, integer_type=False, below_2_31=False)
+    B, n = int(B), system.n_x
+    lead = (B, S) if batched else (S,)
+
+    def shaped(name, v, tail):
+        if v is None:
+            return None
+        a = np.asarray(v, dtype=np.float64)
+        if a.shape != lead + tail:
+            raise ValueError(f"{name} must have shape {lead + tail}, but got {a.shape}")
+        return np.ascontiguousarray(a.reshape((B, S) + tail))
+
+    x0 = shaped("x_0", x_0, (n,))
+    w = shaped("disturbance", disturbance, (int(N), n))
+    rows = None
+    if plant_params is not None and getattr(system, "SYSTEM_ID", None) not in _lib.BOX_SYSTEMS:
+        raise ValueError("plant_params: a user-defined system has no parameter rows (its constants are part of the "
+                         "generated code); only the plant's integrator can differ from the model's")
+    if plant_params is not None:
+        flat = {}
+        unknown = sorted(set(plant_params) - set(system.param_names()))
+        if unknown:
+            raise ValueError(f"unknown parameter name(s) {unknown}; expected some of {sorted(system.param_names())}")
+        for k, v in dict(plant_params).items():
+            a = np.asarray(v, dtype=np.float64)
+            if a.ndim != 0:
+                if a.shape != lead:
+                    raise ValueError(f"{k} must be a scalar or have shape {lead}, but got {a.shape}")
+                a = a.reshape(B * S)
+            flat[k] = a
+        # one row per sample: the samples are the batch axis of the per-trajectory rows
+        rows = batch_param_rows(system, B * S, flat, with_target=False).reshape(B, S, -1)
+    return PolicyRolloutArgs(n_samples=S, x0=x0, w=w, plant_rows=rows, integrator=_integrator_code(integrator))
+
+
+# ---- policy Monte Carlo ----------------------------------------------------------------------------------------------
+PolicyMonteCarlo = namedtuple(
+    "PolicyMonteCarlo", _lib.MONTE_CARLO_STATS + _lib.MONTE_CARLO_COUNTS +
+    ("cost", "x_final", "deviation", "violation", "X", "U", "x_0", "disturbance"), defaults=(None,) * 8)
+PolicyMonteCarlo.__doc__ = """Result of iLQR.policy_monte_carlo.  Per trajectory ([B] each, scalars on a single solver), over
+the samples with a finite cost: cost_mean, cost_std (population), cost_min, cost_max, deviation_mean, deviation_max,
+violation_max (float64, NaN when n_finite is 0), n_finite, n_violating (int).  With samples=True cost, deviation, violation
+([B,] S) and x_final ([B,] S, n_x); with trajectories=True X ([B,] S, n_x, N + 1) and U ([B,] S, n_u, N); with noise=True
+x_0 ([B,] S, n_x) and disturbance ([B,] S, N, n_x) as they were drawn; else None."""
+
+PolicyMonteCarloArgs = NamedTuple(
+    "PolicyMonteCarloArgs",
+    [("n_samples", int), ("seed", int), ("x0_std", ROWS), ("w_std", ROWS), ("distribution", int), ("plant_rows", ROWS),
+     ("integrator", int), ("violation_tol", float), ("first_trajectory", int)])
+
+
+def policy_monte_carlo_args(system, N, B, batched, n_samples, seed=0, x_0_std=None, disturbance_std=None,
+                            distribution="gaussian", plant_params=None, integrator=None, violation_tol=0.0,
+                            first_trajectory=0):
+    """Validated arguments of ``ilqr_policy_monte_carlo`` as (S, seed, x0_std, w_std, distribution code, plant_rows,
+    integrator code, violation_tol, first_trajectory): the standard deviations (B, n_x) float64 or None -- (n_x,) is
+    broadcast over the batch --, plant_rows and the integrator as policy_rollout_args gives them.  Raises ValueError for
+    what policy_rollout_args refuses, a seed outside [0, 2^64), a standard deviation of a wrong shape, negative or not
+    finite, an unknown distribution, a negative or NaN violation_tol, or a negative first_trajectory.  Pure host code
+    (no GPU)."""
+    r = policy_rollout_args(system, N, B, batched, n_samples, None, None, plant_params, integrator)
+    B, n = int(B), system.n_x
+    seed = _seed(seed)
+    x0_std, w_std = _std_rows("x_0_std", x_0_std, B, n), _std_rows("disturbance_std", disturbance_std, B, n)
+    dist = _choice("distribution", distribution, _lib.NOISE_DISTRIBUTIONS)
+    tol = float(violation_tol)
+    if not tol >= 0.0:
+        raise ValueError(f"violation_tol must be >= 0, got {violation_tol!r}")
+    first = _count("first_trajectory", first_trajectory, 0, integer_type=False)
+    return PolicyMonteCarloArgs(n_samples=r.n_samples, seed=seed, x0_std=x0_std, w_std=w_std, distribution=dist,
+                                plant_rows=r.plant_rows, integrator=r.integrator, violation_tol=tol, first_trajectory=first)
+
+
+# ---- sampled control search and sampled MPC --------------------------------------------------------------------------
+# What SampledControls and SampledMPC gain while a penalty is set (iLQR.set_sample_penalty): attributes beside the tuple's
+# own fields, None without a penalty.  The tuple itself (_fields, unpacking, iteration) stays the unpenalised record.
+PENALTY_FIELDS = ("penalty", "violation") + _lib.SAMPLE_PENALTY_STATS + ("round_n_violating", "penalty_samples",
+                                                                        "violation_samples")
+
+
+def _with_penalty_fields(record):
+    class Record(record):
+        def __new__(cls, *args, **kw):
+            extra = {k: kw.pop(k) for k in PENALTY_FIELDS if k in kw}
+            self = super().__new__(cls, *args, **kw)
+            self.__dict__.update(extra)
+            return self
+
+    for k in PENALTY_FIELDS:
+        setattr(Record, k, None)
+    Record.__name__ = Record.__qualname__ = record.__name__
+    return Record
+
+
+SampledControls = _with_penalty_fields(namedtuple(
+    "SampledControls", ("U", "cost", "cost_start") + _lib.SAMPLE_ROUND_STATS + ("round_n_finite", "applied", "X", "cost_samples",
+                                                                             "U_samples"), defaults=(None,) * 4))
+SampledControls.__doc__ ="""Result of iLQR.sample_controls.  U ([B,] n_u, N): the searched controls; cost ([B]): their plain
+cost from x_0; cost_start ([B]): the cost of the controls the call started from; round_cost_nominal, round_cost_min,
+round_ess (float64) and round_n_finite (int), each (R, [B]): per round the cost of its nominal, the minimum over the
+samples with a finite cost (NaN with none), the effective sample size of the softmin weights (1 in "best" mode) and the
+number of finite samples; applied ([B] bool, None without apply=True): where U became the solver's initial guess; X
+([B,] n_x, N + 1) with trajectories=True; cost_samples ([B,] S) and U_samples ([B,] S, n_u, N) of the last round with
+samples=True; else None.  While a penalty is set (set_sample_penalty) every cost above is J + P, and: penalty,
+violation ([B]): P and the largest state-limit violation of U's rollout; round_penalty_start, round_penalty_best,
+round_violation_best (float64) and round_n_violating (int), each (R, [B]): per round P of its nominal, P and the
+violation of its best sample (NaN with no finite sample) and the number of finite samples violating by more than
+violation_tol; penalty_samples, violation_samples ([B,] S) of the last round with samples=True."""
+
+_SEARCH_FIELDS = [("n_samples", int), ("rounds", int), ("seed", int), ("u_std", ROWS), ("mode", int), ("temperature", float),
+                  ("smoothing", float), ("distribution", int), ("first_trajectory", int), ("first_round", int)]
+SampleControlsArgs = NamedTuple("SampleControlsArgs", _SEARCH_FIELDS)
+
+
+def sample_controls_args(system, N, B, batched, n_samples, rounds=1, seed=0, u_std=None, mode="best", temperature=None,
+                         smoothing=0.0, distribution="gaussian", first_trajectory=0, first_round=0):
+    """Validated arguments of ``ilqr_sample_controls`` as (S, R, seed, u_std, mode code, temperature, smoothing,
+    distribution code, first_trajectory, first_round): u_std (B, n_u) float64 -- (n_u,) or a scalar is broadcast over the
+    batch.  Raises ValueError for a system without the search, n_samples or rounds that are not integers >= 1, a seed
+    outside [0, 2^64), a missing, misshapen, negative or non-finite u_std, an unknown mode or distribution, a temperature
+    that is not finite and > 0 in "softmin" mode (it is required there), smoothing outside [0, 1), a negative
+    first_trajectory or first_round, or first_round + rounds > 2^32 - 2.  Pure host code (no GPU)."""
+    refuse_unsupported(system, "the sampled control search is", has_policy_kernels(system))
+    S, R = _count("n_samples", n_samples, 1), _count("rounds", rounds, 1)
+    seed = _seed(seed)
+    std = _std_rows("u_std", u_std, int(B), system.n_u, scalar=True,
+                    required="the standard deviation of the control perturbation, ([B,] n_u)")
+    mcode = _choice("mode", mode, _lib.SAMPLE_MODES)
+    if mcode == _lib.SAMPLE_SOFTMIN:
+        if temperature is None or not (np.isfinite(float(temperature)) and float(temperature) > 0.0):
+            raise ValueError(f"temperature must be finite and > 0 in 'softmin' mode, got {temperature!r}")
+    temp = 1.0 if temperature is None else float(temperature)
+    beta = float(smoothing)
+    if not 0.0 <= beta < 1.0:
+        raise ValueError(f"smoothing must be in [0, 1), got {smoothing!r}")
+    dist = _choice("distribution", distribution, _lib.NOISE_DISTRIBUTIONS)
+    first, first_r = _count("first_trajectory", first_trajectory, 0), _count("first_round", first_round, 0)
+    if first_r + R > 2 ** 32 - 2:
+        raise ValueError("first_round + rounds must be <= 2^32 - 2")
+    return SampleControlsArgs(n_samples=S, rounds=R, seed=seed, u_std=std, mode=mcode, temperature=temp, smoothing=beta,
+                              distribution=dist, first_trajectory=first, first_round=first_r)
+
+
+SampledMPC = _with_penalty_fields(namedtuple(
+    "SampledMPC", ("U_sim", "X_sim", "cost") + _lib.SAMPLE_ROUND_STATS + ("round_n_finite", "U_plan"), defaults=(None,)))
+SampledMPC.__doc__ = """Result of iLQR.sampled_mpc.  U_sim (n_steps, [B,] n_u): the controls applied; X_sim (n_steps, [B,]
+n_x): the plant state AFTER each step; cost (n_steps, [B]): the cost the search reports for each step's plan, from the
+state before the step (the last round's minimum in "best" mode, the plain cost of the averaged plan in "softmin" mode);
+round_cost_nominal, round_cost_min, round_ess (float64) and round_n_finite (int), each (n_steps, R, [B]): the round
+statistics of SampledControls for every round of every step; U_plan (n_steps, [B,] n_u, N) with plans=True: the plan of
+each step before it is shifted, else None.  While a penalty is set (set_sample_penalty) cost is J + P, and: penalty,
+violation (n_steps, [B]): P and the violation of each step's plan ("best" mode: of the last round's best sample);
+round_penalty_start, round_penalty_best, round_violation_best, round_n_violating (n_steps, R, [B]) as SampledControls';
+penalty_samples, violation_samples ([B,] S) of the last step's last round with samples=True."""
+
+SampledMpcArgs = NamedTuple("SampledMpcArgs", [("n_steps", int)] + _SEARCH_FIELDS + [("w", ROWS)])
+
+
+def sampled_mpc_args(system, N, B, batched, n_steps, n_samples, rounds=1, seed=0, u_std=None, mode="softmin", temperature=None,
+                     smoothing=0.0, distribution="gaussian", first_trajectory=0, first_round=0, disturbance=None, dtype=None):
+    """Validated arguments of ``ilqr_sampled_mpc`` as (K, S, R, seed, u_std, mode code, temperature, smoothing,
+    distribution code, first_trajectory, first_round, w): everything ``sample_controls_args`` returns and refuses, with
+    n_steps = K an integer >= 1, first_round + n_steps * rounds <= 2^32 - 2 in place of its stream bound, and w the
+    disturbance (n_steps, [B,] n_x) as (K, B, n_x) float64 -- every value finite (in ``dtype`` too, where one is given)
+    -- or None.  Pure host code (no GPU)."""
+    a = sample_controls_args(system, N, B, batched, n_samples, rounds, seed, u_std, mode, temperature, smoothing,
+                             distribution, first_trajectory, first_round)
+    K, B, n = _count("n_steps", n_steps, 1), int(B), system.n_x
+    if a.first_round + K * a.rounds > 2 ** 32 - 2:
+        raise ValueError("first_round + n_steps * rounds must be <= 2^32 - 2")
+    w = None
+    if disturbance is not None:
+        w = np.asarray(disturbance, dtype=np.float64)
+        want = (K, B, n) if batched else (K, n)
+        if w.shape != want:
+            raise ValueError(f"disturbance must have shape {want}, but got {w.shape}")
+        w = np.ascontiguousarray(w.reshape(K, B, n))
+        with np.errstate(over="ignore"):
+            if not np.isfinite(w if dtype is None else w.astype(dtype)).all():
+                raise ValueError("disturbance must be finite")
+    return SampledMpcArgs(n_steps=K, **a._asdict(), w=w)
+
+
+# ---- the sample penalty ----------------------------------------------------------------------------------------------
+SamplePenaltyArgs = NamedTuple("SamplePenaltyArgs", [("weight", ROWS), ("violation_tol", float)])
+
+
+def sample_penalty_args(system, B, weight, violation_tol=0.0, dtype=None):
+    """Validated arguments of ``ilqr_set_sample_penalty`` as (weight, violation_tol): weight (B,) float64 -- a scalar is
+    broadcast over the batch -- or None (clear).  Raises ValueError for a system without state limits (linear and
+    user-defined systems), a misshapen weight, one that is not finite (in ``dtype`` too, where one is given) and > 0, or a
+    violation_tol that is not finite and >= 0.  Pure host code (no GPU)."""
+    refuse_unsupported(system, "the sample penalty is")
+    if weight is None:
+        return SamplePenaltyArgs(weight=None, violation_tol=0.0)
+    w = np.asarray(weight, dtype=np.float64)
+    if w.shape == ():
+        w = np.broadcast_to(w, (int(B),))
+    if w.shape != (int(B),):
+        raise ValueError(f"weight must be a scalar or have shape ({int(B)},), but got {w.shape}")
+    with np.errstate(over="ignore", under="ignore"):
+        held = w if dtype is None else w.astype(dtype)
+    if not np.isfinite(held).all() or not (held > 0).all():
+        raise ValueError("weight must be finite and > 0")
+    tol = float(violation_tol)
+    if not (np.isfinite(tol) and tol >= 0.0):
+        raise ValueError(f"violation_tol must be finite and >= 0, got {violation_tol!r}")
+    return SamplePenaltyArgs(weight=np.ascontiguousarray(w), violation_tol=tol)
+
+
+# ---- results: the library's arrays and tables, as the records hold them ------------------------------------------------
+def unbatch(a, batched, axis=-1, wrap=False):
+    """An array of the library, which always has a batch axis, as the solver's caller sees it: without that axis on an
+    unbatched solver (B = 1); wrap: as a ``ready`` array."""
+    if not batched:
+        a = a[(slice(None),) * (axis % a.ndim) + (0,)]
+    return ready(a) if wrap else a
+
+
+def table_columns(table, names, batched, wrap=False):
+    """{name: column} of a (..., B, C) table of statistics, one column per name, each a copy of its own and handed on
+    through ``unbatch``."""
+    return {k: unbatch(table[..., i].copy(), batched, wrap=wrap) for i, k in enumerate(names)}

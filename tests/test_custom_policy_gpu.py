@@ -25,6 +25,7 @@ import policy_noise_ref as noise
 import policy_rollout_ref as ref
 import sample_controls_ref as sc
 from precision_bounds import rel_err
+from sampling_common import _assert_same, _bits, _same, _state, _stds
 
 pytestmark = pytest.mark.gpu
 
@@ -48,23 +49,6 @@ def _search_solver(name, shape, dtype):
     x0, U0, u_std = cp.search_inputs(name, shape)
     s = ilqr_amd.iLQR(cp.system(name, dtype), None, x0, U0, N=shape[2], verbose=False, dtype=dtype)
     return s, x0, U0, u_std
-
-
-def _bits(a, b, what):
-    a, b = np.asarray(a), np.asarray(b)
-    assert a.dtype == b.dtype and a.shape == b.shape, f"{what}: {a.dtype} {a.shape} against {b.dtype} {b.shape}"
-    np.testing.assert_array_equal(a, b, err_msg=what)
-
-
-def _same(a, b, keys, what):
-    for k in keys:
-        np.testing.assert_array_equal(getattr(a, k), getattr(b, k), err_msg=f"{what}: {k}")
-
-
-def _stds(B, n, seed=3):
-    """per-trajectory standard deviations, different in every entry"""
-    rng = np.random.default_rng(seed)
-    return rng.uniform(0.01, 0.05, (B, n)), rng.uniform(1e-4, 1e-3, (B, n))
 
 
 # ---- 1. policy_rollout parity ------------------------------------------------------------------------------------------
@@ -326,17 +310,6 @@ def test_apply_then_optimize_trajectory_starts_from_the_searched_controls(dtype)
 
 
 # ---- 4. no side effects --------------------------------------------------------------------------------------------------
-def _state(s):
-    h = s.handle
-    return dict(X=h.get(_lib.X), U=h.get(_lib.U), K=h.get(_lib.K), U_ff=h.get(_lib.UFF), cost=h.get(_lib.COST),
-                status=h.get(_lib.STATUS), iters=h.get(_lib.ITERS), plant_x=h.get(_lib.PLANT_X))
-
-
-def _assert_same(a, b, what):
-    for k in a:
-        np.testing.assert_array_equal(a[k], b[k], err_msg=f"{what}: {k}")
-
-
 def _three_calls(s, S):
     n, m = s.n_x, s.n_u
     r = s.policy_monte_carlo(S, 1, np.full(n, 0.01), np.full(n, 1e-3), samples=True, trajectories=True, noise=True)

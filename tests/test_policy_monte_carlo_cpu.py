@@ -13,6 +13,7 @@ from ilqr_amd import _lib
 
 import policy_noise_ref as noise
 import policy_rollout_ref as ref
+from sampling_common import header_struct
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -82,17 +83,11 @@ def test_header_declares_the_entry_and_the_binding_matches_it():
     assert re.search(r"^int ilqr_policy_monte_carlo\(ilqr_handle h, const ilqr_monte_carlo_desc\* d\);", header, flags=re.M)
     assert re.search(r"enum \{ ILQR_NOISE_GAUSSIAN = 0, ILQR_NOISE_UNIFORM = 1 \};", header)
     assert (_lib.NOISE_GAUSSIAN, _lib.NOISE_UNIFORM) == (0, 1)
-    body = re.search(r"typedef struct ilqr_monte_carlo_desc \{(.*?)\} ilqr_monte_carlo_desc;", header, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = re.findall(r"(uint32_t|int32_t\*|int32_t|uint64_t|double\*|double|const void\*|const double\*|void\*)\s+(\w+);", body)
-    ctype = {"uint32_t": C.c_uint32, "int32_t": C.c_int32, "uint64_t": C.c_uint64, "double": C.c_double,
-             "const double*": C.POINTER(C.c_double), "double*": C.POINTER(C.c_double), "int32_t*": C.POINTER(C.c_int32),
-             "const void*": C.c_void_p, "void*": C.c_void_p}
-    assert [(n, ctype[t]) for t, n in fields] == list(_lib.MonteCarloDesc._fields_)
+    fields = header_struct("ilqr_monte_carlo_desc")
+    assert [(n, t) for t, n in fields] == list(_lib.MonteCarloDesc._fields_)
     assert [n for _, n in fields] == ["struct_size", "n_samples", "integrator", "feedback", "distribution", "first_trajectory",
                                       "seed", "violation_tol", "x0_std", "w_std", "plant_rows", "stats", "counts", "cost",
                                       "x_final", "deviation", "violation", "X", "U", "x0_out", "w_out"]
-    assert len(body.split(";")) - 1 == len(fields)          # every declaration of the struct was recognised
     assert C.sizeof(_lib.MonteCarloDesc) == 24 + 8 + 8 + 13 * 8
     # the entry is additive: the version and the rollout's own struct stay as they were
     assert re.search(r"#define ILQR_ABI_VERSION 5\b", header) and _lib.ABI_VERSION == 5

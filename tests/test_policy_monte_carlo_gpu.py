@@ -23,6 +23,7 @@ from ilqr_amd.systems.examples import example_problems
 
 import policy_noise_ref as noise
 import policy_rollout_ref as ref
+from sampling_common import _assert_same, _same, _state, _stds
 
 pytestmark = pytest.mark.gpu
 
@@ -40,17 +41,6 @@ def _solver(name, X, U, K, dtype, N, **kw):
     s = ilqr_amd.iLQR(sysm, None, X[:, :, 0], U, N=N, verbose=False, dtype=dtype, **kw)
     s.X, s.K = X, K
     return s
-
-
-def _stds(B, n, seed=3):
-    """per-trajectory standard deviations, different in every entry"""
-    rng = np.random.default_rng(seed)
-    return rng.uniform(0.01, 0.05, (B, n)), rng.uniform(1e-4, 1e-3, (B, n))
-
-
-def _same(a, b, keys, what):
-    for k in keys:
-        np.testing.assert_array_equal(getattr(a, k), getattr(b, k), err_msg=f"{what}: {k}")
 
 
 # ---- 1. the draws are the specified ones -----------------------------------------------------------------------------
@@ -294,17 +284,6 @@ def test_statistics_alone_need_no_per_sample_output():
 
 
 # ---- 5. nothing else changes -------------------------------------------------------------------------------------------
-def _state(s):
-    h = s.handle
-    return dict(X=h.get(_lib.X), U=h.get(_lib.U), K=h.get(_lib.K), U_ff=h.get(_lib.UFF), cost=h.get(_lib.COST),
-                status=h.get(_lib.STATUS), iters=h.get(_lib.ITERS), plant_x=h.get(_lib.PLANT_X))
-
-
-def _assert_same(a, b, what):
-    for k in a:
-        np.testing.assert_array_equal(a[k], b[k], err_msg=f"{what}: {k}")
-
-
 def test_a_call_inside_a_solve_changes_nothing():
     B, S, N = 5, 70, 30
     dyn, cost = ref.spec("ua", N)

@@ -15,6 +15,7 @@ from oracle.build import oracle_from_spec
 
 import policy_rollout_ref as ref
 from precision_bounds import SEPARATION, SINGLE_STAGE, rel_err
+from sampling_common import header_struct
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHECKED = ("cost", "x_final", "deviation", "X", "U")
@@ -129,12 +130,8 @@ def test_argument_validation_raises_value_error_before_any_device():
 def test_header_declares_the_entry_and_the_binding_matches_it():
     header = open(os.path.join(ROOT, "include", "ilqr_hip.h")).read()
     assert re.search(r"^int ilqr_policy_rollout\(ilqr_handle h, const ilqr_policy_rollout_desc\* d\);", header, flags=re.M)
-    body = re.search(r"typedef struct ilqr_policy_rollout_desc \{(.*?)\} ilqr_policy_rollout_desc;", header, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = re.findall(r"(uint32_t|int32_t|const void\*|const double\*|void\*)\s+(\w+);", body)
-    ctype = {"uint32_t": C.c_uint32, "int32_t": C.c_int32, "const void*": C.c_void_p, "void*": C.c_void_p,
-             "const double*": C.POINTER(C.c_double)}
-    assert [(n, ctype[t]) for t, n in fields] == list(_lib.PolicyRolloutDesc._fields_)
+    fields = header_struct("ilqr_policy_rollout_desc")
+    assert [(n, t) for t, n in fields] == list(_lib.PolicyRolloutDesc._fields_)
     assert [n for _, n in fields] == ["struct_size", "n_samples", "integrator", "feedback", "x0", "w", "plant_rows", "cost",
                                       "x_final", "deviation", "violation", "X", "U"]
     assert C.sizeof(_lib.PolicyRolloutDesc) == 16 + 9 * 8

@@ -18,6 +18,7 @@ from oracle.build import oracle_from_spec
 
 import policy_rollout_ref as ref
 from precision_bounds import rel_err
+from sampling_common import _assert_same, _state
 
 pytestmark = pytest.mark.gpu
 
@@ -224,17 +225,6 @@ def test_after_a_solve_the_unperturbed_sample_is_the_solution(dtype, flags):
 
 
 # ---- non-interference ------------------------------------------------------------------------------------------------
-def _state(s):
-    h = s.handle
-    return dict(X=h.get(_lib.X), U=h.get(_lib.U), K=h.get(_lib.K), U_ff=h.get(_lib.UFF), cost=h.get(_lib.COST),
-                status=h.get(_lib.STATUS), iters=h.get(_lib.ITERS), plant_x=h.get(_lib.PLANT_X))
-
-
-def _assert_same(a, b, what):
-    for k in a:
-        np.testing.assert_array_equal(a[k], b[k], err_msg=f"{what}: {k}")
-
-
 @pytest.mark.parametrize("flags", [0, _lib.FLAG_NO_PERSIST, _lib.FLAG_NO_FUSE], ids=["default", "no_persist", "no_fuse"])
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 def test_a_call_inside_a_solve_changes_nothing(dtype, flags):

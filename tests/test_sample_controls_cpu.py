@@ -15,6 +15,7 @@ from oracle.build import oracle_from_spec
 import policy_noise_ref as noise
 import policy_rollout_ref as ref
 import sample_controls_ref as sc
+from sampling_common import header_struct
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -92,17 +93,11 @@ def test_header_declares_the_entry_and_the_binding_matches_it():
     assert re.search(r"^int ilqr_sample_controls\(ilqr_handle h, const ilqr_sample_controls_desc\* d\);", header, flags=re.M)
     assert re.search(r"enum \{ ILQR_SAMPLE_BEST = 0, ILQR_SAMPLE_SOFTMIN = 1 \};", header)
     assert (_lib.SAMPLE_BEST, _lib.SAMPLE_SOFTMIN) == (0, 1)
-    body = re.search(r"typedef struct ilqr_sample_controls_desc \{(.*?)\} ilqr_sample_controls_desc;", header, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = re.findall(r"(uint32_t|int32_t\*|int32_t|uint64_t|double\*|double|const void\*|const double\*|void\*)\s+(\w+);", body)
-    ctype = {"uint32_t": C.c_uint32, "int32_t": C.c_int32, "uint64_t": C.c_uint64, "double": C.c_double,
-             "const double*": C.POINTER(C.c_double), "double*": C.POINTER(C.c_double), "int32_t*": C.POINTER(C.c_int32),
-             "const void*": C.c_void_p, "void*": C.c_void_p}
-    assert [(n, ctype[t]) for t, n in fields] == list(_lib.SampleControlsDesc._fields_)
+    fields = header_struct("ilqr_sample_controls_desc")
+    assert [(n, t) for t, n in fields] == list(_lib.SampleControlsDesc._fields_)
     assert [n for _, n in fields] == ["struct_size", "n_samples", "n_rounds", "mode", "distribution", "first_trajectory",
                                       "first_round", "seed", "temperature", "smoothing", "u_std", "U_new", "cost_new", "X_new",
                                       "round_stats", "round_counts", "cost_samples", "U_samples"]
-    assert len(body.split(";")) - 1 == len(fields)          # every declaration of the struct was recognised
     assert C.sizeof(_lib.SampleControlsDesc) == 32 + 3 * 8 + 8 * 8
     # the entry is additive: the version and the neighbouring structs stay as they were
     assert re.search(r"#define ILQR_ABI_VERSION 5\b", header) and _lib.ABI_VERSION == 5

@@ -24,6 +24,7 @@ import policy_noise_ref as noise
 import policy_rollout_ref as ref
 import sample_controls_ref as sc
 from precision_bounds import rel_err
+from sampling_common import _assert_same, _bits, _state
 
 pytestmark = pytest.mark.gpu
 
@@ -40,12 +41,6 @@ def _solver(name, shape, dtype, integrator="rk4", **kw):
     x0, U0, u_std = sc.search_inputs(name, shape)
     s = ilqr_amd.iLQR(ilqr_amd.make_system(dyn, cost), None, x0, U0, N=N, verbose=False, dtype=dtype, **kw)
     return s, x0, U0, u_std
-
-
-def _bits(a, b, what):
-    a, b = np.asarray(a), np.asarray(b)
-    assert a.dtype == b.dtype and a.shape == b.shape, f"{what}: {a.dtype} {a.shape} against {b.dtype} {b.shape}"
-    np.testing.assert_array_equal(a, b, err_msg=what)
 
 
 def _limits(B, m, rows):
@@ -274,17 +269,6 @@ def test_streams_depend_neither_on_the_batch_nor_on_the_sample_count():
 
 
 # ---- 9. nothing else changes -------------------------------------------------------------------------------------------
-def _state(s):
-    h = s.handle
-    return dict(X=h.get(_lib.X), U=h.get(_lib.U), K=h.get(_lib.K), U_ff=h.get(_lib.UFF), cost=h.get(_lib.COST),
-                status=h.get(_lib.STATUS), iters=h.get(_lib.ITERS), plant_x=h.get(_lib.PLANT_X))
-
-
-def _assert_same(a, b, what):
-    for k in a:
-        np.testing.assert_array_equal(a[k], b[k], err_msg=f"{what}: {k}")
-
-
 def test_a_call_inside_a_solve_changes_nothing():
     B, S, N = 5, 70, 30
     dyn, cost = ref.spec("ua", N)

@@ -13,6 +13,7 @@ from ilqr_amd import _lib, iLQR_class, problems
 
 import sample_penalty_ref as sp
 from al_ilqr_ref import ALiLQR
+from sampling_common import header_struct
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = [(n, s, k) for n in sp.SYSTEMS for s in sp.BINDING_SHAPES for k in sp.KINDS]
@@ -84,13 +85,8 @@ def test_header_declares_the_entries_and_the_binding_matches():
                      r"double violation_tol\);", header, flags=re.M)
     assert re.search(r"^int ilqr_sample_penalty_report\(ilqr_handle h, const ilqr_sample_penalty_report_desc\* d\);", header,
                      flags=re.M)
-    body = re.search(r"typedef struct ilqr_sample_penalty_report_desc \{(.*?)\} ilqr_sample_penalty_report_desc;", header,
-                     flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = re.findall(r"(uint32_t|int32_t\*|int32_t|double\*|void\*)\s+(\w+);", body)
-    ctype = {"uint32_t": C.c_uint32, "int32_t": C.c_int32, "double*": C.POINTER(C.c_double), "int32_t*": C.POINTER(C.c_int32),
-             "void*": C.c_void_p}
-    assert [(n, ctype[t]) for t, n in fields] == list(_lib.SamplePenaltyReportDesc._fields_)
+    fields = header_struct("ilqr_sample_penalty_report_desc")
+    assert [(n, t) for t, n in fields] == list(_lib.SamplePenaltyReportDesc._fields_)
     assert [n for _, n in fields] == ["struct_size", "reserved", "penalty_samples", "violation_samples", "penalty_new",
                                       "violation_new", "round_penalty", "round_violating"]
     assert C.sizeof(_lib.SamplePenaltyReportDesc) == 8 + 6 * 8

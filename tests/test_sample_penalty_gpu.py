@@ -23,6 +23,7 @@ import custom_policy_ref as cp
 import policy_rollout_ref as ref
 import sample_penalty_ref as sp
 from precision_bounds import rel_err
+from sampling_common import _bits
 
 pytestmark = pytest.mark.gpu
 
@@ -35,12 +36,6 @@ REPORT = ("penalty", "violation", "round_penalty_start", "round_penalty_best", "
 SAMPLES = ("penalty_samples", "violation_samples")
 PLAIN = ("U", "cost", "cost_start", "round_cost_nominal", "round_cost_min", "round_ess", "round_n_finite", "cost_samples",
          "U_samples")
-
-
-def _bits(a, b, what):
-    a, b = np.asarray(a), np.asarray(b)
-    assert a.dtype == b.dtype and a.shape == b.shape, f"{what}: {a.dtype} {a.shape} against {b.dtype} {b.shape}"
-    np.testing.assert_array_equal(a, b, err_msg=what)
 
 
 def _solver(case, dtype, integrator="rk4", limits=True, plant=False, **kw):

@@ -12,6 +12,7 @@ from ilqr_amd import _lib
 
 import policy_rollout_ref as ref
 import sampled_mpc_ref as smr
+from sampling_common import header_struct
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -118,17 +119,11 @@ def test_requires_a_plant():
 def test_header_declares_the_entry_and_the_binding_matches_it():
     header = open(os.path.join(ROOT, "include", "ilqr_hip.h")).read()
     assert re.search(r"^int ilqr_sampled_mpc\(ilqr_handle h, const ilqr_sampled_mpc_desc\* d\);", header, flags=re.M)
-    body = re.search(r"typedef struct ilqr_sampled_mpc_desc \{(.*?)\} ilqr_sampled_mpc_desc;", header, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = re.findall(r"(uint32_t|int32_t\*|int32_t|uint64_t|double\*|double|const void\*|const double\*|void\*)\s+(\w+);", body)
-    ctype = {"uint32_t": C.c_uint32, "int32_t": C.c_int32, "uint64_t": C.c_uint64, "double": C.c_double,
-             "const double*": C.POINTER(C.c_double), "double*": C.POINTER(C.c_double), "int32_t*": C.POINTER(C.c_int32),
-             "const void*": C.c_void_p, "void*": C.c_void_p}
-    assert [(n, ctype[t]) for t, n in fields] == list(_lib.SampledMpcDesc._fields_)
+    fields = header_struct("ilqr_sampled_mpc_desc")
+    assert [(n, t) for t, n in fields] == list(_lib.SampledMpcDesc._fields_)
     assert [n for _, n in fields] == ["struct_size", "n_samples", "n_rounds", "mode", "distribution", "first_trajectory",
                                       "first_round", "n_steps", "seed", "temperature", "smoothing", "u_std", "w", "u_out",
                                       "x_out", "cost_out", "U_plan", "round_stats", "round_counts"]
-    assert len(body.split(";")) - 1 == len(fields)          # every declaration of the struct was recognised
     assert C.sizeof(_lib.SampledMpcDesc) == 32 + 3 * 8 + 8 * 8
     # the fields it takes from ilqr_sample_controls_desc keep their names, types and order
     shared = [f for f in _lib.SampleControlsDesc._fields_[:11]]

@@ -25,6 +25,7 @@ import policy_rollout_ref as ref
 import sample_controls_ref as sc
 import sampled_mpc_ref as smr
 from precision_bounds import rel_err
+from sampling_common import _bits, _state
 from test_fp64_resolution_gpu import K_STAGE32, _Errors, _per_point_ulps
 
 pytestmark = pytest.mark.gpu
@@ -34,12 +35,9 @@ SEED = smr.SEED
 DTYPES = [np.float32, np.float64]
 MODES = ["softmin", "best"]
 TEMPERATURE = {"pendulum": 3e-3, "ua": 10.0, "dp": 10.0}        # sample_controls_ref.SOFTMIN_CASES' large ones
-
-
-def _bits(a, b, what):
-    a, b = np.asarray(a), np.asarray(b)
-    assert a.dtype == b.dtype and a.shape == b.shape, f"{what}: {a.dtype} {a.shape} against {b.dtype} {b.shape}"
-    np.testing.assert_array_equal(a, b, err_msg=what)
+# for _state: what sampled_mpc moves on, and the policy it must leave alone
+MPC_STATE = (("U", _lib.U), ("X0", _lib.X0), ("PLANT_X", _lib.PLANT_X))
+POLICY = (("X", _lib.X), ("K", _lib.K), ("U_ff", _lib.UFF))
 
 
 def _systems(name, N, plant_integrator):
@@ -61,16 +59,6 @@ def _limits(B, m, rows):
     if rows:
         return sc.limit_rows(B, m)
     return np.full(m, -0.2), np.full(m, 0.15)
-
-
-def _state(s):
-    h = s.handle
-    return {k: h.get(f) for k, f in (("U", _lib.U), ("X0", _lib.X0), ("PLANT_X", _lib.PLANT_X))}
-
-
-def _policy(s):
-    h = s.handle
-    return {k: h.get(f) for k, f in (("X", _lib.X), ("K", _lib.K), ("U_ff", _lib.UFF))}
 
 
 def _check_steps_against_the_search(make, x0, U0, got, n_steps, search, first_round, what):
@@ -122,7 +110,7 @@ def test_a_step_equals_sample_controls_bit_for_bit(name, dtype, mode):
         assert (got.U_plan >= np.broadcast_to(lo, (B, m)).astype(dtype)[None, :, :, None]).all()
         assert (got.U_plan <= np.broadcast_to(hi, (B, m)).astype(dtype)[None, :, :, None]).all()
         # afterwards: U is the last plan shifted, x_0 and the plant state the last logged state
-        after = _state(s)
+        after = _state(s, MPC_STATE)
         _bits(after["U"], smr.shift(got.U_plan[-1]), "U after the call")
         _bits(after["X0"], got.X_sim[-1], "x_0 after the call")
         _bits(after["PLANT_X"], got.X_sim[-1], "plant state after the call")
@@ -187,7 +175,7 @@ def test_two_calls_continue_one(name, dtype, mode):
     tail = two.sampled_mpc(3, first_round=4 + 3 * 2, disturbance=w[3:], **search)
     for k in ilqr_amd.SampledMPC._fields:
         _bits(np.concatenate([getattr(head, k), getattr(tail, k)]), getattr(whole, k), f"{name} {mode}: {k}")
-    a, b = _state(one), _state(two)
+    a, b = _state(one, MPC_STATE), _state(two, MPC_STATE)
     for k in a:
         _bits(a[k], b[k], f"{name} {mode}: {k} after the calls")
     assert not np.array_equal(whole.U_sim[:3], whole.U_sim[3:])
@@ -202,15 +190,15 @@ def test_mpc_run_takes_over(name, dtype):
         s, x0, U0, u_std = _solver(name, shape, dtype, "rk4", maxiter=3)
         s.handle.solve()                                     # X, K and U_ff of a solve, kept by what follows
         s.mpc_reset(x0, U0, keep_state=True)
-        before = _policy(s)
+        before = _state(s, POLICY)
         r = s.sampled_mpc(2, S, 2, SEED, u_std, "softmin", TEMPERATURE[name], 0.5, "uniform")
         return s, before, r
 
     A, before, ra = history()
-    after = _policy(A)
+    after = _state(A, POLICY)
     for k in before:
         _bits(after[k], before[k], f"{name}: {k} is unchanged by sampled_mpc")
-    st = _state(A)
+    st = _state(A, MPC_STATE)
     out_a = A.mpc_run(1)
     Bh, _, rb = history()
     _bits(rb.X_sim, ra.X_sim, "the same history")
@@ -232,7 +220,7 @@ def test_a_horizon_of_one_step():
         search = dict(n_samples=S, rounds=2, seed=SEED, u_std=u_std, mode="best", distribution="uniform")
         got = s.sampled_mpc(3, plans=True, **search)
         _check_steps_against_the_search(lambda: _solver("ua", shape, dtype, inputs=inputs)[0], x0, U0, got, 3, search, 0, f"N = 1 {dtype}")
-        _bits(_state(s)["U"], got.U_plan[-1], "N = 1: nothing to shift")
+        _bits(_state(s, MPC_STATE)["U"], got.U_plan[-1], "N = 1: nothing to shift")
 
 
 def test_a_horizon_beyond_the_sliced_shift_walks():
@@ -248,14 +236,14 @@ def test_a_horizon_beyond_the_sliced_shift_walks():
     got = s.sampled_mpc(2, plans=True, **search)
     assert np.isfinite(got.cost).all()
     _check_steps_against_the_search(make, x0, U0, got, 2, search, 0, "N = 530")
-    _bits(_state(s)["U"], smr.shift(got.U_plan[-1]), "N = 530: U after the call")
+    _bits(_state(s, MPC_STATE)["U"], smr.shift(got.U_plan[-1]), "N = 530: U after the call")
     # one below the threshold the slices shift: the same answer from the other path's neighbour
     at = (B, S, 513)
     inputs_at = (inputs[0], inputs[1][:, :, :513].copy(), inputs[2])
     s2, x0, U0, u_std = _solver("ua", at, np.float32, inputs=inputs_at)
     got2 = s2.sampled_mpc(2, plans=True, **search)
     _check_steps_against_the_search(lambda: _solver("ua", at, np.float32, inputs=inputs_at)[0], x0, U0, got2, 2, search, 0, "N = 513")
-    _bits(_state(s2)["U"], smr.shift(got2.U_plan[-1]), "N = 513: U after the call")
+    _bits(_state(s2, MPC_STATE)["U"], smr.shift(got2.U_plan[-1]), "N = 513: U after the call")
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -373,11 +361,11 @@ def test_errors():
         d = _desc(h, S, keep)
         for k, v in fields.items():
             setattr(d, k, v)
-        before = _state(s)
+        before = _state(s, MPC_STATE)
         rc = lib.ilqr_sampled_mpc(h.h, C.byref(d))
         msg = lib.ilqr_last_error(h.h).decode()
         assert rc == _lib.ERR_INVALID_ARG and what in msg, f"{fields}: rc {rc}, {msg!r}"
-        after = _state(s)
+        after = _state(s, MPC_STATE)
         for k in before:
             _bits(after[k], before[k], f"{fields}: {k} changed by a refused call")
         assert lib.ilqr_sampled_mpc(h.h, C.byref(_desc(h, S, keep))) == _lib.OK, f"after {fields}"

@@ -1,12 +1,15 @@
-"""Every output of the three sampling entries (policy_rollout, policy_monte_carlo, sample_controls) at small shapes, as
-one .npz: run it once per build (ILQR_LIB selects the library; a copy of another checkout runs its own package and
+"""Every output of the sampling entries (policy_rollout, policy_monte_carlo, sample_controls, sampled_mpc, and the last two
+under a sample penalty) at small shapes, as one .npz: run it once per build (ILQR_LIB selects the library; a copy of another checkout runs its own package and
 plugins) and compare the two files with --compare.  A refactor of those entries must leave every array identical.
 
 Systems: the built-in policy systems (pendulum, UA double pendulum, double pendulum) and the policy example plugins.
 fp32 and fp64; B = 3, N = 5, S in {1, 65} (a full wave plus a one-lane tail); plant / model integrator rk4 and
 backward_euler.  Variants, every optional output requested: feedback on / off; control limits shared and as rows (both
 clamp); state limits; model rows and plant rows; per-sample plant rows; both distributions; BEST and SOFTMIN; smoothing 0
-and 0.9; two rounds.  (Limits and parameter rows exist for the built-in systems only.)
+and 0.9; two rounds.  sampled_mpc on a solver with a plant: both modes, with and without a disturbance, the plans, two
+steps of two rounds.  A penalised sample_controls and sampled_mpc (state limits, set_sample_penalty, samples=True) with the
+penalty's attributes of their records.  One unbatched solver (x_0 of shape (n_x,)) through all five calls: its records
+have no batch axis.  (Limits, parameter rows and the penalty exist for the built-in systems only.)
 
     python tools/sampling_dump.py out.npz
     python tools/sampling_dump.py --compare a.npz b.npz [summary.json]
@@ -45,9 +48,21 @@ def inputs(n, m, S):
 
 
 def record(out, tag, result):
-    for k, v in result._asdict().items():
+    """the fields of the record and, where it has them, the penalty's attributes beside them (_asdict() does not see those)"""
+    fields = dict(result._asdict(), **{k: getattr(result, k, None) for k in ilqr_amd.iLQR_class.PENALTY_FIELDS})
+    for k, v in fields.items():
         if v is not None:
             out[f"{tag}/{k}"] = np.asarray(v)
+
+
+def dump_mpc(out, tag, s, x0, U0, S, u_std, dist, w, **kw):
+    """sampled_mpc from (x0, U0): both modes, with and without the disturbance, two steps of two rounds, the plans"""
+    for mode, temp in (("best", None), ("softmin", 10.0)):
+        for name, w_ in (("w", w), ("no_w", None)):
+            s.mpc_reset(x0, U0)
+            record(out, f"{tag}/mpc/{dist}/{mode}/{name}",
+                   s.sampled_mpc(2, S, 2, SEED, u_std, mode, temp, 0.9, dist, first_trajectory=1, first_round=3, disturbance=w_,
+                                 plans=True, **kw))
 
 
 def dump_case(out, name, dtype, integrator, S):
@@ -67,6 +82,7 @@ def dump_case(out, name, dtype, integrator, S):
         setups["limits_shared"] = dict(u_min=-0.2, u_max=0.15, x_min=-x_max, x_max=x_max)
         setups["limits_rows"] = dict(u_min=lo, u_max=hi)
         setups["rows"] = dict(batch_params=rows, plant_params={k: v[::-1].copy() for k, v in rows.items()})
+    w_mpc = np.ascontiguousarray(w[:, 0, :2].transpose(1, 0, 2))      # (n_steps = 2, B, n): what sampled_mpc adds per step
     for setup, kw in setups.items():
         s = ilqr_amd.iLQR(sysm, None, X[:, :, 0], U, N=N, verbose=False, dtype=dtype, **kw)
         s.X, s.K = X, K
@@ -90,6 +106,42 @@ def dump_case(out, name, dtype, integrator, S):
                     record(out, f"{tag}/{setup}/search/{dist}/{mode}/beta{beta}",
                            s.sample_controls(S, 2, SEED, u_std, mode, temp, beta, dist, first_trajectory=1, first_round=3,
                                              samples=True, trajectories=True))
+            if "x_min" not in kw:             # (with state limits only under a penalty: below)
+                sm = ilqr_amd.iLQR(sysm, None, X[:, :, 0], U, N=N, verbose=False, dtype=dtype, plant=sysm, **kw)
+                dump_mpc(out, f"{tag}/{setup}", sm, X[:, :, 0], U, S, u_std, dist, w_mpc)
+    if builtin:
+        # the penalty: state limits the nominal violates, a weight per trajectory, every sample's penalty and violation
+        # (mpc_reset asks a state-limited solver for a multiplier mode; sampled_mpc reads no multipliers)
+        s = ilqr_amd.iLQR(sysm, None, X[:, :, 0], U, N=N, verbose=False, dtype=dtype, plant=sysm, mpc_multipliers="warm",
+                          **setups["limits_shared"])
+        s.set_sample_penalty(np.linspace(5.0, 50.0, B), 1e-3)
+        for mode, temp in (("best", None), ("softmin", 10.0)):
+            record(out, f"{tag}/penalty/search/{mode}",
+                   s.sample_controls(S, 2, SEED, u_std, mode, temp, 0.9, first_trajectory=1, first_round=3, samples=True,
+                                     trajectories=True))
+        dump_mpc(out, f"{tag}/penalty", s, X[:, :, 0], U, S, u_std, "gaussian", w_mpc, samples=True)
+    dump_unbatched(out, tag, sysm, dtype, integrator, S, X[0], U[0], K[0], x0[0], w[0], x0_std[0], w_std[0], u_std[0], builtin)
+
+
+def dump_unbatched(out, tag, sysm, dtype, integrator, S, X, U, K, x0, w, x0_std, w_std, u_std, builtin):
+    """all five calls on a solver built from x_0 of shape (n_x,): the records lose the batch axis"""
+    kw = {}
+    if builtin:
+        x_max = np.full(sysm.n_x, np.inf)
+        x_max[0] = 0.1
+        kw = dict(u_min=-0.2, u_max=0.15, x_min=-x_max, x_max=x_max, mpc_multipliers="warm")
+    s = ilqr_amd.iLQR(sysm, None, X[:, 0], U, N=N, verbose=False, dtype=dtype, plant=sysm, **kw)
+    s.X, s.K = X, K
+    tag = f"{tag}/unbatched"
+    record(out, f"{tag}/rollout", s.policy_rollout(S, x0, w, integrator=integrator, trajectories=True))
+    record(out, f"{tag}/monte_carlo", s.policy_monte_carlo(S, SEED, x0_std, w_std, integrator=integrator, violation_tol=1e-3,
+                                                           samples=True, trajectories=True, noise=True))
+    if builtin:
+        s.set_sample_penalty(20.0, 1e-3)
+    record(out, f"{tag}/search", s.sample_controls(S, 2, SEED, u_std, "softmin", 10.0, 0.9, first_round=3, samples=True,
+                                                   trajectories=True))
+    record(out, f"{tag}/search_apply", s.sample_controls(S, 2, SEED, u_std, "best", first_round=3, apply=True))
+    dump_mpc(out, tag, s, X[:, 0], U, S, u_std, "gaussian", w[0, :2], samples=True)
 
 
 def same(a, b):
