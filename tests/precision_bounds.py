@@ -21,6 +21,12 @@ BOUNDS = {
     "sweep_c5": 5e-13,         # LQ (16, 8) at N = 500, f64 MFMA sweep: measured 5.1e-15
     "sweep_mu": 3e-12,         # Levenberg mu > 0: measured 2.4e-14
     "sweep_tensors": 8e-11,    # RiccatiSweep on random caller-supplied expansions: measured 7.2e-13 (16, 8, 40)
+    # the same on expansions whose Q_uu is indefinite at a third of the steps (tests/indefinite_ref.py: LU fallbacks, closed
+    # forms), every kernel family, mu = 0 and 0.5: measured 9.7e-15 ((8, 4), k); (16, 8) 4.7e-15, tile kernels 9.1e-16
+    "sweep_tensors_lu": 1e-12,
+    # one sweep through the solver routes with a negative / indefinite R, every sweep crossing Q_uu = 0 once (|K| ~ 1e4):
+    # measured 3.6e-13 (dp, R = diag(-0.5, -0.5)); UA 4.8e-14, pendulum 1.1e-15, LQ 6.3e-15, the box sweep 3.0e-13
+    "sweep_lu": 4e-11,
     # one rollout: X, U and cost
     "rollout": 3e-13,          # measured 2.4e-15 (LQ (16, 8)); UA, every integrator, 5.6e-16
     # whole solves: K, X, U, cost (every route, c1 .. c5 shapes, control limits): measured 1.7e-13 (dp, box)

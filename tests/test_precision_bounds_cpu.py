@@ -87,6 +87,28 @@ def test_tensor_sweep_bound_separates(n, m, N):
     _separates("sweep_tensors", {"K": rel_err(K32, K64), "k": rel_err(k32, k64)})
 
 
+@pytest.mark.parametrize("n,m", [(4, 2), (8, 4), (16, 8)])
+def test_tensor_lu_bound_separates(n, m):
+    """The indefinite expansions of tests/test_indefinite_sweep_gpu.py (tests/indefinite_ref.py), rounded to fp32: the fp32
+    oracle's LU misses the fp64 bound on every member."""
+    from indefinite_ref import SWEEP_N, SWEEP_SHAPES, indefinite_expansion
+    c = SWEEP_SHAPES[(n, m)]
+    ex = indefinite_expansion(c["B"], SWEEP_N, n, m, c["seed"], F32)
+    for b in range(c["B"]):
+        one = [a[b] for a in ex]
+        k64, K64 = backward_tensors(*one)
+        k32, K32 = backward_tensors(*one, dtype=F32)
+        _separates("sweep_tensors_lu", {"K": rel_err(K32, K64), "k": rel_err(k32, k64)})
+
+
+@pytest.mark.parametrize("name", ["ua_neg", "dp_indef"])
+def test_sweep_lu_bound_separates(name):
+    """A sweep of a physical system with a negative / indefinite R (the solver-route cases of tests/indefinite_ref.py)."""
+    from indefinite_ref import physical_cases
+    for r in physical_cases()[name][4]:
+        _separates("sweep_lu", {"the better of K and k": r["f32_err_least"]})
+
+
 @pytest.mark.parametrize("integrator", ["rk4", "backward_euler", "euler", "midpoint"])
 def test_rollout_bound_separates(integrator):
     p = problems.ua_double_pendulum(N=100, integrator=integrator)
