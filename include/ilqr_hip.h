@@ -683,6 +683,66 @@ typedef struct ilqr_sample_penalty_report_desc {
 } ilqr_sample_penalty_report_desc;
 int ilqr_sample_penalty_report(ilqr_handle h, const ilqr_sample_penalty_report_desc* d);
 
+/* ---- elites and an adapted per-step standard deviation in the sampled search (CEM; build extension) -------------
+ * ilqr_sample_controls and ilqr_sampled_mpc draw every round with the caller's u_std[b][j] at every step and weigh every
+ * finite sample.  ilqr_set_sample_elites(n_elite = E >= 1) makes every round weigh only its E best samples and draw the
+ * next round with the spread of those elites, step by step: the cross-entropy method (uniform != 0) or elite-truncated
+ * MPPI (uniform == 0).  n_elite = 0 clears the state; the other arguments are then not read.  While it is set, every round
+ * r of the two entries is, for trajectory b:
+ *   1. draw     n_t[j] = Sd^r_t[j] * z_j(...) in place of u_std[b][j] * z_j(...).  The recurrence, the streams, sample 0 =
+ *               the nominal, the clamp, the rollout and the cost are those of ilqr_sample_controls, in the same
+ *               arithmetic (every product rounded on its own, never fused).  Sd^0_t[j] = std_steps[b][j][t] where
+ *               std_steps was given, else the call's u_std[b][j] at every t.  e_t has the variance of n_t only when
+ *               smoothing = 0 or Sd is constant along t
+ *   2. elites   behind the round's weights (finite mask, J_min, s*, the SOFTMIN weights and the round's row, all
+ *               unchanged): the n_e = min(E, n_finite) samples with the lowest (J_s, s) in lexicographic order among the
+ *               finite costs -- ties in J go to the lower s.  A non-elite gets w_s = 0; an elite keeps its SOFTMIN
+ *               weight, or gets w_s = 1 with uniform != 0 and always in BEST mode.  W = the sum of the elites' weights.
+ *               The round's third statistic becomes W^2 / sum_s w_s^2 over the elites in both modes (n_e where the
+ *               weights are 1).  s* is unchanged and always an elite
+ *   3. nominal  the update of ilqr_sample_controls on the truncated weights (SOFTMIN) or the copy of s* (BEST)
+ *   4. spread   v = (sum over the elites of w_s (u_{s,t}[j] - U^{r+1}_t[j])^2) / W, in double from the stored values, a
+ *               fixed order, no floating-point atomics;  Sd^{r+1}_t[j] = max((T) sqrt(v), std_min[b][j]).  With
+ *               n_finite == 0 Sd stays, as the nominal does
+ * With n_e == n_finite, uniform == 0 and SOFTMIN the weights, W and the statistics are left as they stand: the round's
+ * nominal and statistics equal those of the call without elites bit for bit.  Round 0 draws what it draws without elites
+ * (where std_steps is NULL).  The state-limit penalty composes: J is J + P in everything above.
+ * ilqr_sampled_mpc: round 0 of every step starts again from the call's u_std; std_steps is not read there, and the adapted
+ * Sd is neither shifted nor carried from one step to the next.  Everything else in a step is the search above.
+ * A call with first_round = k after ilqr_set(ILQR_U, U_new) and ilqr_set_sample_elites(..., std_steps = the report's
+ * std_steps) continues a k-round call bit for bit.
+ * std_min is [B][n_u] doubles, copied to the device in the handle's dtype; std_steps is [B][n_u][N] in the handle's dtype
+ * or NULL.  The state is read by ilqr_sample_controls and ilqr_sampled_mpc only; descriptors, modes and every other entry
+ * are unchanged.  Everything is checked before the handle or the device is touched.
+ * Returns ILQR_ERR_INVALID_ARG for a NULL handle, n_elite < 0, a NULL std_min with n_elite > 0, or a std_min / std_steps
+ * value that is negative or not finite in the handle's dtype; ILQR_ERR_UNSUPPORTED for ILQR_SYS_LINEAR and for every
+ * ILQR_SYS_CUSTOM handle (a plugin with the policy kernels included: the kernels of this entry are built for the
+ * built-in systems only).  A successful call invalidates the report below.
+ * ILQR_ABI_VERSION stays 5 with this entry, for the reasons given at ilqr_set_batch_limits: it is additive. */
+int ilqr_set_sample_elites(ilqr_handle h, int32_t n_elite, int32_t uniform,
+                           const double* std_min   /* [B][n_u] */,
+                           const void*   std_steps /* [B][n_u][N] handle dtype, or NULL */);
+
+/* What the last ilqr_sample_controls / ilqr_sampled_mpc with elites set left on the device, with S and R of that call
+ * and rounds = R (ilqr_sample_controls) or n_steps * R (ilqr_sampled_mpc, step-major as its round_stats):
+ *   std_steps            Sd after the last round (ilqr_sampled_mpc: after the last step's last round)
+ *   elite                the 0 / 1 mask of the last round's elites
+ *   round_n_elite[r][b]  n_e of every round
+ * The call is synchronous and changes nothing.
+ * Returns ILQR_ERR_INVALID_ARG for a NULL handle or desc, a wrong struct_size, reserved != 0 or every output NULL;
+ * ILQR_ERR_STATE unless the handle's most recent sampling call was an ilqr_sample_controls / ilqr_sampled_mpc with elites
+ * set that succeeded: an ilqr_policy_rollout / ilqr_policy_monte_carlo, a call without elites, or an
+ * ilqr_set_sample_elites after it invalidates the report.
+ * ILQR_ABI_VERSION stays 5 with this entry: it is additive, and no existing descriptor changes. */
+typedef struct ilqr_sample_elite_report_desc {
+    uint32_t struct_size;      /* = sizeof(ilqr_sample_elite_report_desc) */
+    int32_t reserved;          /* 0 */
+    void* std_steps;           /* [B][n_u][N] handle dtype; any output may be NULL, not all */
+    int32_t* elite;            /* [B][S] */
+    int32_t* round_n_elite;    /* [rounds][B] */
+} ilqr_sample_elite_report_desc;
+int ilqr_sample_elite_report(ilqr_handle h, const ilqr_sample_elite_report_desc* d);
+
 /* ---- multi-GPU hook -------------------------------------------
  * Writes 4 doubles to DEVICE memory `dev_out4` on the handle's stream:
  *   { min cost, max |cost - cost_prev|, #trajectories still active, #converged }

@@ -44,7 +44,8 @@ SYMBOLS = (
     "ilqr_mpc_rearm", "ilqr_mpc_run", "ilqr_status_reduce", "ilqr_timing_enable", "ilqr_timing_reset", "ilqr_timing_get", "ilqr_algorithmic_bytes",
     "ilqr_set_control_limits", "ilqr_set_batch_params", "ilqr_set_state_limits", "ilqr_set_mpc_multipliers",
     "ilqr_set_batch_limits", "ilqr_policy_rollout", "ilqr_policy_monte_carlo", "ilqr_sample_controls",
-    "ilqr_sampled_mpc", "ilqr_set_sample_penalty", "ilqr_sample_penalty_report",
+    "ilqr_sampled_mpc", "ilqr_set_sample_penalty", "ilqr_sample_penalty_report", "ilqr_set_sample_elites",
+    "ilqr_sample_elite_report",
 )
 # ilqr_set_batch_params: which rows
 BATCH_MODEL, BATCH_PLANT = 0, 1
@@ -143,6 +144,14 @@ class SamplePenaltyReportDesc(C.Structure):
     ]
 
 
+class SampleEliteReportDesc(C.Structure):
+    """ilqr_sample_elite_report_desc (include/ilqr_hip.h), field for field."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("reserved", C.c_int32),
+        ("std_steps", C.c_void_p), ("elite", C.POINTER(C.c_int32)), ("round_n_elite", C.POINTER(C.c_int32)),
+    ]
+
+
 class IlqrError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libilqr_hip error {code}: {msg}")
@@ -216,6 +225,8 @@ def load():
     lib.ilqr_sampled_mpc.argtypes = [vp, C.POINTER(SampledMpcDesc)]
     lib.ilqr_set_sample_penalty.argtypes = [vp, C.POINTER(cd), cd]
     lib.ilqr_sample_penalty_report.argtypes = [vp, C.POINTER(SamplePenaltyReportDesc)]
+    lib.ilqr_set_sample_elites.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(cd), vp]
+    lib.ilqr_sample_elite_report.argtypes = [vp, C.POINTER(SampleEliteReportDesc)]
     if lib.ilqr_abi_version() != ABI_VERSION:
         raise RuntimeError("libilqr_hip.so ABI version mismatch: rebuild the library")
     _lib = lib
@@ -652,6 +663,35 @@ class Handle:
             shapes.update(penalty_samples=(B, S), violation_samples=(B, S))
         out = self._outputs(d, shapes, dtypes={"round_penalty": np.float64, "round_violating": np.int32})
         self._chk(self.lib.ilqr_sample_penalty_report(self.h, C.byref(d)))
+        return out
+
+    def set_sample_elites(self, n_elite, uniform=True, std_min=None, std_steps=None):
+        """Elites and the adapted per-step standard deviation of sample_controls / sampled_mpc (include/ilqr_hip.h,
+        ilqr_set_sample_elites): n_elite >= 1, std_min (B, n_u) float64 >= 0, std_steps (B, n_u, N) or None; n_elite = 0
+        clears the state (the other arguments are then not read)."""
+        if int(n_elite) == 0:
+            self._chk(self.lib.ilqr_set_sample_elites(self.h, 0, 0, None, None))
+            return
+        lo = None if std_min is None else np.ascontiguousarray(std_min, dtype=np.float64)
+        if lo is not None and lo.shape != (self.B, self.n_u):
+            raise ValueError(f"std_min must have shape ({self.B}, {self.n_u}), but got {lo.shape}")
+        steps = None if std_steps is None else self._in(std_steps, (self.B, self.n_u, self.N))
+        self._chk(self.lib.ilqr_set_sample_elites(self.h, int(n_elite), int(bool(uniform)),
+                                                  None if lo is None else lo.ctypes.data_as(C.POINTER(C.c_double)), _ptr(steps)))
+
+    def sample_elite_report(self, n_samples, rounds, n_steps=None, samples=False):
+        """What the last sample_controls (n_steps=None) or sampled_mpc with elites set left on the device
+        (include/ilqr_hip.h, ilqr_sample_elite_report); n_samples, rounds and n_steps are that call's.  Returns a dict:
+        std_steps (B, n_u, N), round_n_elite (R, B) int32 -- (n_steps, R, B) for sampled_mpc --; elite (B, S) int32 (with
+        samples)."""
+        B, S, R = self.B, int(n_samples), int(rounds)
+        lead = () if n_steps is None else (int(n_steps),)
+        d, _ = self._desc(SampleEliteReportDesc)
+        shapes = dict(std_steps=(B, self.n_u, self.N), round_n_elite=lead + (R, B))
+        if samples:
+            shapes.update(elite=(B, S))
+        out = self._outputs(d, shapes, dtypes={"round_n_elite": np.int32, "elite": np.int32})
+        self._chk(self.lib.ilqr_sample_elite_report(self.h, C.byref(d)))
         return out
 
     # ---- measurement ------------------------------------------------------------------------------

@@ -95,6 +95,12 @@ template <typename T> struct SamplingOps {
     // round's report; null where the system takes no limits (takes_limits: a generated plugin has neither kernel)
     void (*rollout_pen)(const SampleArgs<T>&, const NoiseArgs<T>&, hipStream_t) = nullptr;
     void (*penalty_stats)(const SampleArgs<T>&, hipStream_t) = nullptr;
+    // elites and the adapted standard deviation (ilqr_set_sample_elites): Sd of round 0, the rollouts that draw with Sd
+    // ([1]: penalised), and the round's weights, elites, update of Ub and update of Sd; null where the system is none of
+    // the built-in three (box_system: a generated plugin has none of these kernels)
+    void (*std_fill)(const SampleArgs<T>&, hipStream_t) = nullptr;
+    void (*rollout_elite[2])(const SampleArgs<T>&, const NoiseArgs<T>&, hipStream_t) = {};
+    void (*update_elite)(const SampleArgs<T>&, hipStream_t) = nullptr;
     explicit operator bool() const { return rollout != nullptr; }
 };
 
@@ -308,8 +314,9 @@ template <typename T, typename Dyn> void launch_sample_begin(const SampleArgs<T>
     const size_t n = (size_t)a.B * a.N * Dyn::NU;
     ILQR_LAUNCH((sample_nominal_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.Ub, a.U, a.cur_slot, a.B, a.N, Dyn::NU);
 }
-template <typename T, typename Dyn, bool PEN = false> void launch_sample_rollout(const SampleArgs<T>& a, const NoiseArgs<T>& nz, hipStream_t s) {
-    ILQR_LAUNCH((sample_rollout_kernel<T, Dyn, PEN>), dim3((a.S + 63) / 64, a.B), dim3(64), 0, s, a, nz);
+template <typename T, typename Dyn, bool PEN = false, bool STEPSTD = false>
+void launch_sample_rollout(const SampleArgs<T>& a, const NoiseArgs<T>& nz, hipStream_t s) {
+    ILQR_LAUNCH((sample_rollout_kernel<T, Dyn, PEN, STEPSTD>), dim3((a.S + 63) / 64, a.B), dim3(64), 0, s, a, nz);
 }
 template <typename T> void launch_sample_penalty_stats(const SampleArgs<T>& a, hipStream_t s) {
     ILQR_LAUNCH((sample_penalty_stats_kernel<T>), dim3(a.B), dim3(64), 0, s, a);
@@ -323,6 +330,24 @@ template <typename T, typename Dyn> void launch_sample_update(const SampleArgs<T
     launch_events() = LaunchEvents{nullptr, le.b};
     if (a.mode == ILQR_SAMPLE_SOFTMIN) ILQR_LAUNCH((sample_softmin_kernel<T, Dyn::NU, takes_limits<Dyn>()>), dim3(a.N, a.B), dim3(64), 0, s, a);
     else ILQR_LAUNCH((sample_best_kernel<T>), dim3((rows + 63) / 64, a.B), dim3(64), 0, s, a, (int)Dyn::NU);
+}
+// elites (ilqr_set_sample_elites): Sd of round 0, and a round's four launches -- the weights and the update as above, the
+// elites between them and the update of Sd behind them
+template <typename T, typename Dyn> void launch_sample_std_fill(const SampleArgs<T>& a, hipStream_t s) {
+    const size_t n = (size_t)a.B * a.N * Dyn::NU;
+    ILQR_LAUNCH((sample_std_fill_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, (int)Dyn::NU);
+}
+template <typename T, typename Dyn> void launch_sample_update_elite(const SampleArgs<T>& a, hipStream_t s) {
+    const int rows = a.N * Dyn::NU;
+    // (the phase timer's event pair spans the four launches)
+    const LaunchEvents le = launch_events();
+    launch_events() = LaunchEvents{le.a, nullptr};
+    ILQR_LAUNCH((sample_weights_kernel<T>), dim3(a.B), dim3(64), 0, s, a);
+    ILQR_LAUNCH((sample_elite_kernel<T>), dim3(a.B), dim3(64), 0, s, a);
+    if (a.mode == ILQR_SAMPLE_SOFTMIN) ILQR_LAUNCH((sample_softmin_kernel<T, Dyn::NU, takes_limits<Dyn>()>), dim3(a.N, a.B), dim3(64), 0, s, a);
+    else ILQR_LAUNCH((sample_best_kernel<T>), dim3((rows + 63) / 64, a.B), dim3(64), 0, s, a, (int)Dyn::NU);
+    launch_events() = LaunchEvents{nullptr, le.b};
+    ILQR_LAUNCH((sample_elite_std_kernel<T, Dyn::NU>), dim3(a.N, a.B), dim3(64), 0, s, a);
 }
 
 // sampled MPC (sampled_mpc.hpp): the workgroup shape of mpc_advance_kernel; HET where the plant has rows of its own
@@ -457,6 +482,12 @@ template <typename T, typename Dyn> Ops<T> make_ops() {
         if constexpr (takes_limits<Dyn>()) {
             o.sampling.rollout_pen = launch_sample_rollout<T, Dyn, true>;
             o.sampling.penalty_stats = launch_sample_penalty_stats<T>;
+        }
+        if constexpr (box_system<Dyn>()) {
+            o.sampling.std_fill = launch_sample_std_fill<T, Dyn>;
+            o.sampling.rollout_elite[0] = launch_sample_rollout<T, Dyn, false, true>;
+            o.sampling.rollout_elite[1] = launch_sample_rollout<T, Dyn, true, true>;
+            o.sampling.update_elite = launch_sample_update_elite<T, Dyn>;
         }
     }
     o.eval = [](const EvalArgs<T>& a, hipStream_t s) {

@@ -15,6 +15,9 @@
 // While a state-limit penalty is set (ilqr_set_sample_penalty) the rollout is its PEN instantiation -- J_s + P_s in place
 // of J_s, P_s and the violation stored beside it -- and a fourth launch per round reduces the penalty's report; the
 // weights and the update are the same kernels and read the cost as they always did.
+// While elites are set (ilqr_set_sample_elites) the rollout is its STEPSTD instantiation -- it draws step t with Sd_t in
+// place of u_std -- and two launches stand around the update: sample_elite_kernel truncates the weights to the n_e best
+// samples behind the weights, sample_elite_std_kernel sets Sd to their spread around the new nominal behind the update.
 #pragma once
 #include "policy_rollout.hpp"
 
@@ -55,6 +58,14 @@ template <typename T> struct SampleArgs {
     double pen_tol;                     // violation_tol
     double* __restrict__ pen_stats;     // [B][3] of this round: P of sample 0, P and v of s* (NaN with no finite sample)
     int* __restrict__ pen_counts;       // [B] of this round: the finite samples with v > pen_tol
+    // elites and the adapted per-step standard deviation (ilqr_set_sample_elites): read by the STEPSTD instantiation of
+    // the rollout, sample_std_fill_kernel, sample_elite_kernel and sample_elite_std_kernel only; all null / 0 while unset
+    T* __restrict__ Sd;                 // [N][n_u][B] the standard deviation of the round's draws, the layout of Ub
+    const T* __restrict__ std_min;      // [B][n_u] the floor of Sd
+    const T* __restrict__ std_up;       // [B][n_u][N] Sd of round 0 as the caller gave it, or nullptr: u_std at every t
+    int n_elite, elite_uniform;         // E >= 1; != 0: every elite weighs 1 (always so in BEST mode)
+    int* __restrict__ elite;            // [L] the 0 / 1 mask of the round's elites
+    int* __restrict__ n_e;              // [B] of this round: min(E, n_finite)
 };
 
 // The state-limit penalty of a sample (PEN; the empty form costs nothing):
@@ -104,7 +115,9 @@ __global__ void sample_nominal_kernel(T* __restrict__ Ub, const T* __restrict__ 
 
 // The perturbation law: e_0 = n_0, e_t = beta e_{t-1} + c n_t, u_t = Ub_t + e_t through the model itself; sample 0 is the
 // nominal (e = 0: its draw is made and dropped).  PEN: the state-limit penalty of x_1 .. x_N enters the cost.
-template <typename T, typename Dyn, bool PEN = false> struct PerturbLaw {
+// STEPSTD: n_t = Sd_t (.) z in place of u_std[b] (.) z; Sd_t is wave-uniform as Ub_t is, and Sd_{t+1} is requested beside
+// Ub_{t+1}.
+template <typename T, typename Dyn, bool PEN = false, bool STEPSTD = false> struct PerturbLaw {
     static constexpr int NX = Dyn::NX, NU = Dyn::NU;
     static_assert(!PEN || takes_limits<Dyn>(), "only a system that takes state limits has the penalised rollout");
     static_assert(NU <= 8, "component j of a control takes z_{j mod 4} of the generator call of group j / 4 (noise_draw)");
@@ -113,20 +126,26 @@ template <typename T, typename Dyn, bool PEN = false> struct PerturbLaw {
     const SampleAt k;
     T* const pp;                                  // the model's own constants
     T sd[NU], e[NU], n[NU], ub[NU], ub_n[NU];     // u_std[b], Ub_t and Ub_{t+1}: wave-uniform
+    T sd_n[STEPSTD ? NU : 1];                     // STEPSTD: sd is Sd_t, and this Sd_{t+1}
     SamplePenalty<T, NX, PEN> pen;
 
     ILQR_DEV PerturbLaw(const SampleArgs<T>& a_, const NoiseArgs<T>& nz_, const SampleAt& k_, T* mr, T (&)[NX])
         : a(a_), nz(nz_), k(k_), pp(mr), pen(a_, k_) {
-        uniform_load<T, NU>(a.u_std + (size_t)k.b * NU, sd);
+        if constexpr (!STEPSTD) uniform_load<T, NU>(a.u_std + (size_t)k.b * NU, sd);
 #pragma unroll
         for (int j = 0; j < NU; ++j) {
             e[j] = T(0);
             ub[j] = as_uniform(a.Ub)[(size_t)j * k.B + k.b];
+            if constexpr (STEPSTD) sd[j] = as_uniform((const T*)a.Sd)[(size_t)j * k.B + k.b];
         }
     }
     ILQR_DEV void control(int t, int tn, const T (&)[NX], T (&u)[NU]) {
 #pragma unroll
         for (int j = 0; j < NU; ++j) ub_n[j] = as_uniform(a.Ub)[((size_t)tn * NU + j) * k.B + k.b];
+        if constexpr (STEPSTD) {
+#pragma unroll
+            for (int j = 0; j < NU; ++j) sd_n[j] = as_uniform((const T*)a.Sd)[((size_t)tn * NU + j) * k.B + k.b];
+        }
         noise_draw<T, NU>(nz, (unsigned)k.s, (unsigned)k.b, (unsigned)t, a.stream, sd, n);
 #pragma unroll
         for (int j = 0; j < NU; ++j) {
@@ -142,6 +161,10 @@ template <typename T, typename Dyn, bool PEN = false> struct PerturbLaw {
         for (int i = 0; i < NX; ++i) x[i] = xn[i];
 #pragma unroll
         for (int j = 0; j < NU; ++j) ub[j] = ub_n[j];
+        if constexpr (STEPSTD) {
+#pragma unroll
+            for (int j = 0; j < NU; ++j) sd[j] = sd_n[j];
+        }
         pen.add(x);      // the constraints of x_{t+1} (t + 1 = 1..N)
     }
     ILQR_DEV T total(T cost) const { return pen.total(cost); }
@@ -151,9 +174,10 @@ template <typename T, typename Dyn, bool PEN = false> struct PerturbLaw {
 // The rollout of a round's samples.  Launched with S = 1 it is the rollout of the nominal alone (cost_new / X_new): the
 // same code on the same controls, so the cost of a BEST call's result is the winning sample's cost bit for bit.
 // PEN (ilqr_set_sample_penalty): cost[l] = J + P, and pen[l] = P, viol[l] = v beside it.
-template <typename T, typename Dyn, bool PEN = false>
+// STEPSTD (ilqr_set_sample_elites): the draws of step t scale with Sd_t.
+template <typename T, typename Dyn, bool PEN = false, bool STEPSTD = false>
 __global__ void __launch_bounds__(64) sample_rollout_kernel(SampleArgs<T> a, NoiseArgs<T> nz) {
-    sampled_rollout<T, Dyn, PerturbLaw<T, Dyn, PEN>>(a, nz);
+    sampled_rollout<T, Dyn, PerturbLaw<T, Dyn, PEN, STEPSTD>>(a, nz);
 }
 
 // The weights of a round: one wave per trajectory over its contiguous [S] costs, each lane over its stride of the row and
@@ -271,6 +295,144 @@ __global__ void __launch_bounds__(64) sample_softmin_kernel(SampleArgs<T> a) {
             v = clamp_keep_nan(v, blo[j], bhi[j]);
         }
         if (lane == 0) a.Ub[row * B + b] = v;
+    }
+}
+
+// ---- elites and the adapted standard deviation (include/ilqr_hip.h, ilqr_set_sample_elites) --------------------------
+// Sd_t[j] of round 0: u_std[b][j] at every t, or the caller's std_steps [B][n_u][N] in Sd's layout [N][n_u][B]
+template <typename T>
+__global__ void sample_std_fill_kernel(SampleArgs<T> a, int NU) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (size_t)a.B * a.N * NU) return;
+    const int b = (int)(idx % a.B);
+    const int row = (int)(idx / a.B), t = row / NU, j = row % NU;
+    a.Sd[idx] = a.std_up ? a.std_up[((size_t)b * NU + j) * a.N + t] : a.u_std[(size_t)b * NU + j];
+}
+
+// The image of a cost in the unsigned integers of its width whose order is the order of the finite costs (the image of T
+// orders as the image of the cost widened to double does: the widening is monotone).  -0 is taken as +0 first.
+ILQR_DEV unsigned cost_key(float c) {
+    const unsigned u = __float_as_uint(c + 0.0f);
+    return (u >> 31) ? ~u : u | 0x80000000u;
+}
+ILQR_DEV unsigned long long cost_key(double c) {
+    const unsigned long long u = (unsigned long long)__double_as_longlong(c + 0.0);
+    return (u >> 63) ? ~u : u | 0x8000000000000000ull;
+}
+
+// The elites of a round, launched behind sample_weights_kernel: one wave per trajectory over its contiguous [S] costs.
+// n_e = min(E, n_finite) samples with the lowest (J_s, s) among the finite costs are found by a radix select on
+// cost_key, most significant digit first, four bits a pass: every lane counts its stride of the row into sixteen integer
+// LDS counters (integer atomics: the counts do not depend on their order), every lane reads the sixteen and walks them
+// to the digit that holds the n_e-th key, and the search goes on inside that digit.  It stops early once all keys left
+// under the prefix are elites.  What remains equal to the prefix is taken in s order: 64 samples at a time, s ascending,
+// a ballot and the count of the lanes below.  The last pass writes the mask, w_s (0 for a non-elite; 1 for an elite with
+// `elite_uniform` or in BEST mode, else its SOFTMIN weight as it stands) and sums W and sum w^2 as sample_weights_kernel
+// does: lane strides, then the butterfly, in double.  With n_e == n_finite and SOFTMIN weights kept nothing changes, and
+// w, W and the statistics stay untouched: such a round equals the round without elites bit for bit.
+template <typename T>
+__global__ void __launch_bounds__(64) sample_elite_kernel(SampleArgs<T> a) {
+    using Key = decltype(cost_key(T(0)));
+    constexpr int KB = 8 * (int)sizeof(Key);
+    __shared__ unsigned cnt[16];
+    const int b = blockIdx.x, lane = threadIdx.x, S = a.S;
+    const T* c = a.cost + (size_t)b * S;
+    int* mask = a.elite + (size_t)b * S;
+    const int n_fin = a.counts[b];
+    const int n_e = a.n_elite < n_fin ? a.n_elite : n_fin;
+    const bool unit = a.elite_uniform != 0 || a.mode != ILQR_SAMPLE_SOFTMIN;
+    const bool all = n_e == n_fin;
+    if (lane == 0) a.n_e[b] = n_e;
+    if (all && !unit) {
+        for (int s = lane; s < S; s += 64) {
+            const double ci = (double)c[s];
+            mask[s] = (ci - ci == 0.0) ? 1 : 0;
+        }
+        return;
+    }
+    Key prefix = 0;
+    int k_rem = n_e, sh = KB;
+    while (!all && sh > 0) {
+        const bool first = sh == KB;
+        sh -= 4;
+        if (lane < 16) cnt[lane] = 0u;
+        __syncthreads();
+        for (int s = lane; s < S; s += 64) {
+            const T cs = c[s];
+            const double ci = (double)cs;
+            if (!(ci - ci == 0.0)) continue;
+            const Key key = cost_key(cs);
+            if (first || (key >> (first ? 0 : sh + 4)) == prefix) atomicAdd(&cnt[(unsigned)(key >> sh) & 15u], 1u);
+        }
+        __syncthreads();
+        unsigned cum = 0, dsel = 0, csel = 0, below = 0;
+        bool found = false;
+#pragma unroll
+        for (unsigned d = 0; d < 16; ++d) {
+            const unsigned cd = cnt[d];
+            if (!found && cum + cd >= (unsigned)k_rem) { found = true; dsel = d; csel = cd; below = cum; }
+            cum += cd;
+        }
+        __syncthreads();      // (every lane has read the counters before they are cleared again)
+        prefix = (Key)(prefix << 4) | (Key)dsel;
+        k_rem -= (int)below;
+        if (k_rem == (int)csel) break;      // every key left under the prefix is an elite's
+    }
+    double* w = a.w + (size_t)b * S;
+    double W = 0, W2 = 0;
+    int taken = 0;
+    for (int base = 0; base < S; base += 64) {
+        const int s = base + lane;
+        const bool valid = s < S;
+        const T cs = valid ? c[s] : T(0);
+        const double ci = (double)cs;
+        const bool fin = valid && (ci - ci == 0.0);
+        const Key hi = all ? (Key)0 : (Key)(cost_key(cs) >> sh);
+        const bool tie = fin && !all && hi == prefix;
+        const unsigned long long votes = __ballot(tie);
+        const int rank = taken + __popcll(votes & ((1ull << lane) - 1ull));
+        taken += __popcll(votes);
+        const bool el = fin && (all || hi < prefix || (tie && rank < k_rem));
+        if (valid) {
+            const double wi = !el ? 0.0 : unit ? 1.0 : w[s];
+            mask[s] = el ? 1 : 0;
+            w[s] = wi;
+            W += wi;
+            W2 += wi * wi;
+        }
+    }
+    W = wave_sum(W);
+    W2 = wave_sum(W2);
+    if (lane != 0 || n_e == 0) return;      // (no finite sample: W = 0 and the statistics are already so)
+    a.wsum[b] = W;
+    a.stats[(size_t)b * 3 + 2] = W * W / W2;
+}
+
+// Sd_t[j] <- max((T) sqrt(v), std_min[b][j]), v = (sum over the elites w_s (u_{s,t}[j] - Ub_t[j])^2) / W around the nominal
+// the update has just written, launched behind it: sample_softmin_kernel's mapping and order (one wave per step t of a
+// trajectory, for each j over the contiguous [S] row, each lane over its stride and then a butterfly, no atomics), in
+// double from the stored values.  No finite sample: Sd stays, as Ub does.
+template <typename T, int NU>
+__global__ void __launch_bounds__(64) sample_elite_std_kernel(SampleArgs<T> a) {
+    const int b = blockIdx.y, t = blockIdx.x, lane = threadIdx.x, S = a.S;
+    const size_t B = a.B, L = B * (size_t)S;
+    const double W = a.wsum[b];
+    if (!(W > 0.0)) return;
+    const double* w = a.w + (size_t)b * S;
+#pragma unroll
+    for (int j = 0; j < NU; ++j) {
+        const size_t row = (size_t)t * NU + j;
+        const T* u = a.Us + row * L + (size_t)b * S;
+        const double m = (double)a.Ub[row * B + b];
+        double acc = 0;
+        for (int s = lane; s < S; s += 64) {
+            const double wi = w[s];
+            const double d = (double)u[s] - m;
+            if (wi > 0.0) acc += wi * (d * d);
+        }
+        acc = wave_sum(acc);
+        const T sd = (T)sqrt(acc / W), lo = a.std_min[(size_t)b * NU + j];
+        if (lane == 0) a.Sd[row * B + b] = sd < lo ? lo : sd;
     }
 }
 

@@ -67,6 +67,8 @@ struct SolverBase {
     virtual int sampled_mpc(const ilqr_sampled_mpc_desc& d) = 0;
     virtual int set_sample_penalty(const double* weight, double violation_tol) = 0;
     virtual int sample_penalty_report(const ilqr_sample_penalty_report_desc& d) = 0;
+    virtual int set_sample_elites(int n_elite, int uniform, const double* std_min, const void* std_steps) = 0;
+    virtual int sample_elite_report(const ilqr_sample_elite_report_desc& d) = 0;
 };
 
 int system_dims(int system, int n_x, int n_u);  // 1 if (system, n_x, n_u) is a known combination
@@ -266,6 +268,22 @@ template <typename T> struct PenaltyState {
     bool plan_rollout = false;    // pen / viol behind the samples hold every step's plan (else: the last round's s*)
 };
 
+// The elites of the sampled search (ilqr_set_sample_elites) and what its last call left for ilqr_sample_elite_report.
+// Sd, mask and n_e grow with the calls; std_min and std_steps are the setter's.
+template <typename T> struct EliteState {
+    bool on = false;
+    int n_elite = 0, uniform = 0;
+    DevBuf<T> std_min;            // [B][n_u] in the handle's dtype
+    DevBuf<T> std_steps;          // [B][n_u][N] as the caller gave it; read while has_steps
+    bool has_steps = false;
+    DevBuf<T> Sd;                 // [N][n_u][B] the standard deviation of the round's draws
+    DevBuf<int> mask;             // [L] of the last round
+    DevBuf<int> n_e;              // [rounds][B]
+    // the report: valid while the handle's most recent sampling call was a search with elites that succeeded
+    bool report = false;
+    size_t L = 0, rounds = 0;
+};
+
 // per-trajectory parameters (ilqr_set_batch_params): rows [n_sys + n_x][B] of the model (derived constants, x_target),
 // plant_rows [n_sys][B] of the MPC plant; device tensors of the handle's dtype
 template <typename T> struct BatchParams {
@@ -348,6 +366,7 @@ template <typename T> class SolverT : public SolverBase {
     StateLimits<T> al;
     SamplingBufs<T> smp;
     PenaltyState<T> pen;
+    EliteState<T> el;
 
     // (the device buffers free themselves after this body: DevBuf)
     ~SolverT() override {
@@ -1329,6 +1348,7 @@ template <typename T> class SolverT : public SolverBase {
             if (!std::isfinite(d.plant_rows[i])) return fail(ILQR_ERR_INVALID_ARG, who + ": every plant_rows value must be finite");
         if ((rc = sampling_settle())) return rc;
         pen.report = false;          // (the most recent sampling call is no penalised search)
+        el.report = false;
         const size_t nX = L * NX * (size_t)(N + 1), nU = L * NU * (size_t)N, nW = L * NX * (size_t)N;
         // the disturbances a Monte Carlo call was asked to return (none are drawn without w_std: those are zeros)
         const bool w_back = mc && mc->w_out && mc->w_std;
@@ -1431,14 +1451,23 @@ template <typename T> class SolverT : public SolverBase {
         a.cost = smp.summaries; a.Us = smp.controls.p;
         a.w = smp.weights.p; a.wsum = smp.weights.p + L; a.sel = smp.winners.p;
         if (pen.on) { a.pen_rho = pen.rho.p; a.pen = pen.pen.p; a.viol = pen.viol.p; a.pen_tol = pen.tol; }
+        if (el.on) {
+            a.Sd = el.Sd.p; a.std_min = el.std_min.p; a.std_up = el.has_steps ? el.std_steps.p : nullptr;
+            a.n_elite = el.n_elite; a.elite_uniform = el.uniform; a.elite = el.mask.p;
+        }
         return a;
     }
     // The penalty's buffers for a search of `rounds` rounds and `steps` rollouts of the nominal alone, and the report's
     // shapes; the report itself becomes valid when the call has succeeded (search_done).
     int search_begin(size_t L, size_t rounds, size_t per_step, size_t steps) {
         pen.report = false;
-        if (!pen.on) return ILQR_OK;
+        el.report = false;
         int rc;
+        if (el.on) {
+            if ((rc = grow(el.Sd, (size_t)B * NU * N)) || (rc = grow(el.mask, L)) || (rc = grow(el.n_e, rounds * B))) return rc;
+            el.L = L; el.rounds = rounds;
+        }
+        if (!pen.on) return ILQR_OK;
         if ((rc = grow(pen.pen, L + steps * B)) || (rc = grow(pen.viol, L + steps * B)) ||
             (rc = grow(pen.stats, rounds * B * 3)) || (rc = grow(pen.counts, rounds * B)))
             return rc;
@@ -1449,20 +1478,29 @@ template <typename T> class SolverT : public SolverBase {
         ILQR_HIPCHK(hipStreamSynchronize(stream));
         const int rc = check_launch();
         if (rc == ILQR_OK && pen.on) { pen.report = true; pen.plan_rollout = plan_rollout; }
+        if (rc == ILQR_OK && el.on) el.report = true;
         return rc;
     }
+    // Sd of round 0 (elites: SampleArgs::Sd), at the head of a search
+    int search_std_fill(const SampleArgs<T>& a) {
+        return a.Sd ? timed(ILQR_PHASE_OTHER, [&] { ops.sampling.std_fill(a, stream); }) : ILQR_OK;
+    }
     // One round: the rollout of the samples (penalised while a penalty is set: SampleArgs::pen), the weights and the
-    // update, and behind them the penalty's share of the round's report.  `a` brings the round's stream and rows.
+    // update, and behind them the penalty's share of the round's report.  With elites (SampleArgs::Sd) the rollout draws
+    // with Sd, and the elites and the update of Sd stand around the update.  `a` brings the round's stream and rows.
     int search_round(SampleArgs<T>& a, const NoiseArgs<T>& nz, size_t row) {
         int rc;
         if (a.pen) { a.pen_stats = pen.stats.p + row * B * 3; a.pen_counts = pen.counts.p + row * B; }
+        if (a.Sd) a.n_e = el.n_e.p + row * B;
         if ((rc = search_rollout(a, nz))) return rc;
-        if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.update(a, stream); }))) return rc;
+        if ((rc = timed(ILQR_PHASE_OTHER, [&] { (a.Sd ? ops.sampling.update_elite : ops.sampling.update)(a, stream); }))) return rc;
         if (a.pen && (rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.penalty_stats(a, stream); }))) return rc;
         return ILQR_OK;
     }
     int search_rollout(const SampleArgs<T>& a, const NoiseArgs<T>& nz) {
-        return timed(ILQR_PHASE_OTHER, [&] { (a.pen ? ops.sampling.rollout_pen : ops.sampling.rollout)(a, nz, stream); });
+        return timed(ILQR_PHASE_OTHER, [&] {
+            (a.Sd ? ops.sampling.rollout_elite[a.pen != nullptr] : a.pen ? ops.sampling.rollout_pen : ops.sampling.rollout)(a, nz, stream);
+        });
     }
     // the rollout of the nominal alone (S = 1: sample 0 is the nominal): its cost behind the samples', and while a
     // penalty is set its P and v behind the samples' too, in row `step` of [steps][B]
@@ -1499,7 +1537,7 @@ template <typename T> class SolverT : public SolverBase {
         if ((rc = up_std({d.u_std}, NU)) || (rc = search_begin(L, Rn, Rn, 1))) return rc;
         SampleArgs<T> a = search_args(d, L);
         const NoiseArgs<T> nz = noise_args(d.seed, d.first_trajectory, d.distribution);
-        if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.begin(a, stream); }))) return rc;
+        if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.begin(a, stream); })) || (rc = search_std_fill(a))) return rc;
         for (size_t r = 0; r < Rn; ++r) {
             a.stream = 2u + (unsigned)d.first_round + (unsigned)r;
             a.stats = smp.stats.p + r * B * 3;
@@ -1559,6 +1597,7 @@ template <typename T> class SolverT : public SolverBase {
         // (w arrives in the layout the epilogue reads; the caller's buffer outlives the copy: the call ends synchronised)
         if (d.w) ILQR_HIPCHK(hipMemcpyAsync(smp.w_steps.p, d.w, K * B * NX * sizeof(T), hipMemcpyHostToDevice, stream));
         SampleArgs<T> a = search_args(d, L);
+        a.std_up = nullptr;          // (every step's round 0 draws with u_std: std_steps is sample_controls')
         const NoiseArgs<T> nz = noise_args(d.seed, d.first_trajectory, d.distribution);
         // the nominal alone, for the cost of a SOFTMIN step's plan: the rollout at S = 1, its cost behind the samples'
         const bool plan_cost = d.cost_out && d.mode == ILQR_SAMPLE_SOFTMIN;
@@ -1572,6 +1611,7 @@ template <typename T> class SolverT : public SolverBase {
         m.cost_log = d.cost_out ? mpc_cost_log.p : nullptr; m.plan_log = d.U_plan ? smp.plans.p : nullptr;
         if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.begin(a, stream); }))) return rc;
         for (size_t k = 0; k < K; ++k) {
+            if ((rc = search_std_fill(a))) return rc;
             for (size_t r = 0; r < Rn; ++r) {
                 const size_t row = k * Rn + r;
                 a.stream = 2u + (unsigned)d.first_round + (unsigned)row;
@@ -1666,6 +1706,57 @@ template <typename T> class SolverT : public SolverBase {
             }
         }
         return ILQR_OK;
+    }
+
+    // ---- elites and the adapted standard deviation of the search (include/ilqr_hip.h, ilqr_set_sample_elites) ----------
+    // Everything is checked before the handle or the device is touched.  std_min crosses in the handle's dtype; std_steps
+    // is in it already and is kept as given ([B][n_u][N]: sample_std_fill_kernel converts the layout).
+    int set_sample_elites(int n_elite, int uniform, const double* std_min, const void* std_steps) override {
+        const std::string who = "set_sample_elites";
+        auto bad = [&](const char* what) { return fail(ILQR_ERR_INVALID_ARG, who + ": " + what); };
+        if (!ops.sampling.update_elite)
+            return fail(ILQR_ERR_UNSUPPORTED, who + ": supported for the pendulum, UA double pendulum and double pendulum only");
+        if (n_elite < 0) return bad("n_elite must be >= 0");
+        if (n_elite == 0) {
+            el.on = el.report = el.has_steps = false;
+            return ILQR_OK;
+        }
+        if (!std_min) return bad("std_min is NULL");
+        const size_t n = (size_t)B * NU;
+        std::vector<T> lo(n);
+        for (size_t i = 0; i < n; ++i) {
+            // (finite as the device holds it: a double beyond the handle's dtype would arrive there as +inf)
+            if (!std::isfinite(std_min[i]) || std_min[i] < 0.0 || std_min[i] > (double)std::numeric_limits<T>::max())
+                return bad("every std_min value must be finite in the handle's dtype and >= 0");
+            lo[i] = (T)std_min[i];
+        }
+        const T* steps = (const T*)std_steps;
+        for (size_t i = 0; steps && i < n * N; ++i)
+            if (!std::isfinite(steps[i]) || steps[i] < T(0)) return bad("every std_steps value must be finite and >= 0");
+        int rc;
+        if ((rc = grow(el.std_min, n)) || (steps && (rc = grow(el.std_steps, n * N)))) return rc;
+        ILQR_HIPCHK(hipMemcpyAsync(el.std_min.p, lo.data(), n * sizeof(T), hipMemcpyHostToDevice, stream));
+        if (steps) ILQR_HIPCHK(hipMemcpyAsync(el.std_steps.p, steps, n * N * sizeof(T), hipMemcpyHostToDevice, stream));
+        ILQR_HIPCHK(hipStreamSynchronize(stream));      // (lo and the caller's std_steps outlive the copies)
+        el.on = true;
+        el.n_elite = n_elite;
+        el.uniform = uniform != 0;
+        el.has_steps = steps != nullptr;
+        el.report = false;
+        return ILQR_OK;
+    }
+    // Downloads of what the last search with elites left in `el`; only the layout conversion of Sd is launched.
+    int sample_elite_report(const ilqr_sample_elite_report_desc& d) override {
+        const std::string who = "sample_elite_report";
+        if (!d.std_steps && !d.elite && !d.round_n_elite) return fail(ILQR_ERR_INVALID_ARG, who + ": every output is NULL");
+        if (!el.report)
+            return fail(ILQR_ERR_STATE, who + ": the handle's most recent sampling call was not a sample_controls / sampled_mpc with elites set");
+        int rc;
+        if (d.elite) ILQR_HIPCHK(hipMemcpyAsync(d.elite, el.mask.p, el.L * sizeof(int), hipMemcpyDeviceToHost, stream));
+        if (d.round_n_elite) ILQR_HIPCHK(hipMemcpyAsync(d.round_n_elite, el.n_e.p, el.rounds * B * sizeof(int), hipMemcpyDeviceToHost, stream));
+        if (d.std_steps && ((rc = grow(staging, (size_t)B * NU * N)) || (rc = down_traj(d.std_steps, el.Sd, (size_t)B, NU, N)))) return rc;
+        ILQR_HIPCHK(hipStreamSynchronize(stream));
+        return check_launch();
     }
 
     // ---- pure functional calls --------------------------------------------------------

@@ -21,9 +21,10 @@ import numpy as np
 from . import _lib
 # (the names of the two modules beside this file stay importable from here)
 from .setter_args import _bounds, batch_param_rows, control_limits, mpc_multiplier_mode, state_limits  # noqa: F401
-from .sampling import (PENALTY_FIELDS, PolicyMonteCarlo, PolicyRollout, SampledControls, SampledMPC,  # noqa: F401
+from .sampling import (ELITE_FIELDS, PENALTY_FIELDS, PolicyMonteCarlo, PolicyRollout, SampledControls, SampledMPC,  # noqa: F401
                        _with_penalty_fields, has_policy_kernels, policy_monte_carlo_args, policy_rollout_args,
-                       sample_controls_args, sample_penalty_args, sampled_mpc_args, table_columns, unbatch)
+                       sample_controls_args, sample_elites_args, sample_penalty_args, sampled_mpc_args, table_columns,
+                       unbatch)
 from .systems.system_base import System, ready
 
 STATUS_NAMES = {_lib.TRAJ_ACTIVE: "active", _lib.TRAJ_CONVERGED: "converged",
@@ -113,6 +114,7 @@ class iLQR:
         self.batch_params, self.plant_params = model_rows, plant_rows
         self._h.set_problem(x_0.reshape(self.B, self.n_x), U_init.reshape(self.B, self.n_u, self.N))
         self.sample_penalty = None
+        self.sample_elites = None
         self.status = None
         self.iterations = None
 
@@ -384,6 +386,30 @@ class iLQR:
             rec.update(penalty_samples=self._out(rep["penalty_samples"]), violation_samples=self._out(rep["violation_samples"]))
         return rec
 
+    # ---- elites and the adapted standard deviation of the sampled search -----------------------------
+    def set_sample_elites(self, n_elite, std_min=0.0, uniform=True, std_steps=None):
+        """Weigh only the n_elite best samples of every round of sample_controls and sampled_mpc and draw the next round
+        with their spread, step by step (include/ilqr_hip.h, ilqr_set_sample_elites): the cross-entropy method with
+        uniform=True (every elite weighs 1), elite-truncated MPPI with uniform=False in "softmin" mode (an elite keeps its
+        softmin weight).  After a round the standard deviation of control j at step t becomes the elites' weighted root
+        mean square deviation from the new nominal, not below std_min (a scalar, (n_u,) or (B, n_u)).  Round 0 draws with
+        the call's u_std, or in sample_controls with std_steps ([B,] n_u, N) where given -- the u_std_steps of an earlier
+        call continue it.  None or 0 clears the state.  Only the two sampling calls read it."""
+        a = sample_elites_args(self.system, self.N, self.B, self.batched, n_elite, std_min, uniform, std_steps, self.dtype)
+        self._h.set_sample_elites(**a._asdict())
+        self.sample_elites = None if a.n_elite == 0 else (a.n_elite, a.uniform)
+
+    def _elite_record(self, S, R, n_steps, samples):
+        """The elites' attributes of a SampledControls / SampledMPC, {} while no elites are set."""
+        if self.sample_elites is None:
+            return {}
+        rep = self._h.sample_elite_report(S, R, n_steps, samples)
+        rec = dict(u_std_steps=self._out(rep["std_steps"]),
+                   round_n_elite=unbatch(rep["round_n_elite"], self.batched, wrap=True))
+        if samples:
+            rec.update(elite_samples=unbatch(rep["elite"].astype(bool), self.batched, axis=0))
+        return rec
+
     # ---- sampled control search ---------------------------------------------------------------------
     def sample_controls(self, n_samples, rounds=1, seed=0, u_std=None, mode="best", temperature=None, smoothing=0.0,
                         distribution="gaussian", first_trajectory=0, first_round=0, samples=False, trajectories=False,
@@ -402,12 +428,15 @@ class iLQR:
         set_sample_penalty: every cost here and in the record is then J + P (P the penalty of the violated limits), the
         record carries penalty, violation, round_penalty_start, round_penalty_best, round_violation_best and
         round_n_violating (penalty_samples, violation_samples with samples=True), and apply=True compares the penalised
-        costs: no trajectory is made worse in the penalised sense."""
+        costs: no trajectory is made worse in the penalised sense.  After set_sample_elites every round weighs its best
+        samples only and the next one draws with their spread: the record then carries u_std_steps and round_n_elite
+        (elite_samples with samples=True)."""
         a = sample_controls_args(self.system, self.N, self.B, self.batched, n_samples, rounds, seed, u_std, mode, temperature,
                                  smoothing, distribution, first_trajectory, first_round)
         U_start = self._h.get(_lib.U) if apply else None
         out = self._h.sample_controls(**a._asdict(), samples=samples, trajectories=trajectories)
         penalty = self._penalty_record(a.n_samples, a.rounds, None, samples)      # (before apply=True touches the handle again)
+        penalty.update(self._elite_record(a.n_samples, a.rounds, None, samples))
         stats, counts = out.pop("round_stats"), out.pop("round_counts")
         cost_start = stats[0, :, 0].astype(self.dtype)
         applied = None
@@ -435,7 +464,9 @@ class iLQR:
         sample_controls'.  Returns a SampledMPC; the plans of every step with plans=True.  With state limits only after
         set_sample_penalty: every cost is then J + P, the record carries penalty, violation and the round_penalty_* /
         round_n_violating rows of every step, and with samples=True penalty_samples and violation_samples of the last
-        step's last round.  The multipliers of the state-limited solver are neither read nor changed."""
+        step's last round.  The multipliers of the state-limited solver are neither read nor changed.  After
+        set_sample_elites every step's rounds are those of sample_controls with elites, each step starting from u_std
+        again; the record carries round_n_elite, and u_std_steps (elite_samples with samples=True) of the last step."""
         if self.plant is None:
             raise ValueError("construct the solver with plant=<System> to run MPC steps")
         a = sampled_mpc_args(self.system, self.N, self.B, self.batched, n_steps, n_samples, rounds, seed, u_std, mode,
@@ -445,7 +476,8 @@ class iLQR:
         rec.update(round_n_finite=unbatch(out["round_counts"], self.batched, wrap=True), U_plan=None)
         names = {"u": "U_sim", "x": "X_sim", "cost": "cost", "U_plan": "U_plan"}      # (n_steps, B, ...) each; U_plan with plans
         rec.update({names[k]: unbatch(v, self.batched, axis=1, wrap=True) for k, v in out.items() if k in names})
-        return SampledMPC(**rec, **self._penalty_record(a.n_samples, a.rounds, a.n_steps, samples))
+        return SampledMPC(**rec, **self._penalty_record(a.n_samples, a.rounds, a.n_steps, samples),
+                          **self._elite_record(a.n_samples, a.rounds, a.n_steps, samples))
 
     # ---- MPC (run_iLQR_MPC.py:116-143), device-resident ---------------------------------------------
     def mpc_reset(self, x_0, U_init, keep_state=False):

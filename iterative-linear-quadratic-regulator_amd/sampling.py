@@ -173,15 +173,19 @@ PENALTY_FIELDS = ("penalty", "violation") + _lib.SAMPLE_PENALTY_STATS + ("round_
                                                                         "violation_samples")
 
 
+# What they gain while elites are set (iLQR.set_sample_elites), in the same way: None without elites.
+ELITE_FIELDS = ("u_std_steps", "round_n_elite", "elite_samples")
+
+
 def _with_penalty_fields(record):
     class Record(record):
         def __new__(cls, *args, **kw):
-            extra = {k: kw.pop(k) for k in PENALTY_FIELDS if k in kw}
+            extra = {k: kw.pop(k) for k in PENALTY_FIELDS + ELITE_FIELDS if k in kw}
             self = super().__new__(cls, *args, **kw)
             self.__dict__.update(extra)
             return self
 
-    for k in PENALTY_FIELDS:
+    for k in PENALTY_FIELDS + ELITE_FIELDS:
         setattr(Record, k, None)
     Record.__name__ = Record.__qualname__ = record.__name__
     return Record
@@ -200,7 +204,10 @@ samples=True; else None.  While a penalty is set (set_sample_penalty) every cost
 violation ([B]): P and the largest state-limit violation of U's rollout; round_penalty_start, round_penalty_best,
 round_violation_best (float64) and round_n_violating (int), each (R, [B]): per round P of its nominal, P and the
 violation of its best sample (NaN with no finite sample) and the number of finite samples violating by more than
-violation_tol; penalty_samples, violation_samples ([B,] S) of the last round with samples=True."""
+violation_tol; penalty_samples, violation_samples ([B,] S) of the last round with samples=True.  While elites are set
+(set_sample_elites) round_ess is the effective sample size of the elites' weights, and: u_std_steps ([B,] n_u, N): the
+standard deviations after the last round; round_n_elite (R, [B]) int: the elites of every round; elite_samples ([B,] S)
+bool of the last round with samples=True."""
 
 _SEARCH_FIELDS = [("n_samples", int), ("rounds", int), ("seed", int), ("u_std", ROWS), ("mode", int), ("temperature", float),
                   ("smoothing", float), ("distribution", int), ("first_trajectory", int), ("first_round", int)]
@@ -246,7 +253,9 @@ statistics of SampledControls for every round of every step; U_plan (n_steps, [B
 each step before it is shifted, else None.  While a penalty is set (set_sample_penalty) cost is J + P, and: penalty,
 violation (n_steps, [B]): P and the violation of each step's plan ("best" mode: of the last round's best sample);
 round_penalty_start, round_penalty_best, round_violation_best, round_n_violating (n_steps, R, [B]) as SampledControls';
-penalty_samples, violation_samples ([B,] S) of the last step's last round with samples=True."""
+penalty_samples, violation_samples ([B,] S) of the last step's last round with samples=True.  While elites are set
+(set_sample_elites): u_std_steps ([B,] n_u, N) after the last step's last round, round_n_elite (n_steps, R, [B]), and
+elite_samples ([B,] S) of the last step's last round with samples=True."""
 
 SampledMpcArgs = NamedTuple("SampledMpcArgs", [("n_steps", int)] + _SEARCH_FIELDS + [("w", ROWS)])
 
@@ -301,6 +310,39 @@ def sample_penalty_args(system, B, weight, violation_tol=0.0, dtype=None):
     if not (np.isfinite(tol) and tol >= 0.0):
         raise ValueError(f"violation_tol must be finite and >= 0, got {violation_tol!r}")
     return SamplePenaltyArgs(weight=np.ascontiguousarray(w), violation_tol=tol)
+
+
+# ---- elites and the adapted standard deviation -------------------------------------------------------------------------
+SampleElitesArgs = NamedTuple("SampleElitesArgs", [("n_elite", int), ("uniform", bool), ("std_min", ROWS), ("std_steps", ROWS)])
+
+
+def sample_elites_args(system, N, B, batched, n_elite, std_min=0.0, uniform=True, std_steps=None, dtype=None):
+    """Validated arguments of ``ilqr_set_sample_elites`` as (n_elite, uniform, std_min, std_steps): std_min (B, n_u)
+    float64 -- (n_u,) or a scalar is broadcast over the batch --, std_steps ([B,] n_u, N) as (B, n_u, N) float64 or None;
+    n_elite None or 0 clears the state: (0, False, None, None).  Raises ValueError for a system without the elite kernels
+    (linear and user-defined systems), an n_elite that is not an integer >= 0, a std_min or std_steps of a wrong shape,
+    negative or not finite (in ``dtype`` too, where one is given).  Pure host code (no GPU)."""
+    refuse_unsupported(system, "elite samples are")
+    E = 0 if n_elite is None else _count("n_elite", n_elite, 0)
+    if E == 0:
+        return SampleElitesArgs(n_elite=0, uniform=False, std_min=None, std_steps=None)
+    B, m = int(B), system.n_u
+
+    def held(name, a):
+        with np.errstate(over="ignore"):
+            if not np.isfinite(a if dtype is None else a.astype(dtype)).all() or (a < 0).any():
+                raise ValueError(f"{name} must be finite and >= 0")
+        return a
+
+    lo = held("std_min", _std_rows("std_min", std_min, B, m, scalar=True, required="the floor of the adapted standard deviation"))
+    steps = None
+    if std_steps is not None:
+        steps = np.asarray(std_steps, dtype=np.float64)
+        want = (B, m, int(N)) if batched else (m, int(N))
+        if steps.shape != want:
+            raise ValueError(f"std_steps must have shape {want}, but got {steps.shape}")
+        steps = held("std_steps", np.ascontiguousarray(steps.reshape(B, m, int(N))))
+    return SampleElitesArgs(n_elite=E, uniform=bool(uniform), std_min=lo, std_steps=steps)
 
 
 # ---- results: the library's arrays and tables, as the records hold them ------------------------------------------------
