@@ -493,6 +493,52 @@ typedef struct ilqr_monte_carlo_desc {
 } ilqr_monte_carlo_desc;
 int ilqr_policy_monte_carlo(ilqr_handle h, const ilqr_monte_carlo_desc* d);
 
+/* ---- policy Monte Carlo: quantiles, tail means and exceedance counts on the device (build extension) ---------
+ * ilqr_policy_monte_carlo(h, d) with the risk measures of its samples computed behind the rollout, on the same stream:
+ * the median and the 95 % cost, the mean of the worst 5 % (CVaR), the share of samples above a threshold -- without the
+ * [B][S] rows crossing to the host.  Every output of d has the bits ilqr_policy_monte_carlo gives for the same d, and
+ * every output of d may be NULL as long as one of r's is not.
+ * For trajectory b let F be its samples with a finite cost (the set of the statistics, n = n_finite of them), and for
+ * each of three quantities v -- row ILQR_RISK_COST: cost, ILQR_RISK_DEVIATION: deviation, ILQR_RISK_VIOLATION: violation
+ * -- take the values v_s, s in F, in the handle's dtype, ordered as unsigned integers of their bit patterns (sign bit
+ * flipped for v >= 0, all bits for v < 0, -0 taken as +0; ties by the lower s): a total order on bit patterns that is the
+ * numeric order on finite values.  Write v_(1) <= ... <= v_(n).  For a level p in [0, 1]:
+ *   rank       k_p = min(max(ceil(p * n), 1), n)       one rounded double product of p and (double) n, then ceil: NumPy's
+ *                                                      quantile(method="inverted_cdf")
+ *   quantile   q_p = (double) v_(k_p)                  an order statistic: exact
+ *   tail mean  t_p = (sum_{i = k_p..n} v_(i)) / m,  m = n - k_p + 1       the upper tail: high is bad in all three rows.
+ *              Computed as (sum over s in F above v_(k_p) of (double) v_s + (m - c_gt) q_p) / m, c_gt the number of that
+ *              sum's terms; sums in double, a fixed order (each lane of a wave over its stride, then a butterfly).  p = 0
+ *              gives the mean over F, p = 1 the maximum.  This is the plain average at and above the quantile; the
+ *              Rockafellar-Uryasev estimator of CVaR would weigh v_(k_p) fractionally.
+ * and for a threshold tau (not NaN; +-inf allowed):
+ *   exceed     the number of s in F with (double) v_s > tau
+ * With n == 0 every quantile and tail mean is NaN, every rank 0 and every count 0.  No result depends on scheduling (no
+ * floating-point atomics).  rank is one row per trajectory: n, and so k_p, is the same for the three quantities.
+ * Synchronous; changes nothing another entry reads; ends the reports of ilqr_sample_penalty_report and
+ * ilqr_sample_elite_report as ilqr_policy_monte_carlo does.  A user-defined system is supported as there (a plugin with
+ * the policy kernels); its violation row is all zeros, and the results are those of a row of zeros.
+ * Returns what ilqr_policy_monte_carlo returns for h and d (except that every output of d may be NULL), and
+ * ILQR_ERR_INVALID_ARG -- before any device work, the handle unchanged -- for a NULL r, a wrong struct_size, reserved != 0,
+ * n_levels or n_thresholds outside 0..16, n_levels > 0 with levels NULL, a level that is NaN or outside [0, 1], quantile,
+ * tail_mean or rank given with n_levels == 0, exceed given with n_thresholds == 0 or thresholds NULL, a NaN threshold, or
+ * every output of r NULL.
+ * ILQR_ABI_VERSION stays 5 with this entry, for the reasons given at ilqr_set_batch_limits: it is additive. */
+enum { ILQR_RISK_COST = 0, ILQR_RISK_DEVIATION = 1, ILQR_RISK_VIOLATION = 2, ILQR_RISK_MAX_LEVELS = 16, ILQR_RISK_MAX_THRESHOLDS = 16 };
+typedef struct ilqr_monte_carlo_risk_desc {
+    uint32_t struct_size;      /* = sizeof(ilqr_monte_carlo_risk_desc) */
+    int32_t n_levels;          /* Q, 0..16 */
+    int32_t n_thresholds;      /* M, 0..16 */
+    int32_t reserved;          /* 0 */
+    const double* levels;      /* [Q] in [0, 1] */
+    const double* thresholds;  /* [B][3][M], not NaN; NULL when M == 0 */
+    double* quantile;          /* [B][3][Q]   any output may be NULL, not all */
+    double* tail_mean;         /* [B][3][Q] */
+    int32_t* rank;             /* [B][Q]  k_p */
+    int32_t* exceed;           /* [B][3][M] */
+} ilqr_monte_carlo_risk_desc;
+int ilqr_policy_monte_carlo_risk(ilqr_handle h, const ilqr_monte_carlo_desc* d, const ilqr_monte_carlo_risk_desc* r);
+
 /* ---- sampled control search: best-of-S and MPPI updates of U on the device (build extension) -----------------
  * A cheap search over control sequences before any Riccati sweep is paid for.  For trajectory b, round r = 0..R-1 draws S
  * temporally correlated perturbations of the nominal controls, rolls each out open loop through the model and replaces

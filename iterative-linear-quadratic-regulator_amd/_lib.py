@@ -45,7 +45,7 @@ SYMBOLS = (
     "ilqr_set_control_limits", "ilqr_set_batch_params", "ilqr_set_state_limits", "ilqr_set_mpc_multipliers",
     "ilqr_set_batch_limits", "ilqr_policy_rollout", "ilqr_policy_monte_carlo", "ilqr_sample_controls",
     "ilqr_sampled_mpc", "ilqr_set_sample_penalty", "ilqr_sample_penalty_report", "ilqr_set_sample_elites",
-    "ilqr_sample_elite_report",
+    "ilqr_sample_elite_report", "ilqr_policy_monte_carlo_risk",
 )
 # ilqr_set_batch_params: which rows
 BATCH_MODEL, BATCH_PLANT = 0, 1
@@ -63,6 +63,9 @@ NOISE_GAUSSIAN, NOISE_UNIFORM = 0, 1
 NOISE_DISTRIBUTIONS = {"gaussian": NOISE_GAUSSIAN, "uniform": NOISE_UNIFORM}
 MONTE_CARLO_STATS = ("cost_mean", "cost_std", "cost_min", "cost_max", "deviation_mean", "deviation_max", "violation_max")
 MONTE_CARLO_COUNTS = ("n_finite", "n_violating")
+# ilqr_policy_monte_carlo_risk: the rows of its tables (ILQR_RISK_*), and the caps on levels and thresholds
+RISK_ROWS = ("cost", "deviation", "violation")
+RISK_MAX_LEVELS = RISK_MAX_THRESHOLDS = 16
 # ilqr_sample_controls: the update of the nominal, and the columns of a round's statistics
 SAMPLE_BEST, SAMPLE_SOFTMIN = 0, 1
 SAMPLE_MODES = {"best": SAMPLE_BEST, "softmin": SAMPLE_SOFTMIN}
@@ -107,6 +110,17 @@ class MonteCarloDesc(C.Structure):
         ("stats", C.POINTER(C.c_double)), ("counts", C.POINTER(C.c_int32)),
         ("cost", C.c_void_p), ("x_final", C.c_void_p), ("deviation", C.c_void_p), ("violation", C.c_void_p),
         ("X", C.c_void_p), ("U", C.c_void_p), ("x0_out", C.c_void_p), ("w_out", C.c_void_p),
+    ]
+
+
+class MonteCarloRiskDesc(C.Structure):
+    """ilqr_monte_carlo_risk_desc (include/ilqr_hip.h), field for field."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("n_levels", C.c_int32), ("n_thresholds", C.c_int32), ("reserved", C.c_int32),
+        ("levels", C.POINTER(C.c_double)), ("thresholds", C.POINTER(C.c_double)),
+        ("quantile", C.POINTER(C.c_double)), ("tail_mean", C.POINTER(C.c_double)),
+        ("rank", C.POINTER(C.c_int32)), ("exceed", C.POINTER(C.c_int32)),
     ]
 
 
@@ -221,6 +235,7 @@ def load():
     lib.ilqr_set_batch_limits.argtypes = [vp, ci, vp, vp, ci]
     lib.ilqr_policy_rollout.argtypes = [vp, C.POINTER(PolicyRolloutDesc)]
     lib.ilqr_policy_monte_carlo.argtypes = [vp, C.POINTER(MonteCarloDesc)]
+    lib.ilqr_policy_monte_carlo_risk.argtypes = [vp, C.POINTER(MonteCarloDesc), C.POINTER(MonteCarloRiskDesc)]
     lib.ilqr_sample_controls.argtypes = [vp, C.POINTER(SampleControlsDesc)]
     lib.ilqr_sampled_mpc.argtypes = [vp, C.POINTER(SampledMpcDesc)]
     lib.ilqr_set_sample_penalty.argtypes = [vp, C.POINTER(cd), cd]
@@ -504,13 +519,14 @@ class Handle:
 
     # ---- the sampling entries: closed-loop policy rollouts, Monte Carlo, sampled control search --------
     @staticmethod
-    def _rows_in(d, keep, field, a, shape, what):
-        """d.field <- the float64 array ``a`` of ``shape`` (None in it: any length), kept alive in ``keep``; None: unset."""
+    def _rows_in(d, keep, field, a, shape, what, free="n_sys"):
+        """d.field <- the float64 array ``a`` of ``shape`` (None in it: any length, ``free`` in the message), kept alive in
+        ``keep``; None: unset."""
         if a is None:
             return
         r = np.ascontiguousarray(a, dtype=np.float64)
         if r.ndim != len(shape) or any(want is not None and got != want for got, want in zip(r.shape, shape)):
-            want = "(" + ", ".join("n_sys" if n is None else str(n) for n in shape) + ")"
+            want = "(" + ", ".join(free if n is None else str(n) for n in shape) + ")"
             raise ValueError(f"{what} must have shape {want}, but got {r.shape}")
         keep.append(r)
         setattr(d, field, r.ctypes.data_as(C.POINTER(C.c_double)))
@@ -561,12 +577,14 @@ class Handle:
 
     def policy_monte_carlo(self, n_samples, seed=0, x0_std=None, w_std=None, distribution=NOISE_GAUSSIAN, plant_rows=None,
                            integrator=-1, feedback=True, violation_tol=0.0, first_trajectory=0, samples=False,
-                           trajectories=False, noise=False, statistics=True):
+                           trajectories=False, noise=False, statistics=True, levels=None, thresholds=None):
         """policy_rollout with x_0 and the disturbance drawn on the device and per-trajectory statistics computed there
         (include/ilqr_hip.h, ilqr_policy_monte_carlo).  x0_std, w_std (B, n_x) float64 or None, plant_rows (B, S, n_sys)
         float64 or None.  Returns a dict: stats (B, 7) float64 and counts (B, 2) int32 (with statistics); cost, x_final,
         deviation, violation (with samples); X, U (with trajectories); x0_out (B, S, n_x), w_out (B, S, N, n_x) (with
-        noise)."""
+        noise).  With levels (Q,) or thresholds (B, 3, M) float64 the call is ilqr_policy_monte_carlo_risk and the dict
+        also holds quantile, tail_mean (B, 3, Q) float64 and rank (B, Q) int32 (with levels), exceed (B, 3, M) int32 (with
+        thresholds)."""
         B, S, n, m, N = self.B, int(n_samples), self.n_x, self.n_u, self.N
         Sa = max(S, 0)
         d, keep = self._desc(MonteCarloDesc, n_samples=S, integrator=integrator, feedback=bool(feedback),
@@ -585,7 +603,22 @@ class Handle:
         if noise:
             shapes.update(x0_out=(B, Sa, n), w_out=(B, Sa, N, n))
         out = self._outputs(d, shapes, dtypes={"stats": np.float64, "counts": np.int32})
-        self._chk(self.lib.ilqr_policy_monte_carlo(self.h, C.byref(d)))
+        if levels is None and thresholds is None:
+            self._chk(self.lib.ilqr_policy_monte_carlo(self.h, C.byref(d)))
+            return out
+        r, shapes = MonteCarloRiskDesc(), {}
+        r.struct_size = C.sizeof(MonteCarloRiskDesc)
+        if levels is not None:
+            self._rows_in(r, keep, "levels", levels, (None,), "levels", free="Q")
+            r.n_levels = Q = len(keep[-1])
+            shapes.update(quantile=(B, 3, Q), tail_mean=(B, 3, Q), rank=(B, Q))
+        if thresholds is not None:
+            self._rows_in(r, keep, "thresholds", thresholds, (B, 3, None), "thresholds", free="M")
+            r.n_thresholds = M = keep[-1].shape[2]
+            shapes.update(exceed=(B, 3, M))
+        out.update(self._outputs(r, shapes, dtypes={"quantile": np.float64, "tail_mean": np.float64, "rank": np.int32,
+                                                    "exceed": np.int32}))
+        self._chk(self.lib.ilqr_policy_monte_carlo_risk(self.h, C.byref(d), C.byref(r)))
         return out
 
     def sample_controls(self, n_samples, rounds=1, seed=0, u_std=None, mode=SAMPLE_BEST, temperature=1.0, smoothing=0.0,

@@ -304,6 +304,11 @@ int ilqr_policy_monte_carlo(ilqr_handle h, const ilqr_monte_carlo_desc* d) {
     const int rc = sampling_entry(h, d, "policy_monte_carlo", "ilqr_monte_carlo_desc");
     return rc ? rc : h->impl->policy_monte_carlo(*d);
 }
+int ilqr_policy_monte_carlo_risk(ilqr_handle h, const ilqr_monte_carlo_desc* d, const ilqr_monte_carlo_risk_desc* r) {
+    int rc = sampling_entry(h, d, "policy_monte_carlo_risk", "ilqr_monte_carlo_desc");
+    if (!rc) rc = sampling_entry(h, r, "policy_monte_carlo_risk", "ilqr_monte_carlo_risk_desc");
+    return rc ? rc : h->impl->policy_monte_carlo_risk(*d, *r);
+}
 int ilqr_sample_controls(ilqr_handle h, const ilqr_sample_controls_desc* d) {
     const int rc = sampling_entry(h, d, "sample_controls", "ilqr_sample_controls_desc");
     return rc ? rc : h->impl->sample_controls(*d);

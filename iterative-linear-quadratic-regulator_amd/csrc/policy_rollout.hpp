@@ -465,6 +465,150 @@ __global__ void __launch_bounds__(64) policy_stats_kernel(const T* __restrict__ 
     counts[2 * b + 1] = (int)nv;
 }
 
+// ---- risk measures of a Monte Carlo call (include/ilqr_hip.h, ilqr_policy_monte_carlo_risk) --------------------------
+// The image of a cost in the unsigned integers of its width whose order is the order of the finite costs (the image of T
+// orders as the image of the cost widened to double does: the widening is monotone).  -0 is taken as +0 first.  It is a
+// total order on bit patterns (sample_elite_kernel of sample_controls.hpp selects by it too).  key_value: the value of a
+// value's key, widened (-0 comes back as +0).
+ILQR_DEV unsigned cost_key(float c) {
+    const unsigned u = __float_as_uint(c + 0.0f);
+    return (u >> 31) ? ~u : u | 0x80000000u;
+}
+ILQR_DEV unsigned long long cost_key(double c) {
+    const unsigned long long u = (unsigned long long)__double_as_longlong(c + 0.0);
+    return (u >> 63) ? ~u : u | 0x8000000000000000ull;
+}
+ILQR_DEV double key_value(unsigned k) { return (double)__uint_as_float((k >> 31) ? k & 0x7fffffffu : ~k); }
+ILQR_DEV double key_value(unsigned long long k) {
+    return __longlong_as_double((long long)((k >> 63) ? k & 0x7fffffffffffffffull : ~k));
+}
+ILQR_DEV int wave_sum(int v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+// f(v[s]) for the samples s = lane, lane + 64, ... < S of a row whose cost c[s] is finite, s ascending.  The loads of eight
+// steps of the stride are issued together before the first is used: a pass over a row is bound by the latency of its
+// loads, not by their number (S = 1024: 16 steps a lane, two batches).
+template <typename T, typename F>
+ILQR_DEV void for_finite(const T* __restrict__ v, const T* __restrict__ c, int S, int lane, F&& f) {
+    int s = lane;
+    for (; s + 448 < S; s += 512) {
+        T cs[8], vs[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { cs[j] = c[s + 64 * j]; vs[j] = v[s + 64 * j]; }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const double ci = (double)cs[j];
+            if (ci - ci == 0.0) f(vs[j]);
+        }
+    }
+    for (; s < S; s += 64) {
+        const double ci = (double)c[s];
+        if (ci - ci == 0.0) f(v[s]);
+    }
+}
+// The k-th smallest cost_key (1 <= k <= n) of the values v[s] of the samples whose cost c[s] is finite (n of them), by one
+// wave: a radix select, most significant digit first, four bits a pass.  Every lane counts its stride of the row into the
+// sixteen integer LDS counters `cnt` (integer atomics: the counts do not depend on their order), every lane reads the
+// sixteen and walks them to the digit that holds the k-th key, and the search goes on inside that digit.  Every lane
+// returns the same key; equal keys are equal values, so which of them is "the" k-th does not matter to the caller.
+template <typename T>
+ILQR_DEV auto radix_select(const T* __restrict__ v, const T* __restrict__ c, int S, int k, unsigned* cnt, int lane)
+    -> decltype(cost_key(T(0))) {
+    using Key = decltype(cost_key(T(0)));
+    constexpr int KB = 8 * (int)sizeof(Key);
+    Key prefix = 0;
+    for (int sh = KB - 4; sh >= 0; sh -= 4) {
+        const bool first = sh == KB - 4;
+        if (lane < 16) cnt[lane] = 0u;
+        __syncthreads();
+        for_finite(v, c, S, lane, [&](T vs) {
+            const Key key = cost_key(vs);
+            if (first || (key >> (first ? 0 : sh + 4)) == prefix) atomicAdd(&cnt[(unsigned)(key >> sh) & 15u], 1u);
+        });
+        __syncthreads();
+        unsigned cum = 0, dsel = 0, below = 0;
+        bool found = false;
+#pragma unroll
+        for (unsigned d = 0; d < 16; ++d) {
+            const unsigned cd = cnt[d];
+            if (!found && cum + cd >= (unsigned)k) { found = true; dsel = d; below = cum; }
+            cum += cd;
+        }
+        __syncthreads();      // (every lane has read the counters before they are cleared again)
+        prefix = (Key)(prefix << 4) | (Key)dsel;
+        k -= (int)below;
+    }
+    return prefix;
+}
+
+// Quantiles, upper-tail means and exceedance counts of a Monte Carlo call, launched behind the rollout: grid (B, 3), one
+// wave per trajectory b and quantity r (0 cost, 1 deviation, 2 violation: the rows lie L = B * S apart behind `cost`), over
+// F = the samples of b with a finite cost, n of them (policy_stats_kernel's test, counted here).  For every level p in turn:
+// the rank k = min(max(ceil(p n), 1), n) (one rounded double product), the k-th key by radix_select, then one pass for
+// c_gt = the number of keys above it and the sum of their values, and
+//   quantile[b][r][p] = q = the value of the k-th key        tail_mean[b][r][p] = (sum + (m - c_gt) q) / m,  m = n - k + 1
+// The selects are sequential because a level's pass depends on the row's counts under its own prefix; Q <= 16 of them
+// share the wave and the sixteen counters.  After the levels one pass per block of four thresholds counts the samples of F
+// with (double) v > tau.  Sums in double, each lane over its stride and then the butterfly: a fixed order; no
+// floating-point atomics.  n == 0: NaN, rank 0, counts 0.  rank is written by the cost row's wave (n is the same for all
+// three).  Q or M may be 0; their outputs are then not touched.
+template <typename T>
+__global__ void __launch_bounds__(64) policy_risk_kernel(const T* __restrict__ cost, size_t L, int S, int Q, int M,
+                                                         const double* __restrict__ levels, const double* __restrict__ thresholds,
+                                                         double* __restrict__ quantile, double* __restrict__ tail_mean,
+                                                         int* __restrict__ rank, int* __restrict__ exceed) {
+    using Key = decltype(cost_key(T(0)));
+    __shared__ unsigned cnt[16];
+    const int b = blockIdx.x, r = blockIdx.y, lane = threadIdx.x;
+    const T* c = cost + (size_t)b * S;
+    const T* v = cost + (size_t)r * L + (size_t)b * S;
+    int n = 0;
+    for_finite(c, c, S, lane, [&](T) { n += 1; });
+    n = wave_sum(n);
+    const double nan = __builtin_nan("");
+    for (int p = 0; p < Q; ++p) {
+        const size_t o = ((size_t)b * 3 + r) * Q + p;
+        if (n == 0) {
+            if (lane == 0) { quantile[o] = nan; tail_mean[o] = nan; if (r == 0) rank[(size_t)b * Q + p] = 0; }
+            continue;
+        }
+        const double kd = ceil(levels[p] * (double)n);
+        const int k = kd < 1.0 ? 1 : kd > (double)n ? n : (int)kd;
+        const Key sel = radix_select<T>(v, c, S, k, cnt, lane);
+        const double q = key_value(sel);
+        double sum = 0;
+        int c_gt = 0;
+        for_finite(v, c, S, lane, [&](T vs) {
+            if (cost_key(vs) > sel) { sum += (double)vs; c_gt += 1; }
+        });
+        sum = wave_sum(sum);
+        c_gt = wave_sum(c_gt);
+        if (lane != 0) continue;
+        const int m = n - k + 1;
+        quantile[o] = q;
+        tail_mean[o] = (sum + (double)(m - c_gt) * q) / (double)m;      // (the k-th itself is not above: m - c_gt >= 1)
+        if (r == 0) rank[(size_t)b * Q + p] = k;
+    }
+    for (int j0 = 0; j0 < M; j0 += 4) {
+        const size_t o = ((size_t)b * 3 + r) * M + j0;
+        double tau[4];
+        int above[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) tau[j] = j0 + j < M ? thresholds[o + j] : __builtin_huge_val();
+        for_finite(v, c, S, lane, [&](T vs) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) above[j] += (double)vs > tau[j] ? 1 : 0;
+        });
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int a = wave_sum(above[j]);
+            if (lane == 0 && j0 + j < M) exceed[o + j] = a;
+        }
+    }
+}
+
 // dense[l][c][t] <- dev[t][c][l]: the sample trajectories in the ABI's (dim, time) layout behind the batch axes
 // (layout_ct_kernel's device side is vector-per-lane, [t][l][c]; the samples' is sample-innermost)
 template <typename T>

@@ -309,17 +309,7 @@ __global__ void sample_std_fill_kernel(SampleArgs<T> a, int NU) {
     a.Sd[idx] = a.std_up ? a.std_up[((size_t)b * NU + j) * a.N + t] : a.u_std[(size_t)b * NU + j];
 }
 
-// The image of a cost in the unsigned integers of its width whose order is the order of the finite costs (the image of T
-// orders as the image of the cost widened to double does: the widening is monotone).  -0 is taken as +0 first.
-ILQR_DEV unsigned cost_key(float c) {
-    const unsigned u = __float_as_uint(c + 0.0f);
-    return (u >> 31) ? ~u : u | 0x80000000u;
-}
-ILQR_DEV unsigned long long cost_key(double c) {
-    const unsigned long long u = (unsigned long long)__double_as_longlong(c + 0.0);
-    return (u >> 63) ? ~u : u | 0x8000000000000000ull;
-}
-
+// (cost_key, the order of the costs as unsigned integers: policy_rollout.hpp, where policy_risk_kernel selects by it too)
 // The elites of a round, launched behind sample_weights_kernel: one wave per trajectory over its contiguous [S] costs.
 // n_e = min(E, n_finite) samples with the lowest (J_s, s) among the finite costs are found by a radix select on
 // cost_key, most significant digit first, four bits a pass: every lane counts its stride of the row into sixteen integer

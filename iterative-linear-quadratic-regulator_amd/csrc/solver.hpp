@@ -63,6 +63,7 @@ struct SolverBase {
     virtual int set_batch_limits(int which, const double* lo, const double* hi, int row_len) = 0;
     virtual int policy_rollout(const ilqr_policy_rollout_desc& d) = 0;
     virtual int policy_monte_carlo(const ilqr_monte_carlo_desc& d) = 0;
+    virtual int policy_monte_carlo_risk(const ilqr_monte_carlo_desc& d, const ilqr_monte_carlo_risk_desc& r) = 0;
     virtual int sample_controls(const ilqr_sample_controls_desc& d) = 0;
     virtual int sampled_mpc(const ilqr_sampled_mpc_desc& d) = 0;
     virtual int set_sample_penalty(const double* weight, double violation_tol) = 0;
@@ -249,6 +250,10 @@ template <typename T> struct SamplingBufs {
     DevBuf<int> winners;          // [B]
     DevBuf<double> stats;         // Monte Carlo [B][7]; search [R][B][3] (sampled MPC: [n_steps][R][B][3], counts alike)
     DevBuf<int> counts;           // Monte Carlo [B][2]; search [R][B]
+    // the risk measures of a Monte Carlo call: levels [Q] and thresholds [B][3][M]; quantile and tail_mean [B][3][Q] each;
+    // rank [B][Q] and exceed [B][3][M]
+    DevBuf<double> risk_in, risk_out;
+    DevBuf<int> risk_counts;
     DevBuf<T> w_steps, plans;     // sampled MPC: w [n_steps][B][n_x] as the caller gave it; U_plan [n_steps][N][n_u][B]
 };
 
@@ -1301,14 +1306,33 @@ template <typename T> class SolverT : public SolverBase {
     int policy_rollout(const ilqr_policy_rollout_desc& d) override {
         PolicyCall c{"policy_rollout", d.n_samples, d.integrator, d.feedback, d.x0, d.w, d.plant_rows,
                      d.cost, d.x_final, d.deviation, d.violation, d.X, d.U};
-        return policy_call(c, nullptr);
+        return policy_call(c, nullptr, nullptr);
     }
     // The same rollout with x_0 and w drawn on the device (policy_noise_kernel) and the per-trajectory statistics of its
     // sample summaries (policy_stats_kernel).  What crosses to the device is the seed and two [B][n_x] rows of standard
     // deviations; smp.w is touched only when the disturbances are asked back.  Only what the noise and the statistics add is
     // checked here: policy_call refuses the rest (no such kernels, no problem set, n_samples, integrator, plant_rows).
-    int policy_monte_carlo(const ilqr_monte_carlo_desc& d) override {
-        const char* who = "policy_monte_carlo";
+    int policy_monte_carlo(const ilqr_monte_carlo_desc& d) override { return monte_carlo_call("policy_monte_carlo", d, nullptr); }
+    // The same call with the risk measures of its samples (policy_risk_kernel) behind the rollout.  Only the risk
+    // descriptor is checked here, before anything else and so before any device work; d's outputs may then all be NULL.
+    int policy_monte_carlo_risk(const ilqr_monte_carlo_desc& d, const ilqr_monte_carlo_risk_desc& r) override {
+        const char* who = "policy_monte_carlo_risk";
+        auto bad = [&](const char* what) { return fail(ILQR_ERR_INVALID_ARG, std::string(who) + ": " + what); };
+        const int Q = r.n_levels, M = r.n_thresholds;
+        if (r.reserved != 0) return bad("reserved must be 0");
+        if (Q < 0 || Q > ILQR_RISK_MAX_LEVELS) return bad("n_levels must be in 0..16");
+        if (M < 0 || M > ILQR_RISK_MAX_THRESHOLDS) return bad("n_thresholds must be in 0..16");
+        if (Q > 0 && !r.levels) return bad("levels is NULL");
+        for (int i = 0; i < Q; ++i)
+            if (!(r.levels[i] >= 0.0 && r.levels[i] <= 1.0)) return bad("every level must be in [0, 1] (and not NaN)");
+        if (Q == 0 && (r.quantile || r.tail_mean || r.rank)) return bad("quantile, tail_mean and rank need n_levels >= 1");
+        if (r.exceed && (M == 0 || !r.thresholds)) return bad("exceed needs n_thresholds >= 1 and thresholds");
+        for (size_t i = 0; r.thresholds && i < (size_t)B * 3 * M; ++i)
+            if (std::isnan(r.thresholds[i])) return bad("a threshold is NaN");
+        if (!r.quantile && !r.tail_mean && !r.rank && !r.exceed) return bad("every output of the risk descriptor is NULL");
+        return monte_carlo_call(who, d, &r);
+    }
+    int monte_carlo_call(const char* who, const ilqr_monte_carlo_desc& d, const ilqr_monte_carlo_risk_desc* risk) {
         auto bad = [&](const char* what) { return fail(ILQR_ERR_INVALID_ARG, std::string(who) + ": " + what); };
         if (d.distribution != ILQR_NOISE_GAUSSIAN && d.distribution != ILQR_NOISE_UNIFORM) return bad("unknown distribution");
         if (d.first_trajectory < 0) return bad("first_trajectory must be >= 0");
@@ -1317,11 +1341,11 @@ template <typename T> class SolverT : public SolverBase {
             for (size_t i = 0; sd && i < (size_t)B * NX; ++i)
                 if (!std::isfinite(sd[i]) || sd[i] < 0.0) return bad("every standard deviation must be finite and >= 0");
         }
-        if (!d.stats && !d.counts && !d.cost && !d.x_final && !d.deviation && !d.violation && !d.X && !d.U && !d.x0_out && !d.w_out)
+        if (!risk && !d.stats && !d.counts && !d.cost && !d.x_final && !d.deviation && !d.violation && !d.X && !d.U && !d.x0_out && !d.w_out)
             return bad("every output is NULL");
         PolicyCall c{who, d.n_samples, d.integrator, d.feedback, nullptr, nullptr, d.plant_rows,
                      d.cost, d.x_final, d.deviation, d.violation, d.X, d.U};
-        return policy_call(c, &d);
+        return policy_call(c, &d, risk);
     }
     // what both entries ask of the rollout (the host pointers of ilqr_policy_rollout_desc)
     struct PolicyCall {
@@ -1331,7 +1355,7 @@ template <typename T> class SolverT : public SolverBase {
         const double* plant_rows;
         void *cost, *x_final, *deviation, *violation, *X, *U;
     };
-    int policy_call(const PolicyCall& d, const ilqr_monte_carlo_desc* mc) {
+    int policy_call(const PolicyCall& d, const ilqr_monte_carlo_desc* mc, const ilqr_monte_carlo_risk_desc* risk) {
         const std::string who = d.who;
         int rc;
         size_t L;
@@ -1395,6 +1419,23 @@ template <typename T> class SolverT : public SolverBase {
                                (const T*)a.violation, d.n_samples, mc->violation_tol, smp.stats.p, smp.counts.p);
             if (mc->stats) ILQR_HIPCHK(hipMemcpyAsync(mc->stats, smp.stats.p, (size_t)B * 7 * sizeof(double), hipMemcpyDeviceToHost, stream));
             if (mc->counts) ILQR_HIPCHK(hipMemcpyAsync(mc->counts, smp.counts.p, (size_t)B * 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
+        }
+        if (risk) {
+            // levels and thresholds go up from the caller's arrays (the call ends synchronised); nothing is computed for
+            // a group of outputs the caller left out
+            const int Q = (risk->quantile || risk->tail_mean || risk->rank) ? risk->n_levels : 0, M = risk->exceed ? risk->n_thresholds : 0;
+            const size_t nq = (size_t)B * 3 * Q, nm = (size_t)B * 3 * M;
+            if ((rc = grow(smp.risk_in, Q + nm)) || (rc = grow(smp.risk_out, 2 * nq)) || (rc = grow(smp.risk_counts, (size_t)B * Q + nm))) return rc;
+            double *lev = smp.risk_in.p, *thr = lev + Q, *qu = smp.risk_out.p, *tm = qu + nq;
+            int *rk = smp.risk_counts.p, *ex = rk + (size_t)B * Q;
+            if (Q) ILQR_HIPCHK(hipMemcpyAsync(lev, risk->levels, Q * sizeof(double), hipMemcpyHostToDevice, stream));
+            if (M) ILQR_HIPCHK(hipMemcpyAsync(thr, risk->thresholds, nm * sizeof(double), hipMemcpyHostToDevice, stream));
+            hipLaunchKernelGGL(policy_risk_kernel<T>, dim3(B, 3), dim3(64), 0, stream, (const T*)a.cost, L, d.n_samples, Q, M,
+                               (const double*)lev, (const double*)thr, qu, tm, rk, ex);
+            if (risk->quantile) ILQR_HIPCHK(hipMemcpyAsync(risk->quantile, qu, nq * sizeof(double), hipMemcpyDeviceToHost, stream));
+            if (risk->tail_mean) ILQR_HIPCHK(hipMemcpyAsync(risk->tail_mean, tm, nq * sizeof(double), hipMemcpyDeviceToHost, stream));
+            if (risk->rank) ILQR_HIPCHK(hipMemcpyAsync(risk->rank, rk, (size_t)B * Q * sizeof(int), hipMemcpyDeviceToHost, stream));
+            if (risk->exceed) ILQR_HIPCHK(hipMemcpyAsync(risk->exceed, ex, nm * sizeof(int), hipMemcpyDeviceToHost, stream));
         }
         auto fetch = [&](void* host, const T* dev) -> int {
             if (host) ILQR_HIPCHK(hipMemcpyAsync(host, dev, L * sizeof(T), hipMemcpyDeviceToHost, stream));

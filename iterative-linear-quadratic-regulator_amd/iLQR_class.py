@@ -22,8 +22,8 @@ from . import _lib
 # (the names of the two modules beside this file stay importable from here)
 from .setter_args import _bounds, batch_param_rows, control_limits, mpc_multiplier_mode, state_limits  # noqa: F401
 from .sampling import (ELITE_FIELDS, PENALTY_FIELDS, PolicyMonteCarlo, PolicyRollout, SampledControls, SampledMPC,  # noqa: F401
-                       _with_penalty_fields, has_policy_kernels, policy_monte_carlo_args, policy_rollout_args,
-                       sample_controls_args, sample_elites_args, sample_penalty_args, sampled_mpc_args, table_columns,
+                       _with_penalty_fields, has_policy_kernels, policy_monte_carlo_args, policy_risk_args,
+                       policy_risk_record, policy_rollout_args, sample_controls_args, sample_elites_args, sample_penalty_args, sampled_mpc_args, table_columns,
                        unbatch)
 from .systems.system_base import System, ready
 
@@ -341,7 +341,7 @@ class iLQR:
 
     def policy_monte_carlo(self, n_samples, seed=0, x_0_std=None, disturbance_std=None, distribution="gaussian",
                            plant_params=None, integrator=None, feedback=True, violation_tol=0.0, first_trajectory=0,
-                           samples=False, trajectories=False, noise=False):
+                           samples=False, trajectories=False, noise=False, *, quantiles=None, thresholds=None):
         """policy_rollout under noise drawn on the device, answered per trajectory (include/ilqr_hip.h,
         ilqr_policy_monte_carlo): sample s of trajectory b starts at x_0[b] + x_0_std[b] * z and receives
         disturbance_std[b] * z after every step, z of unit variance ("gaussian" or "uniform") from Philox4x32-10 at
@@ -350,12 +350,21 @@ class iLQR:
         policy_rollout.  Returns a PolicyMonteCarlo: statistics of cost, deviation and violation over the samples with a
         finite cost, n_finite, and n_violating (violation > violation_tol); per-sample arrays with samples=True, X and U
         with trajectories=True, the drawn x_0 and disturbance with noise=True (policy_rollout with those two gives the
-        same bits).  Nothing in the solver changes."""
+        same bits).  quantiles: a sequence of 1..16 levels p in [0, 1]; thresholds: {"cost" | "deviation" | "violation":
+        a scalar, (M,) or (B, M), M <= 16}.  With either, the risk measures of the three quantities are computed on the
+        device behind the rollout (ilqr_policy_monte_carlo_risk) and returned as attributes beside the tuple: per level
+        the quantile (the ceil(p n_finite)-th smallest value: NumPy's method="inverted_cdf") and the mean of the upper
+        tail from it upwards (p = 0.95: the mean of the worst 5 %), per threshold the number of finite samples strictly
+        above it; everything else the call returns is what it returns without them.  Nothing in the solver changes."""
         a = policy_monte_carlo_args(self.system, self.N, self.B, self.batched, n_samples, seed, x_0_std, disturbance_std,
                                     distribution, plant_params, integrator, violation_tol, first_trajectory)
+        risk = policy_risk_args(self.B, self.batched, quantiles, thresholds)
         out = self._h.policy_monte_carlo(**a._asdict(), feedback=feedback, samples=samples, trajectories=trajectories,
-                                         noise=noise)
-        rec = table_columns(out.pop("stats"), _lib.MONTE_CARLO_STATS, self.batched)
+                                         noise=noise, levels=risk.levels, thresholds=risk.thresholds)
+        rec = policy_risk_record(risk, out, self.batched)
+        for k in ("quantile", "tail_mean", "rank", "exceed"):
+            out.pop(k, None)
+        rec.update(table_columns(out.pop("stats"), _lib.MONTE_CARLO_STATS, self.batched))
         rec.update(table_columns(out.pop("counts"), _lib.MONTE_CARLO_COUNTS, self.batched))
         names = {"x0_out": "x_0", "w_out": "disturbance"}
         rec.update({names.get(k, k): self._out(v) for k, v in out.items()})

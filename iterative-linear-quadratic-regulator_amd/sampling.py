@@ -129,14 +129,40 @@ def policy_rollout_args(system, N, B, batched, n_samples, x_0=None, disturbance=
 
 
 # ---- policy Monte Carlo ----------------------------------------------------------------------------------------------
-PolicyMonteCarlo = namedtuple(
+def _with_fields(record, fields):
+    """``record`` (a namedtuple class) with the attributes ``fields`` beside the tuple: keyword arguments of the
+    constructor, None when not given.  The tuple itself (_fields, unpacking, iteration, defaults) stays what it is."""
+    class Record(record):
+        def __new__(cls, *args, **kw):
+            extra = {k: kw.pop(k) for k in fields if k in kw}
+            self = super().__new__(cls, *args, **kw)
+            self.__dict__.update(extra)
+            return self
+
+    for k in fields:
+        setattr(Record, k, None)
+    Record.__name__ = Record.__qualname__ = record.__name__
+    return Record
+
+
+# What PolicyMonteCarlo gains with quantiles= / thresholds= (ilqr_policy_monte_carlo_risk): attributes beside the tuple's
+# own fields, each None when not asked for.
+RISK_FIELDS = (("quantile_levels", "quantile_rank") + tuple(f"{q}_{k}" for q in _lib.RISK_ROWS for k in ("quantiles", "tail_mean"))
+               + tuple(f"{q}_exceeding" for q in _lib.RISK_ROWS))
+
+PolicyMonteCarlo = _with_fields(namedtuple(
     "PolicyMonteCarlo", _lib.MONTE_CARLO_STATS + _lib.MONTE_CARLO_COUNTS +
-    ("cost", "x_final", "deviation", "violation", "X", "U", "x_0", "disturbance"), defaults=(None,) * 8)
+    ("cost", "x_final", "deviation", "violation", "X", "U", "x_0", "disturbance"), defaults=(None,) * 8), RISK_FIELDS)
 PolicyMonteCarlo.__doc__ = """Result of iLQR.policy_monte_carlo.  Per trajectory ([B] each, scalars on a single solver), over
 the samples with a finite cost: cost_mean, cost_std (population), cost_min, cost_max, deviation_mean, deviation_max,
 violation_max (float64, NaN when n_finite is 0), n_finite, n_violating (int).  With samples=True cost, deviation, violation
 ([B,] S) and x_final ([B,] S, n_x); with trajectories=True X ([B,] S, n_x, N + 1) and U ([B,] S, n_u, N); with noise=True
-x_0 ([B,] S, n_x) and disturbance ([B,] S, N, n_x) as they were drawn; else None."""
+x_0 ([B,] S, n_x) and disturbance ([B,] S, N, n_x) as they were drawn; else None.  Beside the tuple, with quantiles=:
+quantile_levels (Q,), quantile_rank ([B,] Q) int -- the rank k_p of every level among the n_finite samples, 0 with none --
+and cost_quantiles, cost_tail_mean, deviation_quantiles, deviation_tail_mean, violation_quantiles, violation_tail_mean
+([B,] Q) float64: the k_p-th smallest value (NumPy's method="inverted_cdf") and the mean of the values from it upwards
+(NaN when n_finite is 0); with thresholds=: cost_exceeding, deviation_exceeding, violation_exceeding ([B,] M_q) int, the
+number of finite samples strictly above each threshold of that key; else None."""
 
 PolicyMonteCarloArgs = NamedTuple(
     "PolicyMonteCarloArgs",
@@ -166,6 +192,71 @@ def policy_monte_carlo_args(system, N, B, batched, n_samples, seed=0, x_0_std=No
                                 plant_rows=r.plant_rows, integrator=r.integrator, violation_tol=tol, first_trajectory=first)
 
 
+# levels, thresholds: the two keyword arguments of ``_lib.Handle.policy_monte_carlo`` behind PolicyMonteCarloArgs' own;
+# widths: {key: M_q}, how many of the M columns of a row of ``thresholds`` are the caller's (the rest is padding)
+PolicyRiskArgs = NamedTuple("PolicyRiskArgs", [("levels", ROWS), ("thresholds", ROWS), ("widths", dict)])
+
+
+def policy_risk_args(B, batched, quantiles=None, thresholds=None):
+    """Validated risk arguments of ``ilqr_policy_monte_carlo_risk`` as (levels, thresholds, widths): levels (Q,) float64 or
+    None; thresholds (B, 3, M) float64 or None, rows in the order of _lib.RISK_ROWS, M the widest key's count, every row
+    padded with +inf (nothing exceeds it: the count is 0); widths {key: M_q} of the keys that were given.  ``quantiles`` is
+    a sequence of 1..16 levels in [0, 1]; ``thresholds`` a dict with any of the keys "cost", "deviation", "violation",
+    each a scalar, (M_q,) -- broadcast over the batch -- or, on a batched solver, (B, M_q), 1 <= M_q <= 16, +-inf
+    allowed.  Raises ValueError for a level that is NaN or outside [0, 1], no level or more than 16, levels that are not
+    one-dimensional, thresholds that are no dict or an empty one, an unknown key, a wrong shape, a NaN threshold, no
+    threshold or more than 16 under a key.  Pure host code (no GPU)."""
+    B = int(B)
+    levels = None
+    if quantiles is not None:
+        levels = np.array(quantiles, dtype=np.float64)
+        if levels.ndim != 1 or not 1 <= levels.size <= _lib.RISK_MAX_LEVELS:
+            raise ValueError(f"quantiles must be a sequence of 1..{_lib.RISK_MAX_LEVELS} levels, but got shape {levels.shape}")
+        if not ((levels >= 0.0) & (levels <= 1.0)).all():
+            raise ValueError("every quantile level must be in [0, 1]")
+    thr, widths = None, {}
+    if thresholds is not None:
+        if not isinstance(thresholds, dict) or not thresholds:
+            raise ValueError(f"thresholds must be a dict with some of the keys {_lib.RISK_ROWS}, got {thresholds!r}")
+        unknown = sorted(set(thresholds) - set(_lib.RISK_ROWS), key=repr)
+        if unknown:
+            raise ValueError(f"unknown threshold key(s) {unknown}; expected some of {_lib.RISK_ROWS}")
+        rows = {}
+        for k, v in thresholds.items():
+            a = np.asarray(v, dtype=np.float64)
+            if a.ndim == 0:
+                a = a.reshape(1)
+            if a.ndim == 1:
+                a = np.broadcast_to(a, (B,) + a.shape)
+            elif not batched or a.ndim != 2 or a.shape[0] != B:
+                want = f"(M,) or ({B}, M)" if batched else "(M,)"
+                raise ValueError(f"thresholds[{k!r}] must be a scalar or have shape {want}, but got {a.shape}")
+            if not 1 <= a.shape[1] <= _lib.RISK_MAX_THRESHOLDS:
+                raise ValueError(f"thresholds[{k!r}] must hold 1..{_lib.RISK_MAX_THRESHOLDS} thresholds, but got {a.shape[1]}")
+            if np.isnan(a).any():
+                raise ValueError(f"thresholds[{k!r}] must not be NaN")
+            rows[k], widths[k] = a, a.shape[1]
+        thr = np.full((B, 3, max(widths.values())), np.inf)
+        for k, a in rows.items():
+            thr[:, _lib.RISK_ROWS.index(k), :a.shape[1]] = a
+    return PolicyRiskArgs(levels=levels, thresholds=thr, widths=widths)
+
+
+def policy_risk_record(args, out, batched):
+    """The RISK_FIELDS of a PolicyMonteCarlo from the tables ``_lib.Handle.policy_monte_carlo`` returned for ``args`` (a
+    PolicyRiskArgs): the rows of quantile, tail_mean (B, 3, Q) and exceed (B, 3, M) under their names, exceed sliced back
+    to each key's own thresholds; the batch axis dropped on a single solver.  What was not asked for is left out."""
+    one = (lambda a: ready(a.copy())) if batched else (lambda a: ready(a[0].copy()))
+    rec = {}
+    if args.levels is not None:
+        rec.update(quantile_levels=ready(args.levels.copy()), quantile_rank=one(out["rank"]))
+        for i, q in enumerate(_lib.RISK_ROWS):
+            rec[f"{q}_quantiles"], rec[f"{q}_tail_mean"] = one(out["quantile"][:, i]), one(out["tail_mean"][:, i])
+    for q, M in args.widths.items():
+        rec[f"{q}_exceeding"] = one(out["exceed"][:, _lib.RISK_ROWS.index(q), :M])
+    return rec
+
+
 # ---- sampled control search and sampled MPC --------------------------------------------------------------------------
 # What SampledControls and SampledMPC gain while a penalty is set (iLQR.set_sample_penalty): attributes beside the tuple's
 # own fields, None without a penalty.  The tuple itself (_fields, unpacking, iteration) stays the unpenalised record.
@@ -178,17 +269,7 @@ ELITE_FIELDS = ("u_std_steps", "round_n_elite", "elite_samples")
 
 
 def _with_penalty_fields(record):
-    class Record(record):
-        def __new__(cls, *args, **kw):
-            extra = {k: kw.pop(k) for k in PENALTY_FIELDS + ELITE_FIELDS if k in kw}
-            self = super().__new__(cls, *args, **kw)
-            self.__dict__.update(extra)
-            return self
-
-    for k in PENALTY_FIELDS + ELITE_FIELDS:
-        setattr(Record, k, None)
-    Record.__name__ = Record.__qualname__ = record.__name__
-    return Record
+    return _with_fields(record, PENALTY_FIELDS + ELITE_FIELDS)
 
 
 SampledControls = _with_penalty_fields(namedtuple(

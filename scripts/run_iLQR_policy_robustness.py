@@ -5,10 +5,13 @@ initial state off by a few degrees and the plant's m2 and l2 off by up to 20 %, 
 and once open loop (the controls U_t alone).  Per trajectory the script reports the share of samples whose final state is
 within the stated tolerance of the target.  With --process-noise SIGMA the closed loop is also run under Gaussian
 process noise of that standard deviation in every state component, drawn on the device (iLQR.policy_monte_carlo), and the
-per-trajectory statistics of its cost and deviation are reported.
+per-trajectory statistics of its cost and deviation are reported.  With --risk both loops are run once more with the
+initial state drawn on the device (and the process noise, if given) and the risk measures of the cost are reported: the
+median, the 95 % quantile, the mean of the worst 5 % and the share of samples above twice the nominal cost
+(iLQR.policy_monte_carlo with quantiles= and thresholds=).
 
     python scripts/run_iLQR_policy_robustness.py [--batch 256] [--samples 1024] [--horizon 200] [--dtype f64] [--seed 0]
-                                                 [--process-noise SIGMA]
+                                                 [--process-noise SIGMA] [--risk]
 """
 import argparse
 import os
@@ -37,6 +40,9 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--process-noise", type=float, default=None, metavar="SIGMA",
                     help="also run the closed loop under N(0, SIGMA^2) process noise drawn on the device (off by default)")
+    ap.add_argument("--risk", action="store_true",
+                    help="also report, closed and open loop, the median and 95 %% cost, the mean of the worst 5 %% and the "
+                         "share of samples above twice the nominal cost, computed on the device (off by default)")
     a = ap.parse_args(argv)
     dtype = np.float64 if a.dtype == "f64" else np.float32
     B, S, N = a.batch, a.samples, a.horizon
@@ -75,6 +81,22 @@ def main(argv=None):
         print(f"process noise sigma = {a.process_noise:g}: {B} x {S} closed-loop rollouts in {el:.3f} s; per trajectory: "
               f"finite samples min {int(mc.n_finite.min())} of {S}, cost mean median {np.median(mc.cost_mean):.3f}, "
               f"cost std median {np.median(mc.cost_std):.3f}, worst deviation from the nominal {np.nanmax(mc.deviation_max):.3f}")
+    if a.risk:
+        # the initial-state offsets above as standard deviations of the device's uniform draws (a uniform on [-h, h] has
+        # standard deviation h / sqrt(3)); the plant is the model
+        x0_std = np.array([ANGLE_OFF, ANGLE_OFF, RATE_OFF, RATE_OFF]) / np.sqrt(3.0)
+        w_std = None if a.process_noise is None else np.full(4, a.process_noise)
+        nominal = np.asarray(solver.cost, np.float64)
+        for label, feedback in (("closed loop", True), ("open loop", False)):
+            t0 = time.time()
+            mc = solver.policy_monte_carlo(S, seed=a.seed, x_0_std=x0_std, disturbance_std=w_std, distribution="uniform",
+                                           feedback=feedback, quantiles=(0.5, 0.95), thresholds={"cost": 2.0 * nominal[:, None]})
+            el = time.time() - t0
+            share = mc.cost_exceeding[:, 0] / np.maximum(mc.n_finite, 1)
+            print(f"risk, {label}: {B} x {S} rollouts in {el:.3f} s; per trajectory, medians over the batch: "
+                  f"median cost {np.nanmedian(mc.cost_quantiles[:, 0]):.3f}, 95 % cost {np.nanmedian(mc.cost_quantiles[:, 1]):.3f}, "
+                  f"mean of the worst 5 % {np.nanmedian(mc.cost_tail_mean[:, 1]):.3f}; share of samples above twice the "
+                  f"nominal cost: median {np.median(share):.3f}, max {share.max():.3f}")
     return shares
 
 
