@@ -789,6 +789,76 @@ typedef struct ilqr_sample_elite_report_desc {
 } ilqr_sample_elite_report_desc;
 int ilqr_sample_elite_report(ilqr_handle h, const ilqr_sample_elite_report_desc* d);
 
+/* ---- noise scenarios in the sampled search: robust costs over device-drawn disturbances (build extension) --------
+ * ilqr_sample_controls and ilqr_sampled_mpc roll every sample out through the noise-free model from the exact x_0, so the
+ * search picks the plan that is best on the nominal.  ilqr_set_sample_scenarios(n_scenarios = M >= 1) makes every sample
+ * roll out under M noise scenarios drawn on the device, and the sample's cost becomes a risk measure of its M scenario
+ * costs.  The state is sticky like ilqr_set_sample_penalty / ilqr_set_sample_elites: while it is set both entries read it;
+ * n_scenarios = 0 clears it (the other arguments are then not read).  M is a power of two in 1..64.
+ * Scenario m = 0..M-1 of trajectory b is exactly Monte Carlo sample m of ilqr_policy_monte_carlo with the same seed,
+ * distribution and the call's first_trajectory:
+ *   x_0     = x_0[b] + x0_std[b] (.) z(b, m, 0, stream 1)
+ *   x_{t+1} = f_model(x_t, u_t) + w_std[b] (.) z(b, m, t, stream 0)
+ * Philox counter (m, first_trajectory + b, t, stream), key = the scenario seed, the transforms of the distribution as
+ * given there, each product std * z rounded to the handle's dtype on its own and the add never fused.  A NULL x0_std /
+ * w_std adds nothing of that kind.  The scenarios depend neither on the sample s, nor on the round, nor on the step of
+ * ilqr_sampled_mpc: every candidate of every round meets the SAME M disturbances (common random numbers).  Fresh
+ * scenarios per round or per step are left out.  The control perturbation of sample s is untouched -- the search's own
+ * seed at stream 2 + first_round + r -- and is the same for the M scenarios of a sample; sample 0 is the nominal.  The
+ * plant is the model (its integrator, its ILQR_BATCH_MODEL rows) as the search's always was; control limits clamp as
+ * before; with the penalty set a scenario's value is its J + P.
+ * With v_0 .. v_{M-1} the scenario values of one sample in the handle's dtype, the sample's cost is NaN if any v_m is not
+ * finite (it then never wins, never weighs and is no elite, as every non-finite cost), and otherwise, computed in double
+ * and converted once to the handle's dtype:
+ *   ILQR_SCENARIO_MEAN   tree(v) / M, tree the level-by-level sum of adjacent pairs (v[0::2] + v[1::2] until one is left)
+ *   ILQR_SCENARIO_MAX    the largest v_m
+ *   ILQR_SCENARIO_TAIL   at level p in [0, 1]: k = min(max(ceil(p M), 1), M) (one rounded double product, the rank rule of
+ *                        ilqr_policy_monte_carlo_risk); order by value, ties to the lower m; with rank_m the 1-based
+ *                        place of v_m in that order: tree(rank_m >= k ? v_m : 0.0) / (M - k + 1), the mean of the
+ *                        M - k + 1 largest.  level is read in this mode only
+ * Every cost the two entries report or read is this aggregate: the weights, the argmin, the softmin, the elites,
+ * round_stats, cost_new, cost_samples, cost_out.  While a penalty is set the report's violation values become the maximum
+ * over the scenarios and its penalty values tree(P_m) / M, whatever the aggregate.  X_new stays the disturbance-free
+ * rollout of U_new (one launch of the rollout without scenarios, only when X_new is given).
+ * Because the scenarios do not change between rounds, in BEST mode the nominal's cost of round r + 1 equals the minimum of
+ * round r and cost_new the last round's minimum, bit for bit; a call continued through first_round continues bit for bit;
+ * one step of ilqr_sampled_mpc equals ilqr_sample_controls from the same state.  With M = 1 and both stds NULL, and after
+ * clearing, both entries give exactly what they give unset.
+ * Both entries additionally refuse batch * n_samples * M >= 2^31 (ILQR_ERR_INVALID_ARG) while scenarios are set.
+ * Returns ILQR_ERR_INVALID_ARG -- all checked before any device work, the handle unchanged -- for a NULL handle, an M that
+ * is not 0 or a power of two <= 64, an unknown aggregate or distribution, a level outside [0, 1] or NaN in TAIL mode, or a
+ * standard deviation that is negative or not finite (in the handle's dtype too); ILQR_ERR_UNSUPPORTED for ILQR_SYS_LINEAR
+ * and for every ILQR_SYS_CUSTOM handle (a plugin with the policy kernels included: the kernels of this entry are built for
+ * the built-in systems only).  A successful call invalidates the report below.
+ * ILQR_ABI_VERSION stays 5 with this entry, for the reasons given at ilqr_set_batch_limits: it is additive, and
+ * ilqr_sample_controls_desc / ilqr_sampled_mpc_desc are unchanged. */
+enum { ILQR_SCENARIO_MEAN = 0, ILQR_SCENARIO_MAX = 1, ILQR_SCENARIO_TAIL = 2 };
+int ilqr_set_sample_scenarios(ilqr_handle h, int32_t n_scenarios, int32_t aggregate /* ILQR_SCENARIO_* */, double level,
+                              uint64_t seed, int32_t distribution /* ILQR_NOISE_* */,
+                              const double* x0_std /* [B][n_x], or NULL */,
+                              const double* w_std  /* [B][n_x], or NULL */);
+
+/* What the last ilqr_sample_controls with scenarios set left on the device, with S and M of that call:
+ *   scenario_cost          the scenario values v_m of U_new, from the rollout cost_new comes from (launched by a call with
+ *                          scenarios whether or not cost_new was asked for)
+ *   scenario_cost_samples  the scenario values of every sample of the LAST round, beside cost_samples
+ *   scenario_X             the M disturbed rollouts of U_new; only when that call was given X_new
+ * The call is synchronous and changes nothing.
+ * Returns ILQR_ERR_INVALID_ARG for a NULL handle or desc, a wrong struct_size, reserved != 0 or every output NULL;
+ * ILQR_ERR_STATE unless the handle's most recent sampling call was an ilqr_sample_controls with scenarios set that
+ * succeeded -- an ilqr_sampled_mpc (its costs are the aggregates, it leaves no report), an ilqr_policy_rollout /
+ * ilqr_policy_monte_carlo, a call without scenarios, or an ilqr_set_sample_scenarios after it invalidates the report -- and
+ * for scenario_X after a call without X_new.
+ * ILQR_ABI_VERSION stays 5 with this entry: it is additive, and no existing descriptor changes. */
+typedef struct ilqr_sample_scenario_report_desc {
+    uint32_t struct_size;          /* = sizeof(ilqr_sample_scenario_report_desc) */
+    int32_t reserved;              /* 0 */
+    void* scenario_cost;           /* [B][M] handle dtype; any output may be NULL, not all */
+    void* scenario_cost_samples;   /* [B][S][M] */
+    void* scenario_X;              /* [B][M][n_x][N+1] */
+} ilqr_sample_scenario_report_desc;
+int ilqr_sample_scenario_report(ilqr_handle h, const ilqr_sample_scenario_report_desc* d);
+
 /* ---- multi-GPU hook -------------------------------------------
  * Writes 4 doubles to DEVICE memory `dev_out4` on the handle's stream:
  *   { min cost, max |cost - cost_prev|, #trajectories still active, #converged }

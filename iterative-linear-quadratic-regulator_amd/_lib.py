@@ -45,7 +45,7 @@ SYMBOLS = (
     "ilqr_set_control_limits", "ilqr_set_batch_params", "ilqr_set_state_limits", "ilqr_set_mpc_multipliers",
     "ilqr_set_batch_limits", "ilqr_policy_rollout", "ilqr_policy_monte_carlo", "ilqr_sample_controls",
     "ilqr_sampled_mpc", "ilqr_set_sample_penalty", "ilqr_sample_penalty_report", "ilqr_set_sample_elites",
-    "ilqr_sample_elite_report", "ilqr_policy_monte_carlo_risk",
+    "ilqr_sample_elite_report", "ilqr_policy_monte_carlo_risk", "ilqr_set_sample_scenarios", "ilqr_sample_scenario_report",
 )
 # ilqr_set_batch_params: which rows
 BATCH_MODEL, BATCH_PLANT = 0, 1
@@ -72,6 +72,10 @@ SAMPLE_MODES = {"best": SAMPLE_BEST, "softmin": SAMPLE_SOFTMIN}
 SAMPLE_ROUND_STATS = ("round_cost_nominal", "round_cost_min", "round_ess")
 # ilqr_sample_penalty_report: the columns of a round's penalty row
 SAMPLE_PENALTY_STATS = ("round_penalty_start", "round_penalty_best", "round_violation_best")
+# ilqr_set_sample_scenarios: the risk measure of a sample's scenario costs (ILQR_SCENARIO_*), and the cap on the scenarios
+SCENARIO_MEAN, SCENARIO_MAX, SCENARIO_TAIL = 0, 1, 2
+SCENARIO_AGGREGATES = {"mean": SCENARIO_MEAN, "max": SCENARIO_MAX, "tail": SCENARIO_TAIL}
+SCENARIO_MAX_COUNT = 64
 
 
 class Config(C.Structure):
@@ -166,6 +170,14 @@ class SampleEliteReportDesc(C.Structure):
     ]
 
 
+class SampleScenarioReportDesc(C.Structure):
+    """ilqr_sample_scenario_report_desc (include/ilqr_hip.h), field for field."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("reserved", C.c_int32),
+        ("scenario_cost", C.c_void_p), ("scenario_cost_samples", C.c_void_p), ("scenario_X", C.c_void_p),
+    ]
+
+
 class IlqrError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libilqr_hip error {code}: {msg}")
@@ -242,6 +254,8 @@ def load():
     lib.ilqr_sample_penalty_report.argtypes = [vp, C.POINTER(SamplePenaltyReportDesc)]
     lib.ilqr_set_sample_elites.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(cd), vp]
     lib.ilqr_sample_elite_report.argtypes = [vp, C.POINTER(SampleEliteReportDesc)]
+    lib.ilqr_set_sample_scenarios.argtypes = [vp, C.c_int32, C.c_int32, cd, C.c_uint64, C.c_int32, C.POINTER(cd), C.POINTER(cd)]
+    lib.ilqr_sample_scenario_report.argtypes = [vp, C.POINTER(SampleScenarioReportDesc)]
     if lib.ilqr_abi_version() != ABI_VERSION:
         raise RuntimeError("libilqr_hip.so ABI version mismatch: rebuild the library")
     _lib = lib
@@ -725,6 +739,41 @@ class Handle:
             shapes.update(elite=(B, S))
         out = self._outputs(d, shapes, dtypes={"round_n_elite": np.int32, "elite": np.int32})
         self._chk(self.lib.ilqr_sample_elite_report(self.h, C.byref(d)))
+        return out
+
+    def set_sample_scenarios(self, n_scenarios, aggregate=SCENARIO_MEAN, level=0.0, seed=0, distribution=NOISE_GAUSSIAN,
+                             x0_std=None, w_std=None):
+        """Noise scenarios in sample_controls / sampled_mpc (include/ilqr_hip.h, ilqr_set_sample_scenarios): every sample is
+        rolled out under M = n_scenarios device-drawn disturbances (a power of two <= 64) and its cost becomes their mean,
+        maximum or upper-tail mean at ``level``.  x0_std, w_std (B, n_x) float64 >= 0 or None; n_scenarios = 0 clears the
+        state (the other arguments are then not read)."""
+        if int(n_scenarios) == 0:
+            self._chk(self.lib.ilqr_set_sample_scenarios(self.h, 0, 0, 0.0, 0, 0, None, None))
+            return
+        rows = []
+        for name, v in (("x0_std", x0_std), ("w_std", w_std)):
+            r = None if v is None else np.ascontiguousarray(v, dtype=np.float64)
+            if r is not None and r.shape != (self.B, self.n_x):
+                raise ValueError(f"{name} must have shape ({self.B}, {self.n_x}), but got {r.shape}")
+            rows.append(r)
+        ptr = [None if r is None else r.ctypes.data_as(C.POINTER(C.c_double)) for r in rows]
+        self._chk(self.lib.ilqr_set_sample_scenarios(self.h, int(n_scenarios), int(aggregate), float(level),
+                                                     int(seed) & 0xFFFFFFFFFFFFFFFF, int(distribution), ptr[0], ptr[1]))
+
+    def sample_scenario_report(self, n_samples, n_scenarios, samples=False, trajectories=False):
+        """What the last sample_controls with scenarios set left on the device (include/ilqr_hip.h,
+        ilqr_sample_scenario_report); n_samples and n_scenarios are that call's and the setter's.  Returns a dict:
+        scenario_cost (B, M); scenario_cost_samples (B, S, M) (with samples); scenario_X (B, M, n_x, N + 1) (with
+        trajectories: the call must have run with them)."""
+        B, S, M = self.B, int(n_samples), int(n_scenarios)
+        d, _ = self._desc(SampleScenarioReportDesc)
+        shapes = dict(scenario_cost=(B, M))
+        if samples:
+            shapes.update(scenario_cost_samples=(B, S, M))
+        if trajectories:
+            shapes.update(scenario_X=(B, M, self.n_x, self.N + 1))
+        out = self._outputs(d, shapes)
+        self._chk(self.lib.ilqr_sample_scenario_report(self.h, C.byref(d)))
         return out
 
     # ---- measurement ------------------------------------------------------------------------------

@@ -355,6 +355,26 @@ int ilqr_sample_elite_report(ilqr_handle h, const ilqr_sample_elite_report_desc*
     }
     return h->impl->sample_elite_report(*d);
 }
+int ilqr_set_sample_scenarios(ilqr_handle h, int32_t n_scenarios, int32_t aggregate, double level, uint64_t seed,
+                              int32_t distribution, const double* x0_std, const double* w_std) {
+    if (!h || !h->impl) return ILQR_ERR_INVALID_ARG;
+    const ilqr_config& c = h->impl->cfg;
+    // (a plugin with the policy kernels included: the scenario kernels are built for the built-in systems only)
+    if (c.system == ILQR_SYS_LINEAR || c.system == ILQR_SYS_CUSTOM) {
+        h->impl->err = "set_sample_scenarios: supported for the pendulum, UA double pendulum and double pendulum only";
+        return ILQR_ERR_UNSUPPORTED;
+    }
+    return h->impl->set_sample_scenarios(n_scenarios, aggregate, level, seed, distribution, x0_std, w_std);
+}
+int ilqr_sample_scenario_report(ilqr_handle h, const ilqr_sample_scenario_report_desc* d) {
+    if (!h || !h->impl) return ILQR_ERR_INVALID_ARG;
+    if (!d || d->struct_size != sizeof(ilqr_sample_scenario_report_desc) || d->reserved != 0) {
+        h->impl->err = "sample_scenario_report: desc is NULL, struct_size does not match this library's "
+                       "ilqr_sample_scenario_report_desc, or reserved is not 0";
+        return ILQR_ERR_INVALID_ARG;
+    }
+    return h->impl->sample_scenario_report(*d);
+}
 int ilqr_timing_enable(ilqr_handle h, int on) { ILQR_FWD(h, timing_enable(on)); }
 int ilqr_timing_reset(ilqr_handle h) { ILQR_FWD(h, timing_reset()); }
 int ilqr_timing_get(ilqr_handle h, double ms[ILQR_N_PHASES], int64_t launches[ILQR_N_PHASES]) {

@@ -101,6 +101,9 @@ template <typename T> struct SamplingOps {
     void (*std_fill)(const SampleArgs<T>&, hipStream_t) = nullptr;
     void (*rollout_elite[2])(const SampleArgs<T>&, const NoiseArgs<T>&, hipStream_t) = {};
     void (*update_elite)(const SampleArgs<T>&, hipStream_t) = nullptr;
+    // noise scenarios (ilqr_set_sample_scenarios): the rollouts with M lanes per sample, [STEPSTD][PEN]; null where the
+    // system is none of the built-in three
+    void (*rollout_scn[2][2])(const ScenarioArgs<T>&, const NoiseArgs<T>&, hipStream_t) = {};
     explicit operator bool() const { return rollout != nullptr; }
 };
 
@@ -318,6 +321,12 @@ template <typename T, typename Dyn, bool PEN = false, bool STEPSTD = false>
 void launch_sample_rollout(const SampleArgs<T>& a, const NoiseArgs<T>& nz, hipStream_t s) {
     ILQR_LAUNCH((sample_rollout_kernel<T, Dyn, PEN, STEPSTD>), dim3((a.S + 63) / 64, a.B), dim3(64), 0, s, a, nz);
 }
+// noise scenarios: lane g of a trajectory's row is scenario g mod M of sample g / M (S * M < 2^31: the host's check)
+template <typename T, typename Dyn, bool PEN, bool STEPSTD>
+void launch_sample_rollout_scn(const ScenarioArgs<T>& a, const NoiseArgs<T>& nz, hipStream_t s) {
+    const unsigned lanes = (unsigned)a.S << a.log2m;
+    ILQR_LAUNCH((sample_rollout_kernel<T, Dyn, PEN, STEPSTD, true>), dim3((lanes + 63u) / 64u, a.B), dim3(64), 0, s, a, nz);
+}
 template <typename T> void launch_sample_penalty_stats(const SampleArgs<T>& a, hipStream_t s) {
     ILQR_LAUNCH((sample_penalty_stats_kernel<T>), dim3(a.B), dim3(64), 0, s, a);
 }
@@ -488,6 +497,10 @@ template <typename T, typename Dyn> Ops<T> make_ops() {
             o.sampling.rollout_elite[0] = launch_sample_rollout<T, Dyn, false, true>;
             o.sampling.rollout_elite[1] = launch_sample_rollout<T, Dyn, true, true>;
             o.sampling.update_elite = launch_sample_update_elite<T, Dyn>;
+            o.sampling.rollout_scn[0][0] = launch_sample_rollout_scn<T, Dyn, false, false>;
+            o.sampling.rollout_scn[0][1] = launch_sample_rollout_scn<T, Dyn, true, false>;
+            o.sampling.rollout_scn[1][0] = launch_sample_rollout_scn<T, Dyn, false, true>;
+            o.sampling.rollout_scn[1][1] = launch_sample_rollout_scn<T, Dyn, true, true>;
         }
     }
     o.eval = [](const EvalArgs<T>& a, hipStream_t s) {

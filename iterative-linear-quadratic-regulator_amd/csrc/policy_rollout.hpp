@@ -218,13 +218,22 @@ struct SampleAt { int b, s; size_t B, L, l; };
 // and forms u_t before the clamp; advance(t, x, xn) moves x and the nominal on to t + 1; total(cost) is what the law stores
 // as the sample's cost (the cost itself, or the cost plus what the law adds to it in one add); finish(x) stores what the
 // law reports beside the cost.  Args (PolicyArgs, SampleArgs) brings B, S, N, integ, dt, params, rows, x0, lim, cost, Xs, Us.
+// A law with noise scenarios (LawScenarios<Law>::value: ScenarioLaw of sample_controls.hpp; Args then brings log2m) rolls
+// every sample out M = 2^log2m times: lane g = blockIdx.x * 64 + lane is scenario m = g mod M of sample s = g / M, so the M
+// scenarios of a sample are adjacent lanes of one wave and the tail guard retires whole groups.  Xs is then
+// [N+1][n_x][L * M], Us is stored by scenario 0 alone (the controls do not depend on the scenario), and in place of the
+// cost store and finish the law's finish_scenarios(value) reduces the M values of the sample across its lanes and stores
+// what it reports.  Everything of it stands under `if constexpr`: a law without scenarios compiles to the code it always did.
+template <typename Law> struct LawScenarios { static constexpr bool value = false; };
 template <typename T, typename Dyn, typename Law, typename Args>
 ILQR_DEV void sampled_rollout(const Args& a, const NoiseArgs<T>& nz) {
     constexpr int NX = Dyn::NX, NU = Dyn::NU;
     constexpr bool LIM = takes_limits<Dyn>();
     using PL = ParamLayout<Dyn::NSYS, NX, NU>;
+    constexpr bool SCN = LawScenarios<Law>::value;
     const int b = blockIdx.y;
-    const int s = blockIdx.x * 64 + threadIdx.x;
+    int s = blockIdx.x * 64 + threadIdx.x;
+    if constexpr (SCN) s >>= a.log2m;
     if (s >= a.S) return;
     const size_t B = a.B, L = B * (size_t)a.S, l = (size_t)b * a.S + s;
     const int N = a.N;
@@ -245,8 +254,13 @@ ILQR_DEV void sampled_rollout(const Args& a, const NoiseArgs<T>& nz) {
     T cost = T(0);
     auto store_x = [&](int t) {
         if (!a.Xs) return;
+        if constexpr (SCN) {
 #pragma unroll
-        for (int i = 0; i < NX; ++i) a.Xs[((size_t)t * NX + i) * L + l] = x[i];
+            for (int i = 0; i < NX; ++i) a.Xs[((((size_t)t * NX + i) * L + l) << a.log2m) + law.m] = x[i];
+        } else {
+#pragma unroll
+            for (int i = 0; i < NX; ++i) a.Xs[((size_t)t * NX + i) * L + l] = x[i];
+        }
     };
     for (int t = 0; t < N; ++t) {
         law.control(t, (t + 1 < N) ? t + 1 : t, x, u);
@@ -256,8 +270,15 @@ ILQR_DEV void sampled_rollout(const Args& a, const NoiseArgs<T>& nz) {
         }
         store_x(t);
         if (a.Us) {
+            if constexpr (SCN) {
+                if (law.m == 0) {
 #pragma unroll
-            for (int j = 0; j < NU; ++j) a.Us[((size_t)t * NU + j) * L + l] = u[j];
+                    for (int j = 0; j < NU; ++j) a.Us[((size_t)t * NU + j) * L + l] = u[j];
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < NU; ++j) a.Us[((size_t)t * NU + j) * L + l] = u[j];
+            }
         }
         cost += Cost<T, Dyn>::stage(p, a.dt, x, u);
         T xn[NX];
@@ -266,8 +287,12 @@ ILQR_DEV void sampled_rollout(const Args& a, const NoiseArgs<T>& nz) {
     }
     store_x(N);
     cost += Cost<T, Dyn>::terminal(p, x);
-    a.cost[l] = law.total(cost);
-    law.finish(x);
+    if constexpr (SCN) {
+        law.finish_scenarios(law.total(cost));
+    } else {
+        a.cost[l] = law.total(cost);
+        law.finish(x);
+    }
 }
 
 // The feedback law (ilqr_policy_rollout; NOISE: ilqr_policy_monte_carlo, x_0 and w drawn here):

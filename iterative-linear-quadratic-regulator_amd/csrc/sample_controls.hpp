@@ -68,6 +68,17 @@ template <typename T> struct SampleArgs {
     int* __restrict__ n_e;              // [B] of this round: min(E, n_finite)
 };
 
+// Noise scenarios (ilqr_set_sample_scenarios): what the scenario rollouts read beside SampleArgs.  It is a record of its
+// own behind SampleArgs, so the kernels without scenarios keep their argument layout and their code.
+// Here Xs is [N+1][n_x][L * M], scenario-innermost (lane l * M + m), and cost / pen / viol hold the aggregates.
+template <typename T> struct ScenarioArgs : SampleArgs<T> {
+    int log2m;                          // M = 2^log2m scenarios per sample, M <= 64
+    int agg;                            // ILQR_SCENARIO_MEAN / MAX / TAIL
+    int rank;                           // TAIL: k = min(max(ceil(level * M), 1), M), from the host
+    NoiseArgs<T> sn;                    // the scenarios' key, first trajectory, distribution, x0_std and w_std
+    T* __restrict__ scn_cost;           // [L * M] the scenario values v_m (J, or J + P), before the aggregate
+};
+
 // The state-limit penalty of a sample (PEN; the empty form costs nothing):
 //   P = sum_{t=1..N} al_phi(bounds_b, x_t, lam = 0, rho_b),   v = max(0, max_{t, q in mask} c_q(x_t))
 // al_phi sums a point's constraints q ascending from 0, and P takes the points t ascending; the sample's cost is
@@ -171,6 +182,98 @@ template <typename T, typename Dyn, bool PEN = false, bool STEPSTD = false> stru
     ILQR_DEV void finish(const T (&)[NX]) { pen.store(a, k.l); }
 };
 
+// The perturbation law under noise scenarios (ilqr_set_sample_scenarios): lane (s, m) rolls sample s out under scenario m,
+// which is Monte Carlo sample m of policy_noise_kernel under the scenarios' own key: x_0 += x0_std[b] (.) z(b, m, 0, stream 1)
+// in the constructor, w_t = w_std[b] (.) z(b, m, t, stream 0) drawn in control() beside the perturbation's draw (neither
+// depends on the state) and added in advance() in an add of its own, before the penalty reads x_{t+1}.  The perturbation is
+// PerturbLaw's, drawn at the sample index s as ever: the M scenarios of a sample apply the same controls.
+// finish_scenarios() reduces the M values of a sample over its M adjacent lanes -- xor butterflies over the masks
+// 1 .. M / 2 and, for the tail mean, M - 1 rotations through the group; no LDS, no atomics, a fixed order -- in double,
+// rounded to T once:
+//   any v_m not finite: NaN.   MEAN: tree(v) / M.   MAX: the largest v_m.
+//   TAIL: rank_m = 1 + the number of lanes m' with (v_m', m') < (v_m, m);  tree(rank_m >= k ? v_m : 0) / (M - k + 1)
+// tree is the sum of adjacent pairs level by level, which the butterfly leaves in every lane.  Lane m = 0 stores the
+// aggregate as the sample's cost, and with PEN tree(P_m) / M and the largest v; every lane stores its own v_m.
+// It is a law of its own around PerturbLaw, not a parameter of it: PerturbLaw's text, and with it the code of the kernels
+// without scenarios, stays what it was.
+template <typename T, typename Dyn, bool PEN, bool STEPSTD> struct ScenarioLaw : PerturbLaw<T, Dyn, PEN, STEPSTD> {
+    using Base = PerturbLaw<T, Dyn, PEN, STEPSTD>;
+    static constexpr int NX = Dyn::NX, NU = Dyn::NU;
+    const ScenarioArgs<T>& sa;
+    const int m;                    // the lane's scenario
+    T wsd[NX], wt[NX];              // w_std[b] (wave-uniform) and the disturbance of the step
+    bool has_w;
+
+    ILQR_DEV ScenarioLaw(const ScenarioArgs<T>& a_, const NoiseArgs<T>& nz_, const SampleAt& k_, T* mr, T (&x)[NX])
+        : Base(a_, nz_, k_, mr, x), sa(a_), m((int)((blockIdx.x * 64 + threadIdx.x) & ((1u << a_.log2m) - 1u))) {
+        const int b = k_.b;
+        if (sa.sn.x0_std) {
+            T sd0[NX], e0[NX];
+            uniform_load<T, NX>(sa.sn.x0_std + (size_t)b * NX, sd0);
+            noise_draw<T, NX>(sa.sn, (unsigned)m, (unsigned)b, 0u, 1u, sd0, e0);
+#pragma unroll
+            for (int i = 0; i < NX; ++i) x[i] += e0[i];
+        }
+        has_w = sa.sn.w_std != nullptr;
+        if (has_w) uniform_load<T, NX>(sa.sn.w_std + (size_t)b * NX, wsd);
+    }
+    ILQR_DEV void control(int t, int tn, const T (&x)[NX], T (&u)[NU]) {
+        Base::control(t, tn, x, u);
+        if (has_w) noise_draw<T, NX>(sa.sn, (unsigned)m, (unsigned)this->k.b, (unsigned)t, 0u, wsd, wt);
+    }
+    ILQR_DEV void advance(int t, T (&x)[NX], const T (&xn)[NX]) {
+        T xw[NX];
+#pragma unroll
+        for (int i = 0; i < NX; ++i) xw[i] = has_w ? xn[i] + wt[i] : xn[i];
+        Base::advance(t, x, xw);
+    }
+    // v is this lane's scenario value; the M lanes of the sample are all here (the tail guard retires whole groups)
+    ILQR_DEV void finish_scenarios(T v) {
+        const int M = 1 << sa.log2m;
+        const size_t l = this->k.l;
+        const double vd = (double)v;
+        int fin = (vd - vd == 0.0) ? 1 : 0;      // neither NaN nor an infinity
+        for (int x = 1; x < M; x <<= 1) fin &= __shfl_xor(fin, x, 64);
+        double r = vd;
+        if (sa.agg == ILQR_SCENARIO_MEAN) {
+            for (int x = 1; x < M; x <<= 1) r += __shfl_xor(r, x, 64);
+            r /= (double)M;
+        } else if (sa.agg == ILQR_SCENARIO_MAX) {
+            for (int x = 1; x < M; x <<= 1) { const double o = __shfl_xor(r, x, 64); r = o > r ? o : r; }
+        } else {
+            // the rank of (v, m) among the group's values, ties to the lower m: every other lane of the group in turn
+            const int base = (int)threadIdx.x - m;
+            int before = 0;
+            for (int j = 1; j < M; ++j) {
+                const int om = (m + j) & (M - 1);
+                const T ov = __shfl(v, base + om, 64);
+                before += (ov < v || (ov == v && om < m)) ? 1 : 0;
+            }
+            r = before + 1 >= sa.rank ? vd : 0.0;
+            for (int x = 1; x < M; x <<= 1) r += __shfl_xor(r, x, 64);
+            r /= (double)(M - sa.rank + 1);
+        }
+        sa.scn_cost[(l << sa.log2m) + (size_t)m] = v;
+        if constexpr (PEN) {
+            double P = (double)this->pen.P;
+            T viol = this->pen.v;
+            for (int x = 1; x < M; x <<= 1) {
+                P += __shfl_xor(P, x, 64);
+                const T o = __shfl_xor(viol, x, 64);
+                viol = o > viol ? o : viol;
+            }
+            if (m == 0) {
+                sa.pen[l] = (T)(P / (double)M);
+                sa.viol[l] = viol;
+            }
+        }
+        if (m == 0) sa.cost[l] = fin ? (T)r : (T)__builtin_nan("");
+    }
+};
+template <typename T, typename Dyn, bool PEN, bool STEPSTD> struct LawScenarios<ScenarioLaw<T, Dyn, PEN, STEPSTD>> {
+    static constexpr bool value = true;
+};
+
 // The rollout of a round's samples.  Launched with S = 1 it is the rollout of the nominal alone (cost_new / X_new): the
 // same code on the same controls, so the cost of a BEST call's result is the winning sample's cost bit for bit.
 // PEN (ilqr_set_sample_penalty): cost[l] = J + P, and pen[l] = P, viol[l] = v beside it.
@@ -178,6 +281,15 @@ template <typename T, typename Dyn, bool PEN = false, bool STEPSTD = false> stru
 template <typename T, typename Dyn, bool PEN = false, bool STEPSTD = false>
 __global__ void __launch_bounds__(64) sample_rollout_kernel(SampleArgs<T> a, NoiseArgs<T> nz) {
     sampled_rollout<T, Dyn, PerturbLaw<T, Dyn, PEN, STEPSTD>>(a, nz);
+}
+// SCN (ilqr_set_sample_scenarios): the same rollout under ScenarioLaw, M lanes per sample, grid (ceil(S * M / 64), B).  It
+// is an overload with a template parameter list and an argument record of its own, not a fifth defaulted parameter of the
+// template above: a template argument is part of a kernel's symbol even where it is defaulted, and the kernels without
+// scenarios keep their symbols, their argument layout and their code this way.
+template <typename T, typename Dyn, bool PEN, bool STEPSTD, bool SCN>
+__global__ void __launch_bounds__(64) sample_rollout_kernel(ScenarioArgs<T> a, NoiseArgs<T> nz) {
+    static_assert(SCN, "without scenarios the rollout is the template above");
+    sampled_rollout<T, Dyn, ScenarioLaw<T, Dyn, PEN, STEPSTD>>(a, nz);
 }
 
 // The weights of a round: one wave per trajectory over its contiguous [S] costs, each lane over its stride of the row and

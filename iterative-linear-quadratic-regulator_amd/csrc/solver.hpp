@@ -70,6 +70,9 @@ struct SolverBase {
     virtual int sample_penalty_report(const ilqr_sample_penalty_report_desc& d) = 0;
     virtual int set_sample_elites(int n_elite, int uniform, const double* std_min, const void* std_steps) = 0;
     virtual int sample_elite_report(const ilqr_sample_elite_report_desc& d) = 0;
+    virtual int set_sample_scenarios(int n_scenarios, int aggregate, double level, unsigned long long seed, int distribution,
+                                     const double* x0_std, const double* w_std) = 0;
+    virtual int sample_scenario_report(const ilqr_sample_scenario_report_desc& d) = 0;
 };
 
 int system_dims(int system, int n_x, int n_u);  // 1 if (system, n_x, n_u) is a known combination
@@ -289,6 +292,22 @@ template <typename T> struct EliteState {
     size_t L = 0, rounds = 0;
 };
 
+// The noise scenarios of the sampled search (ilqr_set_sample_scenarios) and what its last ilqr_sample_controls left for
+// ilqr_sample_scenario_report.  cost: the samples' scenario values [L][M] and, behind them, those of the nominal's own
+// rollout [B][M]; X: the nominal's M disturbed rollouts [N+1][n_x][B * M].
+template <typename T> struct ScenarioState {
+    bool on = false;
+    int log2m = 0, agg = 0, rank = 0, dist = 0;
+    unsigned long long seed = 0;
+    DevBuf<T> std;                // [2][B][n_x] x0_std, w_std in the handle's dtype
+    bool has_x0 = false, has_w = false;
+    DevBuf<T> cost, X;
+    // the report: valid while the handle's most recent sampling call was a sample_controls with scenarios that succeeded
+    bool report = false, has_X = false;
+    size_t L = 0;
+    size_t M() const { return (size_t)1 << log2m; }
+};
+
 // per-trajectory parameters (ilqr_set_batch_params): rows [n_sys + n_x][B] of the model (derived constants, x_target),
 // plant_rows [n_sys][B] of the MPC plant; device tensors of the handle's dtype
 template <typename T> struct BatchParams {
@@ -372,6 +391,7 @@ template <typename T> class SolverT : public SolverBase {
     SamplingBufs<T> smp;
     PenaltyState<T> pen;
     EliteState<T> el;
+    ScenarioState<T> scn;
 
     // (the device buffers free themselves after this body: DevBuf)
     ~SolverT() override {
@@ -1373,6 +1393,7 @@ template <typename T> class SolverT : public SolverBase {
         if ((rc = sampling_settle())) return rc;
         pen.report = false;          // (the most recent sampling call is no penalised search)
         el.report = false;
+        scn.report = false;
         const size_t nX = L * NX * (size_t)(N + 1), nU = L * NU * (size_t)N, nW = L * NX * (size_t)N;
         // the disturbances a Monte Carlo call was asked to return (none are drawn without w_std: those are zeros)
         const bool w_back = mc && mc->w_out && mc->w_std;
@@ -1503,7 +1524,12 @@ template <typename T> class SolverT : public SolverBase {
     int search_begin(size_t L, size_t rounds, size_t per_step, size_t steps) {
         pen.report = false;
         el.report = false;
+        scn.report = false;
         int rc;
+        if (scn.on) {
+            if ((rc = grow(scn.cost, (L + (size_t)B) * scn.M()))) return rc;
+            scn.L = L;
+        }
         if (el.on) {
             if ((rc = grow(el.Sd, (size_t)B * NU * N)) || (rc = grow(el.mask, L)) || (rc = grow(el.n_e, rounds * B))) return rc;
             el.L = L; el.rounds = rounds;
@@ -1533,12 +1559,25 @@ template <typename T> class SolverT : public SolverBase {
         int rc;
         if (a.pen) { a.pen_stats = pen.stats.p + row * B * 3; a.pen_counts = pen.counts.p + row * B; }
         if (a.Sd) a.n_e = el.n_e.p + row * B;
-        if ((rc = search_rollout(a, nz))) return rc;
+        if ((rc = search_rollout(a, nz, false))) return rc;
         if ((rc = timed(ILQR_PHASE_OTHER, [&] { (a.Sd ? ops.sampling.update_elite : ops.sampling.update)(a, stream); }))) return rc;
         if (a.pen && (rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.penalty_stats(a, stream); }))) return rc;
         return ILQR_OK;
     }
-    int search_rollout(const SampleArgs<T>& a, const NoiseArgs<T>& nz) {
+    // `nominal`: the rollout of the nominal alone (nominal_args).  With scenarios set it is the SCN instantiation: the
+    // scenarios' noise is keyed by their own seed at the call's first_trajectory, and the scenario values go to scn.cost
+    // (the nominal's behind the samples').
+    int search_rollout(const SampleArgs<T>& a, const NoiseArgs<T>& nz, bool nominal) {
+        if (scn.on) {
+            ScenarioArgs<T> sa{};
+            static_cast<SampleArgs<T>&>(sa) = a;
+            sa.log2m = scn.log2m; sa.agg = scn.agg; sa.rank = scn.rank;
+            sa.sn = noise_args(scn.seed, (int)nz.first, scn.dist);
+            sa.sn.x0_std = scn.has_x0 ? scn.std.p : nullptr;
+            sa.sn.w_std = scn.has_w ? scn.std.p + (size_t)B * NX : nullptr;
+            sa.scn_cost = scn.cost.p + (nominal ? scn.L * scn.M() : (size_t)0);
+            return timed(ILQR_PHASE_OTHER, [&] { ops.sampling.rollout_scn[a.Sd != nullptr][a.pen != nullptr](sa, nz, stream); });
+        }
         return timed(ILQR_PHASE_OTHER, [&] {
             (a.Sd ? ops.sampling.rollout_elite[a.pen != nullptr] : a.pen ? ops.sampling.rollout_pen : ops.sampling.rollout)(a, nz, stream);
         });
@@ -1563,17 +1602,19 @@ template <typename T> class SolverT : public SolverBase {
         if ((rc = search_desc_check(who, d, (unsigned long long)d.n_rounds, "n_rounds"))) return rc;
         if (!d.U_new && !d.cost_new && !d.X_new && !d.round_stats && !d.round_counts && !d.cost_samples && !d.U_samples)
             return bad("every output is NULL");
-        if ((rc = sample_total(who, d.n_samples, &L)) || (rc = sampling_supported(who)) || (rc = sampling_problem(who)) ||
-            (rc = sampling_settle()))
+        if ((rc = sample_total(who, d.n_samples, &L)) || (rc = scenario_total(who, L)) || (rc = sampling_supported(who)) ||
+            (rc = sampling_problem(who)) || (rc = sampling_settle()))
             return rc;
         const size_t Rn = (size_t)d.n_rounds;
         const size_t nU = L * NU * (size_t)N, nUb = (size_t)B * NU * N, nXb = (size_t)B * NX * (N + 1);
         // (controls: the update reads every sample's controls as the rollout stored them)
-        if ((rc = grow(smp.summaries, L + (size_t)B)) || (rc = grow(smp.controls, nU)) || (rc = grow(smp.nominal, nUb)) ||
+        // (with scenarios B more costs: the disturbance-free rollout behind X_new keeps its cost off cost_new)
+        if ((rc = grow(smp.summaries, L + (size_t)B * (scn.on ? 2 : 1))) || (rc = grow(smp.controls, nU)) || (rc = grow(smp.nominal, nUb)) ||
             (rc = grow(smp.weights, L + (size_t)B)) || (rc = grow(smp.winners, (size_t)B)) ||
             (rc = grow(smp.stats, Rn * B * 3)) || (rc = grow(smp.counts, Rn * B)))
             return rc;
         if (d.X_new && (rc = grow(smp.states, nXb))) return rc;
+        if (scn.on && d.X_new && (rc = grow(scn.X, nXb * scn.M()))) return rc;
         if ((rc = grow(staging, std::max({nUb, d.X_new ? nXb : (size_t)0, d.U_samples ? nU : (size_t)0})))) return rc;
         if ((rc = up_std({d.u_std}, NU)) || (rc = search_begin(L, Rn, Rn, 1))) return rc;
         SampleArgs<T> a = search_args(d, L);
@@ -1587,10 +1628,17 @@ template <typename T> class SolverT : public SolverBase {
         }
         // the nominal alone: the rollout at S = 1 (sample 0 is the nominal), its cost behind the samples' (a penalised call
         // launches it in any case: the report's penalty_new / violation_new come from it)
+        // With scenarios the same launch leaves the report's scenario_cost (and scenario_X), so it is launched in any case,
+        // and X_new, the disturbance-free rollout of U_new, takes one launch of the plain kernel.
         SampleArgs<T> f = nominal_args(a, L, 0);
-        f.Xs = d.X_new ? smp.states.p : nullptr;
-        if (d.cost_new || d.X_new || a.pen) {
-            if ((rc = search_rollout(f, nz))) return rc;
+        f.Xs = !d.X_new ? nullptr : scn.on ? scn.X.p : smp.states.p;
+        if (d.cost_new || d.X_new || a.pen || scn.on) {
+            if ((rc = search_rollout(f, nz, true))) return rc;
+        }
+        if (scn.on && d.X_new) {
+            SampleArgs<T> g = f;
+            g.Xs = smp.states.p; g.cost = f.cost + B;
+            if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.rollout(g, nz, stream); }))) return rc;
         }
         if (d.round_stats) ILQR_HIPCHK(hipMemcpyAsync(d.round_stats, smp.stats.p, Rn * B * 3 * sizeof(double), hipMemcpyDeviceToHost, stream));
         if (d.round_counts) ILQR_HIPCHK(hipMemcpyAsync(d.round_counts, smp.counts.p, Rn * B * sizeof(int), hipMemcpyDeviceToHost, stream));
@@ -1599,7 +1647,10 @@ template <typename T> class SolverT : public SolverBase {
         if (d.U_samples && (rc = down_traj(d.U_samples, smp.controls, L, NU, N))) return rc;
         if (d.U_new && (rc = down_traj(d.U_new, smp.nominal, (size_t)B, NU, N))) return rc;
         if (d.X_new && (rc = down_traj(d.X_new, smp.states, (size_t)B, NX, N + 1))) return rc;
-        return search_done(true);
+        if ((rc = search_done(true))) return rc;
+        scn.report = scn.on;
+        scn.has_X = d.X_new != nullptr;
+        return ILQR_OK;
     }
 
     // Sampled MPC (sampled_mpc.hpp): per step R rounds of the search above from x_0 = the plant state and the epilogue
@@ -1621,7 +1672,9 @@ template <typename T> class SolverT : public SolverBase {
         for (size_t i = 0; w_host && i < K * B * NX; ++i)
             if (!std::isfinite(w_host[i])) return bad("every w value must be finite");
         if (!d.u_out && !d.x_out && !d.cost_out && !d.U_plan && !d.round_stats && !d.round_counts) return bad("every output is NULL");
-        if ((rc = sample_total(who, d.n_samples, &L)) || (rc = sampling_supported(who)) || (rc = sampling_problem(who))) return rc;
+        if ((rc = sample_total(who, d.n_samples, &L)) || (rc = scenario_total(who, L)) || (rc = sampling_supported(who)) ||
+            (rc = sampling_problem(who)))
+            return rc;
         if (!mpc_ready) return fail(ILQR_ERR_STATE, who + " before mpc_reset / mpc_rearm");
         if (cfg.plant_integrator < 0) return fail(ILQR_ERR_STATE, who + ": the handle was created without a plant integrator");
         // (the search's J ignores state limits unless the penalty brings them in)
@@ -1661,7 +1714,7 @@ template <typename T> class SolverT : public SolverBase {
                 if ((rc = search_round(a, nz, row))) return rc;
             }
             if (plan_cost) {
-                if ((rc = search_rollout(nominal_args(a, L, k), nz))) return rc;
+                if ((rc = search_rollout(nominal_args(a, L, k), nz, true))) return rc;
             }
             m.step = (int)k;
             m.stats = (d.cost_out && !plan_cost) ? a.stats : nullptr;
@@ -1796,6 +1849,76 @@ template <typename T> class SolverT : public SolverBase {
         if (d.elite) ILQR_HIPCHK(hipMemcpyAsync(d.elite, el.mask.p, el.L * sizeof(int), hipMemcpyDeviceToHost, stream));
         if (d.round_n_elite) ILQR_HIPCHK(hipMemcpyAsync(d.round_n_elite, el.n_e.p, el.rounds * B * sizeof(int), hipMemcpyDeviceToHost, stream));
         if (d.std_steps && ((rc = grow(staging, (size_t)B * NU * N)) || (rc = down_traj(d.std_steps, el.Sd, (size_t)B, NU, N)))) return rc;
+        ILQR_HIPCHK(hipStreamSynchronize(stream));
+        return check_launch();
+    }
+
+    // ---- noise scenarios of the search (include/ilqr_hip.h, ilqr_set_sample_scenarios) ----------------------------------
+    // (every lane of a call's rollout has an int index: sampled_rollout)
+    int scenario_total(const std::string& who, size_t L) {
+        return !scn.on || L * scn.M() <= (size_t)std::numeric_limits<int>::max()
+                   ? ILQR_OK
+                   : fail(ILQR_ERR_INVALID_ARG, who + ": batch * n_samples * n_scenarios must be < 2^31");
+    }
+    // Everything is checked before the handle or the device is touched.  The standard deviations cross once, in the
+    // handle's dtype.
+    int set_sample_scenarios(int n_scenarios, int aggregate, double level, unsigned long long seed, int distribution,
+                             const double* x0_std, const double* w_std) override {
+        const std::string who = "set_sample_scenarios";
+        auto bad = [&](const char* what) { return fail(ILQR_ERR_INVALID_ARG, who + ": " + what); };
+        if (!ops.sampling.rollout_scn[0][0])
+            return fail(ILQR_ERR_UNSUPPORTED, who + ": supported for the pendulum, UA double pendulum and double pendulum only");
+        if (n_scenarios == 0) {
+            scn.on = scn.report = false;
+            return ILQR_OK;
+        }
+        if (n_scenarios < 1 || n_scenarios > 64 || (n_scenarios & (n_scenarios - 1)) != 0)
+            return bad("n_scenarios must be 0 or a power of two in 1..64");
+        if (aggregate != ILQR_SCENARIO_MEAN && aggregate != ILQR_SCENARIO_MAX && aggregate != ILQR_SCENARIO_TAIL) return bad("unknown aggregate");
+        if (distribution != ILQR_NOISE_GAUSSIAN && distribution != ILQR_NOISE_UNIFORM) return bad("unknown distribution");
+        if (aggregate == ILQR_SCENARIO_TAIL && !(level >= 0.0 && level <= 1.0)) return bad("level must be in [0, 1] (and not NaN)");
+        const size_t n = (size_t)B * NX;
+        std::vector<T> sd(2 * n, T(0));
+        size_t at = 0;
+        for (const double* r : {x0_std, w_std}) {
+            for (size_t i = 0; r && i < n; ++i) {
+                // (finite as the device holds it: a double beyond the handle's dtype would arrive there as +inf)
+                if (!std::isfinite(r[i]) || r[i] < 0.0 || r[i] > (double)std::numeric_limits<T>::max())
+                    return bad("every standard deviation must be finite in the handle's dtype and >= 0");
+                sd[at + i] = (T)r[i];
+            }
+            at += n;
+        }
+        if (int rc = grow(scn.std, 2 * n)) return rc;
+        ILQR_HIPCHK(hipMemcpyAsync(scn.std.p, sd.data(), sd.size() * sizeof(T), hipMemcpyHostToDevice, stream));
+        ILQR_HIPCHK(hipStreamSynchronize(stream));      // (sd outlives the copy)
+        int log2m = 0;
+        while ((1 << log2m) < n_scenarios) ++log2m;
+        scn.on = true;
+        scn.log2m = log2m; scn.agg = aggregate; scn.dist = distribution; scn.seed = seed;
+        scn.rank = 1;
+        if (aggregate == ILQR_SCENARIO_TAIL) {
+            // the rank rule of policy_risk_kernel: one rounded double product
+            const double kd = std::ceil(level * (double)n_scenarios);
+            scn.rank = kd < 1.0 ? 1 : kd > (double)n_scenarios ? n_scenarios : (int)kd;
+        }
+        scn.has_x0 = x0_std != nullptr; scn.has_w = w_std != nullptr;
+        scn.report = false;
+        return ILQR_OK;
+    }
+    // Downloads of what the last sample_controls with scenarios left in `scn`; only the layout conversion of X is launched.
+    int sample_scenario_report(const ilqr_sample_scenario_report_desc& d) override {
+        const std::string who = "sample_scenario_report";
+        if (!d.scenario_cost && !d.scenario_cost_samples && !d.scenario_X) return fail(ILQR_ERR_INVALID_ARG, who + ": every output is NULL");
+        if (!scn.report)
+            return fail(ILQR_ERR_STATE, who + ": the handle's most recent sampling call was not a sample_controls with scenarios set");
+        if (d.scenario_X && !scn.has_X) return fail(ILQR_ERR_STATE, who + ": scenario_X needs a sample_controls call with X_new");
+        const size_t M = scn.M(), nB = (size_t)B * M;
+        int rc;
+        if (d.scenario_cost) ILQR_HIPCHK(hipMemcpyAsync(d.scenario_cost, scn.cost.p + scn.L * M, nB * sizeof(T), hipMemcpyDeviceToHost, stream));
+        if (d.scenario_cost_samples)
+            ILQR_HIPCHK(hipMemcpyAsync(d.scenario_cost_samples, scn.cost.p, scn.L * M * sizeof(T), hipMemcpyDeviceToHost, stream));
+        if (d.scenario_X && ((rc = grow(staging, nB * NX * (size_t)(N + 1))) || (rc = down_traj(d.scenario_X, scn.X, nB, NX, N + 1)))) return rc;
         ILQR_HIPCHK(hipStreamSynchronize(stream));
         return check_launch();
     }

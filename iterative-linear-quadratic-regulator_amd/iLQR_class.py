@@ -21,9 +21,9 @@ import numpy as np
 from . import _lib
 # (the names of the two modules beside this file stay importable from here)
 from .setter_args import _bounds, batch_param_rows, control_limits, mpc_multiplier_mode, state_limits  # noqa: F401
-from .sampling import (ELITE_FIELDS, PENALTY_FIELDS, PolicyMonteCarlo, PolicyRollout, SampledControls, SampledMPC,  # noqa: F401
+from .sampling import (ELITE_FIELDS, PENALTY_FIELDS, SCENARIO_FIELDS, PolicyMonteCarlo, PolicyRollout, SampledControls, SampledMPC,  # noqa: F401
                        _with_penalty_fields, has_policy_kernels, policy_monte_carlo_args, policy_risk_args,
-                       policy_risk_record, policy_rollout_args, sample_controls_args, sample_elites_args, sample_penalty_args, sampled_mpc_args, table_columns,
+                       policy_risk_record, policy_rollout_args, sample_controls_args, sample_elites_args, sample_penalty_args, sample_scenarios_args, sampled_mpc_args, table_columns,
                        unbatch)
 from .systems.system_base import System, ready
 
@@ -115,6 +115,7 @@ class iLQR:
         self._h.set_problem(x_0.reshape(self.B, self.n_x), U_init.reshape(self.B, self.n_u, self.N))
         self.sample_penalty = None
         self.sample_elites = None
+        self.sample_scenarios = None
         self.status = None
         self.iterations = None
 
@@ -419,6 +420,31 @@ class iLQR:
             rec.update(elite_samples=unbatch(rep["elite"].astype(bool), self.batched, axis=0))
         return rec
 
+    # ---- noise scenarios in the sampled search ---------------------------------------------------------
+    def set_sample_scenarios(self, n_scenarios, aggregate="mean", level=None, seed=0, distribution="gaussian", x_0_std=None,
+                             disturbance_std=None):
+        """Roll every sample of sample_controls and sampled_mpc out under n_scenarios = M noise scenarios drawn on the
+        device and take a risk measure of its M scenario costs as the sample's cost (include/ilqr_hip.h,
+        ilqr_set_sample_scenarios): aggregate="mean", "max" (the worst case) or "tail" (the mean of the upper tail from
+        the ceil(level * M)-th smallest cost upwards, CVaR; level in [0, 1] is required there and refused otherwise).  M
+        is a power of two in 1..64.  Scenario m of a trajectory is sample m of policy_monte_carlo with the same seed,
+        distribution, x_0_std and disturbance_std (([B,] n_x), None: nothing of that kind) and feedback=False through the
+        model: every sample of every round and every MPC step meets the same M disturbances, while the control
+        perturbation stays the search's own.  Everything behind the cost -- weights, argmin, softmin, elites, the
+        penalty, apply=True, the MPC loop -- reads the aggregate.  None or 0 clears the state.  Only the two sampling
+        calls read it."""
+        a = sample_scenarios_args(self.system, self.B, n_scenarios, aggregate, level, seed, distribution, x_0_std,
+                                  disturbance_std, self.dtype)
+        self._h.set_sample_scenarios(**a._asdict())
+        self.sample_scenarios = None if a.n_scenarios == 0 else a.n_scenarios
+
+    def _scenario_record(self, S, samples, trajectories):
+        """The scenarios' attributes of a SampledControls, {} while no scenarios are set."""
+        if self.sample_scenarios is None:
+            return {}
+        rep = self._h.sample_scenario_report(S, self.sample_scenarios, samples, trajectories)
+        return {k: self._out(v) for k, v in rep.items()}
+
     # ---- sampled control search ---------------------------------------------------------------------
     def sample_controls(self, n_samples, rounds=1, seed=0, u_std=None, mode="best", temperature=None, smoothing=0.0,
                         distribution="gaussian", first_trajectory=0, first_round=0, samples=False, trajectories=False,
@@ -439,13 +465,16 @@ class iLQR:
         round_n_violating (penalty_samples, violation_samples with samples=True), and apply=True compares the penalised
         costs: no trajectory is made worse in the penalised sense.  After set_sample_elites every round weighs its best
         samples only and the next one draws with their spread: the record then carries u_std_steps and round_n_elite
-        (elite_samples with samples=True)."""
+        (elite_samples with samples=True).  After set_sample_scenarios every cost is the aggregate over the noise scenarios
+        and the record carries scenario_cost (scenario_cost_samples with samples=True, scenario_X with trajectories=True);
+        X stays the disturbance-free rollout of U."""
         a = sample_controls_args(self.system, self.N, self.B, self.batched, n_samples, rounds, seed, u_std, mode, temperature,
                                  smoothing, distribution, first_trajectory, first_round)
         U_start = self._h.get(_lib.U) if apply else None
         out = self._h.sample_controls(**a._asdict(), samples=samples, trajectories=trajectories)
         penalty = self._penalty_record(a.n_samples, a.rounds, None, samples)      # (before apply=True touches the handle again)
         penalty.update(self._elite_record(a.n_samples, a.rounds, None, samples))
+        penalty.update(self._scenario_record(a.n_samples, samples, trajectories))
         stats, counts = out.pop("round_stats"), out.pop("round_counts")
         cost_start = stats[0, :, 0].astype(self.dtype)
         applied = None
@@ -475,7 +504,8 @@ class iLQR:
         round_n_violating rows of every step, and with samples=True penalty_samples and violation_samples of the last
         step's last round.  The multipliers of the state-limited solver are neither read nor changed.  After
         set_sample_elites every step's rounds are those of sample_controls with elites, each step starting from u_std
-        again; the record carries round_n_elite, and u_std_steps (elite_samples with samples=True) of the last step."""
+        again; the record carries round_n_elite, and u_std_steps (elite_samples with samples=True) of the last step.
+        After set_sample_scenarios every step plans under the same noise scenarios and every cost is their aggregate."""
         if self.plant is None:
             raise ValueError("construct the solver with plant=<System> to run MPC steps")
         a = sampled_mpc_args(self.system, self.N, self.B, self.batched, n_steps, n_samples, rounds, seed, u_std, mode,

@@ -268,8 +268,14 @@ PENALTY_FIELDS = ("penalty", "violation") + _lib.SAMPLE_PENALTY_STATS + ("round_
 ELITE_FIELDS = ("u_std_steps", "round_n_elite", "elite_samples")
 
 
+# What SampledControls gains while noise scenarios are set (iLQR.set_sample_scenarios), in the same way: the scenario costs
+# of U, and with samples=True / trajectories=True those of the last round's samples and the disturbed rollouts of U.
+# SampledMPC has the attributes too; there they stay None (its costs are the aggregates).
+SCENARIO_FIELDS = ("scenario_cost", "scenario_cost_samples", "scenario_X")
+
+
 def _with_penalty_fields(record):
-    return _with_fields(record, PENALTY_FIELDS + ELITE_FIELDS)
+    return _with_fields(record, PENALTY_FIELDS + ELITE_FIELDS + SCENARIO_FIELDS)
 
 
 SampledControls = _with_penalty_fields(namedtuple(
@@ -288,7 +294,11 @@ violation of its best sample (NaN with no finite sample) and the number of finit
 violation_tol; penalty_samples, violation_samples ([B,] S) of the last round with samples=True.  While elites are set
 (set_sample_elites) round_ess is the effective sample size of the elites' weights, and: u_std_steps ([B,] n_u, N): the
 standard deviations after the last round; round_n_elite (R, [B]) int: the elites of every round; elite_samples ([B,] S)
-bool of the last round with samples=True."""
+bool of the last round with samples=True.  While noise scenarios are set (set_sample_scenarios) every cost above is the
+aggregate over the M scenarios, violation / violation_samples are the maximum and penalty / penalty_samples the mean over
+them, X stays the disturbance-free rollout of U, and: scenario_cost ([B,] M): the scenario costs of U;
+scenario_cost_samples ([B,] S, M) of the last round with samples=True; scenario_X ([B,] M, n_x, N + 1), the M disturbed
+rollouts of U, with trajectories=True."""
 
 _SEARCH_FIELDS = [("n_samples", int), ("rounds", int), ("seed", int), ("u_std", ROWS), ("mode", int), ("temperature", float),
                   ("smoothing", float), ("distribution", int), ("first_trajectory", int), ("first_round", int)]
@@ -336,7 +346,9 @@ violation (n_steps, [B]): P and the violation of each step's plan ("best" mode: 
 round_penalty_start, round_penalty_best, round_violation_best, round_n_violating (n_steps, R, [B]) as SampledControls';
 penalty_samples, violation_samples ([B,] S) of the last step's last round with samples=True.  While elites are set
 (set_sample_elites): u_std_steps ([B,] n_u, N) after the last step's last round, round_n_elite (n_steps, R, [B]), and
-elite_samples ([B,] S) of the last step's last round with samples=True."""
+elite_samples ([B,] S) of the last step's last round with samples=True.  While noise scenarios are set
+(set_sample_scenarios) every cost is the aggregate over the scenarios; scenario_cost, scenario_cost_samples and scenario_X
+stay None."""
 
 SampledMpcArgs = NamedTuple("SampledMpcArgs", [("n_steps", int)] + _SEARCH_FIELDS + [("w", ROWS)])
 
@@ -424,6 +436,51 @@ def sample_elites_args(system, N, B, batched, n_elite, std_min=0.0, uniform=True
             raise ValueError(f"std_steps must have shape {want}, but got {steps.shape}")
         steps = held("std_steps", np.ascontiguousarray(steps.reshape(B, m, int(N))))
     return SampleElitesArgs(n_elite=E, uniform=bool(uniform), std_min=lo, std_steps=steps)
+
+
+# ---- noise scenarios -------------------------------------------------------------------------------------------------
+SampleScenariosArgs = NamedTuple("SampleScenariosArgs", [("n_scenarios", int), ("aggregate", int), ("level", float), ("seed", int),
+                                                         ("distribution", int), ("x0_std", ROWS), ("w_std", ROWS)])
+
+
+def sample_scenarios_args(system, B, n_scenarios, aggregate="mean", level=None, seed=0, distribution="gaussian", x_0_std=None,
+                          disturbance_std=None, dtype=None):
+    """Validated arguments of ``ilqr_set_sample_scenarios`` as (M, aggregate code, level, seed, distribution code, x0_std,
+    w_std): the standard deviations (B, n_x) float64 or None -- (n_x,) is broadcast over the batch; n_scenarios None or 0
+    clears the state: (0, 0, 0.0, 0, 0, None, None).  Raises ValueError for a system without the scenario kernels (linear
+    and user-defined systems), an n_scenarios that is not an integer power of two in 1..64, an unknown aggregate or
+    distribution, a level that is missing, NaN or outside [0, 1] with "tail" or given with another aggregate, a seed
+    outside [0, 2^64), or a standard deviation of a wrong shape, negative or not finite (in ``dtype`` too, where one is
+    given).  Pure host code (no GPU)."""
+    refuse_unsupported(system, "noise scenarios are")
+    M = 0 if n_scenarios is None else _count("n_scenarios", n_scenarios, 0)
+    if M == 0:
+        return SampleScenariosArgs(n_scenarios=0, aggregate=0, level=0.0, seed=0, distribution=0, x0_std=None, w_std=None)
+    if M > _lib.SCENARIO_MAX_COUNT or M & (M - 1):
+        raise ValueError(f"n_scenarios must be a power of two in 1..{_lib.SCENARIO_MAX_COUNT}, got {n_scenarios!r}")
+    agg = _choice("aggregate", aggregate, _lib.SCENARIO_AGGREGATES)
+    if agg == _lib.SCENARIO_TAIL:
+        if level is None or isinstance(level, bool) or not 0.0 <= float(level) <= 1.0:
+            raise ValueError(f"level must be in [0, 1] with aggregate='tail', got {level!r}")
+        p = float(level)
+    else:
+        if level is not None:
+            raise ValueError(f"level is read with aggregate='tail' only, got {level!r} with {aggregate!r}")
+        p = 0.0
+    seed = _seed(seed)
+    dist = _choice("distribution", distribution, _lib.NOISE_DISTRIBUTIONS)
+    B, n = int(B), system.n_x
+
+    def held(name, v):
+        a = _std_rows(name, v, B, n)
+        if a is not None and dtype is not None:
+            with np.errstate(over="ignore"):
+                if not np.isfinite(a.astype(dtype)).all():
+                    raise ValueError(f"{name} must be finite and >= 0")
+        return a
+
+    return SampleScenariosArgs(n_scenarios=M, aggregate=agg, level=p, seed=seed, distribution=dist,
+                               x0_std=held("x_0_std", x_0_std), w_std=held("disturbance_std", disturbance_std))
 
 
 # ---- results: the library's arrays and tables, as the records hold them ------------------------------------------------
