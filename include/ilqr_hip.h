@@ -539,6 +539,65 @@ typedef struct ilqr_monte_carlo_risk_desc {
 } ilqr_monte_carlo_risk_desc;
 int ilqr_policy_monte_carlo_risk(ilqr_handle h, const ilqr_monte_carlo_desc* d, const ilqr_monte_carlo_risk_desc* r);
 
+/* ---- policy Monte Carlo: per-step state and control envelopes on the device (build extension) ----------------
+ * ilqr_policy_monte_carlo(h, d) -- with r != NULL ilqr_policy_monte_carlo_risk(h, d, r) -- and, computed behind the rollout
+ * on the same stream, the fan chart of its samples: the band the states and the applied controls stay in at every step,
+ * and the number of samples outside the state limits at step t, without the [B][S] sample trajectories crossing to the
+ * host.  Every output of d and r has the bits the call gives without e, and every output of d may be NULL as long as one
+ * of e's is not.
+ * The sample set: for trajectory b, F = its samples with a finite cost, n = n_finite of them (the set of the statistics and
+ * of the risk measures).
+ * The rows: state component i at step t = 0..N, v_s = x_t[i] of sample s; control component j at step t = 0..N-1, v_s = the
+ * control that was applied, after the clamp: the values the call returns as X and U, in the handle's dtype.  -0 is taken
+ * as +0.  Per row, in double over s in F:
+ *   mean = (sum v_s) / n        std = sqrt(sum (v_s - mean)^2 / n)   (population; a second pass)        min, max
+ * Sums run in a fixed order (each lane of a wave over its stride of the row, s ascending, then a butterfly over the
+ * wave); there are no floating-point atomics and no result depends on scheduling.
+ * Per row and level p in [0, 1] (at most 16): the order statistic v_(k_p) by exactly the rank rule and total order of
+ * ilqr_policy_monte_carlo_risk -- k_p = min(max(ceil(p * n), 1), n) from one rounded double product, the values ordered
+ * as the unsigned integers of their bit patterns -- so the result is exact, p = 0 gives the row's min and p = 1 its max.
+ * k_p is one value per trajectory and level, the same for every row: rank [B][Q].
+ * Per step t = 0..N: step_violating[b][t] = the number of s in F with max_j max(0, c_j(x_t)) > d->violation_tol, c_j the
+ * finite state bounds of b (ilqr_set_state_limits, or b's row of ilqr_set_batch_limits) evaluated by the expression and in
+ * the dtype of the rollout's `violation`.  t = 0 counts 0 (the constraints run over t = 1..N); without state limits, and
+ * on a user-defined system, every count is 0.  A sample is counted at some step exactly when its violation >
+ * violation_tol, so the samples flagged at one step at least are n_violating of them.
+ * With n == 0 every moment and quantile is NaN, every rank 0 and every count 0.
+ * Nothing is computed for a group of outputs the caller left out (the x moments, the u moments, x_quantile, u_quantile,
+ * rank, step_violating); the sample trajectories stay on the device unless d->X / d->U ask for them.
+ * Synchronous; changes nothing another entry reads; ends the reports of ilqr_sample_penalty_report and
+ * ilqr_sample_elite_report as ilqr_policy_monte_carlo does.  A user-defined system is supported as there.
+ * Returns what ilqr_policy_monte_carlo (r == NULL) or ilqr_policy_monte_carlo_risk returns for h, d and r (except that every
+ * output of d may be NULL), and ILQR_ERR_INVALID_ARG -- before any device work, the handle unchanged -- for a NULL e, a
+ * wrong struct_size, a non-zero reserved, n_levels outside 0..16, n_levels > 0 with levels NULL, a level that is NaN or
+ * outside [0, 1], x_quantile, u_quantile or rank given with n_levels == 0, or every output of e NULL.
+ * ilqr_policy_envelope_resident_cap(): the longest row (n_samples) the kernel holds in registers and reads from memory
+ * once; longer rows are streamed once per pass.  The results do not depend on it.
+ * ILQR_ABI_VERSION stays 5 with these entries, for the reasons given at ilqr_set_batch_limits: they are additive. */
+enum { ILQR_ENVELOPE_MAX_LEVELS = 16 };
+typedef struct ilqr_monte_carlo_envelope_desc {
+    uint32_t struct_size;      /* = sizeof(ilqr_monte_carlo_envelope_desc) */
+    int32_t n_levels;          /* Q, 0..16 */
+    int32_t reserved[2];       /* 0 */
+    const double* levels;      /* [Q] in [0, 1] */
+    double* x_mean;            /* [B][n_x][N+1]   any output may be NULL, not all of the struct's */
+    double* x_std;
+    double* x_min;
+    double* x_max;
+    double* u_mean;            /* [B][n_u][N] */
+    double* u_std;
+    double* u_min;
+    double* u_max;
+    double* x_quantile;        /* [B][Q][n_x][N+1] */
+    double* u_quantile;        /* [B][Q][n_u][N] */
+    int32_t* rank;             /* [B][Q]  k_p */
+    int32_t* step_violating;   /* [B][N+1] */
+} ilqr_monte_carlo_envelope_desc;
+int ilqr_policy_monte_carlo_envelope(ilqr_handle h, const ilqr_monte_carlo_desc* d,
+                                     const ilqr_monte_carlo_risk_desc* r /* may be NULL */,
+                                     const ilqr_monte_carlo_envelope_desc* e);
+int ilqr_policy_envelope_resident_cap(void);
+
 /* ---- sampled control search: best-of-S and MPPI updates of U on the device (build extension) -----------------
  * A cheap search over control sequences before any Riccati sweep is paid for.  For trajectory b, round r = 0..R-1 draws S
  * temporally correlated perturbations of the nominal controls, rolls each out open loop through the model and replaces

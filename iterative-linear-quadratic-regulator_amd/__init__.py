@@ -10,7 +10,7 @@ Import name: ``ilqr_amd`` (this directory's name is not a valid Python identifie
 from . import _lib  # noqa: F401
 from .iLQR_class import (iLQR, horizon_steps, batch_param_rows, control_limits, state_limits,  # noqa: F401
                          mpc_multiplier_mode, policy_rollout_args, PolicyRollout,
-                         policy_monte_carlo_args, policy_risk_args, PolicyMonteCarlo, sample_controls_args, SampledControls,
+                         policy_monte_carlo_args, policy_risk_args, policy_envelope_args, PolicyMonteCarlo, sample_controls_args, SampledControls,
                          sampled_mpc_args, SampledMPC, sample_penalty_args, sample_elites_args, sample_scenarios_args)
 from .systems import (System, MyPendulum, MyUADoublePendulum, MyDoublePendulum,  # noqa: F401
                       MyLinearSystem)

@@ -46,6 +46,7 @@ SYMBOLS = (
     "ilqr_set_batch_limits", "ilqr_policy_rollout", "ilqr_policy_monte_carlo", "ilqr_sample_controls",
     "ilqr_sampled_mpc", "ilqr_set_sample_penalty", "ilqr_sample_penalty_report", "ilqr_set_sample_elites",
     "ilqr_sample_elite_report", "ilqr_policy_monte_carlo_risk", "ilqr_set_sample_scenarios", "ilqr_sample_scenario_report",
+    "ilqr_policy_monte_carlo_envelope", "ilqr_policy_envelope_resident_cap",
 )
 # ilqr_set_batch_params: which rows
 BATCH_MODEL, BATCH_PLANT = 0, 1
@@ -66,6 +67,9 @@ MONTE_CARLO_COUNTS = ("n_finite", "n_violating")
 # ilqr_policy_monte_carlo_risk: the rows of its tables (ILQR_RISK_*), and the caps on levels and thresholds
 RISK_ROWS = ("cost", "deviation", "violation")
 RISK_MAX_LEVELS = RISK_MAX_THRESHOLDS = 16
+# ilqr_policy_monte_carlo_envelope: the planes of its moments per row, and the cap on its levels
+ENVELOPE_MOMENTS = ("mean", "std", "min", "max")
+ENVELOPE_MAX_LEVELS = 16
 # ilqr_sample_controls: the update of the nominal, and the columns of a round's statistics
 SAMPLE_BEST, SAMPLE_SOFTMIN = 0, 1
 SAMPLE_MODES = {"best": SAMPLE_BEST, "softmin": SAMPLE_SOFTMIN}
@@ -125,6 +129,20 @@ class MonteCarloRiskDesc(C.Structure):
         ("levels", C.POINTER(C.c_double)), ("thresholds", C.POINTER(C.c_double)),
         ("quantile", C.POINTER(C.c_double)), ("tail_mean", C.POINTER(C.c_double)),
         ("rank", C.POINTER(C.c_int32)), ("exceed", C.POINTER(C.c_int32)),
+    ]
+
+
+class MonteCarloEnvelopeDesc(C.Structure):
+    """ilqr_monte_carlo_envelope_desc (include/ilqr_hip.h), field for field."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("n_levels", C.c_int32), ("reserved", C.c_int32 * 2),
+        ("levels", C.POINTER(C.c_double)),
+        ("x_mean", C.POINTER(C.c_double)), ("x_std", C.POINTER(C.c_double)), ("x_min", C.POINTER(C.c_double)),
+        ("x_max", C.POINTER(C.c_double)),
+        ("u_mean", C.POINTER(C.c_double)), ("u_std", C.POINTER(C.c_double)), ("u_min", C.POINTER(C.c_double)),
+        ("u_max", C.POINTER(C.c_double)),
+        ("x_quantile", C.POINTER(C.c_double)), ("u_quantile", C.POINTER(C.c_double)),
+        ("rank", C.POINTER(C.c_int32)), ("step_violating", C.POINTER(C.c_int32)),
     ]
 
 
@@ -248,6 +266,10 @@ def load():
     lib.ilqr_policy_rollout.argtypes = [vp, C.POINTER(PolicyRolloutDesc)]
     lib.ilqr_policy_monte_carlo.argtypes = [vp, C.POINTER(MonteCarloDesc)]
     lib.ilqr_policy_monte_carlo_risk.argtypes = [vp, C.POINTER(MonteCarloDesc), C.POINTER(MonteCarloRiskDesc)]
+    lib.ilqr_policy_monte_carlo_envelope.argtypes = [vp, C.POINTER(MonteCarloDesc), C.POINTER(MonteCarloRiskDesc),
+                                                     C.POINTER(MonteCarloEnvelopeDesc)]
+    lib.ilqr_policy_envelope_resident_cap.argtypes = []
+    lib.ilqr_policy_envelope_resident_cap.restype = ci
     lib.ilqr_sample_controls.argtypes = [vp, C.POINTER(SampleControlsDesc)]
     lib.ilqr_sampled_mpc.argtypes = [vp, C.POINTER(SampledMpcDesc)]
     lib.ilqr_set_sample_penalty.argtypes = [vp, C.POINTER(cd), cd]
@@ -260,6 +282,12 @@ def load():
         raise RuntimeError("libilqr_hip.so ABI version mismatch: rebuild the library")
     _lib = lib
     return lib
+
+
+def envelope_resident_cap():
+    """The longest row (n_samples) policy_envelope_kernel holds in registers, as the loaded library was built
+    (ilqr_policy_envelope_resident_cap); longer rows take its streaming path.  0: every row streams."""
+    return int(load().ilqr_policy_envelope_resident_cap())
 
 
 def device_count():
@@ -591,14 +619,17 @@ class Handle:
 
     def policy_monte_carlo(self, n_samples, seed=0, x0_std=None, w_std=None, distribution=NOISE_GAUSSIAN, plant_rows=None,
                            integrator=-1, feedback=True, violation_tol=0.0, first_trajectory=0, samples=False,
-                           trajectories=False, noise=False, statistics=True, levels=None, thresholds=None):
+                           trajectories=False, noise=False, statistics=True, levels=None, thresholds=None, envelope=None):
         """policy_rollout with x_0 and the disturbance drawn on the device and per-trajectory statistics computed there
         (include/ilqr_hip.h, ilqr_policy_monte_carlo).  x0_std, w_std (B, n_x) float64 or None, plant_rows (B, S, n_sys)
         float64 or None.  Returns a dict: stats (B, 7) float64 and counts (B, 2) int32 (with statistics); cost, x_final,
         deviation, violation (with samples); X, U (with trajectories); x0_out (B, S, n_x), w_out (B, S, N, n_x) (with
         noise).  With levels (Q,) or thresholds (B, 3, M) float64 the call is ilqr_policy_monte_carlo_risk and the dict
         also holds quantile, tail_mean (B, 3, Q) float64 and rank (B, Q) int32 (with levels), exceed (B, 3, M) int32 (with
-        thresholds)."""
+        thresholds).  With envelope (Q,) float64 -- Q may be 0 -- the call is ilqr_policy_monte_carlo_envelope and the dict
+        also holds x_mean, x_std, x_min, x_max (B, n_x, N + 1), u_mean, u_std, u_min, u_max (B, n_u, N) float64 and
+        step_violating (B, N + 1) int32, and with Q >= 1 x_quantile (B, Q, n_x, N + 1), u_quantile (B, Q, n_u, N) float64 and
+        envelope_rank (B, Q) int32."""
         B, S, n, m, N = self.B, int(n_samples), self.n_x, self.n_u, self.N
         Sa = max(S, 0)
         d, keep = self._desc(MonteCarloDesc, n_samples=S, integrator=integrator, feedback=bool(feedback),
@@ -617,9 +648,25 @@ class Handle:
         if noise:
             shapes.update(x0_out=(B, Sa, n), w_out=(B, Sa, N, n))
         out = self._outputs(d, shapes, dtypes={"stats": np.float64, "counts": np.int32})
-        if levels is None and thresholds is None:
+        if levels is None and thresholds is None and envelope is None:
             self._chk(self.lib.ilqr_policy_monte_carlo(self.h, C.byref(d)))
             return out
+        e = None
+        if envelope is not None:
+            e = MonteCarloEnvelopeDesc()
+            e.struct_size = C.sizeof(MonteCarloEnvelopeDesc)
+            self._rows_in(e, keep, "levels", envelope, (None,), "envelope levels", free="Q")
+            e.n_levels = Q = len(keep[-1])
+            shapes = {f"x_{k}": (B, n, N + 1) for k in ENVELOPE_MOMENTS}
+            shapes.update({f"u_{k}": (B, m, N) for k in ENVELOPE_MOMENTS})
+            shapes.update(step_violating=(B, N + 1))
+            if Q:
+                shapes.update(x_quantile=(B, Q, n, N + 1), u_quantile=(B, Q, m, N), rank=(B, Q))
+            dtypes = {k: np.int32 if k in ("rank", "step_violating") else np.float64 for k in shapes}
+            out.update(self._outputs(e, shapes, dtypes=dtypes, names={"rank": "envelope_rank"}))
+            if levels is None and thresholds is None:
+                self._chk(self.lib.ilqr_policy_monte_carlo_envelope(self.h, C.byref(d), None, C.byref(e)))
+                return out
         r, shapes = MonteCarloRiskDesc(), {}
         r.struct_size = C.sizeof(MonteCarloRiskDesc)
         if levels is not None:
@@ -632,7 +679,10 @@ class Handle:
             shapes.update(exceed=(B, 3, M))
         out.update(self._outputs(r, shapes, dtypes={"quantile": np.float64, "tail_mean": np.float64, "rank": np.int32,
                                                     "exceed": np.int32}))
-        self._chk(self.lib.ilqr_policy_monte_carlo_risk(self.h, C.byref(d), C.byref(r)))
+        if e is not None:
+            self._chk(self.lib.ilqr_policy_monte_carlo_envelope(self.h, C.byref(d), C.byref(r), C.byref(e)))
+        else:
+            self._chk(self.lib.ilqr_policy_monte_carlo_risk(self.h, C.byref(d), C.byref(r)))
         return out
 
     def sample_controls(self, n_samples, rounds=1, seed=0, u_std=None, mode=SAMPLE_BEST, temperature=1.0, smoothing=0.0,

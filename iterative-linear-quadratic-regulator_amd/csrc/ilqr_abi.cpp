@@ -309,6 +309,15 @@ int ilqr_policy_monte_carlo_risk(ilqr_handle h, const ilqr_monte_carlo_desc* d, 
     if (!rc) rc = sampling_entry(h, r, "policy_monte_carlo_risk", "ilqr_monte_carlo_risk_desc");
     return rc ? rc : h->impl->policy_monte_carlo_risk(*d, *r);
 }
+int ilqr_policy_monte_carlo_envelope(ilqr_handle h, const ilqr_monte_carlo_desc* d, const ilqr_monte_carlo_risk_desc* r,
+                                     const ilqr_monte_carlo_envelope_desc* e) {
+    const char* who = "policy_monte_carlo_envelope";
+    int rc = sampling_entry(h, d, who, "ilqr_monte_carlo_desc");
+    if (!rc && r) rc = sampling_entry(h, r, who, "ilqr_monte_carlo_risk_desc");
+    if (!rc) rc = sampling_entry(h, e, who, "ilqr_monte_carlo_envelope_desc");
+    return rc ? rc : h->impl->policy_monte_carlo_envelope(*d, r, *e);
+}
+int ilqr_policy_envelope_resident_cap(void) { return ilqr::kEnvelopeCap; }
 int ilqr_sample_controls(ilqr_handle h, const ilqr_sample_controls_desc* d) {
     const int rc = sampling_entry(h, d, "sample_controls", "ilqr_sample_controls_desc");
     return rc ? rc : h->impl->sample_controls(*d);

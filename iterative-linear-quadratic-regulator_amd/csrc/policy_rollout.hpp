@@ -634,6 +634,231 @@ __global__ void __launch_bounds__(64) policy_risk_kernel(const T* __restrict__ c
     }
 }
 
+// ---- the envelope of a Monte Carlo call (include/ilqr_hip.h, ilqr_policy_monte_carlo_envelope) -----------------------
+// Per (trajectory b, step t, component) the S values of the samples are one contiguous row of Xs / Us, beside b's cost row
+// that says which samples are finite (F, n of them: the set of the statistics and the risk measures).  One wave per row:
+// mean, std (population, second pass), min, max in double and the order statistics of up to 16 levels, by the rank rule
+// and the key order of policy_risk_kernel.  -0 is taken as +0 throughout: a value is key_value(cost_key(v)).
+// A row of at most kEnvelopeCap values is read from memory once and held in registers as keys, kEnvelopeHeld a lane (lane
+// holds s = lane + 64 j in slot j), with the finite mask as one bit per slot; both moment passes and every select run out
+// of them.  The select is then binary, most significant bit first: the number of keys still in play whose bit is 0 is a sum
+// of popcounts of wave ballots -- wave-uniform integers, no LDS, no atomics.  Longer rows stream through for_finite and
+// radix_select.  Both forms visit a lane's values in the same order (s ascending), so the sums have the same bits.
+// The cap: 16 slots are 16 (fp32) or 32 (fp64) registers a lane, which leaves both instantiations at or under the 64
+// registers at which a SIMD still holds its 8 waves; S = 1024 is the documented shape.
+#ifndef ILQR_ENVELOPE_RESIDENT_CAP
+#define ILQR_ENVELOPE_RESIDENT_CAP 1024      // build switch: 0 sends every row down the streaming path (tools/policy_envelope_ab.py)
+#endif
+constexpr int kEnvelopeCap = ILQR_ENVELOPE_RESIDENT_CAP;
+constexpr int kEnvelopeHeld = kEnvelopeCap / 64;
+static_assert(kEnvelopeCap % 256 == 0 && kEnvelopeHeld <= 32, "slots come in groups of four, their finite bits in one register");
+
+template <typename T> struct EnvelopeArgs {
+    int B, S, N, nx, nu, Q;
+    int x_rows, u_rows, v_rows;          // waves per trajectory of each group: (N+1) n_x, N n_u, N+1; 0: the group was not asked for
+    size_t L;
+    double tol;                          // violation_tol
+    const T* __restrict__ cost;          // [L]
+    const T* __restrict__ Xs;            // [N+1][n_x][L]
+    const T* __restrict__ Us;            // [N][n_u][L]
+    const double* __restrict__ levels;   // [Q]
+    Limits<T> lim;
+    // outputs in the ABI's (dim, time) layout, each nullptr when not asked for
+    double* __restrict__ x_mom;          // [4][B][n_x][N+1]: mean, std, min, max
+    double* __restrict__ u_mom;          // [4][B][n_u][N]
+    double* __restrict__ x_q;            // [B][Q][n_x][N+1]
+    double* __restrict__ u_q;            // [B][Q][n_u][N]
+    int* __restrict__ rank;              // [B][Q]
+    int* __restrict__ step_violating;    // [B][N+1]
+};
+
+// where a row's results go: component i of C at step t of Tn
+template <typename T> struct EnvelopeRow {
+    int b, i, t, C, Tn;
+    double* mom;
+    double* q;
+};
+
+// The moments and order statistics of one row.  each(f): f(key) for the keys of the row's finite samples, a lane's in
+// ascending s; select(k): the k-th smallest of them, the same on every lane.  n: their number.
+template <typename T, typename Each, typename Select>
+ILQR_DEV void envelope_row(const EnvelopeArgs<T>& a, const EnvelopeRow<T>& o, int n, int lane, Each&& each, Select&& select) {
+    const double nan = __builtin_nan(""), inf = __builtin_huge_val();
+    const size_t at = ((size_t)o.b * o.C + o.i) * o.Tn + o.t, plane = (size_t)a.B * o.C * o.Tn;
+    if (o.mom) {
+        double sum = 0, lo = inf, hi = -inf;
+        each([&](auto key) {
+            const double x = key_value(key);
+            sum += x;
+            lo = x < lo ? x : lo;
+            hi = x > hi ? x : hi;
+        });
+        sum = wave_sum(sum); lo = -wave_max(-lo); hi = wave_max(hi);
+        const double mean = sum / (double)n;
+        double ss = 0;
+        each([&](auto key) {
+            const double x = key_value(key);
+            ss += (x - mean) * (x - mean);
+        });
+        ss = wave_sum(ss);
+        if (lane == 0) {
+            o.mom[at] = n ? mean : nan;
+            o.mom[plane + at] = n ? sqrt(ss / (double)n) : nan;
+            o.mom[2 * plane + at] = n ? lo : nan;
+            o.mom[3 * plane + at] = n ? hi : nan;
+        }
+    }
+    if (!o.q) return;
+    for (int p = 0; p < a.Q; ++p) {
+        double q = nan;
+        if (n) {
+            const double kd = ceil(a.levels[p] * (double)n);
+            const int k = kd < 1.0 ? 1 : kd > (double)n ? n : (int)kd;
+            q = key_value(select(k));
+        }
+        if (lane == 0) o.q[(((size_t)o.b * a.Q + p) * o.C + o.i) * o.Tn + o.t] = q;
+    }
+}
+
+// Grid (x_rows + u_rows + v_rows, or 1 when only the ranks were asked for; B), one wave each: the state rows (t, i), the
+// control rows (t, j), then one wave per step t that counts step_violating[b][t] -- the samples of F whose x_t violates a
+// finite state bound of b by more than tol: max(0, c_q(x_t)) over the constraints in the rollout's order, expression and
+// dtype (FeedbackLaw::advance); t = 0 and a handle without state limits count 0.  Wave 0 of a trajectory writes rank[b].
+template <typename T>
+__global__ void __launch_bounds__(64) policy_envelope_kernel(EnvelopeArgs<T> a) {
+    using Key = decltype(cost_key(T(0)));
+    constexpr int KB = 8 * (int)sizeof(Key), H = kEnvelopeHeld;
+    __shared__ unsigned cnt[16];
+    const int b = blockIdx.y, lane = threadIdx.x, S = a.S;
+    const T* c = a.cost + (size_t)b * S;
+    int r = blockIdx.x;
+    if (r == 0 && a.rank) {
+        int n = 0;
+        for_finite(c, c, S, lane, [&](T) { n += 1; });
+        n = wave_sum(n);
+        if (lane < a.Q) {
+            const double kd = ceil(a.levels[lane] * (double)n);
+            a.rank[(size_t)b * a.Q + lane] = n == 0 ? 0 : kd < 1.0 ? 1 : kd > (double)n ? n : (int)kd;
+        }
+    }
+    EnvelopeRow<T> o{b, 0, 0, 0, 0, nullptr, nullptr};
+    const T* v = nullptr;
+    if (r < a.x_rows) {
+        o.t = r / a.nx; o.i = r % a.nx; o.C = a.nx; o.Tn = a.N + 1; o.mom = a.x_mom; o.q = a.x_q;
+        v = a.Xs + (size_t)r * a.L + (size_t)b * S;
+    } else if ((r -= a.x_rows) < a.u_rows) {
+        o.t = r / a.nu; o.i = r % a.nu; o.C = a.nu; o.Tn = a.N; o.mom = a.u_mom; o.q = a.u_q;
+        v = a.Us + (size_t)r * a.L + (size_t)b * S;
+    } else if ((r -= a.u_rows) < a.v_rows) {
+        const int t = r, nx = a.nx, mask = a.lim.al_mask;
+        int count = 0;
+        if (t >= 1 && mask != 0 && nx <= kALMaxX) {
+            T lo[kALMaxX], hi[kALMaxX];
+#pragma unroll
+            for (int i = 0; i < kALMaxX; ++i) {
+                const bool rows = a.lim.x_lo_rows && i < nx;
+                lo[i] = rows ? a.lim.x_lo_rows[(size_t)i * a.B + b] : a.lim.x_lo[i];
+                hi[i] = rows ? a.lim.x_hi_rows[(size_t)i * a.B + b] : a.lim.x_hi[i];
+            }
+            const T* xt = a.Xs + (size_t)t * nx * a.L + (size_t)b * S;
+            for (int s = lane; s < S; s += 64) {
+                const double ci = (double)c[s];
+                if (!(ci - ci == 0.0)) continue;
+                T x[kALMaxX];
+#pragma unroll
+                for (int i = 0; i < kALMaxX; ++i) x[i] = i < nx ? xt[(size_t)i * a.L + s] : T(0);
+                T viol = T(0);
+#pragma unroll
+                for (int hl = 0; hl < 2; ++hl) {           // the upper bounds (q < n_x), then the lower ones
+#pragma unroll
+                    for (int i = 0; i < kALMaxX; ++i) {
+                        if (i < nx && ((mask >> (hl * nx + i)) & 1)) {
+                            const T cq = hl == 0 ? x[i] - hi[i] : lo[i] - x[i];
+                            viol = cq > viol ? cq : viol;
+                        }
+                    }
+                }
+                count += (double)viol > a.tol ? 1 : 0;
+            }
+        }
+        count = wave_sum(count);
+        if (lane == 0) a.step_violating[(size_t)b * (a.N + 1) + t] = count;
+        return;
+    } else {
+        return;
+    }
+    if (H > 0 && S <= kEnvelopeCap) {
+        // the row, once: slot j of a lane holds the key of sample lane + 64 j; four slots' loads are issued together
+        // (a slot past the row loads the row's last value and stays out of `fin`)
+        Key key[H > 0 ? H : 1];
+        unsigned fin = 0;
+#pragma unroll
+        for (int g = 0; g < H / 4; ++g) {
+            if (256 * g < S) {
+                T cs[4], vs[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int s = lane + 64 * (4 * g + j), sc = s < S ? s : S - 1;
+                    cs[j] = c[sc]; vs[j] = v[sc];
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const double ci = (double)cs[j];
+                    key[4 * g + j] = cost_key(vs[j]);
+                    if (lane + 64 * (4 * g + j) < S && ci - ci == 0.0) fin |= 1u << (4 * g + j);
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) key[4 * g + j] = 0;
+            }
+        }
+        int n = 0;
+#pragma unroll
+        for (int g = 0; g < H / 4; ++g) {
+            if (256 * g < S) {
+#pragma unroll
+                for (int j = 4 * g; j < 4 * g + 4; ++j) n += __popcll(__ballot((fin >> j) & 1u));
+            }
+        }
+        auto each = [&](auto&& f) {
+#pragma unroll
+            for (int g = 0; g < H / 4; ++g) {
+                if (256 * g < S) {
+#pragma unroll
+                    for (int j = 4 * g; j < 4 * g + 4; ++j) {
+                        if ((fin >> j) & 1u) f(key[j]);
+                    }
+                }
+            }
+        };
+        // a key in play agrees with `prefix` above `bit`; with a 0 at `bit` too, (key ^ prefix) >> bit is 0
+        auto select = [&](int k) {
+            Key prefix = 0;
+            for (int bit = KB - 1; bit >= 0; --bit) {
+                int zeros = 0;
+#pragma unroll
+                for (int g = 0; g < H / 4; ++g) {
+                    if (256 * g < S) {
+#pragma unroll
+                        for (int j = 4 * g; j < 4 * g + 4; ++j)
+                            zeros += __popcll(__ballot(((fin >> j) & 1u) && ((key[j] ^ prefix) >> bit) == 0));
+                    }
+                }
+                if (k > zeros) { k -= zeros; prefix |= (Key)1 << bit; }
+            }
+            return prefix;
+        };
+        envelope_row<T>(a, o, n, lane, each, select);
+    } else {
+        int n = 0;
+        for_finite(c, c, S, lane, [&](T) { n += 1; });
+        n = wave_sum(n);
+        auto each = [&](auto&& f) { for_finite(v, c, S, lane, [&](T vs) { f(cost_key(vs)); }); };
+        auto select = [&](int k) { return radix_select<T>(v, c, S, k, cnt, lane); };
+        envelope_row<T>(a, o, n, lane, each, select);
+    }
+}
+
 // dense[l][c][t] <- dev[t][c][l]: the sample trajectories in the ABI's (dim, time) layout behind the batch axes
 // (layout_ct_kernel's device side is vector-per-lane, [t][l][c]; the samples' is sample-innermost)
 template <typename T>

@@ -64,6 +64,8 @@ struct SolverBase {
     virtual int policy_rollout(const ilqr_policy_rollout_desc& d) = 0;
     virtual int policy_monte_carlo(const ilqr_monte_carlo_desc& d) = 0;
     virtual int policy_monte_carlo_risk(const ilqr_monte_carlo_desc& d, const ilqr_monte_carlo_risk_desc& r) = 0;
+    virtual int policy_monte_carlo_envelope(const ilqr_monte_carlo_desc& d, const ilqr_monte_carlo_risk_desc* r,
+                                            const ilqr_monte_carlo_envelope_desc& e) = 0;
     virtual int sample_controls(const ilqr_sample_controls_desc& d) = 0;
     virtual int sampled_mpc(const ilqr_sampled_mpc_desc& d) = 0;
     virtual int set_sample_penalty(const double* weight, double violation_tol) = 0;
@@ -257,6 +259,10 @@ template <typename T> struct SamplingBufs {
     // rank [B][Q] and exceed [B][3][M]
     DevBuf<double> risk_in, risk_out;
     DevBuf<int> risk_counts;
+    // the envelope of a Monte Carlo call: levels [Q]; the x and u moments [4][B][C][T] and quantiles [B][Q][C][T] that were
+    // asked for, one behind the other; rank [B][Q] and step_violating [B][N+1]
+    DevBuf<double> env_in, env_out;
+    DevBuf<int> env_counts;
     DevBuf<T> w_steps, plans;     // sampled MPC: w [n_steps][B][n_x] as the caller gave it; U_plan [n_steps][N][n_u][B]
 };
 
@@ -1326,17 +1332,21 @@ template <typename T> class SolverT : public SolverBase {
     int policy_rollout(const ilqr_policy_rollout_desc& d) override {
         PolicyCall c{"policy_rollout", d.n_samples, d.integrator, d.feedback, d.x0, d.w, d.plant_rows,
                      d.cost, d.x_final, d.deviation, d.violation, d.X, d.U};
-        return policy_call(c, nullptr, nullptr);
+        return policy_call(c, nullptr, nullptr, nullptr);
     }
     // The same rollout with x_0 and w drawn on the device (policy_noise_kernel) and the per-trajectory statistics of its
     // sample summaries (policy_stats_kernel).  What crosses to the device is the seed and two [B][n_x] rows of standard
     // deviations; smp.w is touched only when the disturbances are asked back.  Only what the noise and the statistics add is
     // checked here: policy_call refuses the rest (no such kernels, no problem set, n_samples, integrator, plant_rows).
-    int policy_monte_carlo(const ilqr_monte_carlo_desc& d) override { return monte_carlo_call("policy_monte_carlo", d, nullptr); }
+    int policy_monte_carlo(const ilqr_monte_carlo_desc& d) override { return monte_carlo_call("policy_monte_carlo", d, nullptr, nullptr); }
     // The same call with the risk measures of its samples (policy_risk_kernel) behind the rollout.  Only the risk
     // descriptor is checked here, before anything else and so before any device work; d's outputs may then all be NULL.
     int policy_monte_carlo_risk(const ilqr_monte_carlo_desc& d, const ilqr_monte_carlo_risk_desc& r) override {
         const char* who = "policy_monte_carlo_risk";
+        if (int rc = risk_desc_check(who, r)) return rc;
+        return monte_carlo_call(who, d, &r, nullptr);
+    }
+    int risk_desc_check(const char* who, const ilqr_monte_carlo_risk_desc& r) {
         auto bad = [&](const char* what) { return fail(ILQR_ERR_INVALID_ARG, std::string(who) + ": " + what); };
         const int Q = r.n_levels, M = r.n_thresholds;
         if (r.reserved != 0) return bad("reserved must be 0");
@@ -1350,9 +1360,32 @@ template <typename T> class SolverT : public SolverBase {
         for (size_t i = 0; r.thresholds && i < (size_t)B * 3 * M; ++i)
             if (std::isnan(r.thresholds[i])) return bad("a threshold is NaN");
         if (!r.quantile && !r.tail_mean && !r.rank && !r.exceed) return bad("every output of the risk descriptor is NULL");
-        return monte_carlo_call(who, d, &r);
+        return ILQR_OK;
     }
-    int monte_carlo_call(const char* who, const ilqr_monte_carlo_desc& d, const ilqr_monte_carlo_risk_desc* risk) {
+    // The same call (with r: the risk call) with the per-step envelopes of its samples (policy_envelope_kernel) behind the
+    // rollout.  The envelope descriptor is checked first, then r as ilqr_policy_monte_carlo_risk checks it: before any
+    // device work; d's outputs may then all be NULL.
+    int policy_monte_carlo_envelope(const ilqr_monte_carlo_desc& d, const ilqr_monte_carlo_risk_desc* r,
+                                    const ilqr_monte_carlo_envelope_desc& e) override {
+        const char* who = "policy_monte_carlo_envelope";
+        auto bad = [&](const char* what) { return fail(ILQR_ERR_INVALID_ARG, std::string(who) + ": " + what); };
+        const int Q = e.n_levels;
+        if (e.reserved[0] != 0 || e.reserved[1] != 0) return bad("reserved must be 0");
+        if (Q < 0 || Q > ILQR_ENVELOPE_MAX_LEVELS) return bad("n_levels must be in 0..16");
+        if (Q > 0 && !e.levels) return bad("levels is NULL");
+        for (int i = 0; i < Q; ++i)
+            if (!(e.levels[i] >= 0.0 && e.levels[i] <= 1.0)) return bad("every level must be in [0, 1] (and not NaN)");
+        if (Q == 0 && (e.x_quantile || e.u_quantile || e.rank)) return bad("x_quantile, u_quantile and rank need n_levels >= 1");
+        if (!e.x_mean && !e.x_std && !e.x_min && !e.x_max && !e.u_mean && !e.u_std && !e.u_min && !e.u_max && !e.x_quantile &&
+            !e.u_quantile && !e.rank && !e.step_violating)
+            return bad("every output of the envelope descriptor is NULL");
+        if (r) {
+            if (int rc = risk_desc_check(who, *r)) return rc;
+        }
+        return monte_carlo_call(who, d, r, &e);
+    }
+    int monte_carlo_call(const char* who, const ilqr_monte_carlo_desc& d, const ilqr_monte_carlo_risk_desc* risk,
+                         const ilqr_monte_carlo_envelope_desc* env) {
         auto bad = [&](const char* what) { return fail(ILQR_ERR_INVALID_ARG, std::string(who) + ": " + what); };
         if (d.distribution != ILQR_NOISE_GAUSSIAN && d.distribution != ILQR_NOISE_UNIFORM) return bad("unknown distribution");
         if (d.first_trajectory < 0) return bad("first_trajectory must be >= 0");
@@ -1361,11 +1394,11 @@ template <typename T> class SolverT : public SolverBase {
             for (size_t i = 0; sd && i < (size_t)B * NX; ++i)
                 if (!std::isfinite(sd[i]) || sd[i] < 0.0) return bad("every standard deviation must be finite and >= 0");
         }
-        if (!risk && !d.stats && !d.counts && !d.cost && !d.x_final && !d.deviation && !d.violation && !d.X && !d.U && !d.x0_out && !d.w_out)
+        if (!risk && !env && !d.stats && !d.counts && !d.cost && !d.x_final && !d.deviation && !d.violation && !d.X && !d.U && !d.x0_out && !d.w_out)
             return bad("every output is NULL");
         PolicyCall c{who, d.n_samples, d.integrator, d.feedback, nullptr, nullptr, d.plant_rows,
                      d.cost, d.x_final, d.deviation, d.violation, d.X, d.U};
-        return policy_call(c, &d, risk);
+        return policy_call(c, &d, risk, env);
     }
     // what both entries ask of the rollout (the host pointers of ilqr_policy_rollout_desc)
     struct PolicyCall {
@@ -1375,7 +1408,8 @@ template <typename T> class SolverT : public SolverBase {
         const double* plant_rows;
         void *cost, *x_final, *deviation, *violation, *X, *U;
     };
-    int policy_call(const PolicyCall& d, const ilqr_monte_carlo_desc* mc, const ilqr_monte_carlo_risk_desc* risk) {
+    int policy_call(const PolicyCall& d, const ilqr_monte_carlo_desc* mc, const ilqr_monte_carlo_risk_desc* risk,
+                    const ilqr_monte_carlo_envelope_desc* env) {
         const std::string who = d.who;
         int rc;
         size_t L;
@@ -1401,8 +1435,13 @@ template <typename T> class SolverT : public SolverBase {
         if ((d.x0 || (mc && mc->x0_out)) && (rc = grow(smp.x0, L * NX))) return rc;
         if ((d.w || w_back) && (rc = grow(smp.w, nW))) return rc;
         if (d.plant_rows && (rc = grow(smp.plant, L * (size_t)ops.n_sys_dev))) return rc;
-        if (d.X && (rc = grow(smp.states, nX))) return rc;
-        if (d.U && (rc = grow(smp.controls, nU))) return rc;
+        // the envelope's groups of outputs: the sample trajectories stay on the device for them, whether or not d.X / d.U
+        // ask for them back
+        const bool env_xm = env && (env->x_mean || env->x_std || env->x_min || env->x_max);
+        const bool env_um = env && (env->u_mean || env->u_std || env->u_min || env->u_max);
+        const bool env_x = env_xm || (env && (env->x_quantile || env->step_violating)), env_u = env_um || (env && env->u_quantile);
+        if ((d.X || env_x) && (rc = grow(smp.states, nX))) return rc;
+        if ((d.U || env_u) && (rc = grow(smp.controls, nU))) return rc;
         if ((rc = grow(staging, std::max({L * NX, (d.w || w_back) ? nW : (size_t)0, d.X ? nX : (size_t)0, d.U ? nU : (size_t)0})))) return rc;
         if (d.x0 && (rc = up_tcl(d.x0, smp.x0, L, 1))) return rc;
         if (d.w && (rc = up_tcl(d.w, smp.w, L, N))) return rc;
@@ -1421,8 +1460,8 @@ template <typename T> class SolverT : public SolverBase {
         a.srows = d.plant_rows ? smp.plant.p : nullptr;
         a.lim = limits();
         a.cost = smp.summaries; a.deviation = a.cost + L; a.violation = a.cost + 2 * L; a.x_final = a.cost + 3 * L;
-        a.Xs = d.X ? smp.states.p : nullptr;
-        a.Us = d.U ? smp.controls.p : nullptr;
+        a.Xs = (d.X || env_x) ? smp.states.p : nullptr;
+        a.Us = (d.U || env_u) ? smp.controls.p : nullptr;
         NoiseArgs<T> nz{};
         if (mc) {
             // the standard deviations [2][B][n_x] (x0_std, w_std), and the statistics
@@ -1457,6 +1496,47 @@ template <typename T> class SolverT : public SolverBase {
             if (risk->tail_mean) ILQR_HIPCHK(hipMemcpyAsync(risk->tail_mean, tm, nq * sizeof(double), hipMemcpyDeviceToHost, stream));
             if (risk->rank) ILQR_HIPCHK(hipMemcpyAsync(risk->rank, rk, (size_t)B * Q * sizeof(int), hipMemcpyDeviceToHost, stream));
             if (risk->exceed) ILQR_HIPCHK(hipMemcpyAsync(risk->exceed, ex, nm * sizeof(int), hipMemcpyDeviceToHost, stream));
+        }
+        if (env) {
+            // results are written in the ABI's (dim, time) layout: plain copies bring back what was asked for
+            const int Q = (env->x_quantile || env->u_quantile || env->rank) ? env->n_levels : 0;
+            const size_t nxm = (size_t)B * NX * (N + 1), num = (size_t)B * NU * N;
+            const size_t n_out = (env_xm ? 4 * nxm : 0) + (env_um ? 4 * num : 0) + (env->x_quantile ? Q * nxm : 0) + (env->u_quantile ? Q * num : 0);
+            const size_t n_rank = env->rank ? (size_t)B * Q : 0, n_sv = env->step_violating ? (size_t)B * (N + 1) : 0;
+            if ((rc = grow(smp.env_in, (size_t)Q)) || (rc = grow(smp.env_out, n_out)) || (rc = grow(smp.env_counts, n_rank + n_sv))) return rc;
+            if (Q) ILQR_HIPCHK(hipMemcpyAsync(smp.env_in.p, env->levels, Q * sizeof(double), hipMemcpyHostToDevice, stream));
+            EnvelopeArgs<T> ea{};
+            ea.B = B; ea.S = d.n_samples; ea.N = N; ea.nx = NX; ea.nu = NU; ea.Q = Q;
+            ea.x_rows = (env_xm || env->x_quantile) ? (N + 1) * NX : 0;
+            ea.u_rows = env_u ? N * NU : 0;
+            ea.v_rows = env->step_violating ? N + 1 : 0;
+            ea.L = L; ea.tol = mc->violation_tol;
+            ea.cost = a.cost; ea.Xs = a.Xs; ea.Us = a.Us; ea.levels = smp.env_in.p; ea.lim = a.lim;
+            double* at = smp.env_out.p;
+            if (env_xm) { ea.x_mom = at; at += 4 * nxm; }
+            if (env_um) { ea.u_mom = at; at += 4 * num; }
+            if (env->x_quantile) { ea.x_q = at; at += Q * nxm; }
+            if (env->u_quantile) { ea.u_q = at; at += Q * num; }
+            if (env->rank) ea.rank = smp.env_counts.p;
+            if (env->step_violating) ea.step_violating = smp.env_counts.p + n_rank;
+            const int waves = std::max(ea.x_rows + ea.u_rows + ea.v_rows, 1);
+            if ((rc = timed(ILQR_PHASE_OTHER, [&] {
+                     ILQR_LAUNCH(policy_envelope_kernel<T>, dim3(waves, B), dim3(64), 0, stream, ea);
+                 })))
+                return rc;
+            auto back = [&](void* host, const void* dev, size_t bytes) -> int {
+                if (host) ILQR_HIPCHK(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, stream));
+                return ILQR_OK;
+            };
+            double* const xm[4] = {env->x_mean, env->x_std, env->x_min, env->x_max};
+            double* const um[4] = {env->u_mean, env->u_std, env->u_min, env->u_max};
+            for (int k = 0; k < 4; ++k) {
+                if (env_xm && (rc = back(xm[k], ea.x_mom + k * nxm, nxm * sizeof(double)))) return rc;
+                if (env_um && (rc = back(um[k], ea.u_mom + k * num, num * sizeof(double)))) return rc;
+            }
+            if ((rc = back(env->x_quantile, ea.x_q, Q * nxm * sizeof(double))) || (rc = back(env->u_quantile, ea.u_q, Q * num * sizeof(double))) ||
+                (rc = back(env->rank, ea.rank, n_rank * sizeof(int))) || (rc = back(env->step_violating, ea.step_violating, n_sv * sizeof(int))))
+                return rc;
         }
         auto fetch = [&](void* host, const T* dev) -> int {
             if (host) ILQR_HIPCHK(hipMemcpyAsync(host, dev, L * sizeof(T), hipMemcpyDeviceToHost, stream));

@@ -22,7 +22,7 @@ from . import _lib
 # (the names of the two modules beside this file stay importable from here)
 from .setter_args import _bounds, batch_param_rows, control_limits, mpc_multiplier_mode, state_limits  # noqa: F401
 from .sampling import (ELITE_FIELDS, PENALTY_FIELDS, SCENARIO_FIELDS, PolicyMonteCarlo, PolicyRollout, SampledControls, SampledMPC,  # noqa: F401
-                       _with_penalty_fields, has_policy_kernels, policy_monte_carlo_args, policy_risk_args,
+                       _with_penalty_fields, has_policy_kernels, policy_envelope_args, policy_envelope_record, policy_monte_carlo_args, policy_risk_args,
                        policy_risk_record, policy_rollout_args, sample_controls_args, sample_elites_args, sample_penalty_args, sample_scenarios_args, sampled_mpc_args, table_columns,
                        unbatch)
 from .systems.system_base import System, ready
@@ -342,7 +342,7 @@ class iLQR:
 
     def policy_monte_carlo(self, n_samples, seed=0, x_0_std=None, disturbance_std=None, distribution="gaussian",
                            plant_params=None, integrator=None, feedback=True, violation_tol=0.0, first_trajectory=0,
-                           samples=False, trajectories=False, noise=False, *, quantiles=None, thresholds=None):
+                           samples=False, trajectories=False, noise=False, *, quantiles=None, thresholds=None, envelope=None):
         """policy_rollout under noise drawn on the device, answered per trajectory (include/ilqr_hip.h,
         ilqr_policy_monte_carlo): sample s of trajectory b starts at x_0[b] + x_0_std[b] * z and receives
         disturbance_std[b] * z after every step, z of unit variance ("gaussian" or "uniform") from Philox4x32-10 at
@@ -356,13 +356,21 @@ class iLQR:
         device behind the rollout (ilqr_policy_monte_carlo_risk) and returned as attributes beside the tuple: per level
         the quantile (the ceil(p n_finite)-th smallest value: NumPy's method="inverted_cdf") and the mean of the upper
         tail from it upwards (p = 0.95: the mean of the worst 5 %), per threshold the number of finite samples strictly
-        above it; everything else the call returns is what it returns without them.  Nothing in the solver changes."""
+        above it; everything else the call returns is what it returns without them.  envelope: True (or an empty
+        sequence) or a sequence of 1..16 levels.  With it the fan chart of the samples is computed on the device behind
+        the rollout (ilqr_policy_monte_carlo_envelope) and returned as attributes too: per step the mean, std, min and
+        max of every state and applied control over the finite samples (x_mean .. u_max), step_violating, the number of
+        them outside the state limits at that step by more than violation_tol, and per level the band (x_quantiles,
+        u_quantiles: the same order statistic as quantiles=) -- without the sample trajectories leaving the device.
+        Nothing in the solver changes."""
         a = policy_monte_carlo_args(self.system, self.N, self.B, self.batched, n_samples, seed, x_0_std, disturbance_std,
                                     distribution, plant_params, integrator, violation_tol, first_trajectory)
         risk = policy_risk_args(self.B, self.batched, quantiles, thresholds)
+        env = policy_envelope_args(envelope)
         out = self._h.policy_monte_carlo(**a._asdict(), feedback=feedback, samples=samples, trajectories=trajectories,
-                                         noise=noise, levels=risk.levels, thresholds=risk.thresholds)
+                                         noise=noise, levels=risk.levels, thresholds=risk.thresholds, envelope=env)
         rec = policy_risk_record(risk, out, self.batched)
+        rec.update(policy_envelope_record(env, out, self.batched))
         for k in ("quantile", "tail_mean", "rank", "exceed"):
             out.pop(k, None)
         rec.update(table_columns(out.pop("stats"), _lib.MONTE_CARLO_STATS, self.batched))

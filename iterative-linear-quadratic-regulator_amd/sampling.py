@@ -150,9 +150,14 @@ def _with_fields(record, fields):
 RISK_FIELDS = (("quantile_levels", "quantile_rank") + tuple(f"{q}_{k}" for q in _lib.RISK_ROWS for k in ("quantiles", "tail_mean"))
                + tuple(f"{q}_exceeding" for q in _lib.RISK_ROWS))
 
+# What it gains with envelope= (ilqr_policy_monte_carlo_envelope), in the same way: None when not asked for.
+ENVELOPE_FIELDS = (tuple(f"{v}_{k}" for v in ("x", "u") for k in _lib.ENVELOPE_MOMENTS)
+                   + ("x_quantiles", "u_quantiles", "envelope_levels", "envelope_rank", "step_violating"))
+
 PolicyMonteCarlo = _with_fields(namedtuple(
     "PolicyMonteCarlo", _lib.MONTE_CARLO_STATS + _lib.MONTE_CARLO_COUNTS +
-    ("cost", "x_final", "deviation", "violation", "X", "U", "x_0", "disturbance"), defaults=(None,) * 8), RISK_FIELDS)
+    ("cost", "x_final", "deviation", "violation", "X", "U", "x_0", "disturbance"), defaults=(None,) * 8),
+    RISK_FIELDS + ENVELOPE_FIELDS)
 PolicyMonteCarlo.__doc__ = """Result of iLQR.policy_monte_carlo.  Per trajectory ([B] each, scalars on a single solver), over
 the samples with a finite cost: cost_mean, cost_std (population), cost_min, cost_max, deviation_mean, deviation_max,
 violation_max (float64, NaN when n_finite is 0), n_finite, n_violating (int).  With samples=True cost, deviation, violation
@@ -162,7 +167,12 @@ quantile_levels (Q,), quantile_rank ([B,] Q) int -- the rank k_p of every level 
 and cost_quantiles, cost_tail_mean, deviation_quantiles, deviation_tail_mean, violation_quantiles, violation_tail_mean
 ([B,] Q) float64: the k_p-th smallest value (NumPy's method="inverted_cdf") and the mean of the values from it upwards
 (NaN when n_finite is 0); with thresholds=: cost_exceeding, deviation_exceeding, violation_exceeding ([B,] M_q) int, the
-number of finite samples strictly above each threshold of that key; else None."""
+number of finite samples strictly above each threshold of that key; else None.  With envelope=: per step, over the same
+samples, x_mean, x_std (population), x_min, x_max ([B,] n_x, N + 1) and u_mean, u_std, u_min, u_max ([B,] n_u, N) of the
+states and the applied (clamped) controls, float64, NaN when n_finite is 0; step_violating ([B,] N + 1) int, the finite
+samples whose state at step t is outside the state limits by more than violation_tol (0 at t = 0 and without limits);
+and with levels: envelope_levels (Q,), envelope_rank ([B,] Q) int, x_quantiles ([B,] Q, n_x, N + 1) and u_quantiles
+([B,] Q, n_u, N), the envelope_rank-th smallest value of every row (exact; level 0 is x_min, level 1 x_max); else None."""
 
 PolicyMonteCarloArgs = NamedTuple(
     "PolicyMonteCarloArgs",
@@ -254,6 +264,44 @@ def policy_risk_record(args, out, batched):
             rec[f"{q}_quantiles"], rec[f"{q}_tail_mean"] = one(out["quantile"][:, i]), one(out["tail_mean"][:, i])
     for q, M in args.widths.items():
         rec[f"{q}_exceeding"] = one(out["exceed"][:, _lib.RISK_ROWS.index(q), :M])
+    return rec
+
+
+def policy_envelope_args(envelope=None):
+    """Validated ``envelope`` argument of ``iLQR.policy_monte_carlo`` as the levels (Q,) float64 that
+    ``_lib.Handle.policy_monte_carlo`` takes as ``envelope``, or None when no envelope was asked for.  ``envelope`` is None
+    or False (none), True or an empty sequence (the moments and the counts: Q = 0), or a sequence of 1..16 levels in
+    [0, 1] (the bands too).  Raises ValueError for anything else: a string, a scalar, levels that are not one-dimensional,
+    more than 16, a level that is NaN or outside [0, 1].  Pure host code (no GPU)."""
+    if envelope is None or envelope is False:
+        return None
+    if envelope is True:
+        return np.zeros(0)
+    if isinstance(envelope, (str, bytes)):
+        raise ValueError(f"envelope must be True or a sequence of up to {_lib.ENVELOPE_MAX_LEVELS} levels, got {envelope!r}")
+    try:
+        levels = np.array(envelope, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"envelope must be True or a sequence of up to {_lib.ENVELOPE_MAX_LEVELS} levels, got {envelope!r}") from None
+    if levels.ndim != 1 or levels.size > _lib.ENVELOPE_MAX_LEVELS:
+        raise ValueError(f"envelope must be True or a sequence of up to {_lib.ENVELOPE_MAX_LEVELS} levels, but got shape {levels.shape}")
+    if not ((levels >= 0.0) & (levels <= 1.0)).all():
+        raise ValueError("every envelope level must be in [0, 1]")
+    return levels
+
+
+def policy_envelope_record(levels, out, batched):
+    """The ENVELOPE_FIELDS of a PolicyMonteCarlo from the arrays ``_lib.Handle.policy_monte_carlo`` returned for the
+    envelope ``levels`` (policy_envelope_args'; None: {}), taken out of ``out``; the batch axis dropped on a single solver.
+    What was not asked for is left out."""
+    if levels is None:
+        return {}
+    one = (lambda a: ready(a)) if batched else (lambda a: ready(a[0].copy()))
+    rec = {f"{v}_{k}": one(out.pop(f"{v}_{k}")) for v in ("x", "u") for k in _lib.ENVELOPE_MOMENTS}
+    rec["step_violating"] = one(out.pop("step_violating"))
+    if levels.size:
+        rec.update(envelope_levels=ready(levels.copy()), envelope_rank=one(out.pop("envelope_rank")),
+                   x_quantiles=one(out.pop("x_quantile")), u_quantiles=one(out.pop("u_quantile")))
     return rec
 
 

@@ -8,10 +8,13 @@ process noise of that standard deviation in every state component, drawn on the 
 per-trajectory statistics of its cost and deviation are reported.  With --risk both loops are run once more with the
 initial state drawn on the device (and the process noise, if given) and the risk measures of the cost are reported: the
 median, the 95 % quantile, the mean of the worst 5 % and the share of samples above twice the nominal cost
-(iLQR.policy_monte_carlo with quantiles= and thresholds=).
+(iLQR.policy_monte_carlo with quantiles= and thresholds=).  With --envelope both loops are run the same way and the fan
+chart of the samples is reduced on the device (iLQR.policy_monte_carlo with envelope=): the step and the state where
+the band between the 5 % and the 95 % quantile is widest, and the step at which most samples are outside the state
+limits (none are set by this script, so that count is 0 unless the solver is given some).
 
     python scripts/run_iLQR_policy_robustness.py [--batch 256] [--samples 1024] [--horizon 200] [--dtype f64] [--seed 0]
-                                                 [--process-noise SIGMA] [--risk]
+                                                 [--process-noise SIGMA] [--risk] [--envelope]
 """
 import argparse
 import os
@@ -43,6 +46,9 @@ def main(argv=None):
     ap.add_argument("--risk", action="store_true",
                     help="also report, closed and open loop, the median and 95 %% cost, the mean of the worst 5 %% and the "
                          "share of samples above twice the nominal cost, computed on the device (off by default)")
+    ap.add_argument("--envelope", action="store_true",
+                    help="also report, closed and open loop, where the samples' 5-95 %% band of the states is widest and the "
+                         "step with the most samples outside the state limits, computed on the device (off by default)")
     a = ap.parse_args(argv)
     dtype = np.float64 if a.dtype == "f64" else np.float32
     B, S, N = a.batch, a.samples, a.horizon
@@ -97,6 +103,22 @@ def main(argv=None):
                   f"median cost {np.nanmedian(mc.cost_quantiles[:, 0]):.3f}, 95 % cost {np.nanmedian(mc.cost_quantiles[:, 1]):.3f}, "
                   f"mean of the worst 5 % {np.nanmedian(mc.cost_tail_mean[:, 1]):.3f}; share of samples above twice the "
                   f"nominal cost: median {np.median(share):.3f}, max {share.max():.3f}")
+    if a.envelope:
+        x0_std = np.array([ANGLE_OFF, ANGLE_OFF, RATE_OFF, RATE_OFF]) / np.sqrt(3.0)
+        w_std = None if a.process_noise is None else np.full(4, a.process_noise)
+        names = ("theta_1", "theta_2", "theta_dot_1", "theta_dot_2")
+        for label, feedback in (("closed loop", True), ("open loop", False)):
+            t0 = time.time()
+            mc = solver.policy_monte_carlo(S, seed=a.seed, x_0_std=x0_std, disturbance_std=w_std, distribution="uniform",
+                                           feedback=feedback, envelope=(0.05, 0.95))
+            el = time.time() - t0
+            width = np.nan_to_num(mc.x_quantiles[:, 1] - mc.x_quantiles[:, 0], nan=-np.inf)      # (B, n_x, N + 1)
+            b, i, t = np.unravel_index(np.argmax(width), width.shape)
+            per_step = mc.step_violating.sum(axis=0)
+            print(f"envelope, {label}: {B} x {S} rollouts in {el:.3f} s; the 5-95 % band is widest for {names[i]} at step {t} "
+                  f"(trajectory {b}: {width[b, i, t]:.3f} wide, median over the batch there {np.median(width[:, i, t]):.3f}); "
+                  f"most samples outside the state limits at step {int(np.argmax(per_step))}: {int(per_step.max())} of "
+                  f"{int(mc.n_finite.sum())} finite samples")
     return shares
 
 
