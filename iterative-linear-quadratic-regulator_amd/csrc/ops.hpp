@@ -83,28 +83,25 @@ template <typename T> bool ring_rollout_ok(const KArgs<T>& a, int nx, int nu) {
 template <typename T> struct SamplingOps {
     // the closed-loop rollout; [1]: with x_0 and w drawn on the device ([0] does not read its NoiseArgs)
     void (*policy[2])(const PolicyArgs<T>&, const NoiseArgs<T>&, hipStream_t) = {};
-    // the search: the private copy of the nominal, the rollout of a round's samples (S = 1: of the nominal alone), and the
-    // round's weights and update of Ub
+    // the search: the private copy of the nominal, and the round's weights and update of Ub
     void (*begin)(const SampleArgs<T>&, hipStream_t) = nullptr;
-    void (*rollout)(const SampleArgs<T>&, const NoiseArgs<T>&, hipStream_t) = nullptr;
     void (*update)(const SampleArgs<T>&, hipStream_t) = nullptr;
+    // the rollout of a round's samples (S = 1: of the nominal alone), [STEPSTD][PEN]: drawing with Sd
+    // (ilqr_set_sample_elites), with J + P as its cost (ilqr_set_sample_penalty); and under noise scenarios, M lanes per
+    // sample (ilqr_set_sample_scenarios).  An entry is null where the system lacks the instantiation: PEN where it takes
+    // no limits (takes_limits), STEPSTD and the scenarios where it is none of the built-in three (box_system).
+    void (*rollout[2][2])(const SampleArgs<T>&, const NoiseArgs<T>&, hipStream_t) = {};
+    void (*rollout_scn[2][2])(const ScenarioArgs<T>&, const NoiseArgs<T>&, hipStream_t) = {};
     // sampled MPC: the epilogue of a step (plant step, logs, shift of Ub), and Ub back into U after the last one
     void (*advance)(const SampledMpcArgs<T>&, hipStream_t) = nullptr;
     void (*commit)(const SampleCommitArgs<T>&, hipStream_t) = nullptr;
-    // the state-limit penalty (ilqr_set_sample_penalty): the rollout with J + P as its cost, and the penalty's share of a
-    // round's report; null where the system takes no limits (takes_limits: a generated plugin has neither kernel)
-    void (*rollout_pen)(const SampleArgs<T>&, const NoiseArgs<T>&, hipStream_t) = nullptr;
+    // the penalty's share of a round's report; null where the system takes no limits
     void (*penalty_stats)(const SampleArgs<T>&, hipStream_t) = nullptr;
-    // elites and the adapted standard deviation (ilqr_set_sample_elites): Sd of round 0, the rollouts that draw with Sd
-    // ([1]: penalised), and the round's weights, elites, update of Ub and update of Sd; null where the system is none of
-    // the built-in three (box_system: a generated plugin has none of these kernels)
+    // elites and the adapted standard deviation: Sd of round 0, and the round's weights, elites, update of Ub and update
+    // of Sd; null where the system is none of the built-in three
     void (*std_fill)(const SampleArgs<T>&, hipStream_t) = nullptr;
-    void (*rollout_elite[2])(const SampleArgs<T>&, const NoiseArgs<T>&, hipStream_t) = {};
     void (*update_elite)(const SampleArgs<T>&, hipStream_t) = nullptr;
-    // noise scenarios (ilqr_set_sample_scenarios): the rollouts with M lanes per sample, [STEPSTD][PEN]; null where the
-    // system is none of the built-in three
-    void (*rollout_scn[2][2])(const ScenarioArgs<T>&, const NoiseArgs<T>&, hipStream_t) = {};
-    explicit operator bool() const { return rollout != nullptr; }
+    explicit operator bool() const { return rollout[0][0] != nullptr; }
 };
 
 template <typename T> struct Ops {
@@ -486,16 +483,16 @@ template <typename T, typename Dyn> Ops<T> make_ops() {
     }
     if constexpr (policy_system<Dyn>()) {
         o.sampling = {{launch_policy<T, Dyn, false>, launch_policy<T, Dyn, true>}, launch_sample_begin<T, Dyn>,
-                      launch_sample_rollout<T, Dyn>, launch_sample_update<T, Dyn>, launch_sampled_mpc_advance<T, Dyn>,
+                      launch_sample_update<T, Dyn>, {{launch_sample_rollout<T, Dyn>}}, {}, launch_sampled_mpc_advance<T, Dyn>,
                       launch_sample_commit<T, Dyn>};
         if constexpr (takes_limits<Dyn>()) {
-            o.sampling.rollout_pen = launch_sample_rollout<T, Dyn, true>;
+            o.sampling.rollout[0][1] = launch_sample_rollout<T, Dyn, true>;
             o.sampling.penalty_stats = launch_sample_penalty_stats<T>;
         }
         if constexpr (box_system<Dyn>()) {
             o.sampling.std_fill = launch_sample_std_fill<T, Dyn>;
-            o.sampling.rollout_elite[0] = launch_sample_rollout<T, Dyn, false, true>;
-            o.sampling.rollout_elite[1] = launch_sample_rollout<T, Dyn, true, true>;
+            o.sampling.rollout[1][0] = launch_sample_rollout<T, Dyn, false, true>;
+            o.sampling.rollout[1][1] = launch_sample_rollout<T, Dyn, true, true>;
             o.sampling.update_elite = launch_sample_update_elite<T, Dyn>;
             o.sampling.rollout_scn[0][0] = launch_sample_rollout_scn<T, Dyn, false, false>;
             o.sampling.rollout_scn[0][1] = launch_sample_rollout_scn<T, Dyn, true, false>;

@@ -18,8 +18,9 @@
 // While elites are set (ilqr_set_sample_elites) the rollout is its STEPSTD instantiation -- it draws step t with Sd_t in
 // place of u_std -- and two launches stand around the update: sample_elite_kernel truncates the weights to the n_e best
 // samples behind the weights, sample_elite_std_kernel sets Sd to their spread around the new nominal behind the update.
+// The reductions over a trajectory's samples are built from the pieces of sample_reduce.hpp.
 #pragma once
-#include "policy_rollout.hpp"
+#include "sample_reduce.hpp"
 
 namespace ilqr {
 
@@ -74,7 +75,7 @@ template <typename T> struct SampleArgs {
 template <typename T> struct ScenarioArgs : SampleArgs<T> {
     int log2m;                          // M = 2^log2m scenarios per sample, M <= 64
     int agg;                            // ILQR_SCENARIO_MEAN / MAX / TAIL
-    int rank;                           // TAIL: k = min(max(ceil(level * M), 1), M), from the host
+    int rank;                           // TAIL: k = quantile_rank(level, M), from the host
     NoiseArgs<T> sn;                    // the scenarios' key, first trajectory, distribution, x0_std and w_std
     T* __restrict__ scn_cost;           // [L * M] the scenario values v_m (J, or J + P), before the aggregate
 };
@@ -232,7 +233,7 @@ template <typename T, typename Dyn, bool PEN, bool STEPSTD> struct ScenarioLaw :
         const int M = 1 << sa.log2m;
         const size_t l = this->k.l;
         const double vd = (double)v;
-        int fin = (vd - vd == 0.0) ? 1 : 0;      // neither NaN nor an infinity
+        int fin = finite_cost(vd) ? 1 : 0;
         for (int x = 1; x < M; x <<= 1) fin &= __shfl_xor(fin, x, 64);
         double r = vd;
         if (sa.agg == ILQR_SCENARIO_MEAN) {
@@ -305,7 +306,7 @@ __global__ void __launch_bounds__(64) sample_weights_kernel(SampleArgs<T> a) {
     int smin = 0x7fffffff;
     for (int s = lane; s < S; s += 64) {
         const double ci = (double)c[s];
-        if (!(ci - ci == 0.0)) continue;       // NaN or an infinity
+        if (!finite_cost(ci)) continue;
         n += 1.0;
         if (ci < cmin) { cmin = ci; smin = s; }   // s ascends within a lane: the first of equal costs stays
     }
@@ -322,7 +323,7 @@ __global__ void __launch_bounds__(64) sample_weights_kernel(SampleArgs<T> a) {
         double* w = a.w + (size_t)b * S;
         for (int s = lane; s < S; s += 64) {
             const double ci = (double)c[s];
-            const double wi = (ci - ci == 0.0) ? exp(-(ci - cmin) / a.lambda) : 0.0;
+            const double wi = finite_cost(ci) ? exp(-(ci - cmin) / a.lambda) : 0.0;
             w[s] = wi;
             W += wi;
             W2 += wi * wi;
@@ -352,8 +353,7 @@ __global__ void __launch_bounds__(64) sample_penalty_stats_kernel(SampleArgs<T> 
     const T* v = a.viol + (size_t)b * S;
     double nv = 0;
     for (int s = lane; s < S; s += 64) {
-        const double ci = (double)c[s];
-        if (!(ci - ci == 0.0)) continue;       // NaN or an infinity
+        if (!finite_cost(c[s])) continue;
         nv += (double)v[s] > a.pen_tol ? 1.0 : 0.0;
     }
     nv = wave_sum(nv);
@@ -421,13 +421,10 @@ __global__ void sample_std_fill_kernel(SampleArgs<T> a, int NU) {
     a.Sd[idx] = a.std_up ? a.std_up[((size_t)b * NU + j) * a.N + t] : a.u_std[(size_t)b * NU + j];
 }
 
-// (cost_key, the order of the costs as unsigned integers: policy_rollout.hpp, where policy_risk_kernel selects by it too)
 // The elites of a round, launched behind sample_weights_kernel: one wave per trajectory over its contiguous [S] costs.
 // n_e = min(E, n_finite) samples with the lowest (J_s, s) among the finite costs are found by a radix select on
-// cost_key, most significant digit first, four bits a pass: every lane counts its stride of the row into sixteen integer
-// LDS counters (integer atomics: the counts do not depend on their order), every lane reads the sixteen and walks them
-// to the digit that holds the n_e-th key, and the search goes on inside that digit.  It stops early once all keys left
-// under the prefix are elites.  What remains equal to the prefix is taken in s order: 64 samples at a time, s ascending,
+// cost_key (the digit passes of sample_reduce.hpp, radix_digit), which stops early once all keys left under the prefix
+// are elites.  What remains equal to the prefix is taken in s order: 64 samples at a time, s ascending,
 // a ballot and the count of the lanes below.  The last pass writes the mask, w_s (0 for a non-elite; 1 for an elite with
 // `elite_uniform` or in BEST mode, else its SOFTMIN weight as it stands) and sums W and sum w^2 as sample_weights_kernel
 // does: lane strides, then the butterfly, in double.  With n_e == n_finite and SOFTMIN weights kept nothing changes, and
@@ -446,39 +443,17 @@ __global__ void __launch_bounds__(64) sample_elite_kernel(SampleArgs<T> a) {
     const bool all = n_e == n_fin;
     if (lane == 0) a.n_e[b] = n_e;
     if (all && !unit) {
-        for (int s = lane; s < S; s += 64) {
-            const double ci = (double)c[s];
-            mask[s] = (ci - ci == 0.0) ? 1 : 0;
-        }
+        for (int s = lane; s < S; s += 64) mask[s] = finite_cost(c[s]) ? 1 : 0;
         return;
     }
     Key prefix = 0;
     int k_rem = n_e, sh = KB;
     while (!all && sh > 0) {
-        const bool first = sh == KB;
         sh -= 4;
-        if (lane < 16) cnt[lane] = 0u;
-        __syncthreads();
-        for (int s = lane; s < S; s += 64) {
-            const T cs = c[s];
-            const double ci = (double)cs;
-            if (!(ci - ci == 0.0)) continue;
-            const Key key = cost_key(cs);
-            if (first || (key >> (first ? 0 : sh + 4)) == prefix) atomicAdd(&cnt[(unsigned)(key >> sh) & 15u], 1u);
-        }
-        __syncthreads();
-        unsigned cum = 0, dsel = 0, csel = 0, below = 0;
-        bool found = false;
-#pragma unroll
-        for (unsigned d = 0; d < 16; ++d) {
-            const unsigned cd = cnt[d];
-            if (!found && cum + cd >= (unsigned)k_rem) { found = true; dsel = d; csel = cd; below = cum; }
-            cum += cd;
-        }
-        __syncthreads();      // (every lane has read the counters before they are cleared again)
-        prefix = (Key)(prefix << 4) | (Key)dsel;
-        k_rem -= (int)below;
-        if (k_rem == (int)csel) break;      // every key left under the prefix is an elite's
+        const RadixDigit d = radix_digit(c, c, S, lane, cnt, prefix, sh, k_rem);
+        prefix = (Key)(prefix << 4) | (Key)d.digit;
+        k_rem -= (int)d.below;
+        if (k_rem == (int)d.count) break;      // every key left under the prefix is an elite's
     }
     double* w = a.w + (size_t)b * S;
     double W = 0, W2 = 0;
@@ -487,8 +462,7 @@ __global__ void __launch_bounds__(64) sample_elite_kernel(SampleArgs<T> a) {
         const int s = base + lane;
         const bool valid = s < S;
         const T cs = valid ? c[s] : T(0);
-        const double ci = (double)cs;
-        const bool fin = valid && (ci - ci == 0.0);
+        const bool fin = valid && finite_cost(cs);
         const Key hi = all ? (Key)0 : (Key)(cost_key(cs) >> sh);
         const bool tie = fin && !all && hi == prefix;
         const unsigned long long votes = __ballot(tie);

@@ -1292,8 +1292,9 @@ template <typename T> class SolverT : public SolverBase {
     // sequence, so a call that breaks two rules gets the answer it always got: the system has the kernels; a problem is
     // set; S >= 1; L = B * S < 2^31; then the solver state is settled for reading.
     int fail(int code, std::string msg) { err = std::move(msg); return code; }
-    int sampling_supported(const std::string& who) {
-        return ops.sampling ? ILQR_OK : fail(ILQR_ERR_UNSUPPORTED, who + ": supported for the pendulum, UA double pendulum and double pendulum only");
+    // (`have`: the kernels the entry needs, an entry of ops.sampling)
+    int sampling_supported(const std::string& who, bool have) {
+        return have ? ILQR_OK : fail(ILQR_ERR_UNSUPPORTED, who + ": supported for the pendulum, UA double pendulum and double pendulum only");
     }
     int sampling_problem(const std::string& who) { return have_problem ? ILQR_OK : fail(ILQR_ERR_STATE, who + " before set_problem / mpc_reset"); }
     int sample_count(const std::string& who, int n) { return n >= 1 ? ILQR_OK : fail(ILQR_ERR_INVALID_ARG, who + ": n_samples must be >= 1"); }
@@ -1304,6 +1305,34 @@ template <typename T> class SolverT : public SolverBase {
     int sampling_settle() {
         const int rc = flush_select();
         return rc ? rc : fix_slots(st);
+    }
+    // the most recent sampling call is (so far) no search with a penalty, elites or scenarios to report on
+    void reports_off() { pen.report = el.report = scn.report = false; }
+    // a download on the stream, where the caller asked for one
+    int fetch(void* host, const void* dev, size_t bytes) {
+        if (host) ILQR_HIPCHK(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, stream));
+        return ILQR_OK;
+    }
+    // the levels of a risk or an envelope descriptor
+    int levels_check(const char* who, int Q, int max, const double* levels) {
+        auto bad = [&](const char* what) { return fail(ILQR_ERR_INVALID_ARG, std::string(who) + ": " + what); };
+        static_assert(ILQR_RISK_MAX_LEVELS == 16 && ILQR_ENVELOPE_MAX_LEVELS == 16, "the message names the bound");
+        if (Q < 0 || Q > max) return bad("n_levels must be in 0..16");
+        if (Q > 0 && !levels) return bad("levels is NULL");
+        for (int i = 0; i < Q; ++i)
+            if (!(levels[i] >= 0.0 && levels[i] <= 1.0)) return bad("every level must be in [0, 1] (and not NaN)");
+        return ILQR_OK;
+    }
+    // n standard deviations (`what`: their name in the message) as the device will hold them: finite in the handle's
+    // dtype -- a double beyond it would arrive there as +inf -- and >= 0, cast to T at `out` where one is given.  r may be
+    // NULL: nothing is checked or written.
+    int std_check(const std::string& who, const char* what, const double* r, size_t n, T* out) {
+        for (size_t i = 0; r && i < n; ++i) {
+            if (!std::isfinite(r[i]) || r[i] < 0.0 || r[i] > (double)std::numeric_limits<T>::max())
+                return fail(ILQR_ERR_INVALID_ARG, who + ": every " + what + " must be finite in the handle's dtype and >= 0");
+            if (out) out[i] = (T)r[i];
+        }
+        return ILQR_OK;
     }
     static NoiseArgs<T> noise_args(unsigned long long seed, int first_trajectory, int distribution) {
         NoiseArgs<T> nz{};
@@ -1350,11 +1379,9 @@ template <typename T> class SolverT : public SolverBase {
         auto bad = [&](const char* what) { return fail(ILQR_ERR_INVALID_ARG, std::string(who) + ": " + what); };
         const int Q = r.n_levels, M = r.n_thresholds;
         if (r.reserved != 0) return bad("reserved must be 0");
-        if (Q < 0 || Q > ILQR_RISK_MAX_LEVELS) return bad("n_levels must be in 0..16");
-        if (M < 0 || M > ILQR_RISK_MAX_THRESHOLDS) return bad("n_thresholds must be in 0..16");
-        if (Q > 0 && !r.levels) return bad("levels is NULL");
-        for (int i = 0; i < Q; ++i)
-            if (!(r.levels[i] >= 0.0 && r.levels[i] <= 1.0)) return bad("every level must be in [0, 1] (and not NaN)");
+        // (the count of the thresholds is refused behind the count of the levels and before the levels themselves)
+        if (Q >= 0 && Q <= ILQR_RISK_MAX_LEVELS && (M < 0 || M > ILQR_RISK_MAX_THRESHOLDS)) return bad("n_thresholds must be in 0..16");
+        if (int rc = levels_check(who, Q, ILQR_RISK_MAX_LEVELS, r.levels)) return rc;
         if (Q == 0 && (r.quantile || r.tail_mean || r.rank)) return bad("quantile, tail_mean and rank need n_levels >= 1");
         if (r.exceed && (M == 0 || !r.thresholds)) return bad("exceed needs n_thresholds >= 1 and thresholds");
         for (size_t i = 0; r.thresholds && i < (size_t)B * 3 * M; ++i)
@@ -1371,10 +1398,7 @@ template <typename T> class SolverT : public SolverBase {
         auto bad = [&](const char* what) { return fail(ILQR_ERR_INVALID_ARG, std::string(who) + ": " + what); };
         const int Q = e.n_levels;
         if (e.reserved[0] != 0 || e.reserved[1] != 0) return bad("reserved must be 0");
-        if (Q < 0 || Q > ILQR_ENVELOPE_MAX_LEVELS) return bad("n_levels must be in 0..16");
-        if (Q > 0 && !e.levels) return bad("levels is NULL");
-        for (int i = 0; i < Q; ++i)
-            if (!(e.levels[i] >= 0.0 && e.levels[i] <= 1.0)) return bad("every level must be in [0, 1] (and not NaN)");
+        if (int rc = levels_check(who, Q, ILQR_ENVELOPE_MAX_LEVELS, e.levels)) return rc;
         if (Q == 0 && (e.x_quantile || e.u_quantile || e.rank)) return bad("x_quantile, u_quantile and rank need n_levels >= 1");
         if (!e.x_mean && !e.x_std && !e.x_min && !e.x_max && !e.u_mean && !e.u_std && !e.u_min && !e.u_max && !e.x_quantile &&
             !e.u_quantile && !e.rank && !e.step_violating)
@@ -1408,12 +1432,28 @@ template <typename T> class SolverT : public SolverBase {
         const double* plant_rows;
         void *cost, *x_final, *deviation, *violation, *X, *U;
     };
+    // the groups of outputs an envelope descriptor asks for (none without one): moments and quantiles of the states and
+    // of the controls, the ranks, step_violating
+    struct EnvelopeGroups {
+        bool xm = false, um = false, xq = false, uq = false, rank = false, sv = false;
+        explicit EnvelopeGroups(const ilqr_monte_carlo_envelope_desc* e) {
+            if (!e) return;
+            xm = e->x_mean || e->x_std || e->x_min || e->x_max;
+            um = e->u_mean || e->u_std || e->u_min || e->u_max;
+            xq = e->x_quantile; uq = e->u_quantile; rank = e->rank; sv = e->step_violating;
+        }
+        // the sample trajectories it reads: they stay on the device for it, whether or not the call asks for them back
+        bool x() const { return xm || xq || sv; }
+        bool u() const { return um || uq; }
+    };
+    // Validation, buffers, uploads and the rollout; then the reductions a Monte Carlo call asked for, each behind the
+    // rollout on the stream; then the downloads of the samples.
     int policy_call(const PolicyCall& d, const ilqr_monte_carlo_desc* mc, const ilqr_monte_carlo_risk_desc* risk,
                     const ilqr_monte_carlo_envelope_desc* env) {
         const std::string who = d.who;
         int rc;
         size_t L;
-        if ((rc = sampling_supported(who))) return rc;
+        if ((rc = sampling_supported(who, (bool)ops.sampling))) return rc;
         // (its constants are part of the generated code: the plant can differ from the model in its integrator only)
         if (d.plant_rows && cfg.system == ILQR_SYS_CUSTOM) return fail(ILQR_ERR_UNSUPPORTED, who + ": a user-defined system has no parameter rows");
         if ((rc = sampling_problem(who)) || (rc = sample_count(who, d.n_samples))) return rc;
@@ -1425,9 +1465,7 @@ template <typename T> class SolverT : public SolverBase {
         for (size_t i = 0; d.plant_rows && i < L * ns; ++i)
             if (!std::isfinite(d.plant_rows[i])) return fail(ILQR_ERR_INVALID_ARG, who + ": every plant_rows value must be finite");
         if ((rc = sampling_settle())) return rc;
-        pen.report = false;          // (the most recent sampling call is no penalised search)
-        el.report = false;
-        scn.report = false;
+        reports_off();
         const size_t nX = L * NX * (size_t)(N + 1), nU = L * NU * (size_t)N, nW = L * NX * (size_t)N;
         // the disturbances a Monte Carlo call was asked to return (none are drawn without w_std: those are zeros)
         const bool w_back = mc && mc->w_out && mc->w_std;
@@ -1435,13 +1473,10 @@ template <typename T> class SolverT : public SolverBase {
         if ((d.x0 || (mc && mc->x0_out)) && (rc = grow(smp.x0, L * NX))) return rc;
         if ((d.w || w_back) && (rc = grow(smp.w, nW))) return rc;
         if (d.plant_rows && (rc = grow(smp.plant, L * (size_t)ops.n_sys_dev))) return rc;
-        // the envelope's groups of outputs: the sample trajectories stay on the device for them, whether or not d.X / d.U
-        // ask for them back
-        const bool env_xm = env && (env->x_mean || env->x_std || env->x_min || env->x_max);
-        const bool env_um = env && (env->u_mean || env->u_std || env->u_min || env->u_max);
-        const bool env_x = env_xm || (env && (env->x_quantile || env->step_violating)), env_u = env_um || (env && env->u_quantile);
-        if ((d.X || env_x) && (rc = grow(smp.states, nX))) return rc;
-        if ((d.U || env_u) && (rc = grow(smp.controls, nU))) return rc;
+        const EnvelopeGroups eg(env);
+        const bool keep_X = d.X || eg.x(), keep_U = d.U || eg.u();
+        if (keep_X && (rc = grow(smp.states, nX))) return rc;
+        if (keep_U && (rc = grow(smp.controls, nU))) return rc;
         if ((rc = grow(staging, std::max({L * NX, (d.w || w_back) ? nW : (size_t)0, d.X ? nX : (size_t)0, d.U ? nU : (size_t)0})))) return rc;
         if (d.x0 && (rc = up_tcl(d.x0, smp.x0, L, 1))) return rc;
         if (d.w && (rc = up_tcl(d.w, smp.w, L, N))) return rc;
@@ -1460,8 +1495,8 @@ template <typename T> class SolverT : public SolverBase {
         a.srows = d.plant_rows ? smp.plant.p : nullptr;
         a.lim = limits();
         a.cost = smp.summaries; a.deviation = a.cost + L; a.violation = a.cost + 2 * L; a.x_final = a.cost + 3 * L;
-        a.Xs = (d.X || env_x) ? smp.states.p : nullptr;
-        a.Us = (d.U || env_u) ? smp.controls.p : nullptr;
+        a.Xs = keep_X ? smp.states.p : nullptr;
+        a.Us = keep_U ? smp.controls.p : nullptr;
         NoiseArgs<T> nz{};
         if (mc) {
             // the standard deviations [2][B][n_x] (x0_std, w_std), and the statistics
@@ -1474,75 +1509,12 @@ template <typename T> class SolverT : public SolverBase {
             nz.w_out = w_back ? smp.w.p : nullptr;
         }
         if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.policy[mc != nullptr](a, nz, stream); }))) return rc;
-        if (mc && (mc->stats || mc->counts)) {
-            hipLaunchKernelGGL(policy_stats_kernel<T>, dim3(B), dim3(64), 0, stream, (const T*)a.cost, (const T*)a.deviation,
-                               (const T*)a.violation, d.n_samples, mc->violation_tol, smp.stats.p, smp.counts.p);
-            if (mc->stats) ILQR_HIPCHK(hipMemcpyAsync(mc->stats, smp.stats.p, (size_t)B * 7 * sizeof(double), hipMemcpyDeviceToHost, stream));
-            if (mc->counts) ILQR_HIPCHK(hipMemcpyAsync(mc->counts, smp.counts.p, (size_t)B * 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
-        }
-        if (risk) {
-            // levels and thresholds go up from the caller's arrays (the call ends synchronised); nothing is computed for
-            // a group of outputs the caller left out
-            const int Q = (risk->quantile || risk->tail_mean || risk->rank) ? risk->n_levels : 0, M = risk->exceed ? risk->n_thresholds : 0;
-            const size_t nq = (size_t)B * 3 * Q, nm = (size_t)B * 3 * M;
-            if ((rc = grow(smp.risk_in, Q + nm)) || (rc = grow(smp.risk_out, 2 * nq)) || (rc = grow(smp.risk_counts, (size_t)B * Q + nm))) return rc;
-            double *lev = smp.risk_in.p, *thr = lev + Q, *qu = smp.risk_out.p, *tm = qu + nq;
-            int *rk = smp.risk_counts.p, *ex = rk + (size_t)B * Q;
-            if (Q) ILQR_HIPCHK(hipMemcpyAsync(lev, risk->levels, Q * sizeof(double), hipMemcpyHostToDevice, stream));
-            if (M) ILQR_HIPCHK(hipMemcpyAsync(thr, risk->thresholds, nm * sizeof(double), hipMemcpyHostToDevice, stream));
-            hipLaunchKernelGGL(policy_risk_kernel<T>, dim3(B, 3), dim3(64), 0, stream, (const T*)a.cost, L, d.n_samples, Q, M,
-                               (const double*)lev, (const double*)thr, qu, tm, rk, ex);
-            if (risk->quantile) ILQR_HIPCHK(hipMemcpyAsync(risk->quantile, qu, nq * sizeof(double), hipMemcpyDeviceToHost, stream));
-            if (risk->tail_mean) ILQR_HIPCHK(hipMemcpyAsync(risk->tail_mean, tm, nq * sizeof(double), hipMemcpyDeviceToHost, stream));
-            if (risk->rank) ILQR_HIPCHK(hipMemcpyAsync(risk->rank, rk, (size_t)B * Q * sizeof(int), hipMemcpyDeviceToHost, stream));
-            if (risk->exceed) ILQR_HIPCHK(hipMemcpyAsync(risk->exceed, ex, nm * sizeof(int), hipMemcpyDeviceToHost, stream));
-        }
-        if (env) {
-            // results are written in the ABI's (dim, time) layout: plain copies bring back what was asked for
-            const int Q = (env->x_quantile || env->u_quantile || env->rank) ? env->n_levels : 0;
-            const size_t nxm = (size_t)B * NX * (N + 1), num = (size_t)B * NU * N;
-            const size_t n_out = (env_xm ? 4 * nxm : 0) + (env_um ? 4 * num : 0) + (env->x_quantile ? Q * nxm : 0) + (env->u_quantile ? Q * num : 0);
-            const size_t n_rank = env->rank ? (size_t)B * Q : 0, n_sv = env->step_violating ? (size_t)B * (N + 1) : 0;
-            if ((rc = grow(smp.env_in, (size_t)Q)) || (rc = grow(smp.env_out, n_out)) || (rc = grow(smp.env_counts, n_rank + n_sv))) return rc;
-            if (Q) ILQR_HIPCHK(hipMemcpyAsync(smp.env_in.p, env->levels, Q * sizeof(double), hipMemcpyHostToDevice, stream));
-            EnvelopeArgs<T> ea{};
-            ea.B = B; ea.S = d.n_samples; ea.N = N; ea.nx = NX; ea.nu = NU; ea.Q = Q;
-            ea.x_rows = (env_xm || env->x_quantile) ? (N + 1) * NX : 0;
-            ea.u_rows = env_u ? N * NU : 0;
-            ea.v_rows = env->step_violating ? N + 1 : 0;
-            ea.L = L; ea.tol = mc->violation_tol;
-            ea.cost = a.cost; ea.Xs = a.Xs; ea.Us = a.Us; ea.levels = smp.env_in.p; ea.lim = a.lim;
-            double* at = smp.env_out.p;
-            if (env_xm) { ea.x_mom = at; at += 4 * nxm; }
-            if (env_um) { ea.u_mom = at; at += 4 * num; }
-            if (env->x_quantile) { ea.x_q = at; at += Q * nxm; }
-            if (env->u_quantile) { ea.u_q = at; at += Q * num; }
-            if (env->rank) ea.rank = smp.env_counts.p;
-            if (env->step_violating) ea.step_violating = smp.env_counts.p + n_rank;
-            const int waves = std::max(ea.x_rows + ea.u_rows + ea.v_rows, 1);
-            if ((rc = timed(ILQR_PHASE_OTHER, [&] {
-                     ILQR_LAUNCH(policy_envelope_kernel<T>, dim3(waves, B), dim3(64), 0, stream, ea);
-                 })))
-                return rc;
-            auto back = [&](void* host, const void* dev, size_t bytes) -> int {
-                if (host) ILQR_HIPCHK(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, stream));
-                return ILQR_OK;
-            };
-            double* const xm[4] = {env->x_mean, env->x_std, env->x_min, env->x_max};
-            double* const um[4] = {env->u_mean, env->u_std, env->u_min, env->u_max};
-            for (int k = 0; k < 4; ++k) {
-                if (env_xm && (rc = back(xm[k], ea.x_mom + k * nxm, nxm * sizeof(double)))) return rc;
-                if (env_um && (rc = back(um[k], ea.u_mom + k * num, num * sizeof(double)))) return rc;
-            }
-            if ((rc = back(env->x_quantile, ea.x_q, Q * nxm * sizeof(double))) || (rc = back(env->u_quantile, ea.u_q, Q * num * sizeof(double))) ||
-                (rc = back(env->rank, ea.rank, n_rank * sizeof(int))) || (rc = back(env->step_violating, ea.step_violating, n_sv * sizeof(int))))
-                return rc;
-        }
-        auto fetch = [&](void* host, const T* dev) -> int {
-            if (host) ILQR_HIPCHK(hipMemcpyAsync(host, dev, L * sizeof(T), hipMemcpyDeviceToHost, stream));
-            return ILQR_OK;
-        };
-        if ((rc = fetch(d.cost, a.cost)) || (rc = fetch(d.deviation, a.deviation)) || (rc = fetch(d.violation, a.violation))) return rc;
+        if (mc && (rc = mc_stats(a, *mc))) return rc;
+        if (risk && (rc = mc_risk(a, L, *risk))) return rc;
+        if (env && (rc = mc_envelope(a, L, mc->violation_tol, *env, eg))) return rc;
+        if ((rc = fetch(d.cost, a.cost, L * sizeof(T))) || (rc = fetch(d.deviation, a.deviation, L * sizeof(T))) ||
+            (rc = fetch(d.violation, a.violation, L * sizeof(T))))
+            return rc;
         if (d.x_final && (rc = down_tcl(d.x_final, a.x_final, L, 1))) return rc;
         if (mc && mc->x0_out && (rc = down_tcl(mc->x0_out, smp.x0, L, 1))) return rc;
         if (w_back && (rc = down_tcl(mc->w_out, smp.w, L, N))) return rc;
@@ -1551,6 +1523,74 @@ template <typename T> class SolverT : public SolverBase {
         if (d.U && (rc = down_traj(d.U, smp.controls, L, NU, N))) return rc;
         ILQR_HIPCHK(hipStreamSynchronize(stream));
         return check_launch();
+    }
+    // The reductions of a Monte Carlo call over the sample summaries `a` names (sample_reduce.hpp), queued behind its
+    // rollout: each carves its buffers, launches and queues the downloads of what the caller asked for.
+    // The statistics (smp.stats and smp.counts are grown before the rollout, with the standard deviations).
+    int mc_stats(const PolicyArgs<T>& a, const ilqr_monte_carlo_desc& mc) {
+        if (!mc.stats && !mc.counts) return ILQR_OK;
+        hipLaunchKernelGGL(policy_stats_kernel<T>, dim3(B), dim3(64), 0, stream, (const T*)a.cost, (const T*)a.deviation,
+                           (const T*)a.violation, a.S, mc.violation_tol, smp.stats.p, smp.counts.p);
+        int rc;
+        if ((rc = fetch(mc.stats, smp.stats.p, (size_t)B * 7 * sizeof(double)))) return rc;
+        return fetch(mc.counts, smp.counts.p, (size_t)B * 2 * sizeof(int));
+    }
+    // The risk measures.  Levels and thresholds go up from the caller's arrays (the call ends synchronised); nothing is
+    // computed for a group of outputs the caller left out.
+    int mc_risk(const PolicyArgs<T>& a, size_t L, const ilqr_monte_carlo_risk_desc& risk) {
+        const int Q = (risk.quantile || risk.tail_mean || risk.rank) ? risk.n_levels : 0, M = risk.exceed ? risk.n_thresholds : 0;
+        const size_t nq = (size_t)B * 3 * Q, nm = (size_t)B * 3 * M;
+        int rc;
+        if ((rc = grow(smp.risk_in, Q + nm)) || (rc = grow(smp.risk_out, 2 * nq)) || (rc = grow(smp.risk_counts, (size_t)B * Q + nm))) return rc;
+        double *lev = smp.risk_in.p, *thr = lev + Q, *qu = smp.risk_out.p, *tm = qu + nq;
+        int *rk = smp.risk_counts.p, *ex = rk + (size_t)B * Q;
+        if (Q) ILQR_HIPCHK(hipMemcpyAsync(lev, risk.levels, Q * sizeof(double), hipMemcpyHostToDevice, stream));
+        if (M) ILQR_HIPCHK(hipMemcpyAsync(thr, risk.thresholds, nm * sizeof(double), hipMemcpyHostToDevice, stream));
+        hipLaunchKernelGGL(policy_risk_kernel<T>, dim3(B, 3), dim3(64), 0, stream, (const T*)a.cost, L, a.S, Q, M,
+                           (const double*)lev, (const double*)thr, qu, tm, rk, ex);
+        if ((rc = fetch(risk.quantile, qu, nq * sizeof(double))) || (rc = fetch(risk.tail_mean, tm, nq * sizeof(double))) ||
+            (rc = fetch(risk.rank, rk, (size_t)B * Q * sizeof(int))))
+            return rc;
+        return fetch(risk.exceed, ex, nm * sizeof(int));
+    }
+    // The envelope.  Results are written in the ABI's (dim, time) layout: plain copies bring back what was asked for.
+    int mc_envelope(const PolicyArgs<T>& a, size_t L, double tol, const ilqr_monte_carlo_envelope_desc& env, const EnvelopeGroups& g) {
+        const int Q = (g.xq || g.uq || g.rank) ? env.n_levels : 0;
+        const size_t nxm = (size_t)B * NX * (N + 1), num = (size_t)B * NU * N;
+        const size_t n_out = (g.xm ? 4 * nxm : 0) + (g.um ? 4 * num : 0) + (g.xq ? Q * nxm : 0) + (g.uq ? Q * num : 0);
+        const size_t n_rank = g.rank ? (size_t)B * Q : 0, n_sv = g.sv ? (size_t)B * (N + 1) : 0;
+        int rc;
+        if ((rc = grow(smp.env_in, (size_t)Q)) || (rc = grow(smp.env_out, n_out)) || (rc = grow(smp.env_counts, n_rank + n_sv))) return rc;
+        if (Q) ILQR_HIPCHK(hipMemcpyAsync(smp.env_in.p, env.levels, Q * sizeof(double), hipMemcpyHostToDevice, stream));
+        EnvelopeArgs<T> ea{};
+        ea.B = B; ea.S = a.S; ea.N = N; ea.nx = NX; ea.nu = NU; ea.Q = Q;
+        ea.x_rows = (g.xm || g.xq) ? (N + 1) * NX : 0;
+        ea.u_rows = g.u() ? N * NU : 0;
+        ea.v_rows = g.sv ? N + 1 : 0;
+        ea.L = L; ea.tol = tol;
+        ea.cost = a.cost; ea.Xs = a.Xs; ea.Us = a.Us; ea.levels = smp.env_in.p; ea.lim = a.lim;
+        double* at = smp.env_out.p;
+        if (g.xm) { ea.x_mom = at; at += 4 * nxm; }
+        if (g.um) { ea.u_mom = at; at += 4 * num; }
+        if (g.xq) { ea.x_q = at; at += Q * nxm; }
+        if (g.uq) { ea.u_q = at; at += Q * num; }
+        if (g.rank) ea.rank = smp.env_counts.p;
+        if (g.sv) ea.step_violating = smp.env_counts.p + n_rank;
+        const int waves = std::max(ea.x_rows + ea.u_rows + ea.v_rows, 1);
+        if ((rc = timed(ILQR_PHASE_OTHER, [&] {
+                 ILQR_LAUNCH(policy_envelope_kernel<T>, dim3(waves, B), dim3(64), 0, stream, ea);
+             })))
+            return rc;
+        double* const xm[4] = {env.x_mean, env.x_std, env.x_min, env.x_max};
+        double* const um[4] = {env.u_mean, env.u_std, env.u_min, env.u_max};
+        for (int k = 0; k < 4; ++k) {
+            if (g.xm && (rc = fetch(xm[k], ea.x_mom + k * nxm, nxm * sizeof(double)))) return rc;
+            if (g.um && (rc = fetch(um[k], ea.u_mom + k * num, num * sizeof(double)))) return rc;
+        }
+        if ((rc = fetch(env.x_quantile, ea.x_q, Q * nxm * sizeof(double))) || (rc = fetch(env.u_quantile, ea.u_q, Q * num * sizeof(double))) ||
+            (rc = fetch(env.rank, ea.rank, n_rank * sizeof(int))))
+            return rc;
+        return fetch(env.step_violating, ea.step_violating, n_sv * sizeof(int));
     }
 
     // What the search's descriptors share (ilqr_sample_controls_desc, ilqr_sampled_mpc_desc), refused in the order
@@ -1569,10 +1609,7 @@ template <typename T> class SolverT : public SolverBase {
         if ((unsigned long long)d.first_round + rounds > 0xfffffffeull)
             return bad(std::string("first_round + ") + rounds_what + " must be <= 2^32 - 2");
         if (!d.u_std) return bad("u_std is NULL");
-        for (size_t i = 0; i < (size_t)B * NU; ++i)
-            // (finite as the device holds it: a double beyond the handle's dtype would arrive there as +inf)
-            if (!std::isfinite(d.u_std[i]) || d.u_std[i] < 0.0 || d.u_std[i] > (double)std::numeric_limits<T>::max())
-                return bad("every standard deviation must be finite in the handle's dtype and >= 0");
+        if (int rc = std_check(who, "standard deviation", d.u_std, (size_t)B * NU, nullptr)) return rc;
         if (!(d.smoothing >= 0.0 && d.smoothing < 1.0)) return bad("smoothing must be in [0, 1)");
         if (d.mode == ILQR_SAMPLE_SOFTMIN && !(std::isfinite(d.temperature) && d.temperature > 0.0))
             return bad("temperature must be finite and > 0");
@@ -1602,9 +1639,7 @@ template <typename T> class SolverT : public SolverBase {
     // The penalty's buffers for a search of `rounds` rounds and `steps` rollouts of the nominal alone, and the report's
     // shapes; the report itself becomes valid when the call has succeeded (search_done).
     int search_begin(size_t L, size_t rounds, size_t per_step, size_t steps) {
-        pen.report = false;
-        el.report = false;
-        scn.report = false;
+        reports_off();
         int rc;
         if (scn.on) {
             if ((rc = grow(scn.cost, (L + (size_t)B) * scn.M()))) return rc;
@@ -1658,9 +1693,7 @@ template <typename T> class SolverT : public SolverBase {
             sa.scn_cost = scn.cost.p + (nominal ? scn.L * scn.M() : (size_t)0);
             return timed(ILQR_PHASE_OTHER, [&] { ops.sampling.rollout_scn[a.Sd != nullptr][a.pen != nullptr](sa, nz, stream); });
         }
-        return timed(ILQR_PHASE_OTHER, [&] {
-            (a.Sd ? ops.sampling.rollout_elite[a.pen != nullptr] : a.pen ? ops.sampling.rollout_pen : ops.sampling.rollout)(a, nz, stream);
-        });
+        return timed(ILQR_PHASE_OTHER, [&] { ops.sampling.rollout[a.Sd != nullptr][a.pen != nullptr](a, nz, stream); });
     }
     // the rollout of the nominal alone (S = 1: sample 0 is the nominal): its cost behind the samples', and while a
     // penalty is set its P and v behind the samples' too, in row `step` of [steps][B]
@@ -1682,7 +1715,7 @@ template <typename T> class SolverT : public SolverBase {
         if ((rc = search_desc_check(who, d, (unsigned long long)d.n_rounds, "n_rounds"))) return rc;
         if (!d.U_new && !d.cost_new && !d.X_new && !d.round_stats && !d.round_counts && !d.cost_samples && !d.U_samples)
             return bad("every output is NULL");
-        if ((rc = sample_total(who, d.n_samples, &L)) || (rc = scenario_total(who, L)) || (rc = sampling_supported(who)) ||
+        if ((rc = sample_total(who, d.n_samples, &L)) || (rc = scenario_total(who, L)) || (rc = sampling_supported(who, (bool)ops.sampling)) ||
             (rc = sampling_problem(who)) || (rc = sampling_settle()))
             return rc;
         const size_t Rn = (size_t)d.n_rounds;
@@ -1718,12 +1751,11 @@ template <typename T> class SolverT : public SolverBase {
         if (scn.on && d.X_new) {
             SampleArgs<T> g = f;
             g.Xs = smp.states.p; g.cost = f.cost + B;
-            if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.rollout(g, nz, stream); }))) return rc;
+            if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.rollout[0][0](g, nz, stream); }))) return rc;
         }
-        if (d.round_stats) ILQR_HIPCHK(hipMemcpyAsync(d.round_stats, smp.stats.p, Rn * B * 3 * sizeof(double), hipMemcpyDeviceToHost, stream));
-        if (d.round_counts) ILQR_HIPCHK(hipMemcpyAsync(d.round_counts, smp.counts.p, Rn * B * sizeof(int), hipMemcpyDeviceToHost, stream));
-        if (d.cost_samples) ILQR_HIPCHK(hipMemcpyAsync(d.cost_samples, a.cost, L * sizeof(T), hipMemcpyDeviceToHost, stream));
-        if (d.cost_new) ILQR_HIPCHK(hipMemcpyAsync(d.cost_new, f.cost, (size_t)B * sizeof(T), hipMemcpyDeviceToHost, stream));
+        if ((rc = fetch(d.round_stats, smp.stats.p, Rn * B * 3 * sizeof(double))) || (rc = fetch(d.round_counts, smp.counts.p, Rn * B * sizeof(int))) ||
+            (rc = fetch(d.cost_samples, a.cost, L * sizeof(T))) || (rc = fetch(d.cost_new, f.cost, (size_t)B * sizeof(T))))
+            return rc;
         if (d.U_samples && (rc = down_traj(d.U_samples, smp.controls, L, NU, N))) return rc;
         if (d.U_new && (rc = down_traj(d.U_new, smp.nominal, (size_t)B, NU, N))) return rc;
         if (d.X_new && (rc = down_traj(d.X_new, smp.states, (size_t)B, NX, N + 1))) return rc;
@@ -1752,7 +1784,7 @@ template <typename T> class SolverT : public SolverBase {
         for (size_t i = 0; w_host && i < K * B * NX; ++i)
             if (!std::isfinite(w_host[i])) return bad("every w value must be finite");
         if (!d.u_out && !d.x_out && !d.cost_out && !d.U_plan && !d.round_stats && !d.round_counts) return bad("every output is NULL");
-        if ((rc = sample_total(who, d.n_samples, &L)) || (rc = scenario_total(who, L)) || (rc = sampling_supported(who)) ||
+        if ((rc = sample_total(who, d.n_samples, &L)) || (rc = scenario_total(who, L)) || (rc = sampling_supported(who, (bool)ops.sampling)) ||
             (rc = sampling_problem(who)))
             return rc;
         if (!mpc_ready) return fail(ILQR_ERR_STATE, who + " before mpc_reset / mpc_rearm");
@@ -1803,10 +1835,6 @@ template <typename T> class SolverT : public SolverBase {
         const SampleCommitArgs<T> c{B, N, st.U.p, a.Ub, st.cur_slot};
         if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.commit(c, stream); }))) return rc;
         al.lam_shifted = false;      // (as mpc_rearm)
-        auto fetch = [&](void* host, const void* dev, size_t bytes) -> int {
-            if (host) ILQR_HIPCHK(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, stream));
-            return ILQR_OK;
-        };
         if ((rc = fetch(d.u_out, mpc_u_log.p, K * B * NU * sizeof(T))) || (rc = fetch(d.x_out, mpc_x_log.p, K * B * NX * sizeof(T))) ||
             (rc = fetch(d.cost_out, mpc_cost_log.p, K * B * sizeof(T))) ||
             (rc = fetch(d.round_stats, smp.stats.p, K * Rn * B * 3 * sizeof(double))) ||
@@ -1821,8 +1849,7 @@ template <typename T> class SolverT : public SolverBase {
     // Everything is checked before the handle or the device is touched.  The weights cross once, in the handle's dtype.
     int set_sample_penalty(const double* weight, double violation_tol) override {
         const std::string who = "set_sample_penalty";
-        if (!ops.sampling.rollout_pen)
-            return fail(ILQR_ERR_UNSUPPORTED, who + ": supported for the pendulum, UA double pendulum and double pendulum only");
+        if (int rc = sampling_supported(who, ops.sampling.rollout[0][1] != nullptr)) return rc;
         if (!weight) {
             pen.on = false;
             pen.report = false;
@@ -1853,10 +1880,6 @@ template <typename T> class SolverT : public SolverBase {
         if (!pen.report)
             return fail(ILQR_ERR_STATE, who + ": the handle's most recent sampling call was not a penalised sample_controls / sampled_mpc");
         const size_t L = pen.L, nB = (size_t)B, n_new = pen.steps * nB;
-        auto fetch = [&](void* host, const void* dev, size_t bytes) -> int {
-            if (host) ILQR_HIPCHK(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, stream));
-            return ILQR_OK;
-        };
         int rc;
         if ((rc = fetch(d.penalty_samples, pen.pen.p, L * sizeof(T))) || (rc = fetch(d.violation_samples, pen.viol.p, L * sizeof(T))) ||
             (rc = fetch(d.round_penalty, pen.stats.p, pen.rounds * nB * 3 * sizeof(double))) ||
@@ -1888,8 +1911,8 @@ template <typename T> class SolverT : public SolverBase {
     int set_sample_elites(int n_elite, int uniform, const double* std_min, const void* std_steps) override {
         const std::string who = "set_sample_elites";
         auto bad = [&](const char* what) { return fail(ILQR_ERR_INVALID_ARG, who + ": " + what); };
-        if (!ops.sampling.update_elite)
-            return fail(ILQR_ERR_UNSUPPORTED, who + ": supported for the pendulum, UA double pendulum and double pendulum only");
+        int rc;
+        if ((rc = sampling_supported(who, ops.sampling.rollout[1][0] != nullptr))) return rc;
         if (n_elite < 0) return bad("n_elite must be >= 0");
         if (n_elite == 0) {
             el.on = el.report = el.has_steps = false;
@@ -1898,16 +1921,10 @@ template <typename T> class SolverT : public SolverBase {
         if (!std_min) return bad("std_min is NULL");
         const size_t n = (size_t)B * NU;
         std::vector<T> lo(n);
-        for (size_t i = 0; i < n; ++i) {
-            // (finite as the device holds it: a double beyond the handle's dtype would arrive there as +inf)
-            if (!std::isfinite(std_min[i]) || std_min[i] < 0.0 || std_min[i] > (double)std::numeric_limits<T>::max())
-                return bad("every std_min value must be finite in the handle's dtype and >= 0");
-            lo[i] = (T)std_min[i];
-        }
+        if ((rc = std_check(who, "std_min value", std_min, n, lo.data()))) return rc;
         const T* steps = (const T*)std_steps;
         for (size_t i = 0; steps && i < n * N; ++i)
             if (!std::isfinite(steps[i]) || steps[i] < T(0)) return bad("every std_steps value must be finite and >= 0");
-        int rc;
         if ((rc = grow(el.std_min, n)) || (steps && (rc = grow(el.std_steps, n * N)))) return rc;
         ILQR_HIPCHK(hipMemcpyAsync(el.std_min.p, lo.data(), n * sizeof(T), hipMemcpyHostToDevice, stream));
         if (steps) ILQR_HIPCHK(hipMemcpyAsync(el.std_steps.p, steps, n * N * sizeof(T), hipMemcpyHostToDevice, stream));
@@ -1946,8 +1963,8 @@ template <typename T> class SolverT : public SolverBase {
                              const double* x0_std, const double* w_std) override {
         const std::string who = "set_sample_scenarios";
         auto bad = [&](const char* what) { return fail(ILQR_ERR_INVALID_ARG, who + ": " + what); };
-        if (!ops.sampling.rollout_scn[0][0])
-            return fail(ILQR_ERR_UNSUPPORTED, who + ": supported for the pendulum, UA double pendulum and double pendulum only");
+        int rc;
+        if ((rc = sampling_supported(who, ops.sampling.rollout_scn[0][0] != nullptr))) return rc;
         if (n_scenarios == 0) {
             scn.on = scn.report = false;
             return ILQR_OK;
@@ -1959,29 +1976,16 @@ template <typename T> class SolverT : public SolverBase {
         if (aggregate == ILQR_SCENARIO_TAIL && !(level >= 0.0 && level <= 1.0)) return bad("level must be in [0, 1] (and not NaN)");
         const size_t n = (size_t)B * NX;
         std::vector<T> sd(2 * n, T(0));
-        size_t at = 0;
-        for (const double* r : {x0_std, w_std}) {
-            for (size_t i = 0; r && i < n; ++i) {
-                // (finite as the device holds it: a double beyond the handle's dtype would arrive there as +inf)
-                if (!std::isfinite(r[i]) || r[i] < 0.0 || r[i] > (double)std::numeric_limits<T>::max())
-                    return bad("every standard deviation must be finite in the handle's dtype and >= 0");
-                sd[at + i] = (T)r[i];
-            }
-            at += n;
-        }
-        if (int rc = grow(scn.std, 2 * n)) return rc;
+        if ((rc = std_check(who, "standard deviation", x0_std, n, sd.data())) ||
+            (rc = std_check(who, "standard deviation", w_std, n, sd.data() + n)) || (rc = grow(scn.std, 2 * n)))
+            return rc;
         ILQR_HIPCHK(hipMemcpyAsync(scn.std.p, sd.data(), sd.size() * sizeof(T), hipMemcpyHostToDevice, stream));
         ILQR_HIPCHK(hipStreamSynchronize(stream));      // (sd outlives the copy)
         int log2m = 0;
         while ((1 << log2m) < n_scenarios) ++log2m;
         scn.on = true;
         scn.log2m = log2m; scn.agg = aggregate; scn.dist = distribution; scn.seed = seed;
-        scn.rank = 1;
-        if (aggregate == ILQR_SCENARIO_TAIL) {
-            // the rank rule of policy_risk_kernel: one rounded double product
-            const double kd = std::ceil(level * (double)n_scenarios);
-            scn.rank = kd < 1.0 ? 1 : kd > (double)n_scenarios ? n_scenarios : (int)kd;
-        }
+        scn.rank = aggregate == ILQR_SCENARIO_TAIL ? quantile_rank(level, n_scenarios) : 1;
         scn.has_x0 = x0_std != nullptr; scn.has_w = w_std != nullptr;
         scn.report = false;
         return ILQR_OK;

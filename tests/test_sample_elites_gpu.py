@@ -286,6 +286,38 @@ def test_non_finite_samples_are_no_elites(mode):
     assert (got.u_std_steps[1] != np.float32(ordinary[1, 0])).any()
 
 
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_a_long_row_with_non_finite_samples(dtype):
+    """S = 577 = 512 + 64 + 1: the select's digit passes walk the row eight strides at a time (csrc/sample_reduce.hpp,
+    for_finite), then a full wave, then a one-lane tail, and skip the non-finite samples on the way.  Trajectory 0 draws
+    with a u_std at which a share of its rollouts leaves the range the device's sin / cos reduce (csrc/dynamics.hpp) and
+    diverges (the NumPy reference does not diverge there: the share is asserted on the call's own costs); more than
+    n_elite stay finite, so the select runs."""
+    B, S, N, E = 2, 577, 3, 37
+    x0, U0, u_std = sc.search_inputs("pendulum", (B, S, N))
+    u_std = u_std.copy()
+    u_std[0] = 1e13 if dtype == np.float32 else 1e22
+    dyn, cost = ref.spec("pendulum", N)
+    s = ilqr_amd.iLQR(ilqr_amd.make_system(dyn, cost), None, x0, U0, N=N, verbose=False, dtype=dtype)
+    s.set_sample_elites(E, 0.0, False)
+    got = s.sample_controls(S, 1, SEED, u_std, "softmin", TEMPERATURE["pendulum"], BETA, samples=True)
+    fin = np.isfinite(got.cost_samples)
+    print(f"MEASURED elites long row {np.dtype(dtype).name}: n_finite {fin.sum(axis=1).tolist()} of {S}")
+    assert E < fin[0].sum() < S and fin[1].all()
+    want = se.update(got.cost_samples, got.U_samples, U0.astype(dtype), se.constant_steps(u_std, N, dtype), np.zeros((B, 1)),
+                     E, False, "softmin", TEMPERATURE["pendulum"], dtype)
+    np.testing.assert_array_equal(got.elite_samples, want["mask"])
+    np.testing.assert_array_equal(got.round_n_elite[0], want["n_e"])
+    np.testing.assert_array_equal(got.round_n_elite[0], E)
+    np.testing.assert_array_equal(got.round_n_finite[0], fin.sum(axis=1))
+    assert not got.elite_samples[~fin].any()
+    std = np.stack([se.spread(want["w"][b], got.U_samples[b], got.U[b], np.zeros(1), np.float64) for b in range(B)])
+    if dtype == np.float64:
+        np.testing.assert_allclose(got.u_std_steps, std, rtol=1e-10, atol=0)
+    else:
+        assert (np.abs(got.u_std_steps.astype(np.float64) - std) <= np.spacing(std.astype(np.float32))).all()
+
+
 # ---- 8. sampled MPC --------------------------------------------------------------------------------------------------------
 def _replay(twin, got, x0, U0, n_steps, S, R, first_round, search, what, extra=()):
     """every step of `got` on the twin's sample_controls: x_0 <- the state before the step, U <- the previous plan shifted"""

@@ -1,6 +1,7 @@
 """Every output of the sampling entries (policy_rollout, policy_monte_carlo, sample_controls, sampled_mpc, and the last two
-under a sample penalty) at small shapes, as one .npz: run it once per build (ILQR_LIB selects the library; a copy of another checkout runs its own package and
-plugins) and compare the two files with --compare.  A refactor of those entries must leave every array identical.
+under a sample penalty, with elites and under noise scenarios; the Monte Carlo call with its risk measures and its envelope)
+at small shapes, as one .npz: run it once per build (ILQR_LIB selects the library; a copy of another checkout runs its own
+package and plugins) and compare the two files with --compare.  A refactor of those entries must leave every array identical.
 
 Systems: the built-in policy systems (pendulum, UA double pendulum, double pendulum) and the policy example plugins.
 fp32 and fp64; B = 3, N = 5, S in {1, 65} (a full wave plus a one-lane tail); plant / model integrator rk4 and
@@ -11,22 +12,35 @@ steps of two rounds.  A penalised sample_controls and sampled_mpc (state limits,
 penalty's attributes of their records.  One unbatched solver (x_0 of shape (n_x,)) through all five calls: its records
 have no batch axis.  (Limits, parameter rows and the penalty exist for the built-in systems only.)
 
-    python tools/sampling_dump.py out.npz
+The reductions behind the rollouts, on the built-in systems (dump_reductions): sample_controls and sampled_mpc with elites
+(both modes, uniform on and off, with and without std_steps, n_elite >= n_finite, under the penalty) and with scenarios
+(M = 1, 4, 64; mean, max, tail; with the penalty, with elites, with trajectories); policy_monte_carlo with quantiles= and
+thresholds=, with envelope= as True and as levels, with and without state limits, and all of them in one call.  Trajectory 0
+of these calls has an x_0_std (Monte Carlo) or u_std (elites) at which some samples diverge (DIVERGING), so the finite
+filter has something to filter: the tool prints n_finite and fails unless 0 < n_finite < S there (S > 1).  One longer row
+(long_row): S = 1089 = 1024 + 65 on the pendulum -- past the envelope's resident cap, through for_finite's batched path
+with a one-lane tail.
+
+    python tools/sampling_dump.py out.npz [--systems pendulum,ua,...] [--long-only | --no-long]
     python tools/sampling_dump.py --compare a.npz b.npz [summary.json]
 """
 import json
 import os
 import sys
+import zipfile
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import ilqr_amd  # noqa: E402
-from ilqr_amd import problems  # noqa: E402
+from ilqr_amd import problems, sampling  # noqa: E402
 from ilqr_amd.systems.examples import policy_example_systems  # noqa: E402
 
 B, N, DT, SEED = 3, 5, 0.01, 0x0123456789ABCDEF
 BUILTIN = {"pendulum": problems.pendulum_mpc, "ua": problems.ua_double_pendulum, "dp": problems.double_pendulum}
+ATTRIBUTES = (sampling.PENALTY_FIELDS + sampling.ELITE_FIELDS + sampling.SCENARIO_FIELDS + sampling.RISK_FIELDS
+              + sampling.ENVELOPE_FIELDS)
+FILTER_FAILURES = []
 ROWS = {"pendulum": ("l",), "ua": ("m2", "l2"), "dp": ("m2", "l2")}
 
 
@@ -48,8 +62,8 @@ def inputs(n, m, S):
 
 
 def record(out, tag, result):
-    """the fields of the record and, where it has them, the penalty's attributes beside them (_asdict() does not see those)"""
-    fields = dict(result._asdict(), **{k: getattr(result, k, None) for k in ilqr_amd.iLQR_class.PENALTY_FIELDS})
+    """the fields of the record and, where it has them, the attributes beside them (_asdict() does not see those)"""
+    fields = dict(result._asdict(), **{k: getattr(result, k, None) for k in ATTRIBUTES})
     for k, v in fields.items():
         if v is not None:
             out[f"{tag}/{k}"] = np.asarray(v)
@@ -123,6 +137,116 @@ def dump_case(out, name, dtype, integrator, S):
     dump_unbatched(out, tag, sysm, dtype, integrator, S, X[0], U[0], K[0], x0[0], w[0], x0_std[0], w_std[0], u_std[0], builtin)
 
 
+# (x_0_std, u_std) of trajectory 0 in the reduction cases: at these some of its samples -- not all -- leave the range in
+# which the device's sin / cos reduce their argument (csrc/dynamics.hpp), and their rollouts diverge to a non-finite cost
+# (measured at S = 65, both integrators: 4 .. 62 finite samples)
+DIVERGING = {"pendulum": {"float32": (1e10, 3e12), "float64": (1e18, 3e21)},
+             "ua": {"float32": (1e2, 1e4), "float64": (1e2, 1e4)}, "dp": {"float32": (1e2, 1e4), "float64": (1e2, 1e4)}}
+
+
+def filtered(tag, n_finite, S):
+    """trajectory 0 of a call (its first round) whose finite filter must have something to filter"""
+    n = int(np.asarray(n_finite).reshape(-1, B)[0, 0])
+    print(f"n_finite {tag}: {n} of {S}", flush=True)
+    if S > 1 and not 0 < n < S:
+        FILTER_FAILURES.append(f"{tag}: n_finite = {n} of {S}")
+
+
+def reduction_inputs(name, dtype, n, m):
+    """the standard deviations of the reduction cases, and those with trajectory 0 drawing at the DIVERGING scale"""
+    rng = np.random.default_rng(23)
+    x0_std, w_std, u_std = rng.uniform(0.01, 0.05, (B, n)), rng.uniform(1e-4, 1e-3, (B, n)), rng.uniform(0.05, 0.2, (B, m))
+    x0_big, u_big = x0_std.copy(), u_std.copy()
+    x0_big[0], u_big[0] = DIVERGING[name][np.dtype(dtype).name]
+    return x0_std, w_std, u_std, x0_big, u_big
+
+
+def dump_monte_carlo_reductions(out, tag, s, S, x0_big, w_std, integrator):
+    """quantiles= / thresholds=, envelope= as True and as levels, and all of them in one call"""
+    levels, bands = (0.0, 0.5, 0.95, 1.0), (0.05, 0.5, 0.95)
+    thr = {"cost": (0.5, 1.0, 10.0, 1e3, 1e6), "deviation": 0.05, "violation": 1e-3}      # (five: two blocks of four)
+    mc = lambda dist, **kw: s.policy_monte_carlo(S, SEED, x0_big, w_std, dist, integrator=integrator, violation_tol=1e-3,
+                                                 first_trajectory=2, **kw)
+    for dist in ("gaussian", "uniform"):
+        r = mc(dist, quantiles=levels, thresholds=thr, samples=True)
+        filtered(f"{tag}/risk/{dist}", r.n_finite, S)
+        record(out, f"{tag}/risk/{dist}", r)
+        record(out, f"{tag}/risk_levels_only/{dist}", mc(dist, quantiles=levels))
+        record(out, f"{tag}/risk_thresholds_only/{dist}", mc(dist, thresholds=thr))
+        record(out, f"{tag}/envelope_true/{dist}", mc(dist, envelope=True))
+        record(out, f"{tag}/envelope_levels/{dist}", mc(dist, envelope=bands, trajectories=True))
+        record(out, f"{tag}/envelope_risk/{dist}", mc(dist, envelope=bands, quantiles=levels, thresholds=thr, samples=True))
+
+
+def dump_reductions(out, name, dtype, integrator, S, N_=N, long_row=False):
+    """elites, scenarios, the risk measures and the envelope (built-in systems)"""
+    tag = f"{name}/{np.dtype(dtype).name}/{integrator}/S{S}/reduce"
+    p = BUILTIN[name](N=N_)
+    sysm = ilqr_amd.make_system({**p["dynamics"], "integrator": integrator, "dt": DT}, p["cost"], dtype)
+    n, m = sysm.n_x, sysm.n_u
+    X, U, K, x0, w = inputs(n, m, 1)
+    x0_std, w_std, u_std, x0_big, u_big = reduction_inputs(name, dtype, n, m)
+    x_max = np.full(n, np.inf)
+    x_max[0] = 0.1
+    limits = dict(u_min=-0.2, u_max=0.15, x_min=-x_max, x_max=x_max)
+    w_mpc = np.ascontiguousarray(w[:, 0, :2].transpose(1, 0, 2))
+    solver = lambda **kw: ilqr_amd.iLQR(sysm, None, X[:, :, 0], U, N=N_, verbose=False, dtype=dtype, plant=sysm, **kw)
+
+    # ---- the Monte Carlo reductions, without and with state limits
+    for setup, kw in (("plain", {}), ("limits", limits)):
+        s = solver(**kw)
+        s.X, s.K = X, K
+        dump_monte_carlo_reductions(out, f"{tag}/{setup}/monte_carlo", s, S, x0_big, w_std, integrator)
+        if long_row:
+            break
+
+    # ---- elites (no control limits: the clamp would take the overflow away)
+    search = lambda s_, std, mode, temp, **kw: s_.sample_controls(S, 2, SEED, std, mode, temp, 0.9, first_trajectory=1,
+                                                                  first_round=3, samples=True, **kw)
+    s = solver()
+    rng = np.random.default_rng(29)
+    steps = rng.uniform(0.05, 0.2, (B, m, N_))
+    steps[0] = u_big[0, :, None]
+    for mode, temp in (("best", None), ("softmin", 10.0)):
+        for uniform in (True, False):
+            for name_, std_steps in (("u_std", None), ("std_steps", steps)):
+                if long_row and not (mode == "softmin" and not uniform and std_steps is None):
+                    continue
+                s.set_sample_elites(7 if not long_row else 37, 0.01, uniform, std_steps)
+                at = f"{tag}/elites/{mode}/uniform{int(uniform)}/{name_}"
+                r = search(s, u_big, mode, temp, trajectories=True)
+                filtered(at, r.round_n_finite, S)
+                record(out, f"{at}/search", r)
+                if std_steps is None and not long_row:
+                    dump_mpc(out, at, s, X[:, :, 0], U, S, u_std, "gaussian", w_mpc, samples=True)
+    if long_row:
+        return
+    s.set_sample_elites(S + 5, 0.01, False)           # n_elite >= n_finite: the round without elites
+    record(out, f"{tag}/elites/all/search", search(s, u_big, "softmin", 10.0))
+    s.set_sample_elites(S + 5, 0.01, True)
+    record(out, f"{tag}/elites/all_unit/search", search(s, u_big, "softmin", 10.0))
+    sp = solver(mpc_multipliers="warm", **limits)     # under the penalty (and the control limits)
+    sp.set_sample_penalty(np.linspace(5.0, 50.0, B), 1e-3)
+    sp.set_sample_elites(7, 0.01, False)
+    record(out, f"{tag}/elites/penalty/search", search(sp, u_std, "softmin", 10.0, trajectories=True))
+    dump_mpc(out, f"{tag}/elites/penalty", sp, X[:, :, 0], U, S, u_std, "gaussian", w_mpc, samples=True)
+
+    # ---- scenarios: M = 1, 4, 64, every aggregate; with the penalty, with elites, with trajectories
+    for M in (1, 4, 64):
+        for agg, level in (("mean", None), ("max", None), ("tail", 0.75)):
+            for what, s_ in (("plain", s), ("penalty", sp)):
+                s_.set_sample_elites(7 if M == 4 else None, 0.01, False)
+                s_.set_sample_scenarios(M, agg, level, SEED + 1, "gaussian" if M != 4 else "uniform", x0_std, w_std)
+                at = f"{tag}/scenarios/M{M}/{agg}/{what}"
+                for mode, temp in (("best", None), ("softmin", 10.0)):
+                    record(out, f"{at}/search/{mode}", search(s_, u_std, mode, temp, trajectories=True))
+                    record(out, f"{at}/search_no_X/{mode}", search(s_, u_std, mode, temp))
+                dump_mpc(out, at, s_, X[:, :, 0], U, S, u_std, "gaussian", w_mpc, samples=True)
+    for s_ in (s, sp):
+        s_.set_sample_scenarios(None)
+        s_.set_sample_elites(None)
+
+
 def dump_unbatched(out, tag, sysm, dtype, integrator, S, X, U, K, x0, w, x0_std, w_std, u_std, builtin):
     """all five calls on a solver built from x_0 of shape (n_x,): the records lose the batch axis"""
     kw = {}
@@ -148,15 +272,22 @@ def same(a, b):
     return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b, equal_nan=a.dtype.kind == "f")
 
 
+def load(path):
+    """every array of an .npz as a dict, member by member (np.load's NpzFile searches a list of names on every access:
+    quadratic in the hundred thousand arrays of a dump)"""
+    with zipfile.ZipFile(path) as z:
+        return {name[:-len(".npy")]: np.lib.format.read_array(z.open(name)) for name in z.namelist()}
+
+
 def compare(path_a, path_b, path_json=None):
     """Array by array (NaN equal to NaN).  The summary has one entry per group of calls that share a system, their
     arrays' names and shapes and their result: the values each level of the calls' names takes (the group is their
     product, or lists its calls), the arrays with their shapes, and "identical" when every array of every call is."""
-    a, b = np.load(path_a), np.load(path_b)
+    a, b = load(path_a), load(path_b)
     calls, bad = {}, []
-    for k in sorted(set(a.files) | set(b.files)):
+    for k in sorted(set(a) | set(b)):
         call, _, field = k.rpartition("/")
-        ok = k in a.files and k in b.files and same(a[k], b[k])
+        ok = k in a and k in b and same(a[k], b[k])
         calls.setdefault(call, {})[field] = list(a[k].shape) if ok else "DIFFERENT"
         if not ok:
             bad.append(k)
@@ -182,14 +313,26 @@ def compare(path_a, path_b, path_json=None):
 def main():
     if sys.argv[1] == "--compare":
         sys.exit(compare(*sys.argv[2:5]))
+    args = sys.argv[2:]
+    names = list(BUILTIN) + list(policy_example_systems())
+    if "--systems" in args:
+        names = args[args.index("--systems") + 1].split(",")
     out = {}
-    for name in list(BUILTIN) + list(policy_example_systems()):
+    for name in names if "--long-only" not in args else ():
         for dtype in (np.float32, np.float64):
             for integrator in ("rk4", "backward_euler"):
                 for S in (1, 65):
                     dump_case(out, name, dtype, integrator, S)
+                    if name in BUILTIN:
+                        dump_reductions(out, name, dtype, integrator, S)
+                    print(f"{name} {np.dtype(dtype).name} {integrator} S={S}: {len(out)} arrays", flush=True)
+    if "--no-long" not in args and "pendulum" in names:
+        for dtype in (np.float32, np.float64):
+            dump_reductions(out, "pendulum", dtype, "rk4", 1089, long_row=True)
     np.savez_compressed(sys.argv[1], **out)
     print(f"{len(out)} arrays -> {sys.argv[1]}")
+    if FILTER_FAILURES:
+        sys.exit("the finite filter had nothing to filter:\n" + "\n".join(FILTER_FAILURES))
 
 
 if __name__ == "__main__":
