@@ -918,6 +918,73 @@ typedef struct ilqr_sample_scenario_report_desc {
 } ilqr_sample_scenario_report_desc;
 int ilqr_sample_scenario_report(ilqr_handle h, const ilqr_sample_scenario_report_desc* d);
 
+/* ---- parameter spread: plant parameters drawn on the device (build extension) ---------------------------------
+ * ilqr_policy_monte_carlo and the noise scenarios answer "what if the state is not the state I planned from"; this
+ * entry adds "what if the arm is not the arm I modelled": the system parameters of every Monte Carlo sample and every
+ * search scenario are drawn on the device, from the same counter-based generator, where plant_rows has them drawn on
+ * the host, derived there row by row and uploaded.  The state is sticky like ilqr_set_sample_scenarios.
+ * std is [B][n_sys], n_sys the number of system parameters in parameter-block order as in ilqr_set_batch_params (3 for
+ * the pendulum, 9 for the double pendulums); NULL clears the spread (the other arguments are then not read).
+ *   relative != 0:  sd = |base_j[b]| * std[b][j]     else  sd = std[b][j]       (one rounded double product, on the host)
+ * clip bounds the variate: z is clamped to [-c, c], c = (float)clip, finite and > 0 as a float.  The clamp acts on z, not
+ * on the parameter, so a parameter with sd = 0 comes out as its base exactly and no infinite bounds are needed.
+ * The handle holds std, relative and clip.  base is resolved at every sampling call that reads the spread, not at set
+ * time: an ilqr_set_batch_params between the setter and the call takes effect.
+ * The draw.  For trajectory b, sample s and parameter j, with group g = j / 4: one Philox4x32-10 call at counter
+ * (s, first_trajectory + b, 1 + g, 1) under the key of the call that draws (ilqr_monte_carlo_desc.seed, or the scenario
+ * seed); z is component j mod 4 of that call under that call's distribution, the transforms given at
+ * ilqr_policy_monte_carlo, in fp32.  Stream 1 is the x_0 stream, read there at the third counter words 0 and 2^31 only, so
+ * the words 1 + g (g <= 2) are free: this draw moves no existing stream, and x0_out / w_out keep their bits whether or
+ * not a spread is set.  All ceil(n_sys / 4) calls are made once per sample, before the step loop.
+ *   p_j = base_j[b] + (sd_j[b] * (double) clamp(z, -c, c))
+ * in double, the product rounded on its own and never fused with the add.  The derived constants of the sample are the
+ * block's formulas applied to p in double, each rounded once to the handle's dtype -- the arithmetic of a plant_rows row,
+ * by ONE function the host and the kernels share (derive_sys_constants, csrc/dynamics.hpp), so ilqr_policy_rollout fed
+ * with the drawn p as plant_rows gives the same bits, and a spread of all zeros gives the bits of no spread.
+ * The streams depend neither on B nor on S; a shard draws the fleet's through first_trajectory.
+ * Who reads the spread.
+ *   ilqr_policy_monte_carlo, _risk and _envelope: sample s of trajectory b is rolled out through the plant at the
+ *     constants of its drawn p.  base is the trajectory's plant parameters: the first that is set of its ILQR_BATCH_PLANT
+ *     row, its ILQR_BATCH_MODEL row and the block.  The cost stays the model's.  A call that also passes plant_rows
+ *     returns ILQR_ERR_INVALID_ARG.  Everything said at those entries holds as it stands.
+ *   ilqr_sample_controls and ilqr_sampled_mpc, while scenarios are set: scenario m of trajectory b gets the parameters of
+ *     Monte Carlo sample m, counter (m, first_trajectory + b, 1 + g, 1) under the scenario seed and distribution.  base is
+ *     the trajectory's MODEL parameters (its ILQR_BATCH_MODEL row, else the block): the search's plant is the model.  The
+ *     M parameter sets are the same for every sample, round and MPC step (common random numbers), so every identity stated
+ *     at ilqr_set_sample_scenarios holds unchanged, and "scenario m is exactly Monte Carlo sample m" now covers the
+ *     parameters: bit for bit when the handle has no plant rows and the Monte Carlo call uses the model's integrator with
+ *     feedback = 0.  Without scenarios the search ignores the spread.  X_new stays the disturbance-free rollout at the
+ *     model's own parameters.
+ *   ilqr_policy_rollout, the solves and ilqr_mpc_run ignore the spread.
+ * Left out: fresh parameters per round or step, correlated parameters, a spread on x_target, Q and R, user-defined systems.
+ * Returns ILQR_ERR_INVALID_ARG for a NULL handle, a negative or non-finite std, a clip that is not finite and > 0 as a
+ * float, and for any (b, j) with sd > 0 and sd * c >= |base_j[b]| -- the parameter could reach zero or change sign; a
+ * base of 0 therefore takes no spread.  That rule is checked at set time against the bases of that moment in both
+ * resolution orders, and again, with the same message, by every call that resolves the bases.  ILQR_ERR_UNSUPPORTED for
+ * ILQR_SYS_LINEAR and every ILQR_SYS_CUSTOM handle; clearing with NULL is valid everywhere.  A failed call leaves the
+ * handle unchanged; a successful one invalidates the sampling reports.
+ * ILQR_ABI_VERSION stays 5 with this entry: it is additive, and no existing descriptor changes. */
+int ilqr_set_param_spread(ilqr_handle h, const double* std /* [B][n_sys], or NULL: clear */, int32_t relative, double clip);
+
+/* The drawn parameters p of S samples per trajectory, [B][S][n_sys] doubles: a small kernel that calls the device function
+ * the rollouts call.  A pure function of the handle's spread, its current bases and the descriptor: `base` picks the
+ * resolution order (ILQR_BATCH_PLANT: what ilqr_policy_monte_carlo centres on; ILQR_BATCH_MODEL: what the scenarios
+ * centre on), seed / distribution / first_trajectory are those of the call to reproduce.  Deliberately a function and
+ * not a report of "the last call", so its result can be fed straight into ilqr_policy_rollout's plant_rows.
+ * Synchronous; changes nothing.  Returns ILQR_ERR_STATE without a spread set; ILQR_ERR_INVALID_ARG for a NULL handle or
+ * desc, a wrong struct_size, n_samples < 1, batch * n_samples >= 2^31, an unknown distribution or base,
+ * first_trajectory < 0, params NULL, or bases that break the sign rule above. */
+typedef struct ilqr_param_spread_draw_desc {
+    uint32_t struct_size;     /* = sizeof(ilqr_param_spread_draw_desc) */
+    int32_t n_samples;        /* S >= 1 */
+    int32_t distribution;     /* ILQR_NOISE_* */
+    int32_t first_trajectory; /* >= 0 */
+    int32_t base;             /* ILQR_BATCH_PLANT or ILQR_BATCH_MODEL: which resolution order */
+    uint64_t seed;
+    double* params;           /* [B][S][n_sys] */
+} ilqr_param_spread_draw_desc;
+int ilqr_param_spread_draw(ilqr_handle h, const ilqr_param_spread_draw_desc* d);
+
 /* ---- multi-GPU hook -------------------------------------------
  * Writes 4 doubles to DEVICE memory `dev_out4` on the handle's stream:
  *   { min cost, max |cost - cost_prev|, #trajectories still active, #converged }

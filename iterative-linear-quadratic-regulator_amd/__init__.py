@@ -11,7 +11,8 @@ from . import _lib  # noqa: F401
 from .iLQR_class import (iLQR, horizon_steps, batch_param_rows, control_limits, state_limits,  # noqa: F401
                          mpc_multiplier_mode, policy_rollout_args, PolicyRollout,
                          policy_monte_carlo_args, policy_risk_args, policy_envelope_args, PolicyMonteCarlo, sample_controls_args, SampledControls,
-                         sampled_mpc_args, SampledMPC, sample_penalty_args, sample_elites_args, sample_scenarios_args)
+                         sampled_mpc_args, SampledMPC, sample_penalty_args, sample_elites_args, sample_scenarios_args,
+                         param_spread_args, param_spread_draw_args)
 from .systems import (System, MyPendulum, MyUADoublePendulum, MyDoublePendulum,  # noqa: F401
                       MyLinearSystem)
 from .api import solve, SolveResult, MPCState, mpc_init, mpc_step, make_system, RiccatiSweep  # noqa: F401

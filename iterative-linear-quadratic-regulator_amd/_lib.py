@@ -46,7 +46,7 @@ SYMBOLS = (
     "ilqr_set_batch_limits", "ilqr_policy_rollout", "ilqr_policy_monte_carlo", "ilqr_sample_controls",
     "ilqr_sampled_mpc", "ilqr_set_sample_penalty", "ilqr_sample_penalty_report", "ilqr_set_sample_elites",
     "ilqr_sample_elite_report", "ilqr_policy_monte_carlo_risk", "ilqr_set_sample_scenarios", "ilqr_sample_scenario_report",
-    "ilqr_policy_monte_carlo_envelope", "ilqr_policy_envelope_resident_cap",
+    "ilqr_policy_monte_carlo_envelope", "ilqr_policy_envelope_resident_cap", "ilqr_set_param_spread", "ilqr_param_spread_draw",
 )
 # ilqr_set_batch_params: which rows
 BATCH_MODEL, BATCH_PLANT = 0, 1
@@ -196,6 +196,15 @@ class SampleScenarioReportDesc(C.Structure):
     ]
 
 
+class ParamSpreadDrawDesc(C.Structure):
+    """ilqr_param_spread_draw_desc (include/ilqr_hip.h), field for field."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("n_samples", C.c_int32), ("distribution", C.c_int32), ("first_trajectory", C.c_int32), ("base", C.c_int32),
+        ("seed", C.c_uint64), ("params", C.POINTER(C.c_double)),
+    ]
+
+
 class IlqrError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libilqr_hip error {code}: {msg}")
@@ -278,6 +287,8 @@ def load():
     lib.ilqr_sample_elite_report.argtypes = [vp, C.POINTER(SampleEliteReportDesc)]
     lib.ilqr_set_sample_scenarios.argtypes = [vp, C.c_int32, C.c_int32, cd, C.c_uint64, C.c_int32, C.POINTER(cd), C.POINTER(cd)]
     lib.ilqr_sample_scenario_report.argtypes = [vp, C.POINTER(SampleScenarioReportDesc)]
+    lib.ilqr_set_param_spread.argtypes = [vp, C.POINTER(cd), C.c_int32, cd]
+    lib.ilqr_param_spread_draw.argtypes = [vp, C.POINTER(ParamSpreadDrawDesc)]
     if lib.ilqr_abi_version() != ABI_VERSION:
         raise RuntimeError("libilqr_hip.so ABI version mismatch: rebuild the library")
     _lib = lib
@@ -824,6 +835,29 @@ class Handle:
             shapes.update(scenario_X=(B, M, self.n_x, self.N + 1))
         out = self._outputs(d, shapes)
         self._chk(self.lib.ilqr_sample_scenario_report(self.h, C.byref(d)))
+        return out
+
+    # ---- parameter spread ----------------------------------------------------------------------------
+    def set_param_spread(self, std, relative=True, clip=3.0):
+        """The system parameters of every Monte Carlo sample and every search scenario drawn on the device around the
+        trajectory's own (include/ilqr_hip.h, ilqr_set_param_spread): std (B, n_sys) float64 >= 0 in parameter-block
+        order, relative to |base| or absolute; the variate is clamped to [-clip, clip].  None clears the spread."""
+        if std is None:
+            self._chk(self.lib.ilqr_set_param_spread(self.h, None, 0, 0.0))
+            return
+        r = np.ascontiguousarray(std, dtype=np.float64)
+        if r.ndim != 2 or r.shape[0] != self.B:
+            raise ValueError(f"the parameter spread must have shape ({self.B}, n_sys), but got {r.shape}")
+        self._chk(self.lib.ilqr_set_param_spread(self.h, r.ctypes.data_as(C.POINTER(C.c_double)), int(bool(relative)), float(clip)))
+
+    def param_spread_draw(self, n_samples, n_sys, seed=0, distribution=NOISE_GAUSSIAN, first_trajectory=0, base=BATCH_PLANT):
+        """The parameters the samples of such a call draw, (B, S, n_sys) float64 (include/ilqr_hip.h,
+        ilqr_param_spread_draw); base = BATCH_PLANT: as policy_monte_carlo centres them, BATCH_MODEL: as the scenarios do."""
+        d, _ = self._desc(ParamSpreadDrawDesc, n_samples=n_samples, distribution=distribution, first_trajectory=first_trajectory,
+                          base=base, seed=seed)
+        out = np.empty((self.B, max(int(n_samples), 0), int(n_sys)), dtype=np.float64)
+        d.params = out.ctypes.data_as(C.POINTER(C.c_double))
+        self._chk(self.lib.ilqr_param_spread_draw(self.h, C.byref(d)))
         return out
 
     # ---- measurement ------------------------------------------------------------------------------

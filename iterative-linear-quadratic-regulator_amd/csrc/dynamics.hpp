@@ -205,6 +205,40 @@ template <int NSYS, int NX, int NU> struct ParamLayout {
     static constexpr int TOTAL = QFS + NX * NX;
 };
 
+// The derived system constants of the built-in pendulums from their ABI parameters, in double: pendulum (g, l, d) ->
+// [g/l, d]; double pendulums (g, m1, m2, l1, l2, d1, d2, th1, th2) -> the seven constants listed at DoublePendulum.
+// THE one place these formulas stand: the host (build_device_params, and through it every row of
+// ilqr_set_batch_params and every plant_rows sample) and the kernels that draw a sample's parameters themselves
+// (param_spread_draw, policy_rollout.hpp) both call it, and each rounds a constant once to the handle's dtype.  Contraction
+// is off inside it, so that the device, which has a double FMA, evaluates every product and sum as the host does (baseline
+// x86-64 has none, so the pragma changes nothing there): plain v_mul_f64 / v_add_f64, the division by 4 an exact multiply,
+// and g / l the correctly rounded v_div_scale / v_div_fmas / v_div_fixup sequence.  Same p, same bits on both sides.
+// Returns the number of constants written (0 for a system without such constants).
+constexpr int sys_params_abi(int system) {
+    return system == ILQR_SYS_PENDULUM ? 3 : (system == ILQR_SYS_UA_DOUBLE_PENDULUM || system == ILQR_SYS_DOUBLE_PENDULUM) ? 9 : 0;
+}
+__host__ __device__ __forceinline__ int derive_sys_constants(int system, const double* p, double* d) {
+#pragma clang fp contract(off)
+    if (system == ILQR_SYS_PENDULUM) {
+        const double g = p[0], l = p[1], dd = p[2];
+        d[0] = g / l;
+        d[1] = dd;
+        return 2;
+    }
+    if (system == ILQR_SYS_UA_DOUBLE_PENDULUM || system == ILQR_SYS_DOUBLE_PENDULUM) {
+        const double g = p[0], m1 = p[1], m2 = p[2], l1 = p[3], l2 = p[4], d1 = p[5], d2 = p[6], th1 = p[7], th2 = p[8];
+        d[0] = m2 * l1 * l2;
+        d[1] = (m1 * l1 * l1) / 4 + m2 * l1 * l1 + (m2 * l2 * l2) / 4 + th1 + th2;
+        d[2] = (m2 * l2 * l2) / 4 + th2;
+        d[3] = m2 * g * l2 / 2;
+        d[4] = (m2 + m1 / 2) * g * l1;
+        d[5] = d1;
+        d[6] = d2;
+        return 7;
+    }
+    return 0;
+}
+
 // ---- pendulum (pendulum_sys.py:60-75): derived constants [g/l, d] ------------
 template <typename T> struct Pendulum {
     template <typename S> using rebind = Pendulum<S>;

@@ -384,6 +384,26 @@ int ilqr_sample_scenario_report(ilqr_handle h, const ilqr_sample_scenario_report
     }
     return h->impl->sample_scenario_report(*d);
 }
+int ilqr_set_param_spread(ilqr_handle h, const double* std, int32_t relative, double clip) {
+    if (!h || !h->impl) return ILQR_ERR_INVALID_ARG;
+    const ilqr_config& c = h->impl->cfg;
+    // (clearing with NULL: valid on every handle; a plugin with the policy kernels included: its constants are part of
+    // the generated code)
+    if (std && (c.system == ILQR_SYS_LINEAR || c.system == ILQR_SYS_CUSTOM)) {
+        h->impl->err = "set_param_spread: supported for the pendulum, UA double pendulum and double pendulum only";
+        return ILQR_ERR_UNSUPPORTED;
+    }
+    return h->impl->set_param_spread(std, relative, clip);
+}
+int ilqr_param_spread_draw(ilqr_handle h, const ilqr_param_spread_draw_desc* d) {
+    if (!h || !h->impl) return ILQR_ERR_INVALID_ARG;
+    if (!d || d->struct_size != sizeof(ilqr_param_spread_draw_desc)) {
+        h->impl->err = "param_spread_draw: desc is NULL or struct_size does not match this library's "
+                       "ilqr_param_spread_draw_desc";
+        return ILQR_ERR_INVALID_ARG;
+    }
+    return h->impl->param_spread_draw(*d);
+}
 int ilqr_timing_enable(ilqr_handle h, int on) { ILQR_FWD(h, timing_enable(on)); }
 int ilqr_timing_reset(ilqr_handle h) { ILQR_FWD(h, timing_reset()); }
 int ilqr_timing_get(ilqr_handle h, double ms[ILQR_N_PHASES], int64_t launches[ILQR_N_PHASES]) {

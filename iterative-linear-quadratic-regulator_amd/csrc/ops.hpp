@@ -101,6 +101,12 @@ template <typename T> struct SamplingOps {
     // of Sd; null where the system is none of the built-in three
     void (*std_fill)(const SampleArgs<T>&, hipStream_t) = nullptr;
     void (*update_elite)(const SampleArgs<T>&, hipStream_t) = nullptr;
+    // a parameter spread (ilqr_set_param_spread): the Monte Carlo rollout and the scenario rollouts [STEPSTD][PEN] whose
+    // lanes draw their own plant constants, and the drawn parameters themselves [B][S][n_sys] (ilqr_param_spread_draw);
+    // null where the system is none of the built-in three
+    void (*policy_spread)(const PolicySpreadArgs<T>&, const NoiseArgs<T>&, hipStream_t) = nullptr;
+    void (*rollout_spread[2][2])(const ScenarioSpreadArgs<T>&, const NoiseArgs<T>&, hipStream_t) = {};
+    void (*spread_draw)(const SpreadArgs&, int B, int S, double* out, hipStream_t) = nullptr;
     explicit operator bool() const { return rollout[0][0] != nullptr; }
 };
 
@@ -324,6 +330,18 @@ void launch_sample_rollout_scn(const ScenarioArgs<T>& a, const NoiseArgs<T>& nz,
     const unsigned lanes = (unsigned)a.S << a.log2m;
     ILQR_LAUNCH((sample_rollout_kernel<T, Dyn, PEN, STEPSTD, true>), dim3((lanes + 63u) / 64u, a.B), dim3(64), 0, s, a, nz);
 }
+// a parameter spread: the same grids; the lanes draw their plant constants (policy_rollout.hpp, sample_controls.hpp)
+template <typename T, typename Dyn> void launch_policy_spread(const PolicySpreadArgs<T>& a, const NoiseArgs<T>& nz, hipStream_t s) {
+    ILQR_LAUNCH((policy_spread_kernel<T, Dyn>), dim3((a.S + 63) / 64, a.B), dim3(64), 0, s, a, nz);
+}
+template <typename T, typename Dyn, bool PEN, bool STEPSTD>
+void launch_sample_rollout_spread(const ScenarioSpreadArgs<T>& a, const NoiseArgs<T>& nz, hipStream_t s) {
+    const unsigned lanes = (unsigned)a.S << a.log2m;
+    ILQR_LAUNCH((sample_rollout_spread_kernel<T, Dyn, PEN, STEPSTD>), dim3((lanes + 63u) / 64u, a.B), dim3(64), 0, s, a, nz);
+}
+template <typename T, typename Dyn> void launch_spread_draw(const SpreadArgs& sp, int B, int S, double* out, hipStream_t s) {
+    ILQR_LAUNCH((param_spread_draw_kernel<T, sys_params_abi(Dyn::ID)>), dim3((S + 63) / 64, B), dim3(64), 0, s, sp, S, out);
+}
 template <typename T> void launch_sample_penalty_stats(const SampleArgs<T>& a, hipStream_t s) {
     ILQR_LAUNCH((sample_penalty_stats_kernel<T>), dim3(a.B), dim3(64), 0, s, a);
 }
@@ -498,6 +516,12 @@ template <typename T, typename Dyn> Ops<T> make_ops() {
             o.sampling.rollout_scn[0][1] = launch_sample_rollout_scn<T, Dyn, true, false>;
             o.sampling.rollout_scn[1][0] = launch_sample_rollout_scn<T, Dyn, false, true>;
             o.sampling.rollout_scn[1][1] = launch_sample_rollout_scn<T, Dyn, true, true>;
+            o.sampling.policy_spread = launch_policy_spread<T, Dyn>;
+            o.sampling.rollout_spread[0][0] = launch_sample_rollout_spread<T, Dyn, false, false>;
+            o.sampling.rollout_spread[0][1] = launch_sample_rollout_spread<T, Dyn, true, false>;
+            o.sampling.rollout_spread[1][0] = launch_sample_rollout_spread<T, Dyn, false, true>;
+            o.sampling.rollout_spread[1][1] = launch_sample_rollout_spread<T, Dyn, true, true>;
+            o.sampling.spread_draw = launch_spread_draw<T, Dyn>;
         }
     }
     o.eval = [](const EvalArgs<T>& a, hipStream_t s) {

@@ -174,6 +174,69 @@ ILQR_DEV void noise_draw(const NoiseArgs<T>& nz, unsigned s, unsigned b, unsigne
     }
 }
 
+// ---- device-drawn system parameters (include/ilqr_hip.h, ilqr_set_param_spread) ------------------------------------
+// Sample s of trajectory b rolls out through a plant whose ABI parameters p_j = base_j[b] + sd_j[b] * clamp(z_j, -c, c)
+// are drawn here: z_j is component j mod 4 of ONE Philox call per group g = j / 4 at counter (s, first + b, 1 + g, 1), the
+// x_0 stream, which is otherwise read at the third words 0 and 2^31 only (noise_draw above: step 0, groups 0 and 1), under
+// the key and the distribution of the call that draws.  The product is a double product of its own (noise_mul), the add
+// is never fused with it, and the sample's derived constants are derive_sys_constants(p) rounded once to T -- what the
+// host does with a row of plant_rows, so the explicit route fed with the drawn p gives the same bits.  base, sd ([B][NA]
+// doubles) and c are wave-uniform and come through the scalar unit; nothing per sample is read from memory.
+struct SpreadArgs {
+    const double* __restrict__ base;    // [B][NA] the ABI parameters the draw is centred on, resolved by the host per call
+    const double* __restrict__ sd;      // [B][NA] their standard deviations (relative ones already scaled by |base|)
+    float clip;                         // c: z is clamped to [-c, c]
+    int dist;                           // ILQR_NOISE_GAUSSIAN / ILQR_NOISE_UNIFORM
+    unsigned k0, k1, first;             // the key and the global index of trajectory 0, as NoiseArgs
+};
+
+// p[0..NA) of sample s of trajectory b, in double
+template <int NA> ILQR_DEV void param_spread_values(const SpreadArgs& sp, unsigned s, unsigned b, double (&p)[NA]) {
+#pragma clang fp contract(off)
+    const uniform_ptr<double> base = as_uniform(sp.base) + (size_t)b * NA, sd = as_uniform(sp.sd) + (size_t)b * NA;
+    const float c = sp.clip;
+#pragma unroll
+    for (int g = 0; g < (NA + 3) / 4; ++g) {
+        unsigned r[4];
+        philox4x32_10(s, sp.first + b, 1u + (unsigned)g, 1u, sp.k0, sp.k1, r);
+        float z[4];
+        noise_z<4>(sp.dist, r, z);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int j = 4 * g + i;
+            if (j < NA) {
+                const float zc = z[i] < -c ? -c : z[i] > c ? c : z[i];
+                const double e = noise_mul(sd[j < NA ? j : 0], (double)zc);
+                p[j < NA ? j : 0] = base[j < NA ? j : 0] + e;
+            }
+        }
+    }
+}
+
+// the derived constants of the sample, each rounded once to T
+template <typename T, typename Dyn>
+ILQR_DEV void param_spread_draw(const SpreadArgs& sp, unsigned s, unsigned b, T (&pp)[Dyn::NSYS]) {
+    constexpr int NA = sys_params_abi(Dyn::ID);
+    static_assert(NA > 0 && NA <= 12, "a built-in pendulum: at most three generator calls (third counter words 1..3)");
+    double p[NA], d[Dyn::NSYS];
+    param_spread_values<NA>(sp, s, b, p);
+    derive_sys_constants(Dyn::ID, p, d);
+#pragma unroll
+    for (int q = 0; q < Dyn::NSYS; ++q) pp[q] = (T)d[q];
+}
+
+// p of every sample of a call, [B][S][NA] doubles (ilqr_param_spread_draw): the function the rollouts call, stored
+// (T only names the library's translation unit of that dtype: each carries its own copy)
+template <typename T, int NA>
+__global__ void __launch_bounds__(64) param_spread_draw_kernel(SpreadArgs sp, int S, double* __restrict__ out) {
+    const int b = blockIdx.y, s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= S) return;
+    double p[NA];
+    param_spread_values<NA>(sp, (unsigned)s, (unsigned)b, p);
+#pragma unroll
+    for (int j = 0; j < NA; ++j) out[((size_t)b * S + s) * NA + j] = p[j];
+}
+
 // Does the system take control and state limits (ilqr_set_control_limits, ilqr_set_state_limits)?  A user-defined system
 // does not: its handle can hold none, Limits' arrays are sized for the built-in systems (kBoxMaxU, kALMaxX), and the
 // sampling kernels of such a Dyn neither read a bound nor clamp -- the violation is 0.
@@ -425,6 +488,28 @@ __global__ void __launch_bounds__(64) policy_rollout_kernel(PolicyArgs<T> a) {
 template <typename T, typename Dyn, bool SROWS>
 __global__ void __launch_bounds__(64) policy_noise_kernel(PolicyArgs<T> a, NoiseArgs<T> nz) {
     sampled_rollout<T, Dyn, FeedbackLaw<T, Dyn, SROWS, true>>(a, nz);
+}
+
+// The Monte Carlo rollout under a parameter spread (ilqr_set_param_spread): the NOISE law with a third source of the
+// plant's constants beside the per-sample rows (SROWS) and the trajectory's row -- every lane draws its own.  It is a law
+// of its own around FeedbackLaw with an argument record of its own behind PolicyArgs (as ScenarioLaw and ScenarioArgs
+// are for the search), not a parameter of it: the kernels above keep their symbols, their argument layout and their code.
+// pp per lane turns the step's scalar operands into VGPRs, as SROWS does; the draw is a few dozen fp64 instructions
+// once per lane, in front of the step loop.
+template <typename T> struct PolicySpreadArgs : PolicyArgs<T> {
+    SpreadArgs sp;
+};
+template <typename T, typename Dyn> struct SpreadFeedbackLaw : FeedbackLaw<T, Dyn, false, true> {
+    using Base = FeedbackLaw<T, Dyn, false, true>;
+    static constexpr int NX = Dyn::NX;
+    ILQR_DEV SpreadFeedbackLaw(const PolicySpreadArgs<T>& a_, const NoiseArgs<T>& nz_, const SampleAt& k_, T* mr, T (&x)[NX])
+        : Base(a_, nz_, k_, mr, x) {
+        param_spread_draw<T, Dyn>(a_.sp, (unsigned)k_.s, (unsigned)k_.b, this->pp);
+    }
+};
+template <typename T, typename Dyn>
+__global__ void __launch_bounds__(64) policy_spread_kernel(PolicySpreadArgs<T> a, NoiseArgs<T> nz) {
+    sampled_rollout<T, Dyn, SpreadFeedbackLaw<T, Dyn>>(a, nz);
 }
 
 // dense[l][c][t] <- dev[t][c][l]: the sample trajectories in the ABI's (dim, time) layout behind the batch axes

@@ -275,6 +275,28 @@ template <typename T, typename Dyn, bool PEN, bool STEPSTD> struct LawScenarios<
     static constexpr bool value = true;
 };
 
+// The scenario law under a parameter spread (ilqr_set_param_spread while scenarios are set): scenario m of trajectory b
+// rolls out through the model at the parameters of Monte Carlo sample m, drawn in the constructor under the scenarios' key
+// (param_spread_draw, policy_rollout.hpp) around the trajectory's MODEL parameters.  The M parameter sets are the same for
+// every sample, round and MPC step, as the scenarios' noise is.  Where PerturbLaw::pp points at the wave-uniform model row,
+// this law holds its own pp[NSYS] per lane, which hides the pointer: the rollout reads law.pp.  A law and an argument
+// record of their own around ScenarioLaw and ScenarioArgs, so the kernels that exist keep their symbols and their code.
+template <typename T> struct ScenarioSpreadArgs : ScenarioArgs<T> {
+    SpreadArgs sp;
+};
+template <typename T, typename Dyn, bool PEN, bool STEPSTD> struct ScenarioSpreadLaw : ScenarioLaw<T, Dyn, PEN, STEPSTD> {
+    using Base = ScenarioLaw<T, Dyn, PEN, STEPSTD>;
+    static constexpr int NX = Dyn::NX;
+    T pp[Dyn::NSYS];
+    ILQR_DEV ScenarioSpreadLaw(const ScenarioSpreadArgs<T>& a_, const NoiseArgs<T>& nz_, const SampleAt& k_, T* mr, T (&x)[NX])
+        : Base(a_, nz_, k_, mr, x) {
+        param_spread_draw<T, Dyn>(a_.sp, (unsigned)this->m, (unsigned)k_.b, pp);
+    }
+};
+template <typename T, typename Dyn, bool PEN, bool STEPSTD> struct LawScenarios<ScenarioSpreadLaw<T, Dyn, PEN, STEPSTD>> {
+    static constexpr bool value = true;
+};
+
 // The rollout of a round's samples.  Launched with S = 1 it is the rollout of the nominal alone (cost_new / X_new): the
 // same code on the same controls, so the cost of a BEST call's result is the winning sample's cost bit for bit.
 // PEN (ilqr_set_sample_penalty): cost[l] = J + P, and pen[l] = P, viol[l] = v beside it.
@@ -291,6 +313,11 @@ template <typename T, typename Dyn, bool PEN, bool STEPSTD, bool SCN>
 __global__ void __launch_bounds__(64) sample_rollout_kernel(ScenarioArgs<T> a, NoiseArgs<T> nz) {
     static_assert(SCN, "without scenarios the rollout is the template above");
     sampled_rollout<T, Dyn, ScenarioLaw<T, Dyn, PEN, STEPSTD>>(a, nz);
+}
+// the scenario rollout under a parameter spread: a kernel of its own name, so no symbol above changes
+template <typename T, typename Dyn, bool PEN, bool STEPSTD>
+__global__ void __launch_bounds__(64) sample_rollout_spread_kernel(ScenarioSpreadArgs<T> a, NoiseArgs<T> nz) {
+    sampled_rollout<T, Dyn, ScenarioSpreadLaw<T, Dyn, PEN, STEPSTD>>(a, nz);
 }
 
 // The weights of a round: one wave per trajectory over its contiguous [S] costs, each lane over its stride of the row and

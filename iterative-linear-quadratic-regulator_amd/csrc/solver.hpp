@@ -75,6 +75,8 @@ struct SolverBase {
     virtual int set_sample_scenarios(int n_scenarios, int aggregate, double level, unsigned long long seed, int distribution,
                                      const double* x0_std, const double* w_std) = 0;
     virtual int sample_scenario_report(const ilqr_sample_scenario_report_desc& d) = 0;
+    virtual int set_param_spread(const double* std, int relative, double clip) = 0;
+    virtual int param_spread_draw(const ilqr_param_spread_draw_desc& d) = 0;
 };
 
 int system_dims(int system, int n_x, int n_u);  // 1 if (system, n_x, n_u) is a known combination
@@ -106,21 +108,12 @@ inline int persist_small_max() {
 inline std::vector<double> build_device_params(int system, int nx, int nu, const double* p) {
     std::vector<double> d;
     const double* q = p;
-    if (system == ILQR_SYS_PENDULUM) {
-        const double g = p[0], l = p[1], dd = p[2];
-        d = {g / l, dd};
-        q = p + 3;
-    } else if (system == ILQR_SYS_UA_DOUBLE_PENDULUM || system == ILQR_SYS_DOUBLE_PENDULUM) {
-        const double g = p[0], m1 = p[1], m2 = p[2], l1 = p[3], l2 = p[4], d1 = p[5], d2 = p[6], th1 = p[7],
-                     th2 = p[8];
-        d = {m2 * l1 * l2,
-             (m1 * l1 * l1) / 4 + m2 * l1 * l1 + (m2 * l2 * l2) / 4 + th1 + th2,
-             (m2 * l2 * l2) / 4 + th2,
-             m2 * g * l2 / 2,
-             (m2 + m1 / 2) * g * l1,
-             d1,
-             d2};
-        q = p + 9;
+    if (sys_params_abi(system) > 0) {
+        // the pendulums: the formulas the kernels of a parameter spread evaluate too (derive_sys_constants, dynamics.hpp)
+        double c[7];
+        const int nc = derive_sys_constants(system, p, c);
+        d.assign(c, c + nc);
+        q = p + sys_params_abi(system);
     } else if (system == ILQR_SYS_CUSTOM) {
         q = p;  // user-defined dynamics carry their constants in the generated code
     } else {  // linear: A, B verbatim
@@ -314,10 +307,25 @@ template <typename T> struct ScenarioState {
     size_t M() const { return (size_t)1 << log2m; }
 };
 
+// The parameter spread (ilqr_set_param_spread): what the setter gave, and the device rows a call resolves from it and the
+// bases of that moment -- base and sd, [2][B][n_sys] doubles, one upload per call.
+struct ParamSpread {
+    bool on = false;
+    std::vector<double> std;      // [B][n_sys] as given
+    int relative = 0;
+    double clip = 0;
+    std::vector<double> host;     // base, sd as uploaded (outlives the copy: every call that resolves ends synchronised)
+    DevBuf<double> dev;
+    DevBuf<double> drawn;         // ilqr_param_spread_draw: p [B][S][n_sys] on its way back
+    SpreadArgs args{};            // what the rollouts of the current call read: set by SolverT::spread_resolve
+};
+
 // per-trajectory parameters (ilqr_set_batch_params): rows [n_sys + n_x][B] of the model (derived constants, x_target),
 // plant_rows [n_sys][B] of the MPC plant; device tensors of the handle's dtype
 template <typename T> struct BatchParams {
     std::vector<double> abi_params;   // the parameter block as given at ilqr_create
+    // the ABI rows as given, [B][row_len] while that kind is set: what a parameter spread is centred on (ParamSpread)
+    std::vector<double> abi_rows[2];  // [ILQR_BATCH_MODEL], [ILQR_BATCH_PLANT]
     DevBuf<T> rows, plant_rows;
     bool model_set = false, plant_set = false;
     bool on() const { return model_set || plant_set; }
@@ -398,6 +406,7 @@ template <typename T> class SolverT : public SolverBase {
     PenaltyState<T> pen;
     EliteState<T> el;
     ScenarioState<T> scn;
+    ParamSpread spread;
 
     // (the device buffers free themselves after this body: DevBuf)
     ~SolverT() override {
@@ -1264,6 +1273,8 @@ template <typename T> class SolverT : public SolverBase {
         if (int rf = flush_select()) return rf;
         lin_stale = true;   // an expansion in HBM was taken at the old parameters
         ILQR_HIPCHK(het.alloc(which == ILQR_BATCH_PLANT && host_rows, nh, ops.n_sys_dev, B));
+        if (host_rows) het.abi_rows[which].assign(host_rows, host_rows + (size_t)B * row_len);
+        else het.abi_rows[which].clear();
         // one derived row per trajectory: [nh][B] (model) or [n_sys][B] (plant)
         if (which == ILQR_BATCH_MODEL) {
             het.model_set = host_rows != nullptr;
@@ -1464,6 +1475,10 @@ template <typename T> class SolverT : public SolverBase {
         const int ns = n_sys_abi();
         for (size_t i = 0; d.plant_rows && i < L * ns; ++i)
             if (!std::isfinite(d.plant_rows[i])) return fail(ILQR_ERR_INVALID_ARG, who + ": every plant_rows value must be finite");
+        // a parameter spread: every sample of a Monte Carlo call draws its plant parameters around the trajectory's
+        const bool spr = mc && spread.on;
+        if (spr && d.plant_rows) return fail(ILQR_ERR_INVALID_ARG, who + ": plant_rows and a parameter spread");
+        if (spr && (rc = spread_resolve(who, ILQR_BATCH_PLANT, mc->seed, mc->first_trajectory, mc->distribution))) return rc;
         if ((rc = sampling_settle())) return rc;
         reports_off();
         const size_t nX = L * NX * (size_t)(N + 1), nU = L * NU * (size_t)N, nW = L * NX * (size_t)N;
@@ -1508,7 +1523,14 @@ template <typename T> class SolverT : public SolverBase {
             nz.x0_out = mc->x0_out ? smp.x0.p : nullptr;
             nz.w_out = w_back ? smp.w.p : nullptr;
         }
-        if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.policy[mc != nullptr](a, nz, stream); }))) return rc;
+        if (spr) {
+            PolicySpreadArgs<T> pa{};
+            static_cast<PolicyArgs<T>&>(pa) = a;
+            pa.sp = spread.args;
+            if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.policy_spread(pa, nz, stream); }))) return rc;
+        } else if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.policy[mc != nullptr](a, nz, stream); }))) {
+            return rc;
+        }
         if (mc && (rc = mc_stats(a, *mc))) return rc;
         if (risk && (rc = mc_risk(a, L, *risk))) return rc;
         if (env && (rc = mc_envelope(a, L, mc->violation_tol, *env, eg))) return rc;
@@ -1691,6 +1713,13 @@ template <typename T> class SolverT : public SolverBase {
             sa.sn.x0_std = scn.has_x0 ? scn.std.p : nullptr;
             sa.sn.w_std = scn.has_w ? scn.std.p + (size_t)B * NX : nullptr;
             sa.scn_cost = scn.cost.p + (nominal ? scn.L * scn.M() : (size_t)0);
+            if (spread.on) {
+                // every scenario at its own drawn model parameters (resolved once per call: search_spread)
+                ScenarioSpreadArgs<T> ss{};
+                static_cast<ScenarioArgs<T>&>(ss) = sa;
+                ss.sp = spread.args;
+                return timed(ILQR_PHASE_OTHER, [&] { ops.sampling.rollout_spread[a.Sd != nullptr][a.pen != nullptr](ss, nz, stream); });
+            }
             return timed(ILQR_PHASE_OTHER, [&] { ops.sampling.rollout_scn[a.Sd != nullptr][a.pen != nullptr](sa, nz, stream); });
         }
         return timed(ILQR_PHASE_OTHER, [&] { ops.sampling.rollout[a.Sd != nullptr][a.pen != nullptr](a, nz, stream); });
@@ -1715,7 +1744,7 @@ template <typename T> class SolverT : public SolverBase {
         if ((rc = search_desc_check(who, d, (unsigned long long)d.n_rounds, "n_rounds"))) return rc;
         if (!d.U_new && !d.cost_new && !d.X_new && !d.round_stats && !d.round_counts && !d.cost_samples && !d.U_samples)
             return bad("every output is NULL");
-        if ((rc = sample_total(who, d.n_samples, &L)) || (rc = scenario_total(who, L)) || (rc = sampling_supported(who, (bool)ops.sampling)) ||
+        if ((rc = sample_total(who, d.n_samples, &L)) || (rc = scenario_total(who, L)) || (rc = search_spread(who, d.first_trajectory)) || (rc = sampling_supported(who, (bool)ops.sampling)) ||
             (rc = sampling_problem(who)) || (rc = sampling_settle()))
             return rc;
         const size_t Rn = (size_t)d.n_rounds;
@@ -1784,7 +1813,7 @@ template <typename T> class SolverT : public SolverBase {
         for (size_t i = 0; w_host && i < K * B * NX; ++i)
             if (!std::isfinite(w_host[i])) return bad("every w value must be finite");
         if (!d.u_out && !d.x_out && !d.cost_out && !d.U_plan && !d.round_stats && !d.round_counts) return bad("every output is NULL");
-        if ((rc = sample_total(who, d.n_samples, &L)) || (rc = scenario_total(who, L)) || (rc = sampling_supported(who, (bool)ops.sampling)) ||
+        if ((rc = sample_total(who, d.n_samples, &L)) || (rc = scenario_total(who, L)) || (rc = search_spread(who, d.first_trajectory)) || (rc = sampling_supported(who, (bool)ops.sampling)) ||
             (rc = sampling_problem(who)))
             return rc;
         if (!mpc_ready) return fail(ILQR_ERR_STATE, who + " before mpc_reset / mpc_rearm");
@@ -2003,6 +2032,100 @@ template <typename T> class SolverT : public SolverBase {
         if (d.scenario_cost_samples)
             ILQR_HIPCHK(hipMemcpyAsync(d.scenario_cost_samples, scn.cost.p, scn.L * M * sizeof(T), hipMemcpyDeviceToHost, stream));
         if (d.scenario_X && ((rc = grow(staging, nB * NX * (size_t)(N + 1))) || (rc = down_traj(d.scenario_X, scn.X, nB, NX, N + 1)))) return rc;
+        ILQR_HIPCHK(hipStreamSynchronize(stream));
+        return check_launch();
+    }
+
+    // ---- parameter spread (include/ilqr_hip.h, ilqr_set_param_spread) ---------------------------------------------------
+    // base [B][n_sys] in the resolution order `order`: ILQR_BATCH_PLANT: the plant row, the model row, the block;
+    // ILQR_BATCH_MODEL: the model row, the block
+    void spread_bases(int order, double* base) const {
+        const size_t ns = (size_t)n_sys_abi();
+        for (size_t b = 0; b < (size_t)B; ++b) {
+            const double* src = (order == ILQR_BATCH_PLANT && het.plant_set) ? het.abi_rows[ILQR_BATCH_PLANT].data() + b * ns
+                                : het.model_set                               ? het.abi_rows[ILQR_BATCH_MODEL].data() + b * (ns + NX)
+                                                                              : het.abi_params.data();
+            std::copy(src, src + ns, base + b * ns);
+        }
+    }
+    // base and sd [B][n_sys] of `std_` at the bases of this moment, and the sign rule: no parameter with a spread may
+    // reach zero or change sign inside the clamp
+    int spread_rows(const std::string& who, const std::vector<double>& std_, int relative, double clip, int order, double* base, double* sd) {
+        const size_t ns = (size_t)n_sys_abi();
+        const double c = (double)(float)clip;
+        spread_bases(order, base);
+        for (size_t i = 0; i < (size_t)B * ns; ++i) {
+            sd[i] = relative ? std::fabs(base[i]) * std_[i] : std_[i];
+            if (sd[i] > 0.0 && sd[i] * c >= std::fabs(base[i]))
+                return fail(ILQR_ERR_INVALID_ARG, who + ": the spread of parameter " + std::to_string(i % ns) + " of trajectory " + std::to_string(i / ns) +
+                                                      " reaches zero or changes its sign (sd * clip >= |base|)");
+        }
+        return ILQR_OK;
+    }
+    // Everything is checked before the handle is touched; nothing crosses to the device here (the bases are resolved, and
+    // base and sd uploaded, by every call that reads the spread).
+    int set_param_spread(const double* std_, int relative, double clip) override {
+        const std::string who = "set_param_spread";
+        auto bad = [&](const char* what) { return fail(ILQR_ERR_INVALID_ARG, who + ": " + what); };
+        if (!std_) {
+            spread.on = false;
+            reports_off();
+            return ILQR_OK;
+        }
+        int rc;
+        if ((rc = sampling_supported(who, ops.sampling.policy_spread != nullptr))) return rc;
+        const size_t n = (size_t)B * n_sys_abi();
+        for (size_t i = 0; i < n; ++i)
+            if (!std::isfinite(std_[i]) || std_[i] < 0.0) return bad("every standard deviation must be finite and >= 0");
+        const float c = (float)clip;
+        if (!std::isfinite(clip) || !std::isfinite(c) || !(c > 0.0f)) return bad("clip must be finite and > 0 (as a float too)");
+        const std::vector<double> given(std_, std_ + n);
+        std::vector<double> rows(2 * n);
+        for (int order : {ILQR_BATCH_PLANT, ILQR_BATCH_MODEL})
+            if ((rc = spread_rows(who, given, relative, clip, order, rows.data(), rows.data() + n))) return rc;
+        spread.on = true;
+        spread.std = given;
+        spread.relative = relative ? 1 : 0;
+        spread.clip = clip;
+        reports_off();
+        return ILQR_OK;
+    }
+    // base and sd of this call, one upload of 2 * B * n_sys doubles, and the record its rollouts read (spread.args)
+    int spread_resolve(const std::string& who, int order, unsigned long long seed, int first_trajectory, int distribution) {
+        const size_t n = (size_t)B * n_sys_abi();
+        std::vector<double> rows(2 * n);
+        int rc;
+        if ((rc = spread_rows(who, spread.std, spread.relative, spread.clip, order, rows.data(), rows.data() + n)) || (rc = grow(spread.dev, 2 * n)))
+            return rc;
+        spread.host.swap(rows);     // (nothing queued reads the old one: every call that resolves ends synchronised)
+        ILQR_HIPCHK(hipMemcpyAsync(spread.dev.p, spread.host.data(), 2 * n * sizeof(double), hipMemcpyHostToDevice, stream));
+        SpreadArgs& sp = spread.args;
+        sp.base = spread.dev.p; sp.sd = spread.dev.p + n;
+        sp.clip = (float)spread.clip; sp.dist = distribution;
+        sp.k0 = (unsigned)(seed & 0xffffffffull); sp.k1 = (unsigned)(seed >> 32); sp.first = (unsigned)first_trajectory;
+        return ILQR_OK;
+    }
+    // the search reads the spread while scenarios are set: the scenarios' key, the model's parameters
+    int search_spread(const std::string& who, int first_trajectory) {
+        return scn.on && spread.on ? spread_resolve(who, ILQR_BATCH_MODEL, scn.seed, first_trajectory, scn.dist) : ILQR_OK;
+    }
+    // p of S samples per trajectory as the rollouts of such a call draw them; reads the spread and the bases, writes its
+    // own buffers only
+    int param_spread_draw(const ilqr_param_spread_draw_desc& d) override {
+        const std::string who = "param_spread_draw";
+        auto bad = [&](const char* what) { return fail(ILQR_ERR_INVALID_ARG, who + ": " + what); };
+        int rc;
+        size_t L;
+        if ((rc = sample_count(who, d.n_samples)) || (rc = sample_total(who, d.n_samples, &L))) return rc;
+        if (d.distribution != ILQR_NOISE_GAUSSIAN && d.distribution != ILQR_NOISE_UNIFORM) return bad("unknown distribution");
+        if (d.first_trajectory < 0) return bad("first_trajectory must be >= 0");
+        if (d.base != ILQR_BATCH_PLANT && d.base != ILQR_BATCH_MODEL) return bad("base must be ILQR_BATCH_PLANT or ILQR_BATCH_MODEL");
+        if (!d.params) return bad("params is NULL");
+        if (!spread.on) return fail(ILQR_ERR_STATE, who + " without a parameter spread set (ilqr_set_param_spread)");
+        const size_t n = L * (size_t)n_sys_abi();
+        if ((rc = spread_resolve(who, d.base, d.seed, d.first_trajectory, d.distribution)) || (rc = grow(spread.drawn, n))) return rc;
+        if ((rc = timed(ILQR_PHASE_OTHER, [&] { ops.sampling.spread_draw(spread.args, B, d.n_samples, spread.drawn.p, stream); }))) return rc;
+        ILQR_HIPCHK(hipMemcpyAsync(d.params, spread.drawn.p, n * sizeof(double), hipMemcpyDeviceToHost, stream));
         ILQR_HIPCHK(hipStreamSynchronize(stream));
         return check_launch();
     }

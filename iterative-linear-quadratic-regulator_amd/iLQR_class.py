@@ -23,7 +23,7 @@ from . import _lib
 from .setter_args import _bounds, batch_param_rows, control_limits, mpc_multiplier_mode, state_limits  # noqa: F401
 from .sampling import (ELITE_FIELDS, PENALTY_FIELDS, SCENARIO_FIELDS, PolicyMonteCarlo, PolicyRollout, SampledControls, SampledMPC,  # noqa: F401
                        _with_penalty_fields, has_policy_kernels, policy_envelope_args, policy_envelope_record, policy_monte_carlo_args, policy_risk_args,
-                       policy_risk_record, policy_rollout_args, sample_controls_args, sample_elites_args, sample_penalty_args, sample_scenarios_args, sampled_mpc_args, table_columns,
+                       policy_risk_record, policy_rollout_args, sample_controls_args, sample_elites_args, sample_penalty_args, sample_scenarios_args, sampled_mpc_args, param_spread_args, param_spread_draw_args, table_columns,
                        unbatch)
 from .systems.system_base import System, ready
 
@@ -116,6 +116,7 @@ class iLQR:
         self.sample_penalty = None
         self.sample_elites = None
         self.sample_scenarios = None
+        self.param_spread = None
         self.status = None
         self.iterations = None
 
@@ -362,9 +363,12 @@ class iLQR:
         max of every state and applied control over the finite samples (x_mean .. u_max), step_violating, the number of
         them outside the state limits at that step by more than violation_tol, and per level the band (x_quantiles,
         u_quantiles: the same order statistic as quantiles=) -- without the sample trajectories leaving the device.
+        After set_param_spread every sample also draws its own plant parameters (plant_params is then refused).
         Nothing in the solver changes."""
         a = policy_monte_carlo_args(self.system, self.N, self.B, self.batched, n_samples, seed, x_0_std, disturbance_std,
                                     distribution, plant_params, integrator, violation_tol, first_trajectory)
+        if plant_params is not None and self.param_spread is not None:
+            raise ValueError("plant_params and a parameter spread (set_param_spread): give one source of the samples' parameters")
         risk = policy_risk_args(self.B, self.batched, quantiles, thresholds)
         env = policy_envelope_args(envelope)
         out = self._h.policy_monte_carlo(**a._asdict(), feedback=feedback, samples=samples, trajectories=trajectories,
@@ -454,6 +458,34 @@ class iLQR:
         return {k: self._out(v) for k, v in rep.items()}
 
     # ---- sampled control search ---------------------------------------------------------------------
+    # ---- parameter spread: plant parameters drawn on the device ---------------------------------------
+    def set_param_spread(self, std, relative=True, clip=3.0):
+        """What if the arm is not the arm I modelled?  Draw the system parameters of every policy_monte_carlo sample, and
+        of every noise scenario of sample_controls / sampled_mpc, on the device (include/ilqr_hip.h,
+        ilqr_set_param_spread): p = base + sd * clamp(z, -clip, clip), z of unit variance from the call's own generator
+        (counter (s, first_trajectory + b, 1 + j // 4, 1): the streams depend neither on the batch nor on n_samples).
+        std is {name: scalar or (B,)} over system.param_names(); names left out get 0; sd = |base| * std with
+        relative=True, else std.  base is resolved at every call: for policy_monte_carlo the trajectory's plant parameters
+        (set_plant_params, else set_batch_params, else the system's own), for the scenarios its model parameters.  A
+        parameter that could reach zero or change its sign inside the clamp is refused.  policy_rollout with
+        plant_params=param_spread_draw(...) is the explicit route and gives the same bits.  None or {} clears the spread.
+        policy_rollout, the solves and mpc_run ignore it, and so does the search without scenarios."""
+        a = param_spread_args(self.system, self.B, std, relative, clip, self.batch_params, self.plant_params)
+        self._h.set_param_spread(**a._asdict())
+        self.param_spread = None if a.std is None else a
+
+    def param_spread_draw(self, n_samples, seed=0, distribution="gaussian", first_trajectory=0, of="plant"):
+        """The parameters the samples of a policy_monte_carlo call with these arguments draw (of="plant"), or the scenarios
+        of a search with this scenario seed and distribution (of="model"): {name: ([B,] S)} float64 for every parameter
+        name (include/ilqr_hip.h, ilqr_param_spread_draw), ready to be policy_rollout's plant_params.  A function of the
+        spread, the parameters as set now and the arguments; nothing in the solver changes."""
+        a = param_spread_draw_args(self.system, n_samples, seed, distribution, first_trajectory, of)
+        if self.param_spread is None:
+            raise ValueError("param_spread_draw needs a parameter spread (set_param_spread)")
+        names = self.system.param_names()
+        p = self._h.param_spread_draw(n_sys=len(names), **a._asdict())
+        return {name: self._out(np.ascontiguousarray(p[:, :, j])) for j, name in enumerate(names)}
+
     def sample_controls(self, n_samples, rounds=1, seed=0, u_std=None, mode="best", temperature=None, smoothing=0.0,
                         distribution="gaussian", first_trajectory=0, first_round=0, samples=False, trajectories=False,
                         apply=False):

@@ -532,6 +532,77 @@ def sample_scenarios_args(system, B, n_scenarios, aggregate="mean", level=None, 
 
 
 # ---- results: the library's arrays and tables, as the records hold them ------------------------------------------------
+# ---- parameter spread ------------------------------------------------------------------------------------------------
+ParamSpreadArgs = NamedTuple("ParamSpreadArgs", [("std", ROWS), ("relative", bool), ("clip", float)])
+ParamSpreadDrawArgs = NamedTuple("ParamSpreadDrawArgs", [("n_samples", int), ("seed", int), ("distribution", int),
+                                                         ("first_trajectory", int), ("base", int)])
+PARAM_SPREAD_BASES = {"plant": _lib.BATCH_PLANT, "model": _lib.BATCH_MODEL}
+
+
+def param_spread_bases(system, B, model_rows=None, plant_rows=None):
+    """The parameters a spread is centred on, {"plant": (B, n_sys), "model": (B, n_sys)} float64, from the rows the solver
+    was given (``batch_param_rows``; None: not set): the plant's are the first that is set of the plant rows, the model rows
+    and the system's own block; the model's are the model rows, else the block."""
+    n_sys = len(system.param_names())
+    block = np.broadcast_to(np.asarray(system.param_block(), dtype=np.float64)[:n_sys], (int(B), n_sys))
+    model = block if model_rows is None else np.asarray(model_rows, dtype=np.float64)[:, :n_sys]
+    plant = model if plant_rows is None else np.asarray(plant_rows, dtype=np.float64)[:, :n_sys]
+    return {"plant": plant, "model": model}
+
+
+def param_spread_args(system, B, std, relative=True, clip=3.0, model_rows=None, plant_rows=None):
+    """Validated arguments of ``ilqr_set_param_spread`` as (std, relative, clip): std (B, n_sys) float64 in parameter-block
+    order from {name: scalar or (B,)} over ``system.param_names()`` (names left out get 0), or None (from None or an empty
+    dict: clear).  Raises ValueError for a system without a parameter spread, an unknown name, a wrong shape, a negative or
+    non-finite value, a clip that is not finite and > 0 (as a float32 too), or a parameter that could reach zero or change
+    its sign inside the clamp -- sd * clip >= |base| with sd = |base| * std (relative) or std, against the plant's and the
+    model's parameters as ``model_rows`` / ``plant_rows`` give them (``param_spread_bases``).  Pure host code (no GPU)."""
+    if std is None or (isinstance(std, dict) and not std):
+        return ParamSpreadArgs(std=None, relative=bool(relative), clip=float(clip))
+    refuse_unsupported(system, "a parameter spread is", getattr(system, "SYSTEM_ID", None) in _lib.BOX_SYSTEMS
+                       and getattr(system, "PARAM_NAMES", None) is not None)
+    if not isinstance(std, dict):
+        raise ValueError(f"std must be a dict {{name: scalar or ({int(B)},)}} or None, got {type(std).__name__}")
+    B, names = int(B), system.param_names()
+    unknown = sorted(set(std) - set(names))
+    if unknown:
+        raise ValueError(f"unknown parameter name(s) {unknown}; expected some of {sorted(names)}")
+    rows = np.zeros((B, len(names)), dtype=np.float64)
+    for j, name in enumerate(names):
+        if name not in std:
+            continue
+        v = np.asarray(std[name], dtype=np.float64)
+        if v.ndim != 0 and v.shape != (B,):
+            raise ValueError(f"{name} must be a scalar or have shape ({B},), but got {v.shape}")
+        if not np.isfinite(v).all() or (v < 0).any():
+            raise ValueError(f"the spread of {name} must be finite and >= 0")
+        rows[:, j] = v
+    number = isinstance(clip, (int, float, np.integer, np.floating)) and not isinstance(clip, bool)
+    with np.errstate(over="ignore"):
+        c = float(np.float32(clip)) if number else float("nan")      # what the device clamps with
+    if not (np.isfinite(c) and c > 0.0):
+        raise ValueError(f"clip must be finite and > 0 (as a float32 too), got {clip!r}")
+    for of, base in param_spread_bases(system, B, model_rows, plant_rows).items():
+        sd = np.abs(base) * rows if relative else rows
+        bad = np.argwhere((sd > 0) & (sd * c >= np.abs(base)))
+        if len(bad):
+            b, j = (int(i) for i in bad[0])
+            raise ValueError(f"the spread of {names[j]} reaches zero or changes its sign (trajectory {b}, the {of}'s "
+                             f"parameters): sd * clip = {sd[b, j] * c!r} >= |base| = {abs(base[b, j])!r}")
+    return ParamSpreadArgs(std=rows, relative=bool(relative), clip=float(clip))
+
+
+def param_spread_draw_args(system, n_samples, seed=0, distribution="gaussian", first_trajectory=0, of="plant"):
+    """Validated arguments of ``ilqr_param_spread_draw`` as (S, seed, distribution code, first_trajectory, base code).
+    Raises ValueError for n_samples < 1, a seed outside [0, 2^64), an unknown distribution, a negative first_trajectory or
+    an ``of`` that is neither "plant" nor "model".  Pure host code (no GPU)."""
+    S = _count("n_samples", n_samples, 1, integer_type=False)
+    return ParamSpreadDrawArgs(n_samples=S, seed=_seed(seed),
+                               distribution=_choice("distribution", distribution, _lib.NOISE_DISTRIBUTIONS),
+                               first_trajectory=_count("first_trajectory", first_trajectory, 0, integer_type=False),
+                               base=_choice("base (of=)", of, PARAM_SPREAD_BASES))
+
+
 def unbatch(a, batched, axis=-1, wrap=False):
     """An array of the library, which always has a batch axis, as the solver's caller sees it: without that axis on an
     unbatched solver (B = 1); wrap: as a ``ready`` array."""

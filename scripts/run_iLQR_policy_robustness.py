@@ -11,10 +11,13 @@ median, the 95 % quantile, the mean of the worst 5 % and the share of samples ab
 (iLQR.policy_monte_carlo with quantiles= and thresholds=).  With --envelope both loops are run the same way and the fan
 chart of the samples is reduced on the device (iLQR.policy_monte_carlo with envelope=): the step and the state where
 the band between the 5 % and the 95 % quantile is widest, and the step at which most samples are outside the state
-limits (none are set by this script, so that count is 0 unless the solver is given some).
+limits (none are set by this script, so that count is 0 unless the solver is given some).  With --param-std REL the closed
+and the open loop are run once more as the same study on the device alone: every sample's m2 and l2 are drawn there with
+the relative standard deviation REL around the model's (iLQR.set_param_spread), the initial state as with --risk, and
+the per-trajectory statistics of the cost and the share of samples within tolerance are reported.
 
     python scripts/run_iLQR_policy_robustness.py [--batch 256] [--samples 1024] [--horizon 200] [--dtype f64] [--seed 0]
-                                                 [--process-noise SIGMA] [--risk] [--envelope]
+                                                 [--process-noise SIGMA] [--risk] [--envelope] [--param-std REL]
 """
 import argparse
 import os
@@ -49,6 +52,9 @@ def main(argv=None):
     ap.add_argument("--envelope", action="store_true",
                     help="also report, closed and open loop, where the samples' 5-95 %% band of the states is widest and the "
                          "step with the most samples outside the state limits, computed on the device (off by default)")
+    ap.add_argument("--param-std", type=float, default=None, metavar="REL",
+                    help="also run both loops with every sample's m2 and l2 drawn on the device, relative standard deviation "
+                         "REL (off by default)")
     a = ap.parse_args(argv)
     dtype = np.float64 if a.dtype == "f64" else np.float32
     B, S, N = a.batch, a.samples, a.horizon
@@ -119,6 +125,23 @@ def main(argv=None):
                   f"(trajectory {b}: {width[b, i, t]:.3f} wide, median over the batch there {np.median(width[:, i, t]):.3f}); "
                   f"most samples outside the state limits at step {int(np.argmax(per_step))}: {int(per_step.max())} of "
                   f"{int(mc.n_finite.sum())} finite samples")
+    if a.param_std is not None:
+        x0_std = np.array([ANGLE_OFF, ANGLE_OFF, RATE_OFF, RATE_OFF]) / np.sqrt(3.0)
+        w_std = None if a.process_noise is None else np.full(4, a.process_noise)
+        solver.set_param_spread({"m2": a.param_std, "l2": a.param_std})
+        for label, feedback in (("closed loop", True), ("open loop", False)):
+            t0 = time.time()
+            mc = solver.policy_monte_carlo(S, seed=a.seed, x_0_std=x0_std, disturbance_std=w_std, distribution="uniform",
+                                           feedback=feedback, samples=True)
+            el = time.time() - t0
+            err = np.abs(np.asarray(mc.x_final, np.float64) - target)
+            ok = np.isfinite(mc.cost) & (err[..., :2].max(axis=-1) <= TOL_ANGLE) & (err[..., 2:].max(axis=-1) <= TOL_RATE)
+            share = ok.mean(axis=1)
+            print(f"parameter spread {a.param_std:g}, {label}: {B} x {S} rollouts in {el:.3f} s, m2 and l2 drawn on the device; "
+                  f"share of samples within tolerance per trajectory: min {share.min():.3f}, median {np.median(share):.3f}, "
+                  f"max {share.max():.3f}; cost mean median {np.nanmedian(mc.cost_mean):.3f}, cost std median "
+                  f"{np.nanmedian(mc.cost_std):.3f}")
+        solver.set_param_spread(None)
     return shares
 
 

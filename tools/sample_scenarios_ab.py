@@ -17,6 +17,7 @@ margin within which a difference says nothing.  The one prior for a / b is the M
 sample_rollout_kernel appear under their own names.
 
     python tools/sample_scenarios_ab.py [--rounds 7] [--batch 64] [--samples 128] [--scenarios 8] [--horizon 200] [--search-rounds 4]
+        [--param-std 0]   (> 0: leg a's scenarios also draw m2 and l2 with this relative spread, ilqr_set_param_spread)
 """
 import argparse
 import json
@@ -34,11 +35,14 @@ U_STD, BETA, TEMPERATURE = 2.0, 0.9, 50.0          # tools/sample_controls_ab.py
 W_STD = 1e-3
 
 
-def setup(dtype, B, N):
+def setup(dtype, B, N, rel=0.0):
     p = problems.ua_double_pendulum(N=N)
     sysm = ilqr_amd.make_system(p["dynamics"], p["cost"], dtype)
     x0, U0 = problems.ua_batch(B, seed=0, restarts=True, N=N)
-    return ilqr_amd.iLQR(sysm, None, x0, U0, N=N, maxiter=3, verbose=False, dtype=dtype)
+    s = ilqr_amd.iLQR(sysm, None, x0, U0, N=N, maxiter=3, verbose=False, dtype=dtype)
+    if rel:      # a parameter spread: read by leg a alone (the search ignores it without scenarios)
+        s.set_param_spread({"m2": rel, "l2": rel})
+    return s
 
 
 def call(s, S, R, M):
@@ -58,8 +62,8 @@ def legs(S, M):
     return (("a", S, M), ("b", S * M, 0), ("c", S, 0))
 
 
-def run(dtype, B, S, M, N, R, rounds):
-    s = setup(dtype, B, N)
+def run(dtype, B, S, M, N, R, rounds, rel=0.0):
+    s = setup(dtype, B, N, rel)
     s.handle.timing_enable(True)
     warm = {k: call(s, Sk, R, Mk)[2] for k, Sk, Mk in legs(S, M)}
     res = {k: [] for k, _, _ in legs(S, M)}
@@ -67,7 +71,7 @@ def run(dtype, B, S, M, N, R, rounds):
         for k, Sk, Mk in legs(S, M):
             res[k].append(call(s, Sk, R, Mk)[:2])
     dev = {k: np.array([d for d, _ in v]) for k, v in res.items()}
-    out = dict(dtype=np.dtype(dtype).name, B=B, S=S, M=M, N=N, R=R)
+    out = dict(dtype=np.dtype(dtype).name, B=B, S=S, M=M, N=N, R=R, param_std=rel)
     for k in res:
         out[f"{k}_device_ms"] = [round(float(v), 4) for v in dev[k]]
         out[f"{k}_wall_ms"] = [round(w, 2) for _, w in res[k]]
@@ -78,8 +82,8 @@ def run(dtype, B, S, M, N, R, rounds):
     return out
 
 
-def kernels(dtype, B, S, M, N, R):
-    s = setup(dtype, B, N)
+def kernels(dtype, B, S, M, N, R, rel=0.0):
+    s = setup(dtype, B, N, rel)
     for k, Sk, Mk in legs(S, M) * 4:
         call(s, Sk, R, Mk)
 
@@ -94,14 +98,16 @@ def main():
     ap.add_argument("--search-rounds", type=int, default=4, help="R of the search")
     ap.add_argument("--dtype", choices=["float32", "float64", "both"], default="both")
     ap.add_argument("--kernels", action="store_true", help="a warm-up and three calls per leg, for a kernel trace")
+    ap.add_argument("--param-std", type=float, default=0.0,
+                    help="leg a's scenarios also draw m2 and l2 with this relative spread (set_param_spread); legs b and c ignore it")
     a = ap.parse_args()
     for dtype in (np.float32, np.float64):
         if a.dtype not in ("both", np.dtype(dtype).name):
             continue
         if a.kernels:
-            kernels(dtype, a.batch, a.samples, a.scenarios, a.horizon, a.search_rounds)
+            kernels(dtype, a.batch, a.samples, a.scenarios, a.horizon, a.search_rounds, a.param_std)
             continue
-        print(json.dumps(run(dtype, a.batch, a.samples, a.scenarios, a.horizon, a.search_rounds, a.rounds)), flush=True)
+        print(json.dumps(run(dtype, a.batch, a.samples, a.scenarios, a.horizon, a.search_rounds, a.rounds, a.param_std)), flush=True)
 
 
 if __name__ == "__main__":
